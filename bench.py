@@ -5,17 +5,21 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --config cfg2                                 (SwinIR-light x2 inference, 48x48 LR, bs 16: BASELINE cfg2)
     python bench.py --config cfg4 | cfg5                          (HAT x4 / DAT x4 inference, 64x64 LR, bs 16: BASELINE cfg4 / cfg5)
+    python bench.py --full                                        (adds the extra legs below to the line)
+    python bench.py --dump-outputs DIR                            (after the timed steps: what the last step handed its caller, DIR/*.npy)
 
 A step = forward + L1 loss + backward + (N>1: RCCL gradient all-reduce, overlapped) + clip 1.0 + AdamW on
-one batch of synthetic LR/HR patches already resident in HBM.  Prints ONE JSON line on rank 0.
-Weak scaling: every rank processes its own 32 patches.
+one batch of synthetic LR/HR patches already resident in HBM, every step from the same seeded weights and fresh AdamW state
+(StepStart).  Prints ONE JSON line on rank 0.
+Weak scaling: every rank processes its own 32 patches.  Without --full a run only sets up, warms up, times the --steps
+steps (and writes --dump-outputs), so that its cost outside the timed steps stays small.
 
-The JSON line's `roofline` has the dominant kernel family (HIP events inside the timed region) and `roofline.step`: the
+With --full the JSON line's `roofline` has the dominant kernel family (HIP events inside the timed region) and `roofline.step`: the
 whole step against the MFMA roofline (SURVEY 8d's primary bound) plus HBM bytes per step -- measured (rocprofv3 PMC summary
 under profiles/, used only while its kernel-source digest matches the library being run) vs the block-fused compulsory
 bytes of SURVEY 8d.
 
-Extra legs (rank 0, N=1):
+Extra legs (--full only; rank 0, N=1):
   roofline     -- HIP-event timing of the dominant kernel family (the linear-layer MFMA GEMM) bracketed
                   inside the timed steps by libsrk's probe; achieved = algorithmic bytes / kernel time (HBM-bound
                   family), with the MFMA view alongside.
@@ -43,6 +47,50 @@ PROBE_STRIDE = 5
 FAMILY_TRAFFIC_FILE = "r03_pmc_linear_gemm_stream_traffic.json"     # rocprofv3 PMC summaries this round's library was measured with
 STEP_TRAFFIC_FILE = "r03_pmc_step_traffic.json"
 HBM_PEAK_GBS = 8000.0                # HBM3E spec (MI355X_MICROARCH.md; ~6.3 TB/s is the measured copy ceiling)
+DUMP_MAX_ELEMS = 6_000_000           # --dump-outputs: elements per array at most (three arrays stay under 64 MB)
+
+
+def dump_outputs(path, **arrays):
+    """--dump-outputs: write each array as `path/<name>.npy` (float tensors as float32, the loss as float64).  An array longer
+    than DUMP_MAX_ELEMS is written as a fixed sample of its flattened elements: the same seeded indices in every run, so that
+    two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.to(torch.float64 if name == "loss" else torch.float32).cpu().numpy())
+
+
+def dump_train_step(path, model, loss):
+    """A train step hands its caller the loss and, in the module, the stepped weights and the step's gradients (on the SwinIR
+    engine: views of its flat buffers), each flattened in parameters() order."""
+    params = list(model.parameters())
+    dump_outputs(path, loss=loss.reshape(1), weights=torch.cat([p.detach().reshape(-1) for p in params]),
+                 grads=torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in params]))
+
+
+class StepStart:
+    """The state every warm-up and timed train step starts from: the seeded initial weights (and buffers) with fresh optimizer
+    moments.  The backward sums weight gradients with fp32 atomics in no fixed order, and a training trajectory amplifies those
+    last-bit differences from step to step (Adam's normalised update, bf16 rounding of the next forward); restarting every step
+    from the same state keeps each step's inputs -- and so what it computes and --dump-outputs writes -- the same in every run.
+    The restore is a fused copy and a fused zero fill, a few hundred MB of HBM traffic per step."""
+
+    def __init__(self, tensors):
+        self.tensors = list(tensors)
+        self.saved = [t.detach().clone() for t in self.tensors]
+
+    @torch.no_grad()
+    def restore(self, moments=()):
+        torch._foreach_copy_(self.tensors, self.saved)
+        by_device = {}
+        for t in moments:                        # fused fills need one device per list (torch's eager AdamW keeps `step` on the host)
+            by_device.setdefault(t.device, []).append(t)
+        for ts in by_device.values():
+            torch._foreach_zero_(ts)
 
 
 def synthetic_batch(batch, device, seed):
@@ -235,9 +283,12 @@ def bench_inference(args):
                 y = model(x)
         barrier()
         elapsed = time.perf_counter() - t0
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, output=y)
         roof = None
-        if rank == 0 and not args.no_roofline:      # un-timed extra pass with every GEMM launch bracketed (eager: events
-            _lib.check(lib.srk_set_option(b"probe_stride", 1))       # cannot be recorded inside a captured graph)
+        if rank == 0 and args.full and not args.no_roofline:
+            # un-timed extra pass with every GEMM launch bracketed (eager: events cannot be recorded inside a captured graph)
+            _lib.check(lib.srk_set_option(b"probe_stride", 1))
             _lib.check(lib.srk_probe_begin(1, 4000))
             for _ in range(5):
                 model(x)
@@ -271,7 +322,7 @@ def bench_inference(args):
         if roof is not None:
             roof["step"] = {"mfma_frac": tfl_step / MFMA_BF16_PEAK_TFLOPS, "algorithmic_tflop_per_step": bs * flop_per_image / 1e12}
             out["roofline"] = roof
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_infer(args.config)
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -307,7 +358,10 @@ def bench_hat_train(args):
         from tpu_superresolution_amd.training import GraphedTrainStep
         gstep = GraphedTrainStep(model, opt, max_grad_norm=1.0, warmup=2)
 
+    start = StepStart([*model.parameters(), *model.buffers()])
+
     def step():
+        start.restore([t for st in opt.state.values() for t in st.values() if torch.is_tensor(t)])   # moments and step counts
         if graphed:
             return gstep(lr_img, hr_img)
         opt.zero_grad(set_to_none=True)
@@ -336,6 +390,8 @@ def bench_hat_train(args):
     barrier()
     elapsed = time.perf_counter() - t0
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
+    if rank == 0 and args.dump_outputs:
+        dump_train_step(args.dump_outputs, model, loss)
     t = torch.tensor([elapsed], dtype=torch.float64, device=device)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -351,7 +407,7 @@ def bench_hat_train(args):
         out = {"metric": f"HR pixels/sec, {what[0]} x4 train step, 64x64 LR, bs=16/GPU", "value": value, "unit": "HR pixels/s", "n_gpus": world,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
                "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-               "config": {"workload": what[1] + "bwd + clip 1.0 + AdamW (torch foreach), 64x64 LR -> 256x256 HR, random-init weights, drop_path 0.1",
+               "config": {"workload": what[1] + "bwd + clip 1.0 + AdamW (torch foreach), 64x64 LR -> 256x256 HR, random-init weights, drop_path 0.1; every step starts from the seeded weights and fresh AdamW state",
                           "batch_per_gpu": bs, "global_batch": bs * world, "parallelism": f"dp{world}", "per_gpu_value": value / world,
                           "ms_per_step_median": step_ms[len(step_ms) // 2], "step_tflops_per_gpu": flop_step / (ms_per_step * 1e-3) / 1e12,
                           "launch": "one hipGraph replay per step (training.GraphedTrainStep)" if graphed else "eager launches",
@@ -411,8 +467,12 @@ def main():
     ap.add_argument("--config", choices=["cfg3", "cfg2", "cfg4", "cfg5"], default="cfg3",
                     help="cfg3 (default): the headline train step; cfg2: SwinIR-light x2 / cfg4: HAT x4 / cfg5: DAT x4 inference")
     ap.add_argument("--batch", type=int, default=None, help="samples per GPU (BASELINE: 32 for cfg3, 16 for cfg2)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: the roofline probe, the CPU baseline and (cfg3) the PSNR check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step handed its caller as DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-graph", action="store_true", help="cfg2 / --train legs: time the eager launch loop instead of a hipGraph replay")
     ap.add_argument("--train", action="store_true", help="cfg4 / cfg5: time a HAT / DAT TRAIN step (fwd + L1 + bwd + clip + AdamW) instead of inference")
     ap.add_argument("--use-checkpoint", action="store_true",
@@ -421,7 +481,7 @@ def main():
                     help="developer A/B: srk_set_option(NAME, VALUE) before the model is built (repeatable)")
     args = ap.parse_args()
     if args.steps is None:
-        args.steps = {"cfg3": 50, "cfg2": 200, "cfg4": 10, "cfg5": 10}[args.config]     # >= 50 steps, median reported beside
+        args.steps = 5 if args.train else {"cfg3": 50, "cfg2": 200, "cfg4": 10, "cfg5": 10}[args.config]     # >= 50 steps, median reported beside
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus, sys.argv[1:])           # never returns
     if not torch.cuda.is_available():
@@ -433,8 +493,6 @@ def main():
     if args.train:
         if args.config not in ("cfg4", "cfg5"):
             raise SystemExit("--train selects the HAT / DAT train step: use it with --config cfg4 or cfg5 (cfg3, the default, is a train step already)")
-        if args.steps == 10:
-            args.steps = 5
         return bench_hat_train(args)
     if args.config in INFER:
         return bench_inference(args)
@@ -465,16 +523,23 @@ def main():
     if world > 1 and dp._sync is not None:
         dp._sync.time_exposed = True
 
+    start = StepStart([model._engine.flat])             # the engine's flat fp32 weights (every parameter is a view of it)
+
+    def step():
+        start.restore([opt._m, opt._v] if opt._m is not None else ())
+        opt._step = 0
+        return train_step(model, opt, lr_img, hr_img, sync)
+
     def barrier():
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
 
     for _ in range(args.warmup):
-        loss, bad = train_step(model, opt, lr_img, hr_img, sync)
+        loss, bad = step()
     barrier()
 
-    probe = (not args.no_roofline) and rank == 0
+    probe = args.full and not args.no_roofline and rank == 0
     lib = _lib.lib()
     if probe:
         # family 1 = linear-layer GEMMs (7 launches per Swin block; 8 where the fused qkv+attention kernel does not apply).
@@ -490,12 +555,14 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
-        loss, bad = train_step(model, opt, lr_img, hr_img, sync)
+        loss, bad = step()
         marks[i + 1].record()
     barrier()
     elapsed = time.perf_counter() - t0
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     median_ms = step_ms[len(step_ms) // 2]
+    if rank == 0 and args.dump_outputs:
+        dump_train_step(args.dump_outputs, model, loss)
     exposed = dp._sync.exposed_ms() if (world > 1 and dp._sync is not None) else None
     roof = None
     if probe:
@@ -533,7 +600,8 @@ def main():
                "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
                "config": {"workload": ("cfg3 with use_checkpoint=True (NOT the BASELINE line): " if args.use_checkpoint else "") +
                                       "BASELINE cfg3: SwinIR classical x4 (dim 180, 6x6 blocks, window 8) train step = fwd + L1 + bwd "
-                                      "+ clip 1.0 + AdamW, 64x64 LR patches -> 256x256 HR, random-init weights, drop_path 0.1",
+                                      "+ clip 1.0 + AdamW, 64x64 LR patches -> 256x256 HR, random-init weights, drop_path 0.1; every step starts from the seeded "
+                                      "weights and fresh AdamW state",
                           "batch_per_gpu": args.batch, "global_batch": args.batch * world, "parallelism": f"dp{world}",
                           "per_gpu_value": value / world,
                           "ms_per_step_median": median_ms, "ms_per_step_min": step_ms[0], "ms_per_step_max": step_ms[-1],
@@ -567,7 +635,7 @@ def main():
                                         "compulsory_bytes_per_step": comp,
                                         "traffic_ratio": (hbm_step / comp) if hbm_step else None},
                                "hbm_family": roof}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
             out["psnr_delta_db"] = None
             try:

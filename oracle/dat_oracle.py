@@ -21,7 +21,7 @@ evaluated once per block from the closed-form offset table; BatchNorm is its inf
 Eval semantics by default (BatchNorm uses running statistics).  ``train_mode(record)`` switches every BatchNorm to batch statistics
 (nn.BatchNorm2d in training, momentum 0.1: biased variance for the normalisation, unbiased for the running estimate) and records the
 updated running buffers; ``loss_and_grads`` is torch autograd over this functional model -- the training oracle pinned by
-tests/golden/g14c_dat_train.npz (the reference's own DAT in .train(), oracle/make_golden.py::gen_g14c).
+tests/golden/g14c_dat_train.part*.npz (the reference's own DAT in .train(), oracle/make_golden.py::gen_g14c).
 """
 from __future__ import annotations
 

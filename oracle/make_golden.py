@@ -11,7 +11,9 @@ state_dict schema.
 """
 from __future__ import annotations
 
+import glob
 import hashlib
+import io
 import os
 import sys
 
@@ -24,6 +26,7 @@ from oracle import swinir_oracle as O  # noqa: E402
 from oracle.ref_import import import_reference  # noqa: E402
 
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+GOLDEN_FILE_LIMIT = 960 * 1024      # every committed file stays under 1 MiB
 
 
 def sha1(a: np.ndarray) -> str:
@@ -34,10 +37,35 @@ def sd_to_np(sd):
     return {"sd." + k: v.detach().cpu().numpy() for k, v in sd.items()}
 
 
+def _npz(arrays) -> bytes:
+    buf = io.BytesIO()
+    np.savez_compressed(buf, **arrays)
+    return buf.getvalue()
+
+
 def save(name, **arrays):
-    path = os.path.join(OUT, name + ".npz")
-    np.savez_compressed(path, **arrays)
-    print(f"wrote {path}  ({os.path.getsize(path) / 1024:.1f} KiB)")
+    """-> tests/golden/<name>.npz; a fixture that compresses to more than GOLDEN_FILE_LIMIT is stored instead as <name>.part1.npz,
+    <name>.part2.npz, ... (the arrays in order, every file under the limit), which tests/conftest.py::load_golden joins."""
+    for old in glob.glob(os.path.join(OUT, glob.escape(name) + ".npz")) + glob.glob(os.path.join(OUT, glob.escape(name) + ".part*.npz")):
+        os.remove(old)
+    whole = _npz(arrays)
+    if len(whole) <= GOLDEN_FILE_LIMIT:
+        files = {name + ".npz": whole}
+    else:
+        parts, size = [{}], 0
+        for k, v in arrays.items():
+            n = len(_npz({k: v}))          # zip members are compressed one by one: the sizes add up
+            if parts[-1] and size + n > GOLDEN_FILE_LIMIT:
+                parts.append({})
+                size = 0
+            parts[-1][k] = v
+            size += n
+        files = {f"{name}.part{i + 1}.npz": _npz(p) for i, p in enumerate(parts)}
+    for fn, blob in files.items():
+        path = os.path.join(OUT, fn)
+        with open(path, "wb") as f:
+            f.write(blob)
+        print(f"wrote {path}  ({len(blob) / 1024:.1f} KiB)")
 
 
 def build_ref_model(ns, cfg: O.SwinIRConfig, sd):

@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -15,8 +16,24 @@ def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
 
 
+class _JoinedGolden(dict):
+    """The arrays of a golden vector stored in parts (oracle/make_golden.py::save keeps every file under 1 MiB), read like an npz."""
+
+    @property
+    def files(self):
+        return list(self)
+
+
 def load_golden(name):
-    return np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+    path = os.path.join(GOLDEN, name + ".npz")
+    parts = glob.glob(os.path.join(GOLDEN, glob.escape(name) + ".part*.npz"))
+    if os.path.exists(path) or not parts:
+        return np.load(path, allow_pickle=False)
+    out = _JoinedGolden()
+    for part in sorted(parts, key=lambda p: int(p[:-len(".npz")].rsplit(".part", 1)[1])):
+        with np.load(part, allow_pickle=False) as z:
+            out.update((k, z[k]) for k in z.files)
+    return out
 
 
 @pytest.fixture(scope="session")

@@ -1,4 +1,6 @@
-"""Copy the artefacts of tools/_measure.sh (gpurun_out/m_*) into profiles/ as the round's final evidence."""
+"""Copy the artefacts of tools/_measure.sh (OUT/m_*) into profiles/ as the round's final evidence.
+
+    python tools/install_profiles.py TAG OUT        (OUT: the directory `tools/_measure.sh TAG OUT` wrote)"""
 import csv
 import glob
 import json
@@ -8,8 +10,9 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G, P = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
-tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
+if len(sys.argv) != 3:
+    raise SystemExit(__doc__)
+tag, G, P = sys.argv[1], os.path.abspath(sys.argv[2]), os.path.join(ROOT, "profiles")
 
 subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "pmc_traffic.py"), f"{G}/m_pmc_fetch", f"{G}/m_pmc_write", "gemm_stream|mlp_fused",
                        f"{P}/{tag}_pmc_linear_gemm_stream_traffic.json"], stdout=subprocess.DEVNULL)
@@ -45,7 +48,7 @@ fam = d["roofline"]["hbm_family"]
 traffic = json.load(open(f"{P}/{tag}_pmc_linear_gemm_stream_traffic.json"))["avg_hbm_bytes_per_launch"]
 hdr = f"""# rocprofv3 --kernel-trace --stats of the default bench command ({tag})
 
-Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --no-cpu-baseline` (25 train steps of cfg3,
+Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --no-cpu-baseline` (25 train steps of cfg3,
 bs 32, incl. 5 warm-up, `--steps 20`; the HIP-event probe brackets every {fam.get('sampled_every', 1)}th launch of the roofline family during the 20 timed steps).
 Bench line of the same run: `{tag}_final_bench_line_under_rocprof.json`; un-profiled bench line: `{tag}_final_bench_line.json`
 ({d['ms_per_step']:.2f} ms/step = {d['value'] / 1e6:.1f} M HR px/s).
