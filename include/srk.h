@@ -295,6 +295,15 @@ int srk_win256_attention_fwd(const uint16_t* qkv, int ldq, int CA, const float* 
 int srk_win_attention_fwd_padded(const uint16_t* qkv, int ldq, int CA, const float* bias, int table_rows, uint16_t* out, int ldo, int B, int H,
                                  int W, int Hp, int Wp, int wh, int ww, int shift_y, int shift_x, int num_heads, float scale, int overlap,
                                  srk_stream_t stream);
+/* ---- SwinIR with small windows (csrc/attn_small.hip) -------------------------------------------------------------------------------
+ * (Shifted-)window attention forward for ws x ws windows, 2 <= ws <= 7 (N = ws^2 <= 49 tokens; WindowAttention.forward
+ * network_swinir.py:114-145 + the roll / partition / reverse of SwinTransformerBlock.forward :240-279).  qkv bf16 [T][ldq] in RASTER
+ * token order (q | k | v at columns 0 / CA / 2 CA, head h at +32 h, head_dim zero-padded to 32, q NOT pre-scaled); out bf16 [T][ldo]
+ * raster.  table: the relative_position_bias_table parameter fp32 [(2 ws - 1)^2][num_heads], indexed in closed form; shift > 0 applies
+ * the mask of calculate_mask :216-237 for the H x W map.  Windows are padded to 32 / 64 keys that are EXCLUDED from the softmax.
+ * SRK_E_UNSUPPORTED outside 2 <= ws <= 7, SRK_E_SHAPE when H or W is not a multiple of ws. */
+int srk_win_small_attention_fwd(const uint16_t* qkv, int ldq, int CA, const float* table, uint16_t* out, int ldo, int B, int H, int W,
+                                int ws, int shift, int num_heads, float scale, srk_stream_t stream);
 /* ChannelAttention gate of CAB (:41-57): gate[b][c] = out_scale * sigmoid(W2 relu(W1 mean_b + b1) + b2), mean over the HW tokens
  * of x bf16 [B*HW][CP]; w1 [S][C], w2 [C][S] fp32 (the 1x1 convs).  workspace: srk_channel_gate_workspace bytes. */
 size_t srk_channel_gate_workspace(int B, int HW, int CP);

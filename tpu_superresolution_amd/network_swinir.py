@@ -12,8 +12,10 @@ Covered by the HIP path: window_size 8, head_dim <= 32, embed_dim <= 256, in_cha
 '3conv', patch_norm=True, ape (at img_size), use_checkpoint, all four heads -- 'pixelshuffle' (x2/x3/x4/x8), 'pixelshuffledirect'
 (upscale^2 * in_chans <= 16), 'nearest+conv' (x2/x4) and '' (denoising, upscale 1) -- and ``forward_features`` as a callable
 (inference).  window_size 16 runs INFERENCE through the 256-token window attention of the HAT path (``swinir_w16.py``; the two
-pixel-shuffle heads, '1conv').  Other constructor options (other window sizes, patch_norm=False, dropout > 0) build the same
-state_dict but raise ``NotImplementedError`` in ``forward``.
+pixel-shuffle heads, '1conv').  window_size 2..7 -- 7 is this constructor's default and the window of the SwinIR JPEG-artifact
+models -- runs INFERENCE through the same sequence with the small-window attention kernel (csrc/attn_small.hip; heads
+'pixelshuffle', 'pixelshuffledirect' and '' (denoising / JPEG), '1conv', img_size > window_size).  Other constructor options (other
+window sizes, patch_norm=False, dropout > 0) build the same state_dict but raise ``NotImplementedError`` in ``forward``.
 """
 from __future__ import annotations
 
@@ -417,6 +419,12 @@ class SwinIR(nn.Module):
             if torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters()):
                 raise SrkUnsupported("SwinIR(window_size=16) on the HIP path is inference-only: call model.eval() / torch.no_grad() "
                                      "(training runs with window_size 8)")
+            from . import swinir_w16
+            return swinir_w16.forward(self, x)
+        if self.window_size < 8:          # windows of <= 49 tokens: the same host-orchestrated sequence with the small-window attention
+            if torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters()):
+                raise SrkUnsupported(f"SwinIR(window_size={self.window_size}) on the HIP path is inference-only: call model.eval() / "
+                                     "torch.no_grad() (training runs with window_size 8)")
             from . import swinir_w16
             return swinir_w16.forward(self, x)
         eng = self._bind(x.device)

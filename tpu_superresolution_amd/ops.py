@@ -146,6 +146,22 @@ def window_attention_bwd_fused(xn: torch.Tensor, w_qkv: torch.Tensor, b_qkv: Opt
     return d_qkv, d_table
 
 
+def window_attention_small_fwd(qkv: torch.Tensor, table: torch.Tensor, B: int, H: int, W: int, window_size: int, shift: int,
+                               num_heads: int, scale: float) -> torch.Tensor:
+    """(Shifted-)window attention for ws x ws windows, 2 <= ws <= 7, in raster token order.  qkv bf16 [B*H*W, 3*CA] (q | k | v at
+    columns 0 / CA / 2 CA, head h at +32 h, head_dim zero-padded to 32, q not scaled); table = relative_position_bias_table fp32
+    [(2 ws - 1)^2, num_heads] -> out bf16 [B*H*W, num_heads*32]."""
+    T, ldq = qkv.shape
+    if T != B * H * W or ldq % 3 or qkv.dtype != torch.bfloat16:
+        raise ValueError(f"qkv must be bf16 [B*H*W = {B * H * W}, 3*CA], got {qkv.dtype} {tuple(qkv.shape)}")
+    if 2 <= window_size <= 7 and (table.dtype != torch.float32 or tuple(table.shape) != ((2 * window_size - 1) ** 2, num_heads)):
+        raise ValueError(f"table must be fp32 [{(2 * window_size - 1) ** 2}, {num_heads}], got {table.dtype} {tuple(table.shape)}")
+    out = torch.empty((T, num_heads * 32), dtype=torch.bfloat16, device=qkv.device)
+    check(lib().srk_win_small_attention_fwd(_p(qkv), ldq, ldq // 3, _p(table), _p(out), num_heads * 32, B, H, W, window_size, shift,
+                                            num_heads, float(scale), _stream()))
+    return out
+
+
 def rel_pos_bias_expand(table: torch.Tensor) -> torch.Tensor:
     nH = table.shape[1]
     out = torch.empty((nH, 64, 64), dtype=torch.float32, device=table.device)

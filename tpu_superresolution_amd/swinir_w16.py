@@ -13,6 +13,12 @@ branch (hat_arch.py:281-325 vs network_swinir.py:240-279), so the kernels are th
     RSTB conv + skip, conv_after_body, head               implicit-GEMM 3x3 convs with residual / LeakyReLU / PixelShuffle / image epilogues
 
 Inference only ('pixelshuffle' and 'pixelshuffledirect' heads, resi_connection '1conv', no ape); a grad-enabled training forward raises.
+
+The same sequence runs ``SwinIR(window_size=2..7)`` (7 is the constructor's default; the SwinIR JPEG-artifact models use it): only the
+attention launch differs -- srk_win_small_attention_fwd (csrc/attn_small.hip: windows of <= 49 tokens padded to 32 / 64 with the padded
+keys excluded, bias table indexed in the kernel, arithmetic shift mask with shift = ws // 2) -- and the denoising / JPEG head ''
+(x + conv_last(res), network_swinir.py:832-836) is covered too.  Token counts are then not always multiples of 64: the token-row buffers
+are padded to a multiple of 64 rows, so that the persistent GEMMs and the fused MLP cover every row-wise step.
 """
 from __future__ import annotations
 
@@ -29,16 +35,20 @@ from .hat_arch import _gemm, _head_map, _pack_conv, _pack_linear, _pack_vec, _ps
 
 
 def unsupported_reason(m) -> str:
-    if m.upsampler not in ("pixelshuffle", "pixelshuffledirect"):
-        return f"window_size=16 with upsampler={m.upsampler!r}"
+    ws = m.window_size
+    heads = ("pixelshuffle", "pixelshuffledirect") + (("",) if ws < 8 else ())
+    if m.upsampler not in heads:
+        return f"window_size={ws} with upsampler={m.upsampler!r}"
     if m.resi_connection != "1conv" or m.ape or not m.patch_norm or not m.qkv_bias or m.patch_size != 1 or m.drop_rate or m.attn_drop_rate:
-        return "window_size=16 with resi_connection != '1conv', ape, patch_norm=False, qkv_bias=False, patch_size != 1 or dropout"
+        return f"window_size={ws} with resi_connection != '1conv', ape, patch_norm=False, qkv_bias=False, patch_size != 1 or dropout"
     if m.embed_dim > 256 or any(m.embed_dim % h or m.embed_dim // h > 32 for h in m.heads):
         return "embed_dim > 256 or head_dim > 32"
+    if m.upsampler == "" and m.upscale != 1:
+        return "upsampler='' with upscale != 1"
     if m.upsampler == "pixelshuffledirect" and m.upscale ** 2 * m.in_chans > 16:
         return "pixelshuffledirect with upscale^2 * in_chans > 16"
-    if any(blk.window_size != 16 for layer in m.layers for blk in layer.residual_group.blocks):
-        return "window_size=16 with img_size <= 16 (the blocks fall back to one window of the image size)"
+    if any(blk.window_size != ws for layer in m.layers for blk in layer.residual_group.blocks) or (ws < 8 and min(m.patches_resolution) <= ws):
+        return f"window_size={ws} with img_size <= {ws} (the blocks fall back to one window of the image size)"
     return ""
 
 
@@ -84,9 +94,10 @@ def pack(m, device) -> Dict[str, torch.Tensor]:
                     k += 1
             P["Wlast"] = _pack_conv(m.conv_last.weight, 16, 64)
             P["blast"] = _pack_vec(m.conv_last.bias, 16)
-        else:
-            P["Wdirect"] = _pack_conv(m.upsample[0].weight, 16, CP)
-            P["bdirect"] = _pack_vec(m.upsample[0].bias, 16)
+        else:       # 'pixelshuffledirect': UpsampleOneStep's conv; '': conv_last (embed_dim -> in_chans, :832-836)
+            direct = m.upsample[0] if m.upsampler == "pixelshuffledirect" else m.conv_last
+            P["Wdirect"] = _pack_conv(direct.weight, 16, CP)
+            P["bdirect"] = _pack_vec(direct.bias, 16)
         pk.resolve(P)
     m._w16_packed, m._w16_version, m._w16_device = P, ver, device
     return P
@@ -108,7 +119,7 @@ def _forward(m, x: torch.Tensor, P: Dict[str, torch.Tensor]) -> torch.Tensor:
     dev = x.device
     st = torch.cuda.current_stream(dev).cuda_stream
     B, Cin, H0, W0 = x.shape
-    ws, s = 16, m.upscale
+    ws, s = m.window_size, m.upscale
     H, W = _rup(H0, ws), _rup(W0, ws)
     if (H - H0 >= H0) or (W - W0 >= W0):
         raise RuntimeError(f"reflect padding {H0}x{W0} -> {H}x{W} needs pad < size (as torch 'reflect')")
@@ -120,16 +131,24 @@ def _forward(m, x: torch.Tensor, P: Dict[str, torch.Tensor]) -> torch.Tensor:
     mean3 = (C.c_float * 3)(*(m.mean.flatten().tolist() if m.in_chans == 3 else [0.0, 0.0, 0.0]))
     img4 = torch.empty(T, 4, **f32)
     check(L.srk_img_prep(x.data_ptr(), img4.data_ptr(), B, Cin, H0, W0, H, W, float(m.img_range), C.byref(mean3), st))
-    f0 = torch.empty(T, CP, **f32)
+    # token rows: the persistent GEMMs and the fused MLP cover multiples of 64 rows.  Windows of 8 x 8 / 16 x 16 tokens make T one; with
+    # smaller windows (8 x 63 x 63 = 31752 tokens) the row buffers get TR = T rounded up to 64 rows and every row-wise kernel runs on all
+    # TR: the padding rows are never read by the attention or the 3x3 convs (their geometry is B x H x W) and never reach the output
+    TR = _rup(T, 64)
+    f0 = torch.empty(TR, CP, **f32)
+    if TR > T:
+        f0[T:].zero_()
     check(L.srk_stem_conv(img4.data_ptr(), m.conv_first.weight.data_ptr(), m.conv_first.bias.data_ptr(), f0.data_ptr(), B, H, W, Cin, C_, CP, st))
     _, cur, _, _ = ops.layernorm_fwd(f0, m.patch_embed.norm.weight, m.patch_embed.norm.bias, C_, out_bf16=False, out_f32=True)
 
     CAmax = max(h * 32 for h in m.heads)
-    qkv, ao = torch.empty(T, 3 * CAmax, **b16), torch.empty(T, CAmax, **b16)
-    xn2, hh, xb = torch.empty(T, CP, **b16), torch.empty(T, HP, **b16), torch.empty(T, CP, **b16)
-    stat_a, stat_b = torch.empty(T, **f32), torch.empty(T, **f32)
-    xn_a, xn_b = torch.empty(T, CP, **b16), torch.empty(T, CP, **b16)
-    fused_mlp_ok = (CP == 192 and HP == 384 and T % 64 == 0 and T >= 64 * torch.cuda.get_device_properties(dev).multi_processor_count)
+    qkv, ao = torch.empty(TR, 3 * CAmax, **b16), torch.empty(TR, CAmax, **b16)
+    if TR > T:
+        ao[T:].zero_()
+    xn2, hh, xb = torch.empty(TR, CP, **b16), torch.empty(TR, HP, **b16), torch.empty(TR, CP, **b16)
+    stat_a, stat_b = torch.empty(TR, **f32), torch.empty(TR, **f32)
+    xn_a, xn_b = torch.empty(TR, CP, **b16), torch.empty(TR, CP, **b16)
+    fused_mlp_ok = (CP == 192 and HP == 384 and TR % 64 == 0 and TR >= 64 * torch.cuda.get_device_properties(dev).multi_processor_count)
     ln_fusable = CP in (64, 128, 192)
 
     def next_norm(norm, dst):
@@ -140,10 +159,10 @@ def _forward(m, x: torch.Tensor, P: Dict[str, torch.Tensor]) -> torch.Tensor:
             args = (None, None, None, None, None, 0) if nn_ is None else (nn_["out"].data_ptr(), nn_["mean"].data_ptr(), nn_["rstd"].data_ptr(),
                                                                        nn_["gamma"].data_ptr(), nn_["beta"].data_ptr(), nn_["C"])
             check(L.srk_mlp_fused_fwd(xn_in.data_ptr(), P[pre + "W1"].data_ptr(), P[pre + "b1"].data_ptr(), P[pre + "W2"].data_ptr(),
-                                      P[pre + "b2"].data_ptr(), x_res.data_ptr(), out.data_ptr(), _ptr(out_b), *args, T, st))
+                                      P[pre + "b2"].data_ptr(), x_res.data_ptr(), out.data_ptr(), _ptr(out_b), *args, TR, st))
         else:
-            _gemm(st, _lib.LD_ROWS, _lib.EP_GELU, xn_in, P[pre + "W1"], T, HP, CP, lda=CP, bias=P[pre + "b1"], outb2=hh)
-            _gemm(st, _lib.LD_ROWS, _lib.EP_RES, hh, P[pre + "W2"], T, CP, HP, lda=HP, bias=P[pre + "b2"], res=x_res, outf=out, outb=out_b, xn=nn_)
+            _gemm(st, _lib.LD_ROWS, _lib.EP_GELU, xn_in, P[pre + "W1"], TR, HP, CP, lda=CP, bias=P[pre + "b1"], outb2=hh)
+            _gemm(st, _lib.LD_ROWS, _lib.EP_RES, hh, P[pre + "W2"], TR, CP, HP, lda=HP, bias=P[pre + "b2"], res=x_res, outf=out, outb=out_b, xn=nn_)
 
     xn1 = None
     for li, layer in enumerate(m.layers):
@@ -156,22 +175,27 @@ def _forward(m, x: torch.Tensor, P: Dict[str, torch.Tensor]) -> torch.Tensor:
             pre = f"{li}.{bi}."
             if xn1 is None:
                 xn1, _, _, _ = ops.layernorm_fwd(cur, blk.norm1.weight, blk.norm1.bias, C_)
-            _gemm(st, _lib.LD_ROWS, _lib.EP_BF16, xn1, P[pre + "Wqkv"], T, 3 * CA, CP, lda=CP, bias=P[pre + "bqkv"], outb=qkv, ldo=3 * CA)
+            _gemm(st, _lib.LD_ROWS, _lib.EP_BF16, xn1, P[pre + "Wqkv"], TR, 3 * CA, CP, lda=CP, bias=P[pre + "bqkv"], outb=qkv, ldo=3 * CA)
             tab = blk.attn.relative_position_bias_table
             sh = blk.shift_size
-            check(L.srk_win256_attention_fwd(qkv.data_ptr(), 3 * CA, CA, tab.data_ptr(), tab.shape[0], ao.data_ptr(), CA, B, H, W, ws, ws, sh, sh, nH,
-                                             scale, 0, st))
-            x1 = torch.empty(T, CP, **f32)
-            _gemm(st, _lib.LD_ROWS, _lib.EP_RES, ao, P[pre + "Wproj"], T, CP, CA, lda=CA, bias=P[pre + "bproj"], res=cur, outf=x1,
+            if ws == 16:
+                check(L.srk_win256_attention_fwd(qkv.data_ptr(), 3 * CA, CA, tab.data_ptr(), tab.shape[0], ao.data_ptr(), CA, B, H, W, ws, ws, sh,
+                                                 sh, nH, scale, 0, st))
+            else:
+                check(L.srk_win_small_attention_fwd(qkv.data_ptr(), 3 * CA, CA, tab.data_ptr(), ao.data_ptr(), CA, B, H, W, ws, sh, nH, scale, st))
+            x1 = torch.empty(TR, CP, **f32)
+            _gemm(st, _lib.LD_ROWS, _lib.EP_RES, ao, P[pre + "Wproj"], TR, CP, CA, lda=CA, bias=P[pre + "bproj"], res=cur, outf=x1,
                   xn=dict(out=xn2, mean=stat_a, rstd=stat_b, gamma=blk.norm2.weight, beta=blk.norm2.bias, C=C_))
-            nxt = torch.empty(T, CP, **f32)
+            nxt = torch.empty(TR, CP, **f32)
             last = bi == len(blocks) - 1
             dst = xn_a if xn1 is not xn_a else xn_b
             nn_ = None if last else next_norm(blocks[bi + 1].norm1, dst)
             mlp(pre, xn2, x1, nxt, out_b=xb if last else None, nn_=nn_)
             cur = nxt
             xn1 = dst if nn_ is not None else None
-        nxt = torch.empty(T, CP, **f32)
+        nxt = torch.empty(TR, CP, **f32)
+        if TR > T:
+            nxt[T:].zero_()
         following = m.layers[li + 1].residual_group.blocks[0].norm1 if li + 1 < len(m.layers) else m.norm
         nn_ = next_norm(following, xn_a)
         _gemm(st, _lib.LD_CONV3, _lib.EP_RES, xb, P[f"{li}.Wconv"], T, CP, 9 * CP, conv=(B, H, W, CP), bias=P[f"{li}.bconv"], res=layer_in, outf=nxt,
@@ -196,6 +220,7 @@ def _forward(m, x: torch.Tensor, P: Dict[str, torch.Tensor]) -> torch.Tensor:
             _gemm(st, _lib.LD_CONV3, _lib.EP_PS, src, P[f"Wup{k}"], B * h * w, N, 9 * 64, conv=(B, h, w, 64), bias=P[f"bup{k}"], outb=up, r=r, Cs=64, ldo=N)
             src, h, w, k = up, h * r, w * r, k + 1
         _gemm(st, _lib.LD_CONV3, _lib.EP_IMG, src, P["Wlast"], B * h * w, 16, 9 * 64, conv=(B, h, w, 64), bias=P["blast"], outf=y, img=img)
-    else:
-        _gemm(st, _lib.LD_CONV3, _lib.EP_PS_IMG, fb, P["Wdirect"], T, 16, 9 * CP, conv=(B, H, W, CP), bias=P["bdirect"], outf=y, img=dict(img), r=s)
+    else:       # UpsampleOneStep (:594-615), or '' with upscale 1: x + conv_last(res), x = the normalised, padded input (:832-836)
+        _gemm(st, _lib.LD_CONV3, _lib.EP_PS_IMG, fb, P["Wdirect"], T, 16, 9 * CP, conv=(B, H, W, CP), bias=P["bdirect"], outf=y, img=dict(img), r=s,
+              res=img4 if m.upsampler == "" else None)
     return y
