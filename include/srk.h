@@ -214,10 +214,30 @@ int srk_grad_sumsq(const float* grads, int64_t n, float* sumsq, srk_stream_t str
  * computed on the device from sumsq[0] (no host sync); grads are first divided by grad_div (world size).
  * max_norm <= 0 disables clipping.  step is the 1-based step count.  nonfinite: optional DEVICE counter (the one
  * srk_l1_loss_fwd_bwd fills, :133-143); when it is non-zero, or when the gradient norm itself is NaN/Inf, the call leaves
- * params and both moments untouched -- the reference raises before backward/step (:159-165), so the weights survive the raise. */
+ * params and both moments untouched -- the reference raises before backward/step (:159-165), so the weights survive the raise.
+ * beta1 / beta2 are read as the decimals they were written as (the shortest decimal that rounds to the fp32): 1 - beta and the bias
+ * corrections are formed from it in fp64 and rounded once, as torch does. */
 int srk_adamw_clip_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
                         const float* sumsq, float max_norm, float grad_div, float lr, float beta1, float beta2, float eps,
                         float weight_decay, int step, const int32_t* nonfinite, srk_stream_t stream);
+/* The same two over a LIST of separate fp32 tensors (the parameters of a host-orchestrated model: HAT, DAT), in the multi-tensor-apply
+ * form: grads / params / exp_avg / exp_avg_sq are HOST arrays of n_tensors DEVICE pointers, numel the element counts (>= 0; a tensor
+ * of 0 elements is skipped).  The table of a chunk of tensors travels by value in the kernel arguments: no upload, no allocation, no
+ * host wait, so both calls can be captured into a hipGraph; launches per call = ceil(n_tensors / chunk), chunk = 160 (sumsq) / 80
+ * (step).  Tensors need 4-byte alignment only (16-byte access where every pointer of a tensor allows it).
+ * srk_multi_grad_sumsq ACCUMULATES the total sum of squares into sumsq[0].
+ * srk_multi_adamw_clip_step: the arithmetic, the gate (nonfinite, NaN / Inf norm) and the arguments of srk_adamw_clip_step, element for
+ * element the same function.  hyper: optional DEVICE {lr, 1 - beta1^step, sqrt(1 - beta2^step)} (what srk_adamw_hyper computes on the
+ * host); when given it replaces lr and step, so a captured launch follows the learning rate and the step count that the host writes
+ * there before every replay.  SRK_E_SHAPE: n_tensors <= 0, a negative count, step < 1, grad_div <= 0; SRK_E_NULL: a null list, or a null entry
+ * with a non-zero count. */
+int srk_multi_grad_sumsq(const float* const* grads, const int64_t* numel, int n_tensors, float* sumsq, srk_stream_t stream);
+int srk_multi_adamw_clip_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                              const int64_t* numel, int n_tensors, const float* sumsq, float max_norm, float grad_div, float lr,
+                              float beta1, float beta2, float eps, float weight_decay, int step, const float* hyper,
+                              const int32_t* nonfinite, srk_stream_t stream);
+/* HOST: out3 = {lr, 1 - beta1^step, sqrt(1 - beta2^step)} exactly as the step kernels' launchers compute them. */
+int srk_adamw_hyper(float lr, float beta1, float beta2, int step, float* out3);
 
 /* ---- generic GEMM / 3x3 conv with the fused epilogues, for host-orchestrated models (HAT: tpu_superresolution_amd/hat_arch.py)
  * D[m][n] = sum_k A[m][k] W[n][k] (+ epilogue).  A bf16: SRK_LD_ROWS [M][lda]; SRK_LD_CONV3 NHWC [B][H][Wd][CinP] (3x3, pad 1,

@@ -4,6 +4,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include "adamw.h"
 #include "kernels.h"
 #include "wgrad.h"
 
@@ -479,6 +480,51 @@ int srk_adamw_clip_step(float* params, const float* grads, float* exp_avg, float
   SRK_REQUIRE(step >= 1 && grad_div > 0.f, SRK_E_SHAPE, "adamw: step=%d grad_div=%f", step, grad_div);
   return srk_launch_adamw(params, grads, exp_avg, exp_avg_sq, n, sumsq, nonfinite, max_norm, grad_div, lr, beta1, beta2, eps,
                           weight_decay, step, (hipStream_t)stream);
+}
+
+static int check_tensor_list(const char* fn, const void* const* const* lists, const char* const* names, int n_lists, const int64_t* numel,
+                             int n_tensors) {
+  SRK_REQUIRE(n_tensors > 0, SRK_E_SHAPE, "%s: n_tensors=%d", fn, n_tensors);
+  SRK_REQUIRE(numel != nullptr, SRK_E_NULL, "%s: null pointer 'numel'", fn);
+  for (int l = 0; l < n_lists; ++l) SRK_REQUIRE(lists[l] != nullptr, SRK_E_NULL, "%s: null pointer '%s'", fn, names[l]);
+  for (int t = 0; t < n_tensors; ++t) {
+    SRK_REQUIRE(numel[t] >= 0 && numel[t] <= ((int64_t)1 << 34), SRK_E_SHAPE, "%s: numel[%d]=%lld", fn, t, (long long)numel[t]);
+    for (int l = 0; l < n_lists; ++l)
+      SRK_REQUIRE(lists[l][t] != nullptr || numel[t] == 0, SRK_E_NULL, "%s: null pointer '%s[%d]'", fn, names[l], t);
+  }
+  return SRK_OK;
+}
+
+int srk_multi_grad_sumsq(const float* const* grads, const int64_t* numel, int n_tensors, float* sumsq, srk_stream_t stream) {
+  const void* const* lists[1] = {(const void* const*)grads};
+  const char* names[1] = {"grads"};
+  const int rc = check_tensor_list(__func__, lists, names, 1, numel, n_tensors);
+  if (rc != SRK_OK) return rc;
+  REQ_PTR(sumsq);
+  return srk_launch_multi_sumsq(grads, (const long long*)numel, n_tensors, sumsq, (hipStream_t)stream);
+}
+
+int srk_multi_adamw_clip_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                              const int64_t* numel, int n_tensors, const float* sumsq, float max_norm, float grad_div, float lr,
+                              float beta1, float beta2, float eps, float weight_decay, int step, const float* hyper,
+                              const int32_t* nonfinite, srk_stream_t stream) {
+  const void* const* lists[4] = {(const void* const*)params, (const void* const*)grads, (const void* const*)exp_avg,
+                                 (const void* const*)exp_avg_sq};
+  const char* names[4] = {"params", "grads", "exp_avg", "exp_avg_sq"};
+  const int rc = check_tensor_list(__func__, lists, names, 4, numel, n_tensors);
+  if (rc != SRK_OK) return rc;
+  SRK_REQUIRE(max_norm <= 0.f || sumsq != nullptr, SRK_E_NULL, "multi adamw: clipping needs sumsq");
+  SRK_REQUIRE(step >= 1 && grad_div > 0.f, SRK_E_SHAPE, "multi adamw: step=%d grad_div=%f", step, grad_div);
+  return srk_launch_multi_adamw(params, grads, exp_avg, exp_avg_sq, (const long long*)numel, n_tensors, sumsq, nonfinite, hyper, max_norm,
+                                grad_div, lr, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
+}
+
+int srk_adamw_hyper(float lr, float beta1, float beta2, int step, float* out3) {
+  REQ_PTR(out3);
+  SRK_REQUIRE(step >= 1, SRK_E_SHAPE, "adamw_hyper: step=%d", step);
+  out3[0] = lr;
+  adamw_bias_corrections(beta1, beta2, step, &out3[1], &out3[2]);
+  return SRK_OK;
 }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 // shuffle / mask / relative-position index), weight pack / gradient unpack, image pre/post
 // processing, the 3-channel stem conv, small-Cout conv gradients, L1 loss, fused AdamW + global-norm
 // clip, and the on-device probe of the transposing LDS read.
+#include "adamw.h"
 #include "kernels.h"
 #include "pack.h"
 #include "wgrad.h"
@@ -879,28 +880,13 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v, long long n,
                                                     const float* __restrict__ sumsq, float max_norm, float grad_div,
-                                                    float lr, float beta1, float beta2, float eps, float wd, float bc1,
-                                                    float bc2_sqrt, const int* __restrict__ nonfinite) {
-  // a non-finite forward (counter of the loss kernel) or a non-finite gradient norm leaves weights and moments untouched:
-  // the reference raises before backward/step (finetune_swinir.py:159-165), so the model must survive for that raise
-  if (nonfinite != nullptr && *nonfinite != 0) return;
-  float coef = 1.0f / grad_div;
-  if (sumsq != nullptr) {
-    const float ss = *sumsq;
-    if (!(ss == ss) || ss > 3.0e38f) return;
-    if (max_norm > 0.f) {
-      const float total = sqrtf(ss) / grad_div;
-      const float c = max_norm / (total + 1e-6f);
-      coef *= c < 1.0f ? c : 1.0f;
-    }
-  }
+                                                    float lr, float beta1, float beta2, float omb1, float omb2, float eps, float wd,
+                                                    float bc1, float bc2_sqrt, const int* __restrict__ nonfinite) {
+  float coef;
+  if (!adamw_gate_coef(sumsq, nonfinite, max_norm, grad_div, coef)) return;          // gate + clip coefficient: adamw.h
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float gi = g[i] * coef;
-    float pi = p[i] * (1.0f - lr * wd);
-    const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
-    const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi -= (lr / bc1) * (mi / denom);
+    float pi = p[i], mi = m[i], vi = v[i];
+    adamw_elem(pi, g[i], mi, vi, coef, lr, beta1, beta2, omb1, omb2, eps, wd, bc1, bc2_sqrt);
     p[i] = pi;
     m[i] = mi;
     v[i] = vi;
@@ -1200,10 +1186,10 @@ int srk_launch_sumsq(const float* g, long long n, float* out, hipStream_t stream
 int srk_launch_adamw(float* p, const float* g, float* m, float* v, long long n, const float* sumsq, const int* nonfinite, float max_norm,
                      float grad_div, float lr, float beta1, float beta2, float eps, float wd, int step,
                      hipStream_t stream) {
-  const float bc1 = 1.0f - powf(beta1, (float)step);
-  const float bc2 = 1.0f - powf(beta2, (float)step);
+  float bc1, bc2_sqrt;
+  adamw_bias_corrections(beta1, beta2, step, &bc1, &bc2_sqrt);
   hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, stream, p, g, m, v, n, sumsq, max_norm,
-                     grad_div, lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), nonfinite);
+                     grad_div, lr, beta1, beta2, adamw_one_minus(beta1), adamw_one_minus(beta2), eps, wd, bc1, bc2_sqrt, nonfinite);
   return srk_check_launch("adamw");
 }
 

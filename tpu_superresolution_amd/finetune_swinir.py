@@ -9,6 +9,11 @@ out ("best_swinir_finetune_<scale>.pt", "bestpsnr_swinir_finetune_<scale>.pt" wi
 same epoch print line (:337-342).  Differences, all additive: bf16 MFMA is built into the kernels (no autocast
 context), the step uses the fused L1 / clip / AdamW kernels, `--weights` may be omitted (random init) and
 `--drop_path_rate` exposes the constructor default (0.1) that the reference leaves implicit.
+
+Also additive: `--arch hat|dat` fine-tunes HAT / DAT (build_sr_model) through the same loop -- the fused, device-gated clip + AdamW step
+over their parameter lists (optim.FusedAdamW, csrc/optim_multi.hip), checkpoints "best_<arch>_finetune_<scale>.pt" /
+"bestpsnr_<arch>_finetune_<scale>.pt" -- and `--graph` replays their whole train step as one hipGraph (training.GraphedTrainStep; one
+process, fixed batch shape).  With more than one process HAT / DAT average their gradients through distributed.ListGradSynchronizer.
 """
 from __future__ import annotations
 
@@ -89,12 +94,13 @@ class DevicePoolLoader:
             yield self.pool.sample(mine[b * self.batch_size:(b + 1) * self.batch_size])
 
 
-def train_one_epoch(model, loader, optimizer, device, sync=None, check_finite=True):
+def train_one_epoch(model, loader, optimizer, device, sync=None, check_finite=True, graphed=None):
+    """graphed: a training.GraphedTrainStep over (model, optimizer) that runs the step instead of train_step (--graph)."""
     model.train()
     total, n, t0 = 0.0, 0, time.time()
     for lr, hr in loader:
         lr, hr = lr.to(device, non_blocking=True), hr.to(device, non_blocking=True)
-        loss, bad = train_step(model, optimizer, lr, hr, sync)
+        loss, bad = graphed(lr, hr) if graphed is not None else train_step(model, optimizer, lr, hr, sync)
         if check_finite:
             assert_finite_step(loss, bad)          # RuntimeError like finetune_swinir.py:133-143
         total += float(loss)
@@ -179,9 +185,17 @@ def main(argv=None):
     ap.add_argument("--gpu_data_shard_mb", type=int, default=0,
                     help="additive, with --gpu_data: keep the decoded set in pinned host shards of this size and prefetch them "
                          "to the device one ahead (0 = whole set resident on the device)")
+    ap.add_argument("--arch", type=str, choices=["swinir", "hat", "dat"], default="swinir",
+                    help="additive: the model to fine-tune (build_sr_model)")
+    ap.add_argument("--graph", action="store_true",
+                    help="additive, --arch hat|dat, one process: capture the train step into a hipGraph and replay it")
     args = ap.parse_args(argv)
+    if args.graph and args.arch == "swinir":
+        ap.error("--graph captures the host-orchestrated train step of --arch hat / dat (SwinIR's step is one C call already)")
 
     rank, world, local = init_from_env()
+    if args.graph and world > 1:
+        raise SystemExit("--graph is for one process (gradient all-reduce stays outside graphs)")
     seed_everything(args.seed)
     if args.workers is None:
         cpu = os.cpu_count() or 4
@@ -210,7 +224,7 @@ def main(argv=None):
     valid_loader = make_loader(valid_ds, max(1, args.batch_size // 2), args.workers, pin=not args.no_pin, shuffle=False,
                                drop_last=False, persistent=not args.no_persistent)
 
-    model = build_model(scale_int, args.drop_path_rate)
+    model = build_model(scale_int, args.drop_path_rate) if args.arch == "swinir" else build_sr_model(args.arch, scale_int, args.drop_path_rate)
     if args.weights:
         ckpt = torch.load(args.weights, map_location="cpu", weights_only=True)
         state = ckpt["params"] if isinstance(ckpt, dict) and "params" in ckpt else (ckpt.get("model", ckpt) if isinstance(ckpt, dict) else ckpt)
@@ -231,8 +245,19 @@ def main(argv=None):
         n_train = sum(1 for p in model.parameters() if p.requires_grad)
         print(f"[params] trainable tensors: {n_train} / total: {len(list(model.parameters()))}")
 
-    dp = DataParallelSwinIR(model)
-    dp.attach(device)                 # weights are now identical on every rank (broadcast from rank 0)
+    if args.arch == "swinir":
+        dp = DataParallelSwinIR(model)
+        dp.attach(device)                 # weights are now identical on every rank (broadcast from rank 0)
+    else:
+        dp = None
+        if world > 1:
+            # HAT / DAT: separate parameter tensors.  Same weights (and BatchNorm statistics) everywhere, then per-segment gradient
+            # SUMS overlapped with the backward (hat_train / dat_train call model.grad_sync); the optimizer divides by the world size
+            import torch.distributed as dist
+            from .distributed import ListGradSynchronizer
+            for t in [*model.parameters(), *model.buffers()]:
+                dist.broadcast(t.data, src=0)
+            dp = model.grad_sync = ListGradSynchronizer(average=False)
     if world > 1:
         # per-rank randomness from here on: DropPath masks and crop corners must differ between ranks, or stochastic
         # depth / crop diversity would not scale with the world size (bench.py seeds 1234 + rank the same way)
@@ -241,11 +266,16 @@ def main(argv=None):
                      max_grad_norm=args.grad_clip if args.grad_clip and args.grad_clip > 0 else None, grad_div=float(world))
     sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=args.epochs, eta_min=args.min_lr) if args.scheduler == "Cosine" else None
 
+    graphed = None
+    if args.graph:
+        from .training import GraphedTrainStep
+        graphed = GraphedTrainStep(model, opt)          # drop_last=True keeps the batch shape fixed
+
     best_loss, best_psnr, t_all = float("inf"), -float("inf"), time.time()
     for epoch in range(1, args.epochs + 1):
         if sampler is not None:
             sampler.set_epoch(epoch)
-        tr_loss, tr_t = train_one_epoch(model, train_loader, opt, device, dp if world > 1 else None)
+        tr_loss, tr_t = train_one_epoch(model, train_loader, opt, device, dp if world > 1 else None, graphed=graphed)
         val_loss, val_psnr, val_t = validate(model, valid_loader, device)
         if sched is not None:
             sched.step()
@@ -257,11 +287,11 @@ def main(argv=None):
         if val_loss < best_loss:
             best_loss = val_loss
             torch.save({"model": sd, "epoch": epoch, "best_val_loss": best_loss, "val_psnr": val_psnr, "args": vars(args)},
-                       f"best_swinir_finetune_{args.scale}.pt")
+                       f"best_{args.arch}_finetune_{args.scale}.pt")
         if val_psnr > best_psnr:
             best_psnr = val_psnr
             torch.save({"model": sd, "epoch": epoch, "best_val_psnr": best_psnr, "val_loss": val_loss, "args": vars(args)},
-                       f"bestpsnr_swinir_finetune_{args.scale}.pt")
+                       f"bestpsnr_{args.arch}_finetune_{args.scale}.pt")
     if rank == 0:
         print(f"[time] total: {fmt(time.time() - t_all)}")
         print(f"[done] best_val_loss={best_loss:.6f}, best_val_psnr={best_psnr:.2f} dB")

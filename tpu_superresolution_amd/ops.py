@@ -344,6 +344,60 @@ def ssim(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0):
     return per, mean
 
 
+class TensorTable:
+    """Host table of a list of fp32 device tensors for the multi-tensor kernels (srk_multi_*): one ctypes array of data pointers per
+    role plus the element counts.  Only pointers are kept; the caller keeps the tensors alive until the launches have run."""
+
+    def __init__(self, n: int):
+        self.n = int(n)
+        self.numel = (C.c_int64 * self.n)()
+        self.ptrs = {}
+
+    def set(self, role: str, tensors, first: bool = False) -> None:
+        """first=True also records the element counts; every later role must match them."""
+        if len(tensors) != self.n:
+            raise ValueError(f"multi-tensor optimizer: {len(tensors)} {role} tensors for a table of {self.n}")
+        arr = self.ptrs.get(role)
+        if arr is None:
+            arr = self.ptrs[role] = (C.c_void_p * self.n)()
+        cur, numel, f32 = None, self.numel, torch.float32
+        for i, t in enumerate(tensors):
+            if t.dtype is not f32:
+                raise TypeError(f"multi-tensor optimizer: {role}[{i}] must be float32 (got {t.dtype})")
+            if cur is None and t.is_cuda:
+                cur = torch.cuda.current_device()
+            if not t.is_cuda or t.device.index != cur or not t.is_contiguous():
+                _p(t)          # raises with the reason (CPU tensor, another device, not contiguous)
+            arr[i] = t.data_ptr()
+            if first:
+                numel[i] = t.numel()
+            elif t.numel() != numel[i]:
+                raise ValueError(f"multi-tensor optimizer: {role}[{i}] has {t.numel()} elements, expected {numel[i]}")
+
+
+def multi_grad_sumsq(table: TensorTable, sumsq: torch.Tensor, role: str = "grads") -> None:
+    """sumsq[0] += sum over the table's tensors of sum(g * g); ceil(n / 160) launches, capturable."""
+    check(lib().srk_multi_grad_sumsq(table.ptrs[role], table.numel, table.n, _p(sumsq), _stream()))
+
+
+def multi_adamw_clip_step(table: TensorTable, sumsq: Optional[torch.Tensor], max_norm: float, grad_div: float, lr: float, beta1: float,
+                          beta2: float, eps: float, weight_decay: float, step: int, hyper: Optional[torch.Tensor] = None,
+                          nonfinite: Optional[torch.Tensor] = None) -> None:
+    """clip + AdamW over the table's params / grads / exp_avg / exp_avg_sq (srk_multi_adamw_clip_step); ceil(n / 80) launches,
+    capturable.  hyper: optional device {lr, bc1, bc2_sqrt} (adamw_hyper) that replaces `lr` and `step`."""
+    pt = table.ptrs
+    check(lib().srk_multi_adamw_clip_step(pt["params"], pt["grads"], pt["exp_avg"], pt["exp_avg_sq"], table.numel, table.n, _p(sumsq),
+                                          float(max_norm), float(grad_div), float(lr), float(beta1), float(beta2), float(eps),
+                                          float(weight_decay), int(step), _p(hyper), _p(nonfinite), _stream()))
+
+
+def adamw_hyper(lr: float, beta1: float, beta2: float, step: int) -> Tuple[float, float, float]:
+    """(lr, 1 - beta1^step, sqrt(1 - beta2^step)) exactly as the step kernels' launchers compute them (host only)."""
+    out = (C.c_float * 3)()
+    check(lib().srk_adamw_hyper(float(lr), float(beta1), float(beta2), int(step), C.byref(out)))
+    return out[0], out[1], out[2]
+
+
 def l1_loss_fwd_bwd(pred: torch.Tensor, target: torch.Tensor, want_grad: bool = True, grad_scale: float = 1.0):
     """-> (loss fp32 [1], d_pred | None, nonfinite int32 [1])   (finetune_swinir.py:66-67, :133-143)."""
     loss = torch.zeros(1, dtype=torch.float32, device=pred.device)

@@ -1,10 +1,16 @@
-"""Fused global-norm clip + AdamW over the engine's flat fp32 buffers (libsrk kernels).
+"""Fused global-norm clip + AdamW (libsrk kernels): over the engine's flat fp32 buffers for SwinIR, over the list of separate
+parameter tensors (multi-tensor kernels, csrc/optim_multi.hip) for every other model (HAT, DAT).
 
 Semantics = ``torch.nn.utils.clip_grad_norm_(params, max_norm)`` followed by ``torch.optim.AdamW.step()``
 as used by the reference training loop (finetune_swinir.py:168-171, :303), without the host sync the
 reference's clip performs: the clip coefficient is computed on the device from the gradient sum of
 squares.  Subclasses ``torch.optim.Optimizer`` only so that LR schedulers (CosineAnnealingLR,
 finetune_swinir.py:307-309) can drive ``param_groups[0]['lr']``.
+
+List path under hipGraph capture (training.GraphedTrainStep): kernel arguments are frozen at capture, so the captured step kernel reads
+the learning rate and the two bias-correction factors from a 3-float device tensor.  ``begin_replay()`` advances the step count and
+rewrites that tensor from ``param_groups[0]['lr']`` before every replay (LR schedulers keep working, the bias correction follows the
+step count); ``end_replay()`` bumps the version counters that the models' bf16 pack caches are keyed on.
 """
 from __future__ import annotations
 
@@ -12,6 +18,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
+from . import ops
 from ._lib import check, lib
 from .network_swinir import SwinIR
 
@@ -21,7 +28,7 @@ def _stream(device) -> int:
 
 
 class FusedAdamW(torch.optim.Optimizer):
-    def __init__(self, model: SwinIR, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+    def __init__(self, model: torch.nn.Module, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, max_grad_norm: Optional[float] = None, grad_div: float = 1.0):
         params = [p for p in model.parameters() if p.requires_grad]
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
@@ -34,7 +41,88 @@ class FusedAdamW(torch.optim.Optimizer):
         self._sumsq: Optional[torch.Tensor] = None
         self._ranges: Optional[List[Tuple[int, int]]] = None
         self._engine_id = None
+        # every model but SwinIR: separate parameter tensors, moments in self.state[p] (torch's own layout, so that
+        # Optimizer.state_dict / load_state_dict carry them), one pointer table per set of parameters that have a gradient
+        self._flat = isinstance(model, SwinIR)
+        self._hyper: Optional[torch.Tensor] = None          # device {lr, 1 - beta1^step, sqrt(1 - beta2^step)} for captured steps
+        self._table: Optional[ops.TensorTable] = None
+        self._table_key = None
 
+    # ---- list path (HAT, DAT, any nn.Module) -------------------------------------------------------------------------------------
+    def _stepped(self) -> List[torch.Tensor]:
+        """Parameters this step updates: trainable and with a gradient (torch skips the others too)."""
+        return [p for p in self.param_groups[0]["params"] if p.requires_grad and p.grad is not None]
+
+    def _prepare_list(self, with_state: bool) -> Optional[ops.TensorTable]:
+        ps = self._stepped()
+        if not ps:
+            return None
+        dev = ps[0].device
+        if self._sumsq is None or self._sumsq.device != dev:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("FusedAdamW: run one eager step before capturing (state is allocated outside the graph)")
+            self._sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
+            self._hyper = torch.zeros(3, dtype=torch.float32, device=dev)
+        key = tuple(p.data_ptr() for p in ps)
+        if self._table is None or self._table_key != key:
+            self._table, self._table_key = ops.TensorTable(len(ps)), key
+            self._table.set("params", ps, first=True)
+        tab = self._table
+        tab.set("grads", [p.grad for p in ps])          # every step: the backward hands out freshly allocated tensors
+        if with_state and "exp_avg" not in tab.ptrs:
+            for p in ps:
+                st = self.state[p]
+                if "exp_avg" not in st:
+                    if torch.cuda.is_current_stream_capturing():
+                        raise RuntimeError("FusedAdamW: run one eager step before capturing (state is allocated outside the graph)")
+                    st["exp_avg"] = torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
+            tab.set("exp_avg", [self.state[p]["exp_avg"] for p in ps])
+            tab.set("exp_avg_sq", [self.state[p]["exp_avg_sq"] for p in ps])
+        tab.keep = ps
+        return tab
+
+    def _write_hyper(self) -> None:
+        grp = self.param_groups[0]
+        b1, b2 = grp["betas"]
+        self._hyper.copy_(torch.tensor(ops.adamw_hyper(grp["lr"], b1, b2, self._step), dtype=torch.float32))
+
+    def begin_replay(self) -> None:
+        """Before every replay of a captured step: advance the step count and hand lr / bias corrections to the captured kernels."""
+        if self._flat or self._hyper is None:
+            raise RuntimeError("FusedAdamW.begin_replay(): no captured list-path step")
+        self._step += 1
+        self._write_hyper()
+
+    def end_replay(self) -> None:
+        """After a replay: the weights (and the model's buffers) changed behind the host's back; bump the version counters that the
+        bf16 pack caches of HAT / DAT are keyed on."""
+        torch._C._increment_version(list(self.param_groups[0]["params"]) + list(self.model.buffers()))
+
+    def _step_list(self, nonfinite: Optional[torch.Tensor]):
+        tab = self._prepare_list(with_state=True)
+        if tab is None:
+            return None
+        grp = self.param_groups[0]
+        dev = tab.keep[0].device
+        if nonfinite is not None and (nonfinite.dtype != torch.int32 or nonfinite.device != dev):
+            raise ValueError("nonfinite must be an int32 tensor on the model's device")
+        clip = self.max_grad_norm if self.max_grad_norm and self.max_grad_norm > 0 else 0.0
+        b1, b2 = grp["betas"]
+        capturing = torch.cuda.is_current_stream_capturing()
+        with torch.cuda.device(dev):
+            self._sumsq.zero_()
+            ops.multi_grad_sumsq(tab, self._sumsq)
+            if not capturing:
+                self._step += 1          # a captured step advances in begin_replay()
+            ops.multi_adamw_clip_step(tab, self._sumsq, clip, self.grad_div, grp["lr"], b1, b2, grp["eps"], grp["weight_decay"],
+                                      max(self._step, 1), hyper=self._hyper if capturing else None, nonfinite=nonfinite)
+        # the kernels wrote through raw pointers: tell the pack caches (hat_arch.HAT._pack, dat_arch.DAT._pack, hat_train /
+        # dat_train pack_*) that the parameters changed.  Under capture this makes the NEXT forward outside the graph re-pack.
+        torch._C._increment_version(tab.keep)
+        return None
+
+    # ---- flat path (SwinIR) ----------------------------------------------------------------------------------------------------------
     def _prepare(self):
         eng = self.model._engine
         if eng is None:
@@ -62,6 +150,14 @@ class FusedAdamW(torch.optim.Optimizer):
     @torch.no_grad()
     def grad_norm(self) -> torch.Tensor:
         """Global L2 norm of the (averaged) gradients as a device tensor (no host sync)."""
+        if not self._flat:
+            tab = self._prepare_list(with_state=False)
+            if tab is None:
+                raise RuntimeError("FusedAdamW.grad_norm(): no parameter has a gradient")
+            with torch.cuda.device(tab.keep[0].device):
+                self._sumsq.zero_()
+                ops.multi_grad_sumsq(tab, self._sumsq)
+                return self._sumsq.sqrt() / self.grad_div
         eng = self._prepare()
         g = eng.ensure_grad()
         with torch.cuda.device(eng.device):
@@ -77,6 +173,8 @@ class FusedAdamW(torch.optim.Optimizer):
         bad batch cannot destroy the model before the caller's finite check raises (finetune_swinir.py:159-165)."""
         if closure is not None:
             raise RuntimeError("FusedAdamW does not support closures")
+        if not self._flat:
+            return self._step_list(nonfinite)
         eng = self._prepare()
         g = eng.ensure_grad()
         grp = self.param_groups[0]
@@ -102,7 +200,9 @@ class FusedAdamW(torch.optim.Optimizer):
         return None
 
     def zero_grad(self, set_to_none: bool = True):
-        eng = self.model._engine
+        if not self._flat and not set_to_none:
+            return super().zero_grad(set_to_none=False)
+        eng = getattr(self.model, "_engine", None)
         if set_to_none or eng is None or eng.flat_grad is None:
             for p in self.model.parameters():
                 p.grad = None
@@ -110,7 +210,7 @@ class FusedAdamW(torch.optim.Optimizer):
             eng.flat_grad.zero_()
 
     def state_dict(self):
-        sd = super().state_dict()
+        sd = super().state_dict()          # list path: the per-parameter moments are in sd["state"], as torch.optim.AdamW keeps them
         sd["fused"] = {"step": self._step, "exp_avg": self._m, "exp_avg_sq": self._v}
         return sd
 
@@ -122,3 +222,4 @@ class FusedAdamW(torch.optim.Optimizer):
             self._step = int(fused["step"])
             self._m, self._v = fused["exp_avg"], fused["exp_avg_sq"]
             self._engine_id = None
+        self._table = None          # list path: the moments were replaced, rebuild the pointer table

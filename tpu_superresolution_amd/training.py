@@ -73,12 +73,23 @@ class GraphedTrainStep:
     (world size 1: collectives stay outside graphs here), nothing in the step that reads a device value on the host.  The first call
     runs ``warmup`` eager steps (kernel attributes, caches and workspaces get set up outside the capture), then captures.  DropPath
     factors are drawn OUTSIDE the graph, before every replay, into a static buffer the captured forward reads (``model.draw_drop_path``
-    / ``model._drop_override``): a fresh draw per step does not depend on how the graph-captured generator advances."""
+    / ``model._drop_override``): a fresh draw per step does not depend on how the graph-captured generator advances.
+
+    With an ``optim.FusedAdamW`` the step is the project's own: no ``clip_grad_norm_`` (the optimizer's ``max_grad_norm`` clips on the
+    device; the ``max_grad_norm`` argument here is not used) and ``opt.step(nonfinite=bad)``, so a non-finite prediction inside a replay
+    leaves weights and moments untouched.  The captured step kernel reads the learning rate and the bias corrections from device memory:
+    ``opt.begin_replay()`` advances the step count and rewrites them from ``param_groups[0]['lr']`` before every replay, so an LR
+    scheduler stepped between calls takes effect.
+
+        step = GraphedTrainStep(model, FusedAdamW(model, lr=2e-5, max_grad_norm=1.0))"""
 
     def __init__(self, model, optimizer, max_grad_norm: float = 1.0, warmup: int = 2):
         if getattr(model, "grad_sync", None) is not None:
             raise ValueError("GraphedTrainStep: detach the gradient synchronizer (graph capture is for single-process steps)")
         self.model, self.opt, self.max_grad_norm, self.warmup = model, optimizer, float(max_grad_norm), int(warmup)
+        self.fused = hasattr(optimizer, "begin_replay")          # optim.FusedAdamW
+        if self.fused and getattr(optimizer, "_flat", False):
+            raise ValueError("GraphedTrainStep is for host-orchestrated models (HAT / DAT); SwinIR's step is one C call per pass already")
         self.graph = None
         self.x = self.t = self.loss = self.bad = self.drop = None
 
@@ -86,8 +97,11 @@ class GraphedTrainStep:
         self.opt.zero_grad(set_to_none=True)
         loss, bad = l1_loss_checked(self.model(x), t)
         loss.backward()
-        torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.max_grad_norm)
-        self.opt.step()
+        if self.fused:
+            self.opt.step(nonfinite=bad)          # clip + AdamW, gated on the device by the non-finite counter
+        else:
+            torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.max_grad_norm)
+            self.opt.step()
         return loss.detach(), bad
 
     def __call__(self, lr_img: torch.Tensor, hr_img: torch.Tensor):
@@ -114,7 +128,11 @@ class GraphedTrainStep:
         self.t.copy_(hr_img)
         if self.drop is not None:
             self.drop.copy_(draw(lr_img.shape[0], lr_img.device))
+        if self.fused:
+            self.opt.begin_replay()
         self.graph.replay()
+        if self.fused:
+            self.opt.end_replay()
         return self.loss, self.bad
 
     def close(self) -> None:
