@@ -276,6 +276,12 @@ typedef struct {
   const float* rowscale; int rows_per_sample;   /* SRK_EP_RES: outf = res + rowscale[m / rows_per_sample] * (v + bias)  (DropPath factor per sample) or null */
   const float* ln_x; const float* ln_mean; const float* ln_rstd; const float* ln_gamma; float* ln_dgamma; float* ln_dbeta; int ln_C;   /* SRK_EP_LNBWD */
 } srk_gemm_args;
+/* Checked on the host before any launch: SRK_E_NULL when an output / operand the epilogue needs is null (outb: BF16 / LRELU / RES_BF16 /
+ * PS / DGELU / DLRELU; outb2: GELU; outf: RES / IMG / PS_IMG / F32_BF16 / LNBWD; res: RES / RES_BF16; aux: DGELU / DLRELU); SRK_E_SHAPE
+ * for an image head without N == 16, 1 <= Cimg <= 4, Cimg * r * r <= 16 (PS_IMG, r >= 1), 0 < Hc <= H * r, 0 < Wc <= Wd * r (r = 1
+ * for IMG); for PS without r >= 1, Cs % 64 == 0, N == r * r * Cs; for a fused LayerNorm without 0 < xn_C <= N and ldo == N;
+ * SRK_E_UNSUPPORTED for a (loader, epilogue) pair that is not built (LD_ROWS: BF16 GELU RES RES_BF16 LRELU DGELU DLRELU LNBWD;
+ * LD_CONV3: all but LNBWD; LD_CONV3_PS: BF16 DLRELU). */
 int srk_gemm_ex(const srk_gemm_args* args, srk_stream_t stream);
 /* Mlp.forward + residual (+ next LayerNorm) in one kernel (csrc/gemm_stream.hip): out = res + gelu(xn W1^T + b1) W2^T + b2.
  * xn bf16 [M][192], W1 bf16 [384][192], W2 bf16 [192][384], res / out fp32 [M][192]; C 180 / hidden 360 zero-padded. */

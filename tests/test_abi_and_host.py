@@ -94,6 +94,76 @@ def test_index_entry_points_validate_arguments_without_a_gpu(lib):
     assert h.srk_window_partition(C.c_void_p(16), C.c_void_p(16), 1, 13, 8, 3, 8, 4, None) == -1
 
 
+def test_gemm_ex_refuses_bad_argument_blocks_without_a_gpu(lib):
+    """srk_gemm_ex returns on the host, before any launch, for a missing output, an image head / PixelShuffle / fused-LayerNorm
+    geometry it cannot honour, and a loader the epilogue does not go with.  The addresses are dummies that are never dereferenced:
+    every block here is one the entry point rejects."""
+    h = lib.lib()
+    P = 4096                                                     # a non-null address; never read or written
+
+    def block(loader, ep, **kw):
+        a = lib.GemmArgs()
+        a.loader, a.epilogue = loader, ep
+        a.A, a.W, a.lda = P, P, 64
+        a.M, a.N, a.K, a.ldo = 64, 64, 64, 64
+        a.bias, a.outf, a.outb, a.outb2, a.res, a.aux = P, P, P, P, P, P
+        if loader != lib.LD_ROWS:
+            a.B, a.H, a.Wd, a.CinP, a.K = 2, 4, 8, 64, 576
+        for k, v in kw.items():
+            setattr(a, k, v)
+        return a
+
+    def refused(a, code):
+        rc = h.srk_gemm_ex(C.byref(a), None)
+        assert rc == code, (rc, code, h.srk_last_error())
+        assert h.srk_last_error(), "no message"
+
+    E_SHAPE, E_NULL, E_UNSUPPORTED = -1, -2, -3
+    R_, C3 = lib.LD_ROWS, lib.LD_CONV3
+    # a null where the epilogue stores
+    for ep, field in ((lib.EP_BF16, "outb"), (lib.EP_LRELU, "outb"), (lib.EP_GELU, "outb2"), (lib.EP_RES, "outf"), (lib.EP_RES, "res"),
+                      (lib.EP_RES_BF16, "outb"), (lib.EP_RES_BF16, "res"), (lib.EP_DGELU, "outb"), (lib.EP_DLRELU, "aux")):
+        refused(block(R_, ep, **{field: None}), E_NULL)
+    refused(block(C3, lib.EP_PS, N=256, r=2, Cs=64, outb=None), E_NULL)
+    refused(block(C3, lib.EP_F32_BF16, outf=None), E_NULL)
+    img = dict(N=16, Cimg=3, Hc=4, Wc=8, inv_range=1.0)
+    refused(block(C3, lib.EP_IMG, **{**img, "outf": None}), E_NULL)
+    refused(block(C3, lib.EP_PS_IMG, **{**img, "r": 2, "outf": None}), E_NULL)
+    # image heads
+    refused(block(C3, lib.EP_IMG, **{**img, "N": 64}), E_SHAPE)
+    refused(block(C3, lib.EP_IMG, **{**img, "Cimg": 0}), E_SHAPE)
+    refused(block(C3, lib.EP_IMG, **{**img, "Cimg": 5}), E_SHAPE)            # mean[4] is indexed by channel
+    refused(block(C3, lib.EP_IMG, **{**img, "Hc": 0}), E_SHAPE)
+    refused(block(C3, lib.EP_IMG, **{**img, "Hc": 5}), E_SHAPE)              # H = 4
+    refused(block(C3, lib.EP_IMG, **{**img, "Wc": 9}), E_SHAPE)              # Wd = 8
+    refused(block(C3, lib.EP_PS_IMG, **{**img, "r": 0}), E_SHAPE)
+    refused(block(C3, lib.EP_PS_IMG, **{**img, "r": 3}), E_SHAPE)            # 3 * 9 > 16 columns: channels would be dropped silently
+    assert b"Cimg * r * r <= 16" in h.srk_last_error()
+    refused(block(C3, lib.EP_PS_IMG, **{**img, "r": 2, "Hc": 9, "Wc": 16}), E_SHAPE)
+    refused(block(C3, lib.EP_PS_IMG, **{**img, "r": 2, "Hc": 8, "Wc": 17}), E_SHAPE)
+    # conv + PixelShuffle
+    refused(block(C3, lib.EP_PS, N=256, r=0, Cs=64), E_SHAPE)
+    refused(block(C3, lib.EP_PS, N=128, r=2, Cs=32), E_SHAPE)
+    refused(block(C3, lib.EP_PS, N=192, r=2, Cs=64), E_SHAPE)
+    # fused LayerNorm of EP_RES
+    ln = dict(xn_out=P, xn_mean=P, xn_rstd=P, xn_gamma=P, xn_beta=P)
+    refused(block(R_, lib.EP_RES, **ln, xn_C=0), E_SHAPE)
+    refused(block(R_, lib.EP_RES, **ln, xn_C=65), E_SHAPE)
+    refused(block(R_, lib.EP_RES, **ln, xn_C=60, ldo=128), E_SHAPE)
+    # a row scale without its epilogue / without rows_per_sample
+    refused(block(R_, lib.EP_BF16, rowscale=P, rows_per_sample=64), E_SHAPE)
+    refused(block(R_, lib.EP_RES, rowscale=P, rows_per_sample=0), E_SHAPE)
+    # loaders and epilogues outside the exposed surface
+    lnb = dict(ln_x=P, ln_mean=P, ln_rstd=P, ln_gamma=P, ln_dgamma=P, ln_dbeta=P, ln_C=60, bias=None)
+    refused(block(C3, lib.EP_LNBWD, **lnb), E_UNSUPPORTED)
+    refused(block(R_, lib.EP_LNBWD, **{**lnb, "ln_dbeta": None}), E_NULL)
+    refused(block(R_, lib.EP_LNBWD, **{**lnb, "ln_C": 65}), E_SHAPE)
+    refused(block(3, lib.EP_BF16), E_UNSUPPORTED)
+    refused(block(R_, 100), E_UNSUPPORTED)
+    refused(block(R_, 1), E_UNSUPPORTED)
+    assert h.srk_gemm_ex(None, None) == E_NULL
+
+
 def test_options_are_process_wide_with_per_plan_values():
     """SURVEY 8b 're-entrant': srk_set_option writes ONE process-wide value per option (every thread sees it -- the autograd engine runs
     the backward on its own thread); a plan carries its own values (srk_swinir_plan_set_option), applied in a thread-private copy of the

@@ -230,10 +230,38 @@ int srk_gemm_ex(const srk_gemm_args* a, srk_stream_t stream) {
   p.rowscale = a->rowscale; p.rows_per_sample = a->rows_per_sample;
   SRK_REQUIRE(a->rowscale == nullptr || ((a->epilogue == SRK_EP_RES || a->epilogue == SRK_EP_LNBWD) && a->rows_per_sample > 0), SRK_E_SHAPE,
               "gemm_ex: rowscale goes with SRK_EP_RES / SRK_EP_LNBWD and rows_per_sample > 0");
+  SRK_REQUIRE(a->xn_out == nullptr || (a->xn_C > 0 && a->xn_C <= a->N && a->ldo == a->N), SRK_E_SHAPE,
+              "gemm_ex: fused LayerNorm needs 0 < xn_C <= N and ldo == N (xn_C=%d N=%d ldo=%d)", a->xn_C, a->N, a->ldo);
   p.flops = 2.0 * a->M * (double)a->N * a->K;
   switch (a->epilogue) {
-    case SRK_EP_BF16: case SRK_EP_GELU: case SRK_EP_RES: case SRK_EP_LRELU: case SRK_EP_PS: case SRK_EP_IMG: case SRK_EP_PS_IMG: case SRK_EP_RES_BF16:
+    case SRK_EP_BF16: case SRK_EP_LRELU:
+      SRK_REQUIRE(a->outb != nullptr, SRK_E_NULL, "gemm_ex: epilogue %d needs outb", a->epilogue);
       break;
+    case SRK_EP_GELU:
+      SRK_REQUIRE(a->outb2 != nullptr, SRK_E_NULL, "gemm_ex: SRK_EP_GELU needs outb2");
+      break;
+    case SRK_EP_RES:
+      SRK_REQUIRE(a->outf != nullptr && a->res != nullptr, SRK_E_NULL, "gemm_ex: SRK_EP_RES needs outf and res");
+      break;
+    case SRK_EP_RES_BF16:
+      SRK_REQUIRE(a->outb != nullptr && a->res != nullptr, SRK_E_NULL, "gemm_ex: SRK_EP_RES_BF16 needs outb and res");
+      break;
+    case SRK_EP_PS:
+      SRK_REQUIRE(a->outb != nullptr, SRK_E_NULL, "gemm_ex: SRK_EP_PS needs outb");
+      SRK_REQUIRE(a->r >= 1 && a->Cs > 0 && a->Cs % 64 == 0 && a->N == a->r * a->r * a->Cs, SRK_E_SHAPE,
+                  "gemm_ex: SRK_EP_PS needs r >= 1, Cs %% 64 == 0 and N == r * r * Cs (r=%d Cs=%d N=%d)", a->r, a->Cs, a->N);
+      break;
+    case SRK_EP_IMG: case SRK_EP_PS_IMG: {
+      SRK_REQUIRE(a->outf != nullptr, SRK_E_NULL, "gemm_ex: the image heads need outf");
+      SRK_REQUIRE(a->N == 16 && a->Cimg >= 1 && a->Cimg <= 4, SRK_E_SHAPE, "gemm_ex: the image heads need N == 16 and 1 <= Cimg <= 4 (N=%d Cimg=%d)",
+                  a->N, a->Cimg);
+      const int r = a->epilogue == SRK_EP_PS_IMG ? a->r : 1;
+      SRK_REQUIRE(r >= 1 && a->Cimg * r * r <= 16, SRK_E_SHAPE, "gemm_ex: SRK_EP_PS_IMG needs r >= 1 and Cimg * r * r <= 16 (Cimg=%d r=%d)",
+                  a->Cimg, a->r);
+      SRK_REQUIRE(a->Hc > 0 && a->Wc > 0 && a->Hc <= (long long)a->H * r && a->Wc <= (long long)a->Wd * r, SRK_E_SHAPE,
+                  "gemm_ex: image crop %d x %d outside 1 .. %d x %d (H x Wd times r)", a->Hc, a->Wc, a->H, a->Wd);
+      break;
+    }
     case SRK_EP_DGELU: case SRK_EP_DLRELU:
       SRK_REQUIRE(a->aux != nullptr && a->outb != nullptr, SRK_E_NULL, "gemm_ex: the activation-gradient epilogues need aux and outb");
       break;
@@ -241,8 +269,9 @@ int srk_gemm_ex(const srk_gemm_args* a, srk_stream_t stream) {
       SRK_REQUIRE(a->outf != nullptr, SRK_E_NULL, "gemm_ex: SRK_EP_F32_BF16 needs outf");
       break;
     case SRK_EP_LNBWD:
-      SRK_REQUIRE(a->loader == SRK_LD_ROWS && a->outf && a->ln_x && a->ln_mean && a->ln_rstd && a->ln_gamma && a->ln_dgamma && a->ln_dbeta, SRK_E_NULL,
-                  "gemm_ex: SRK_EP_LNBWD needs LD_ROWS, outf and the LayerNorm operands");
+      SRK_REQUIRE(a->loader == SRK_LD_ROWS, SRK_E_UNSUPPORTED, "gemm_ex: SRK_EP_LNBWD goes with SRK_LD_ROWS only (loader %d)", a->loader);
+      SRK_REQUIRE(a->outf && a->ln_x && a->ln_mean && a->ln_rstd && a->ln_gamma && a->ln_dgamma && a->ln_dbeta, SRK_E_NULL,
+                  "gemm_ex: SRK_EP_LNBWD needs outf and the LayerNorm operands");
       SRK_REQUIRE((a->N == 64 || a->N == 128 || a->N == 192) && a->ln_C > 0 && a->ln_C <= a->N && a->ldo == a->N && a->bias == nullptr, SRK_E_SHAPE,
                   "gemm_ex: SRK_EP_LNBWD needs N = 64 / 128 / 192 = ldo (one tile holds a whole row), no bias");
       p.ln_x = a->ln_x; p.ln_mean = a->ln_mean; p.ln_rstd = a->ln_rstd; p.ln_gamma = a->ln_gamma; p.ln_dgamma = a->ln_dgamma;
