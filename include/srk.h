@@ -220,6 +220,14 @@ int srk_grad_sumsq(const float* grads, int64_t n, float* sumsq, srk_stream_t str
 int srk_adamw_clip_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
                         const float* sumsq, float max_norm, float grad_div, float lr, float beta1, float beta2, float eps,
                         float weight_decay, int step, const int32_t* nonfinite, srk_stream_t stream);
+/* srk_adamw_clip_step that also keeps an exponential moving average of the weights: after the update of element i,
+ * ema[i] = ema_decay * ema[i] + (1 - ema_decay) * params[i] with the NEW params[i] (still in a register: one more read and one more
+ * write of an fp32 array).  params / exp_avg / exp_avg_sq come out bit for bit as from srk_adamw_clip_step.  A gated call (nonfinite,
+ * NaN / Inf norm) leaves ema untouched together with the weights and moments.  ema_decay in [0, 1) (else SRK_E_SHAPE; NaN too); it is
+ * read as the decimal it was written as, like the betas.  ema_decay = 0 copies the weights.  Null ema: SRK_E_NULL. */
+int srk_adamw_clip_ema_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                            const float* sumsq, float max_norm, float grad_div, float lr, float beta1, float beta2, float eps,
+                            float weight_decay, int step, float ema_decay, const int32_t* nonfinite, srk_stream_t stream);
 /* The same two over a LIST of separate fp32 tensors (the parameters of a host-orchestrated model: HAT, DAT), in the multi-tensor-apply
  * form: grads / params / exp_avg / exp_avg_sq are HOST arrays of n_tensors DEVICE pointers, numel the element counts (>= 0; a tensor
  * of 0 elements is skipped).  The table of a chunk of tensors travels by value in the kernel arguments: no upload, no allocation, no
@@ -236,6 +244,15 @@ int srk_multi_adamw_clip_step(float* const* params, const float* const* grads, f
                               const int64_t* numel, int n_tensors, const float* sumsq, float max_norm, float grad_div, float lr,
                               float beta1, float beta2, float eps, float weight_decay, int step, const float* hyper,
                               const int32_t* nonfinite, srk_stream_t stream);
+/* srk_multi_adamw_clip_step with the EMA of srk_adamw_clip_ema_step: ema is a fifth HOST array of n_tensors DEVICE pointers.  The
+ * chunk is 72 tensors (a fifth pointer per tensor in the by-value table), so launches per call = ceil(n_tensors / 72); the call
+ * without EMA keeps its 80.  ema_decay is a launch-time constant (frozen into a captured launch); hyper as above.  Checks of
+ * srk_multi_adamw_clip_step, plus SRK_E_NULL for a null ema list or a null ema[i] with a non-zero count and SRK_E_SHAPE for an
+ * ema_decay outside [0, 1) or NaN. */
+int srk_multi_adamw_clip_ema_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                  float* const* ema, const int64_t* numel, int n_tensors, const float* sumsq, float max_norm,
+                                  float grad_div, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                                  float ema_decay, const float* hyper, const int32_t* nonfinite, srk_stream_t stream);
 /* HOST: out3 = {lr, 1 - beta1^step, sqrt(1 - beta2^step)} exactly as the step kernels' launchers compute them. */
 int srk_adamw_hyper(float lr, float beta1, float beta2, int step, float* out3);
 

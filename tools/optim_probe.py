@@ -2,12 +2,17 @@
 inside the whole graphed step, for
   (a) torch:  clip_grad_norm_ + torch.optim.AdamW(capturable=True)      -- what bench.py builds for cfg4 / cfg5
   (b) fused:  optim.FusedAdamW (multi-tensor kernels, csrc/optim_multi.hip)
+  (c) fused_ema:  (b) with ema_decay = 0.999: the EMA of the weights advanced inside the step kernel
+  (d) fused_then_foreach:  (b) followed by torch._foreach_mul_ + torch._foreach_add_(.., alpha=) on clones of the weights: the unfused
+      way to the same average
 eager and replayed from a hipGraph.  One process; every number is a median over `--repeats` windows of `--reps` steps taken after a
-warm-up, (a) and (b) alternating window by window; min and max of the windows are kept beside it as the run-to-run spread.  Device time
+warm-up, the variants alternating window by window; min and max of the windows are kept beside it as the run-to-run spread.  Device time
 = hip events around a window; host time = wall clock around the same window including the final synchronise.  Launch counts come from
 torch.profiler (kernel + memcpy/memset records of one step) and are null when the profiler is unavailable.
 
-    python tools/optim_probe.py --out profiles/r05_optim_probe.json [--archs hat dat] [--no-profile]
+    python tools/optim_probe.py --out profiles/r06_optim_ema_probe.json [--archs hat dat] [--no-profile]
+
+(profiles/r05_optim_probe.json is the record of (a) and (b) from before the EMA variants existed.)
 """
 import argparse
 import json
@@ -24,6 +29,9 @@ sys.path.insert(0, ROOT)
 from tpu_superresolution_amd.finetune_swinir import build_sr_model  # noqa: E402
 from tpu_superresolution_amd.optim import FusedAdamW  # noqa: E402
 from tpu_superresolution_amd.training import GraphedTrainStep, l1_loss_checked  # noqa: E402
+
+
+EMA_DECAY = 0.999
 
 
 def batch(bs, device, seed=1000):
@@ -116,30 +124,50 @@ def probe(arch, args, out, flush):
 
     def fused_part():
         f_opt.step()
-    res["fused_launches_expected"] = 1 + math.ceil(len(params) / 160) + math.ceil(len(params) / 80)
-    res["eager"] = compare({"torch": torch_part, "fused": fused_part}, args.reps, args.repeats)
-    flush()
-    g_t, g_f = capture(torch_part), capture(fused_part)
+    e_opt = FusedAdamW(model, lr=2e-5, weight_decay=0.0, max_grad_norm=1.0, ema_decay=EMA_DECAY)
+    u_opt = FusedAdamW(model, lr=2e-5, weight_decay=0.0, max_grad_norm=1.0)
+    weights = [p.detach() for p in params]
+    avg = [w.clone() for w in weights]
 
-    def fused_replay():
-        f_opt.begin_replay()
-        g_f.replay()
-        f_opt.end_replay()
-    res["graphed"] = compare({"torch": g_t.replay, "fused": fused_replay}, args.reps, args.repeats)
+    def fused_ema_part():
+        e_opt.step()
+
+    def fused_then_foreach_part():
+        u_opt.step()
+        torch._foreach_mul_(avg, EMA_DECAY)
+        torch._foreach_add_(avg, weights, alpha=1.0 - EMA_DECAY)
+    res["fused_launches_expected"] = 1 + math.ceil(len(params) / 160) + math.ceil(len(params) / 80)
+    res["fused_ema_launches_expected"] = 1 + math.ceil(len(params) / 160) + math.ceil(len(params) / 72)
+    # the average costs one more read and one more write of an fp32 array
+    res["ema_extra_bytes_per_step"] = 2 * 4 * res["elements"]
+    parts = {"torch": torch_part, "fused": fused_part, "fused_ema": fused_ema_part, "fused_then_foreach": fused_then_foreach_part}
+    res["eager"] = compare(parts, args.reps, args.repeats)
+    flush()
+    graphs = {k: capture(fn) for k, fn in parts.items()}
+
+    def replay_of(opt, g):
+        def run():
+            opt.begin_replay()
+            g.replay()
+            opt.end_replay()
+        return run
+    res["graphed"] = compare({"torch": graphs["torch"].replay, "fused": replay_of(f_opt, graphs["fused"]),
+                              "fused_ema": replay_of(e_opt, graphs["fused_ema"]),
+                              "fused_then_foreach": replay_of(u_opt, graphs["fused_then_foreach"])}, args.reps, args.repeats)
     flush()
     if not args.no_profile:
-        res["launches"] = {"torch": count_launches(torch_part), "fused": count_launches(fused_part)}
+        res["launches"] = {k: count_launches(fn) for k, fn in parts.items()}
         flush()
-    del g_t, g_f, t_opt, f_opt, model, params
+    del graphs, t_opt, f_opt, e_opt, u_opt, avg, weights, model, params
     torch.cuda.empty_cache()
 
     # ---- the whole graphed train step with either optimizer ----------------------------------------------------------------------------
     steps = {}
-    for name in ("torch", "fused"):
+    for name in ("torch", "fused", "fused_ema"):
         torch.manual_seed(42)
         m = build_sr_model(arch, 4, 0.1).to(dev).train()
         opt = (torch.optim.AdamW(m.parameters(), lr=2e-5, weight_decay=0.0, capturable=True) if name == "torch"
-               else FusedAdamW(m, lr=2e-5, weight_decay=0.0, max_grad_norm=1.0))
+               else FusedAdamW(m, lr=2e-5, weight_decay=0.0, max_grad_norm=1.0, ema_decay=EMA_DECAY if name == "fused_ema" else None))
         gs = GraphedTrainStep(m, opt, max_grad_norm=1.0, warmup=2)
         gs(lr_img, hr_img)
         steps[name] = (lambda gs=gs: gs(lr_img, hr_img))
@@ -149,7 +177,7 @@ def probe(arch, args, out, flush):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r05_optim_probe.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r06_optim_ema_probe.json"))
     ap.add_argument("--archs", nargs="+", default=["hat", "dat"], choices=["hat", "dat"])
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--reps", type=int, default=50)
@@ -160,6 +188,7 @@ def main():
         raise SystemExit("the probe measures on the GPU (no CPU fallback)")
     torch.cuda.set_device(0)
     out = {"device": torch.cuda.get_device_name(0), "batch": args.batch, "lr_patch": 64, "scale": 4, "reps": args.reps, "repeats": args.repeats,
+           "ema_decay": EMA_DECAY,
            "note": "ms per step: median / min / max over `repeats` alternating windows of `reps` steps; cfg4 = hat, cfg5 = dat"}
 
     def flush():
@@ -171,8 +200,9 @@ def main():
         probe(arch, args, out, flush)
         r = out[arch]
         for mode in ("eager", "graphed", "graphed_train_step"):
-            print(f"[{arch}] {mode:18s} torch {r[mode]['torch']['device_ms']['median']:8.3f} ms  fused {r[mode]['fused']['device_ms']['median']:8.3f} ms "
-                  f"(device, median; host {r[mode]['torch']['host_ms']['median']:.3f} / {r[mode]['fused']['host_ms']['median']:.3f})", flush=True)
+            print(f"[{arch}] {mode:18s} " + "  ".join(f"{k} {v['device_ms']['median']:.3f} [{v['device_ms']['min']:.3f}-{v['device_ms']['max']:.3f}]"
+                                                      f" (host {v['host_ms']['median']:.3f})" for k, v in r[mode].items()) + "  ms, device median [min-max]",
+                  flush=True)
         print(f"[{arch}] launches {r.get('launches')}", flush=True)
 
 

@@ -106,8 +106,10 @@ _SIGNATURES = {
     "srk_ssim": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     "srk_grad_sumsq": (_i, [_vp, _i64, _vp, _vp]),
     "srk_adamw_clip_step": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _f, _f, _f, _i, _vp, _vp]),
+    "srk_adamw_clip_ema_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _f, _f, _f, _i, _f, _vp, _vp]),
     "srk_multi_grad_sumsq": (_i, [_vp, _vp, _i, _vp, _vp]),
     "srk_multi_adamw_clip_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _f, _f, _f, _f, _f, _f, _f, _i, _vp, _vp, _vp]),
+    "srk_multi_adamw_clip_ema_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _f, _f, _f, _f, _f, _f, _f, _i, _f, _vp, _vp, _vp]),
     "srk_adamw_hyper": (_i, [_f, _f, _f, _i, C.POINTER(C.c_float * 3)]),
     "srk_gemm_ex": (_i, [C.POINTER(GemmArgs), _vp]),
     "srk_mlp_fused_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),

@@ -67,3 +67,11 @@ __device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v
   m = mi;
   v = vi;
 }
+
+// Exponential moving average of the weights, folded into the step: p_new is the value adamw_elem has just produced (still in a
+// register).  omd = adamw_one_minus(decay), from the host, as for the betas: fp32(0.999) puts 1 - decay 1.3e-5 off.  decay itself
+// multiplies the old average as the fp32 it is.  Two products and one sum, each rounded on its own.
+__device__ __forceinline__ void adamw_ema_elem(float& e, float p_new, float decay, float omd) {
+#pragma clang fp contract(off)
+  e = decay * e + omd * p_new;
+}

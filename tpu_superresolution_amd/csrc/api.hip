@@ -482,6 +482,17 @@ int srk_adamw_clip_step(float* params, const float* grads, float* exp_avg, float
                           weight_decay, step, (hipStream_t)stream);
 }
 
+int srk_adamw_clip_ema_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                            const float* sumsq, float max_norm, float grad_div, float lr, float beta1, float beta2, float eps,
+                            float weight_decay, int step, float ema_decay, const int32_t* nonfinite, srk_stream_t stream) {
+  REQ_PTR(params); REQ_PTR(grads); REQ_PTR(exp_avg); REQ_PTR(exp_avg_sq); REQ_PTR(ema);
+  SRK_REQUIRE(max_norm <= 0.f || sumsq != nullptr, SRK_E_NULL, "adamw ema: clipping needs sumsq");
+  SRK_REQUIRE(step >= 1 && grad_div > 0.f, SRK_E_SHAPE, "adamw ema: step=%d grad_div=%f", step, grad_div);
+  SRK_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, SRK_E_SHAPE, "adamw ema: ema_decay=%g (0 <= decay < 1)", (double)ema_decay);
+  return srk_launch_adamw_ema(params, grads, exp_avg, exp_avg_sq, ema, n, sumsq, nonfinite, max_norm, grad_div, lr, beta1, beta2, eps,
+                              weight_decay, step, ema_decay, (hipStream_t)stream);
+}
+
 static int check_tensor_list(const char* fn, const void* const* const* lists, const char* const* names, int n_lists, const int64_t* numel,
                              int n_tensors) {
   SRK_REQUIRE(n_tensors > 0, SRK_E_SHAPE, "%s: n_tensors=%d", fn, n_tensors);
@@ -517,6 +528,22 @@ int srk_multi_adamw_clip_step(float* const* params, const float* const* grads, f
   SRK_REQUIRE(step >= 1 && grad_div > 0.f, SRK_E_SHAPE, "multi adamw: step=%d grad_div=%f", step, grad_div);
   return srk_launch_multi_adamw(params, grads, exp_avg, exp_avg_sq, (const long long*)numel, n_tensors, sumsq, nonfinite, hyper, max_norm,
                                 grad_div, lr, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
+}
+
+int srk_multi_adamw_clip_ema_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                  float* const* ema, const int64_t* numel, int n_tensors, const float* sumsq, float max_norm,
+                                  float grad_div, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                                  float ema_decay, const float* hyper, const int32_t* nonfinite, srk_stream_t stream) {
+  const void* const* lists[5] = {(const void* const*)params, (const void* const*)grads, (const void* const*)exp_avg,
+                                 (const void* const*)exp_avg_sq, (const void* const*)ema};
+  const char* names[5] = {"params", "grads", "exp_avg", "exp_avg_sq", "ema"};
+  const int rc = check_tensor_list(__func__, lists, names, 5, numel, n_tensors);
+  if (rc != SRK_OK) return rc;
+  SRK_REQUIRE(max_norm <= 0.f || sumsq != nullptr, SRK_E_NULL, "multi adamw ema: clipping needs sumsq");
+  SRK_REQUIRE(step >= 1 && grad_div > 0.f, SRK_E_SHAPE, "multi adamw ema: step=%d grad_div=%f", step, grad_div);
+  SRK_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, SRK_E_SHAPE, "multi adamw ema: ema_decay=%g (0 <= decay < 1)", (double)ema_decay);
+  return srk_launch_multi_adamw_ema(params, grads, exp_avg, exp_avg_sq, ema, (const long long*)numel, n_tensors, sumsq, nonfinite, hyper,
+                                    max_norm, grad_div, lr, beta1, beta2, eps, weight_decay, step, ema_decay, (hipStream_t)stream);
 }
 
 int srk_adamw_hyper(float lr, float beta1, float beta2, int step, float* out3) {

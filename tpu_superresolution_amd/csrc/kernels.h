@@ -70,9 +70,11 @@ int srk_launch_nchw_tokens(const float* src, float* dst, int B, int C, int CP, i
 int srk_launch_l1_loss(const float* pred, const float* target, float* dpred, float* loss_sum, unsigned* nonfinite, long long n, float grad_scale, hipStream_t stream);
 int srk_launch_sumsq(const float* g, long long n, float* out, hipStream_t stream);
 int srk_launch_adamw(float* p, const float* g, float* m, float* v, long long n, const float* sumsq, const int* nonfinite, float max_norm, float grad_div, float lr, float beta1, float beta2, float eps, float wd, int step, hipStream_t stream);
+int srk_launch_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, long long n, const float* sumsq, const int* nonfinite, float max_norm, float grad_div, float lr, float beta1, float beta2, float eps, float wd, int step, float ema_decay, hipStream_t stream);
 // optim_multi.hip: the same two over lists of separate tensors, ceil(n_tensors / chunk) launches, tables by value in the kernel arguments
 int srk_launch_multi_sumsq(const float* const* grads, const long long* numel, int n_tensors, float* out, hipStream_t stream);
 int srk_launch_multi_adamw(float* const* p, const float* const* g, float* const* m, float* const* v, const long long* numel, int n_tensors, const float* sumsq, const int* nonfinite, const float* hyper, float max_norm, float grad_div, float lr, float beta1, float beta2, float eps, float wd, int step, hipStream_t stream);
+int srk_launch_multi_adamw_ema(float* const* p, const float* const* g, float* const* m, float* const* v, float* const* e, const long long* numel, int n_tensors, const float* sumsq, const int* nonfinite, const float* hyper, float max_norm, float grad_div, float lr, float beta1, float beta2, float eps, float wd, int step, float ema_decay, hipStream_t stream);
 int srk_launch_probe_trread(const bf16_t* in, bf16_t* out, hipStream_t stream);
 int srk_launch_win256_attn_fwd(const bf16_t* qkv, int ldq, int CA, const float* bias, int table_rows, bf16_t* out, int ldo, int B, int H, int W, int wh, int ww, int sy, int sx, int nH, float scale, int overlap, hipStream_t stream);
 int srk_launch_win_attn_fwd_padded(const bf16_t* qkv, int ldq, int CA, const float* bias, int table_rows, bf16_t* out, int ldo, int B, int H, int W, int Hp, int Wp, int wh, int ww, int sy, int sx, int nH, float scale, int overlap, hipStream_t stream);

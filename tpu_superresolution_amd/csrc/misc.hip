@@ -877,20 +877,48 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
   if (threadIdx.x == 0) atomicAdd(out, red[0] + red[1] + red[2] + red[3]);
 }
 
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                    float* __restrict__ m, float* __restrict__ v, long long n,
-                                                    const float* __restrict__ sumsq, float max_norm, float grad_div,
-                                                    float lr, float beta1, float beta2, float omb1, float omb2, float eps, float wd,
-                                                    float bc1, float bc2_sqrt, const int* __restrict__ nonfinite) {
+// One body for the step without and with the EMA of the weights (compile-time flag): adamw_kernel keeps its arguments, its registers
+// and its instructions per element; adamw_ema_kernel adds one read and one write of the fp32 average per element.  first / stride:
+// the grid-stride walk, formed in the kernels themselves (there the compiler knows the workgroup size is uniform).
+template <bool EMA>
+__device__ __forceinline__ void adamw_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                           float* __restrict__ v, long long n, const float* __restrict__ sumsq, float max_norm,
+                                           float grad_div, float lr, float beta1, float beta2, float omb1, float omb2, float eps,
+                                           float wd, float bc1, float bc2_sqrt, const int* __restrict__ nonfinite,
+                                           float* __restrict__ ema, float decay, float omd, long long first, long long stride) {
   float coef;
   if (!adamw_gate_coef(sumsq, nonfinite, max_norm, grad_div, coef)) return;          // gate + clip coefficient: adamw.h
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+  for (long long i = first; i < n; i += stride) {
     float pi = p[i], mi = m[i], vi = v[i];
     adamw_elem(pi, g[i], mi, vi, coef, lr, beta1, beta2, omb1, omb2, eps, wd, bc1, bc2_sqrt);
     p[i] = pi;
     m[i] = mi;
     v[i] = vi;
+    if constexpr (EMA) {
+      float ei = ema[i];
+      adamw_ema_elem(ei, pi, decay, omd);
+      ema[i] = ei;
+    }
   }
+}
+
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                    float* __restrict__ m, float* __restrict__ v, long long n,
+                                                    const float* __restrict__ sumsq, float max_norm, float grad_div,
+                                                    float lr, float beta1, float beta2, float omb1, float omb2, float eps, float wd,
+                                                    float bc1, float bc2_sqrt, const int* __restrict__ nonfinite) {
+  adamw_body<false>(p, g, m, v, n, sumsq, max_norm, grad_div, lr, beta1, beta2, omb1, omb2, eps, wd, bc1, bc2_sqrt, nonfinite, nullptr,
+                    0.f, 0.f, (long long)blockIdx.x * blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x);
+}
+
+__global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, float* __restrict__ ema, long long n,
+                                                        const float* __restrict__ sumsq, float max_norm, float grad_div, float lr,
+                                                        float beta1, float beta2, float omb1, float omb2, float eps, float wd,
+                                                        float bc1, float bc2_sqrt, float decay, float omd,
+                                                        const int* __restrict__ nonfinite) {
+  adamw_body<true>(p, g, m, v, n, sumsq, max_norm, grad_div, lr, beta1, beta2, omb1, omb2, eps, wd, bc1, bc2_sqrt, nonfinite, ema, decay,
+                   omd, (long long)blockIdx.x * blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1191,6 +1219,17 @@ int srk_launch_adamw(float* p, const float* g, float* m, float* v, long long n, 
   hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, stream, p, g, m, v, n, sumsq, max_norm,
                      grad_div, lr, beta1, beta2, adamw_one_minus(beta1), adamw_one_minus(beta2), eps, wd, bc1, bc2_sqrt, nonfinite);
   return srk_check_launch("adamw");
+}
+
+int srk_launch_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, long long n, const float* sumsq, const int* nonfinite,
+                         float max_norm, float grad_div, float lr, float beta1, float beta2, float eps, float wd, int step,
+                         float ema_decay, hipStream_t stream) {
+  float bc1, bc2_sqrt;
+  adamw_bias_corrections(beta1, beta2, step, &bc1, &bc2_sqrt);
+  hipLaunchKernelGGL(adamw_ema_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, stream, p, g, m, v, ema, n, sumsq, max_norm,
+                     grad_div, lr, beta1, beta2, adamw_one_minus(beta1), adamw_one_minus(beta2), eps, wd, bc1, bc2_sqrt, ema_decay,
+                     adamw_one_minus(ema_decay), nonfinite);
+  return srk_check_launch("adamw_ema");
 }
 
 int srk_launch_probe_trread(const bf16_t* in, bf16_t* out, hipStream_t stream) {

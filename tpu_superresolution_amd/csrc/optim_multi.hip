@@ -12,6 +12,10 @@
 // 180-element bias costs one workgroup and a 180 x 180 x 9 conv weight 72.  BLOCK is a multiple of 4, so a tensor whose base pointers
 // are 16-byte aligned is walked with 16-byte loads and stores and a scalar tail of < 4 elements; a tensor with a pointer that is only
 // 4-byte aligned (a view at an odd storage offset) takes the scalar loop.  Plain C++ / vector stores only.
+//
+// EMA of the weights (srk_multi_adamw_clip_ema_step): the same body with a compile-time flag and a table of its own that carries a
+// fifth pointer per tensor (52 B instead of 44 B), so its chunk is 72 tensors; the table, the chunk and the launch count of the call
+// without EMA are what they were.
 #include <hip/hip_runtime.h>
 
 #include "adamw.h"
@@ -34,6 +38,18 @@ struct StepTable {
   int start[STEP_TENSORS + 1];            // first block of tensor t; start[nt] = grid size
 };
 
+constexpr int EMA_TENSORS = 72;           // 72 * 52 B + 4 B = 3748 B of table, + 80 B of scalars and pointers
+
+struct EmaStepTable {
+  float* p[EMA_TENSORS];
+  const float* g[EMA_TENSORS];
+  float* m[EMA_TENSORS];
+  float* v[EMA_TENSORS];
+  float* e[EMA_TENSORS];
+  long long n[EMA_TENSORS];
+  int start[EMA_TENSORS + 1];
+};
+
 struct SumsqTable {
   const float* g[SUMSQ_TENSORS];
   long long n[SUMSQ_TENSORS];
@@ -41,6 +57,7 @@ struct SumsqTable {
 };
 
 static_assert(sizeof(StepTable) + 64 <= 4096 && sizeof(SumsqTable) + 64 <= 4096, "kernel arguments must stay below 4 KB");
+static_assert(sizeof(EmaStepTable) + 96 <= 4096, "kernel arguments must stay below 4 KB");
 
 struct AdamwScalars {
   float max_norm, grad_div, lr, beta1, beta2, omb1, omb2, eps, wd, bc1, bc2_sqrt;          // omb = adamw_one_minus(beta)
@@ -85,10 +102,12 @@ __global__ __launch_bounds__(THREADS) void multi_sumsq_kernel(const SumsqTable t
 }
 
 // hyper: optional DEVICE {lr, bc1, bc2_sqrt}; when given it replaces the three host scalars, so that a captured launch follows a
-// learning-rate schedule and the step count (the host rewrites the three floats before every replay)
-__global__ __launch_bounds__(THREADS) void multi_adamw_kernel(const StepTable tab, int nt, const float* __restrict__ sumsq,
-                                                              const int* __restrict__ nonfinite, const float* __restrict__ hyper,
-                                                              AdamwScalars a) {
+// learning-rate schedule and the step count (the host rewrites the three floats before every replay).
+// One body for both tables; EMA = true also advances tab.e (adamw_ema_elem) with the weight the step has just produced.
+template <bool EMA, class Table>
+__device__ __forceinline__ void multi_adamw_body(const Table& tab, int nt, const float* __restrict__ sumsq,
+                                                 const int* __restrict__ nonfinite, const float* __restrict__ hyper, AdamwScalars a,
+                                                 float decay, float omd) {
   float coef;
   if (!adamw_gate_coef(sumsq, nonfinite, a.max_norm, a.grad_div, coef)) return;
   if (hyper != nullptr) {
@@ -102,10 +121,14 @@ __global__ __launch_bounds__(THREADS) void multi_adamw_kernel(const StepTable ta
   const float* __restrict__ g = tab.g[t] + off;
   float* __restrict__ m = tab.m[t] + off;
   float* __restrict__ v = tab.v[t] + off;
+  float* __restrict__ e = nullptr;
+  if constexpr (EMA) e = tab.e[t] + off;
   const long long rest = tab.n[t] - off;
   const int len = rest < STEP_BLOCK ? (int)rest : STEP_BLOCK;
   int done = 0;
-  if (aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v)) {
+  bool vec = aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v);
+  if constexpr (EMA) vec = vec && aligned16(e);
+  if (vec) {
     const int nvec = len >> 2;
     float4* __restrict__ p4 = reinterpret_cast<float4*>(p);
     const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
@@ -121,6 +144,15 @@ __global__ __launch_bounds__(THREADS) void multi_adamw_kernel(const StepTable ta
       p4[i] = pi;
       m4[i] = mi;
       v4[i] = vi;
+      if constexpr (EMA) {
+        float4* __restrict__ e4 = reinterpret_cast<float4*>(e);
+        float4 ei = e4[i];
+        adamw_ema_elem(ei.x, pi.x, decay, omd);
+        adamw_ema_elem(ei.y, pi.y, decay, omd);
+        adamw_ema_elem(ei.z, pi.z, decay, omd);
+        adamw_ema_elem(ei.w, pi.w, decay, omd);
+        e4[i] = ei;
+      }
     }
     done = nvec << 2;
   }
@@ -130,7 +162,24 @@ __global__ __launch_bounds__(THREADS) void multi_adamw_kernel(const StepTable ta
     p[i] = pi;
     m[i] = mi;
     v[i] = vi;
+    if constexpr (EMA) {
+      float ei = e[i];
+      adamw_ema_elem(ei, pi, decay, omd);
+      e[i] = ei;
+    }
   }
+}
+
+__global__ __launch_bounds__(THREADS) void multi_adamw_kernel(const StepTable tab, int nt, const float* __restrict__ sumsq,
+                                                              const int* __restrict__ nonfinite, const float* __restrict__ hyper,
+                                                              AdamwScalars a) {
+  multi_adamw_body<false>(tab, nt, sumsq, nonfinite, hyper, a, 0.f, 0.f);
+}
+
+__global__ __launch_bounds__(THREADS) void multi_adamw_ema_kernel(const EmaStepTable tab, int nt, const float* __restrict__ sumsq,
+                                                                  const int* __restrict__ nonfinite, const float* __restrict__ hyper,
+                                                                  AdamwScalars a, float decay, float omd) {
+  multi_adamw_body<true>(tab, nt, sumsq, nonfinite, hyper, a, decay, omd);
 }
 
 inline long long blocks_of(long long n, int block) { return (n + block - 1) / block; }
@@ -180,6 +229,37 @@ int srk_launch_multi_adamw(float* const* p, const float* const* g, float* const*
     if (blocks == 0) continue;
     hipLaunchKernelGGL(multi_adamw_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, stream, tab, nt, sumsq, nonfinite, hyper, a);
     const int rc = srk_check_launch("multi_adamw");
+    if (rc != SRK_OK) return rc;
+  }
+  return SRK_OK;
+}
+
+int srk_launch_multi_adamw_ema(float* const* p, const float* const* g, float* const* m, float* const* v, float* const* e,
+                               const long long* numel, int n_tensors, const float* sumsq, const int* nonfinite, const float* hyper,
+                               float max_norm, float grad_div, float lr, float beta1, float beta2, float eps, float wd, int step,
+                               float ema_decay, hipStream_t stream) {
+  AdamwScalars a = {max_norm, grad_div, lr, beta1, beta2, adamw_one_minus(beta1), adamw_one_minus(beta2), eps, wd, 1.f, 1.f};
+  adamw_bias_corrections(beta1, beta2, step, &a.bc1, &a.bc2_sqrt);
+  const float omd = adamw_one_minus(ema_decay);
+  for (int base = 0; base < n_tensors; base += EMA_TENSORS) {
+    const int nt = n_tensors - base < EMA_TENSORS ? n_tensors - base : EMA_TENSORS;
+    EmaStepTable tab = {};
+    long long blocks = 0;
+    for (int t = 0; t < nt; ++t) {
+      tab.p[t] = p[base + t];
+      tab.g[t] = g[base + t];
+      tab.m[t] = m[base + t];
+      tab.v[t] = v[base + t];
+      tab.e[t] = e[base + t];
+      tab.n[t] = numel[base + t];
+      tab.start[t] = (int)blocks;
+      blocks += blocks_of(tab.n[t], STEP_BLOCK);
+    }
+    tab.start[nt] = (int)blocks;
+    if (blocks == 0) continue;
+    hipLaunchKernelGGL(multi_adamw_ema_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, stream, tab, nt, sumsq, nonfinite, hyper, a,
+                       ema_decay, omd);
+    const int rc = srk_check_launch("multi_adamw_ema");
     if (rc != SRK_OK) return rc;
   }
   return SRK_OK;

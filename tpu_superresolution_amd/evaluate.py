@@ -4,7 +4,7 @@
 
 Same ten flags, same pipeline and prints: eval transform (grayscale -> bicubic LR to HR size -> [0,1], :78) ->
 ``Shuffled2DPaired(split="test")`` -> min/max peek (:96-112) -> bicubic baseline PSNR/SSIM (:115-134) -> ``MS_ResUNet()``
-+ checkpoint (``{"model": sd}`` or a raw state_dict, strict, :136-145) -> per-batch fp32 PSNR (:24-29) and SSIM,
++ checkpoint (``{"model": sd}``, ``{"params": sd}``, ``{"params_ema": sd}`` or a raw state_dict, strict, :136-145) -> per-batch fp32 PSNR (:24-29) and SSIM,
 non-finite guard (:172-178), optional bilinear resize to the HR size (:181-184), PNG dumps
 ``idx_%06d_{lr,hr,sr}.png`` under the policy --save_indices > --save_every/--save_start > first --save_n, always capped
 by --save_n (:199-225) -> summary (:229-234).
@@ -44,12 +44,24 @@ def save_tensor_as_png(x: torch.Tensor, path: Path, per_image_rescale: bool = Fa
     img.save(str(path))
 
 
-def _load_state(path: str):
+PARAM_KEYS = ("model", "params", "params_ema")          # envelopes, in the order 'auto' tries them
+
+
+def _load_state(path: str, param_key: str = "auto"):
+    """-> (state_dict, message).  'auto': the first of 'model', 'params', 'params_ema' the file has (the published HAT / DAT files hold
+    only 'params_ema', the exponential moving average of the weights), else the file is a raw state_dict.  A named key must exist."""
     ckpt = torch.load(path, map_location="cpu", weights_only=True)
-    if isinstance(ckpt, dict) and "model" in ckpt:
-        return ckpt["model"], "[ckpt] loaded state_dict from 'model' key"
-    if isinstance(ckpt, dict) and "params" in ckpt:
-        return ckpt["params"], "[ckpt] loaded state_dict from 'params' key"
+    if param_key != "auto":
+        if param_key not in PARAM_KEYS:
+            raise ValueError(f"param_key must be 'auto' or one of {PARAM_KEYS} (got {param_key!r})")
+        if not isinstance(ckpt, dict) or param_key not in ckpt:
+            have = [str(k) for k in ckpt] if isinstance(ckpt, dict) else []
+            raise KeyError(f"{path}: no '{param_key}' key; the file has {have[:12]}{' ...' if len(have) > 12 else ''}")
+        return ckpt[param_key], f"[ckpt] loaded state_dict from '{param_key}' key"
+    if isinstance(ckpt, dict):
+        for k in PARAM_KEYS:
+            if k in ckpt:
+                return ckpt[k], f"[ckpt] loaded state_dict from '{k}' key"
     return ckpt, "[ckpt] loaded raw state_dict"
 
 
@@ -67,6 +79,8 @@ def main(argv=None):
     ap.add_argument("--save_indices", type=str, default="",
                     help="explicit comma-separated indices, e.g. '0,100,200'; takes priority over save_every")
     ap.add_argument("--arch", type=str, choices=["ms_resunet", "swinir", "hat", "dat"], default="ms_resunet")       # additive
+    ap.add_argument("--param_key", type=str, choices=["auto", *PARAM_KEYS], default="auto",
+                    help="additive: which envelope of the checkpoint to load (auto: model, then params, then params_ema)")
     ap.add_argument("--device", type=str, default=None, help="additive: force 'cpu' / 'cuda' (default: cuda if available)")
     args = ap.parse_args(argv)
 
@@ -115,7 +129,7 @@ def main(argv=None):
         model = build_sr_model(args.arch, scale_int, drop_path_rate=0.0)
     else:
         model = MS_ResUNet()
-    state, msg = _load_state(args.ckpt)
+    state, msg = _load_state(args.ckpt, args.param_key)
     model.load_state_dict(state, strict=True)
     print(msg)
     model = model.to(device).eval()

@@ -189,7 +189,12 @@ def main(argv=None):
                     help="additive: the model to fine-tune (build_sr_model)")
     ap.add_argument("--graph", action="store_true",
                     help="additive, --arch hat|dat, one process: capture the train step into a hipGraph and replay it")
+    ap.add_argument("--ema_decay", type=float, default=0.0,
+                    help="additive: keep an exponential moving average of the weights inside the fused optimizer step (0 = off; "
+                         "published recipes use 0.999); validation runs on it and checkpoints gain 'params_ema'")
     args = ap.parse_args(argv)
+    if not 0.0 <= args.ema_decay < 1.0:          # also refuses NaN
+        ap.error(f"--ema_decay must be in [0, 1) (got {args.ema_decay})")
     if args.graph and args.arch == "swinir":
         ap.error("--graph captures the host-orchestrated train step of --arch hat / dat (SwinIR's step is one C call already)")
 
@@ -227,7 +232,9 @@ def main(argv=None):
     model = build_model(scale_int, args.drop_path_rate) if args.arch == "swinir" else build_sr_model(args.arch, scale_int, args.drop_path_rate)
     if args.weights:
         ckpt = torch.load(args.weights, map_location="cpu", weights_only=True)
-        state = ckpt["params"] if isinstance(ckpt, dict) and "params" in ckpt else (ckpt.get("model", ckpt) if isinstance(ckpt, dict) else ckpt)
+        state = ckpt
+        if isinstance(ckpt, dict):          # envelopes, in this order; 'params_ema' is what published HAT / DAT files hold
+            state = next((ckpt[k] for k in ("params", "model", "params_ema") if k in ckpt), ckpt)
         missing, unexpected = model.load_state_dict(state, strict=True)
         if rank == 0:
             print(f"[weights] loaded: {args.weights}")
@@ -263,7 +270,8 @@ def main(argv=None):
         # depth / crop diversity would not scale with the world size (bench.py seeds 1234 + rank the same way)
         seed_everything(args.seed + rank)
     opt = FusedAdamW(model, lr=args.lr, weight_decay=args.weight_decay,
-                     max_grad_norm=args.grad_clip if args.grad_clip and args.grad_clip > 0 else None, grad_div=float(world))
+                     max_grad_norm=args.grad_clip if args.grad_clip and args.grad_clip > 0 else None, grad_div=float(world),
+                     ema_decay=args.ema_decay or None)
     sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=args.epochs, eta_min=args.min_lr) if args.scheduler == "Cosine" else None
 
     graphed = None
@@ -276,7 +284,11 @@ def main(argv=None):
         if sampler is not None:
             sampler.set_epoch(epoch)
         tr_loss, tr_t = train_one_epoch(model, train_loader, opt, device, dp if world > 1 else None, graphed=graphed)
-        val_loss, val_psnr, val_t = validate(model, valid_loader, device)
+        if args.ema_decay:          # validate what gets shipped: the averaged weights (ranks hold identical averages)
+            with opt.swap_ema():
+                val_loss, val_psnr, val_t = validate(model, valid_loader, device)
+        else:
+            val_loss, val_psnr, val_t = validate(model, valid_loader, device)
         if sched is not None:
             sched.step()
         if rank != 0:
@@ -284,13 +296,16 @@ def main(argv=None):
         print(f"[{args.scale}] epoch {epoch:03d}/{args.epochs} | lr={opt.param_groups[0]['lr']:.2e} | "
               f"train L1={tr_loss:.6f} ({tr_t:.1f}s) | val L1={val_loss:.6f}, PSNR={val_psnr:.2f}dB ({val_t:.1f}s)")
         sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}     # un-prefixed keys, like the reference
+        # with --ema_decay: the average next to the raw weights, under the key of the published checkpoints; without: the files as ever
+        more = {"params_ema": opt.ema_state_dict()} if args.ema_decay else {}
+        saved_args = {k: v for k, v in vars(args).items() if k != "ema_decay" or args.ema_decay}
         if val_loss < best_loss:
             best_loss = val_loss
-            torch.save({"model": sd, "epoch": epoch, "best_val_loss": best_loss, "val_psnr": val_psnr, "args": vars(args)},
+            torch.save({"model": sd, **more, "epoch": epoch, "best_val_loss": best_loss, "val_psnr": val_psnr, "args": saved_args},
                        f"best_{args.arch}_finetune_{args.scale}.pt")
         if val_psnr > best_psnr:
             best_psnr = val_psnr
-            torch.save({"model": sd, "epoch": epoch, "best_val_psnr": best_psnr, "val_loss": val_loss, "args": vars(args)},
+            torch.save({"model": sd, **more, "epoch": epoch, "best_val_psnr": best_psnr, "val_loss": val_loss, "args": saved_args},
                        f"bestpsnr_{args.arch}_finetune_{args.scale}.pt")
     if rank == 0:
         print(f"[time] total: {fmt(time.time() - t_all)}")

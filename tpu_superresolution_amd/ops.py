@@ -380,15 +380,54 @@ def multi_grad_sumsq(table: TensorTable, sumsq: torch.Tensor, role: str = "grads
     check(lib().srk_multi_grad_sumsq(table.ptrs[role], table.numel, table.n, _p(sumsq), _stream()))
 
 
+def _ema_decay(ema_decay) -> Optional[float]:
+    """None / 0 -> None (EMA off); a decay in (0, 1) as a float; anything else raises."""
+    if ema_decay is None:
+        return None
+    d = float(ema_decay)
+    if not 0.0 <= d < 1.0:          # also refuses NaN
+        raise ValueError(f"ema_decay must be in [0, 1) (got {ema_decay!r})")
+    return d or None
+
+
 def multi_adamw_clip_step(table: TensorTable, sumsq: Optional[torch.Tensor], max_norm: float, grad_div: float, lr: float, beta1: float,
                           beta2: float, eps: float, weight_decay: float, step: int, hyper: Optional[torch.Tensor] = None,
-                          nonfinite: Optional[torch.Tensor] = None) -> None:
+                          nonfinite: Optional[torch.Tensor] = None, ema_decay: Optional[float] = None) -> None:
     """clip + AdamW over the table's params / grads / exp_avg / exp_avg_sq (srk_multi_adamw_clip_step); ceil(n / 80) launches,
-    capturable.  hyper: optional device {lr, bc1, bc2_sqrt} (adamw_hyper) that replaces `lr` and `step`."""
+    capturable.  hyper: optional device {lr, bc1, bc2_sqrt} (adamw_hyper) that replaces `lr` and `step`.
+    ema_decay (not None): srk_multi_adamw_clip_ema_step, which also advances the table's "ema" tensors toward the new weights;
+    ceil(n / 72) launches.  The decay is a launch-time constant."""
     pt = table.ptrs
-    check(lib().srk_multi_adamw_clip_step(pt["params"], pt["grads"], pt["exp_avg"], pt["exp_avg_sq"], table.numel, table.n, _p(sumsq),
-                                          float(max_norm), float(grad_div), float(lr), float(beta1), float(beta2), float(eps),
-                                          float(weight_decay), int(step), _p(hyper), _p(nonfinite), _stream()))
+    if ema_decay is None:
+        check(lib().srk_multi_adamw_clip_step(pt["params"], pt["grads"], pt["exp_avg"], pt["exp_avg_sq"], table.numel, table.n,
+                                              _p(sumsq), float(max_norm), float(grad_div), float(lr), float(beta1), float(beta2),
+                                              float(eps), float(weight_decay), int(step), _p(hyper), _p(nonfinite), _stream()))
+        return
+    check(lib().srk_multi_adamw_clip_ema_step(pt["params"], pt["grads"], pt["exp_avg"], pt["exp_avg_sq"], pt["ema"], table.numel, table.n,
+                                              _p(sumsq), float(max_norm), float(grad_div), float(lr), float(beta1), float(beta2),
+                                              float(eps), float(weight_decay), int(step), float(ema_decay), _p(hyper), _p(nonfinite),
+                                              _stream()))
+
+
+def adamw_clip_step(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,
+                    sumsq: Optional[torch.Tensor], max_norm: float, grad_div: float, lr: float, beta1: float, beta2: float, eps: float,
+                    weight_decay: float, step: int, nonfinite: Optional[torch.Tensor] = None, ema: Optional[torch.Tensor] = None,
+                    ema_decay: Optional[float] = None, offset: int = 0, numel: Optional[int] = None) -> None:
+    """The flat counterpart: clip + AdamW over elements [offset, offset + numel) of contiguous fp32 buffers (srk_adamw_clip_step), or,
+    with `ema` and `ema_decay`, srk_adamw_clip_ema_step, which also advances the same range of `ema`."""
+    n = params.numel() - offset if numel is None else int(numel)
+    if offset < 0 or n < 0 or offset + n > params.numel():
+        raise ValueError(f"adamw_clip_step: range [{offset}, {offset + n}) outside a buffer of {params.numel()} elements")
+    bufs = [params, grads, exp_avg, exp_avg_sq] + ([ema] if ema_decay is not None else [])
+    for t in bufs:
+        if t is None or t.dtype is not torch.float32 or t.numel() != params.numel():
+            raise ValueError("adamw_clip_step: params, grads, exp_avg, exp_avg_sq (and ema) must be float32 buffers of one size")
+    at = [_p(t) + 4 * offset for t in bufs]
+    tail = (_p(sumsq), float(max_norm), float(grad_div), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step))
+    if ema_decay is None:
+        check(lib().srk_adamw_clip_step(*at, n, *tail, _p(nonfinite), _stream()))
+    else:
+        check(lib().srk_adamw_clip_ema_step(*at, n, *tail, float(ema_decay), _p(nonfinite), _stream()))
 
 
 def adamw_hyper(lr: float, beta1: float, beta2: float, step: int) -> Tuple[float, float, float]:

@@ -11,9 +11,16 @@ List path under hipGraph capture (training.GraphedTrainStep): kernel arguments a
 the learning rate and the two bias-correction factors from a 3-float device tensor.  ``begin_replay()`` advances the step count and
 rewrites that tensor from ``param_groups[0]['lr']`` before every replay (LR schedulers keep working, the bias correction follows the
 step count); ``end_replay()`` bumps the version counters that the models' bf16 pack caches are keyed on.
+
+EMA of the weights (``ema_decay``): the step kernels also advance ``ema = decay * ema + (1 - decay) * p_new`` while the new weight is
+in a register, so the average is gated and captured with the step.  It advances for exactly the tensors / ranges a step updates: a
+frozen parameter has none, and a trainable parameter without a gradient in some step is skipped by the step and so by the average in
+that step.  Buffers (DAT's BatchNorm statistics) are not averaged: ``ema_state_dict()`` returns their live values.
 """
 from __future__ import annotations
 
+import contextlib
+from collections import OrderedDict
 from typing import List, Optional, Tuple
 
 import torch
@@ -29,12 +36,17 @@ def _stream(device) -> int:
 
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, model: torch.nn.Module, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 1e-2, max_grad_norm: Optional[float] = None, grad_div: float = 1.0):
+                 weight_decay: float = 1e-2, max_grad_norm: Optional[float] = None, grad_div: float = 1.0,
+                 ema_decay: Optional[float] = None):
+        ema_decay = ops._ema_decay(ema_decay)          # None / 0 = off; outside [0, 1): ValueError
         params = [p for p in model.parameters() if p.requires_grad]
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.model = model
         self.max_grad_norm = max_grad_norm
         self.grad_div = float(grad_div)          # world size for data-parallel gradient averaging
+        self.ema_decay = ema_decay
+        self._swapped = False          # inside swap_ema(): the weights hold the average and the other way round
+        self._ema: Optional[torch.Tensor] = None          # flat path: the average of eng.flat (frozen ranges stay equal to the weights)
         self._step = 0
         self._m: Optional[torch.Tensor] = None
         self._v: Optional[torch.Tensor] = None
@@ -79,6 +91,14 @@ class FusedAdamW(torch.optim.Optimizer):
                     st["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
             tab.set("exp_avg", [self.state[p]["exp_avg"] for p in ps])
             tab.set("exp_avg_sq", [self.state[p]["exp_avg_sq"] for p in ps])
+            if self.ema_decay is not None:
+                for p in ps:          # starts from the weights as they are before the parameter's first update (also after loading a
+                    st = self.state[p]          # state that has no average)
+                    if "ema" not in st:
+                        if torch.cuda.is_current_stream_capturing():
+                            raise RuntimeError("FusedAdamW: run one eager step before capturing (state is allocated outside the graph)")
+                        st["ema"] = p.detach().to(torch.float32).clone(memory_format=torch.contiguous_format)
+                tab.set("ema", [self.state[p]["ema"] for p in ps])
         tab.keep = ps
         return tab
 
@@ -116,7 +136,8 @@ class FusedAdamW(torch.optim.Optimizer):
             if not capturing:
                 self._step += 1          # a captured step advances in begin_replay()
             ops.multi_adamw_clip_step(tab, self._sumsq, clip, self.grad_div, grp["lr"], b1, b2, grp["eps"], grp["weight_decay"],
-                                      max(self._step, 1), hyper=self._hyper if capturing else None, nonfinite=nonfinite)
+                                      max(self._step, 1), hyper=self._hyper if capturing else None, nonfinite=nonfinite,
+                                      ema_decay=self.ema_decay)
         # the kernels wrote through raw pointers: tell the pack caches (hat_arch.HAT._pack, dat_arch.DAT._pack, hat_train /
         # dat_train pack_*) that the parameters changed.  Under capture this makes the NEXT forward outside the graph re-pack.
         torch._C._increment_version(tab.keep)
@@ -132,6 +153,11 @@ class FusedAdamW(torch.optim.Optimizer):
                 self._m, self._v = self._m.to(eng.device), self._v.to(eng.device)
             else:
                 self._m, self._v = torch.zeros_like(eng.flat), torch.zeros_like(eng.flat)
+            if self.ema_decay is not None:
+                if self._ema is not None and self._ema.numel() == eng.flat.numel():
+                    self._ema = self._ema.to(eng.device)
+                else:
+                    self._ema = eng.flat.clone()          # before the first update
             self._sumsq = torch.zeros(1, dtype=torch.float32, device=eng.device)
             trainable = {n for n, p in self.model.named_parameters() if p.requires_grad}
             ranges: List[Tuple[int, int]] = []
@@ -173,6 +199,8 @@ class FusedAdamW(torch.optim.Optimizer):
         bad batch cannot destroy the model before the caller's finite check raises (finetune_swinir.py:159-165)."""
         if closure is not None:
             raise RuntimeError("FusedAdamW does not support closures")
+        if self._swapped:
+            raise RuntimeError("FusedAdamW.step() inside swap_ema(): the weights hold the average")
         if not self._flat:
             return self._step_list(nonfinite)
         eng = self._prepare()
@@ -192,6 +220,11 @@ class FusedAdamW(torch.optim.Optimizer):
             self._step += 1
             b1, b2 = grp["betas"]
             for b, e in self._ranges:
+                if self.ema_decay is not None:
+                    ops.adamw_clip_step(eng.flat, g, self._m, self._v, self._sumsq, clip, self.grad_div, grp["lr"], b1, b2, grp["eps"],
+                                        grp["weight_decay"], self._step, nonfinite=nonfinite, ema=self._ema, ema_decay=self.ema_decay,
+                                        offset=b, numel=e - b)
+                    continue
                 check(lib().srk_adamw_clip_step(eng.flat.data_ptr() + 4 * b, g.data_ptr() + 4 * b, self._m.data_ptr() + 4 * b,
                                                 self._v.data_ptr() + 4 * b, e - b, self._sumsq.data_ptr(), float(clip),
                                                 self.grad_div, float(grp["lr"]), float(b1), float(b2), float(grp["eps"]),
@@ -212,6 +245,8 @@ class FusedAdamW(torch.optim.Optimizer):
     def state_dict(self):
         sd = super().state_dict()          # list path: the per-parameter moments are in sd["state"], as torch.optim.AdamW keeps them
         sd["fused"] = {"step": self._step, "exp_avg": self._m, "exp_avg_sq": self._v}
+        if self.ema_decay is not None:
+            sd["fused"]["ema"] = self._ema          # flat path; the list path keeps it in sd["state"][i]["ema"]
         return sd
 
     def load_state_dict(self, state_dict):
@@ -221,5 +256,70 @@ class FusedAdamW(torch.optim.Optimizer):
         if fused is not None:
             self._step = int(fused["step"])
             self._m, self._v = fused["exp_avg"], fused["exp_avg_sq"]
+            self._ema = fused.get("ema") if self.ema_decay is not None else None          # absent: starts from the current weights
             self._engine_id = None
         self._table = None          # list path: the moments were replaced, rebuild the pointer table
+
+    # ---- EMA of the weights ----------------------------------------------------------------------------------------------------------
+    def _ema_pairs(self) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+        """(weights, average) pairs that exist: one per stepped parameter on the list path, the two flat buffers on the flat path."""
+        if self._flat:
+            eng = getattr(self.model, "_engine", None)
+            if eng is None or self._ema is None or self._engine_id != id(eng):
+                return []
+            return [(eng.flat, self._ema)]
+        return [(p, self.state[p]["ema"]) for p in self.param_groups[0]["params"] if "ema" in self.state.get(p, {})]
+
+    @torch.no_grad()
+    def ema_state_dict(self):
+        """The model's state_dict (same keys, same order, on the CPU) with the average in place of every parameter that has one.
+        Parameters that never stepped (frozen) come as the weights they are; buffers (DAT's BatchNorm statistics, index tables) are
+        not averaged and come as their live values."""
+        if self.ema_decay is None:
+            raise RuntimeError("FusedAdamW.ema_state_dict(): ema_decay is not set")
+        if self._swapped:
+            raise RuntimeError("FusedAdamW.ema_state_dict() inside swap_ema(): the average is in the model (model.state_dict())")
+        named = dict(self.model.named_parameters())
+        avg = {}
+        if self._flat:
+            pairs = self._ema_pairs()
+            if pairs:
+                avg = self.model._engine.views(pairs[0][1])
+        else:
+            avg = {n: self.state[p]["ema"] for n, p in named.items() if "ema" in self.state.get(p, {})}
+        out = OrderedDict()
+        for k, v in self.model.state_dict().items():
+            src = avg[k].reshape(v.shape) if k in avg and k in named else v
+            out[k] = src.detach().cpu().clone()
+        return out
+
+    def _exchange(self, pairs) -> None:
+        with torch.no_grad():
+            ws, es = [w for w, _ in pairs], [e for _, e in pairs]
+            tmp = [w.detach().clone() for w in ws]
+            for w, e, t in zip(ws, es, tmp):          # by content: a captured graph and SwinIR's parameter views hold the pointers
+                w.copy_(e.view_as(w))
+                e.copy_(t.view_as(e))
+        if self._flat:
+            self.model._engine.packed_valid = False
+        else:
+            torch._C._increment_version([w for w, _ in pairs])
+
+    @contextlib.contextmanager
+    def swap_ema(self):
+        """``with opt.swap_ema():`` the model runs on the averaged weights (validation, export); weights and average change places by
+        content and change back on exit, also after an exception.  The bf16 pack caches are invalidated on entry and on exit."""
+        if self.ema_decay is None:
+            raise RuntimeError("FusedAdamW.swap_ema(): ema_decay is not set")
+        if self._swapped:
+            raise RuntimeError("FusedAdamW.swap_ema() does not nest")
+        pairs = self._ema_pairs()
+        if self._step < 1 or not pairs:
+            raise RuntimeError("FusedAdamW.swap_ema(): no step has run yet, there is no average to swap in")
+        self._exchange(pairs)
+        self._swapped = True
+        try:
+            yield self
+        finally:
+            self._exchange(pairs)
+            self._swapped = False
