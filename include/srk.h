@@ -87,11 +87,16 @@ size_t srk_window_attention_bwd_fused_scratch(int64_t B_, int nH);
 int srk_rel_pos_bias_expand(const float* table, float* bias_dense, int nH, srk_stream_t stream);
 /* y[M][N] = a[M][K] . w[N][K]^T + bias  (bf16 in, fp32 accumulate, bf16 out); K % 64 == 0, N % 64 == 0 */
 int srk_linear_bf16(const uint16_t* a, const uint16_t* w, const float* bias, uint16_t* y, int M, int N, int K, srk_stream_t stream);
-/* dw[N][K] += y[M][N]^T . x[M][K] ; db[N] += colsum(y)   (bf16 in, fp32 out, accumulating; db may be null) */
+/* dw[N][K] += y[M][N]^T . x[M][K] ; db[N] += colsum(y)   (bf16 in, fp32 out, accumulating; db may be null).  Any M > 0 (rows beyond M are
+ * never read); N % 64 == 0, K % 64 == 0 (else SRK_E_SHAPE); y and x 16-byte aligned (else SRK_E_ALIGN). */
 int srk_linear_wgrad_bf16(const uint16_t* y, const uint16_t* x, float* dw, float* db, int M, int N, int K, srk_stream_t stream);
 /* Up to four of these with the same M as ONE launch (the four linear layers of a transformer block: the launch then fills the chip with
- * few row splits per tile).  Problems whose N and K are all multiples of 192 go out together; any other mix is launched one by one.
- * ldy / ldx: row strides in elements (0: N / K).  dw [N][K] and db [N] (or null) are ACCUMULATED, as srk_linear_wgrad_bf16. */
+ * few row splits per tile).  Problems of one TILE CLASS go out together -- the class of a problem is (c(N), c(K)) with c(v) = 3 if v % 192 == 0,
+ * else 2 if v % 128 == 0, else 1 (the tile is 64 c(N) x 64 c(K)); a list that mixes classes is launched one problem after the other.
+ * ldy / ldx: row strides in elements (0: N / K).  dw [N][K] and db [N] (or null) are ACCUMULATED, as srk_linear_wgrad_bf16.
+ * Checked on the host before any launch: SRK_E_SHAPE for count outside 1..4, M <= 0, N or K not a positive multiple of 64, ldy < N, ldx < K;
+ * SRK_E_NULL for a null problems / y / x / dw; SRK_E_ALIGN for y or x not 16-byte aligned and for ldy % 8 != 0 or ldx % 8 != 0 (the kernels
+ * read 16-byte pieces at y + m * ldy and x + m * ldx). */
 typedef struct {
   const void* y; int ldy;      /* bf16 [M][ldy]: gradient of the layer output */
   const void* x; int ldx;      /* bf16 [M][ldx]: layer input */
@@ -102,7 +107,9 @@ int srk_linear_wgrad_multi_bf16(const srk_wgrad_problem* problems, int count, in
 /* 3x3/s1/p1 conv on NHWC bf16 [B][H][W][CinP] with packed weights [N][9*CinP] (tap-major), + bias -> bf16 NHWC [..][N] */
 int srk_conv3x3_bf16(const uint16_t* x, const uint16_t* w, const float* bias, uint16_t* y, int B, int H, int W, int CinP, int N,
                      srk_stream_t stream);
-/* dw[N][9*CinP] += conv weight gradient (y = d output NHWC bf16 [..][N], x = input NHWC bf16 [..][CinP]); db += sum y */
+/* dw[N][9*CinP] += conv weight gradient (y = d output NHWC bf16 [..][N], x = input NHWC bf16 [..][CinP]); db += sum y (db may be null).
+ * dw is tap-major: column ((dy + 1) * 3 + (dx + 1)) * CinP + ci.  B, H, W > 0, N % 64 == 0, CinP % 64 == 0 (else SRK_E_SHAPE); y and x
+ * 16-byte aligned (else SRK_E_ALIGN). */
 int srk_conv3x3_wgrad_bf16(const uint16_t* y, const uint16_t* x, float* dw, float* db, int B, int H, int W, int CinP, int N,
                            srk_stream_t stream);
 int srk_cast_f32_bf16(const float* x, uint16_t* y, int64_t n, srk_stream_t stream);
@@ -384,17 +391,26 @@ int srk_layernorm_bwd(const uint16_t* dy, const float* x, const float* mean, con
 int srk_add_f32_bf16(float* a, const float* b, uint16_t* ab_bf16, int64_t n, srk_stream_t stream);
 int srk_add_bf16_into_f32(float* a, const uint16_t* b, int64_t n, srk_stream_t stream);
 int srk_add_f32(float* out, const float* a, const float* b, int64_t n, srk_stream_t stream);
-/* image head backwards: d_pred fp32 NCHW [B][Cimg][Hc][Wc] -> gy fp32 [B*H*W][CoP] (times inv_range; r > 1: un-pixel-shuffled);
- * weight / input gradients of a 3x3 conv with few output channels (conv_last), fp32 parameters [Co][Cin][3][3] */
+/* image head backwards: d_pred fp32 NCHW [B][Cimg][Hc][Wc] -> gy fp32 [B*H*W][CoP] (times inv_range; r > 1: un-pixel-shuffled, column
+ * c*r*r + i*r + j of pixel (y, x) = d_pred[c][y*r + i][x*r + j]); columns >= Cimg*r*r and everything outside the Hc x Wc crop are zero.
+ * SRK_E_SHAPE unless B, H, W > 0, r >= 1, CoP is 4 or 16, 1 <= Cimg, Cimg*r*r <= CoP, 0 < Hc <= H*r, 0 < Wc <= W*r.
+ * srk_smallconv_wgrad / _dgrad: weight / input gradients of a 3x3 conv with few output channels (conv_last, UpsampleOneStep), fp32
+ * parameters [Co][Cin][3][3]: dw and db [Co] are ACCUMULATED from x bf16 NHWC [..][CinP] and gy; dx bf16 NHWC [..][CinP] is WRITTEN (pad
+ * channels >= Cin zero).  SRK_E_SHAPE unless B, H, W > 0, CoP is 4 or 16, 1 <= Co <= CoP, 1 <= Cin <= CinP, CinP % 64 == 0, CinP <= 256;
+ * SRK_E_ALIGN unless x, gy and dx are 16-byte aligned; SRK_E_NULL for any null pointer (db included). */
 int srk_img_grad_prep(const float* d_pred, float* gy, int B, int Cimg, int Hc, int Wc, int H, int W, int r, int CoP, float inv_range,
                       srk_stream_t stream);
 int srk_smallconv_wgrad(const uint16_t* x, const float* gy, float* dw, float* db, int B, int H, int W, int Cin, int CinP, int Co, int CoP,
                         srk_stream_t stream);
 int srk_smallconv_dgrad(const float* gy, const float* weight, uint16_t* dx, int B, int H, int W, int Cin, int CinP, int Co, int CoP,
                         srk_stream_t stream);
-/* conv_first backwards: dw [C][Cin][3][3], db [C] ACCUMULATED from the padded NHWC4 image and gy fp32 [B*H*W][CP] */
+/* conv_first backwards: dw [C][Cin][3][3], db [C] ACCUMULATED from the padded NHWC4 image and gy fp32 [B*H*W][CP].  SRK_E_SHAPE unless
+ * B, H, W > 0, 1 <= Cin <= 4, 1 <= C <= CP, C <= 256, CP % 4 == 0; SRK_E_ALIGN unless img4 and gy are 16-byte aligned.  With CP == 192, at
+ * least 16384 pixels (a multiple of 32) and a registered workspace (srk_set_wgrad_workspace) the sums are formed in a fixed order. */
 int srk_stem_wgrad(const float* img4, const float* gy, float* dw, float* db, int B, int H, int W, int Cin, int C, int CP, srk_stream_t stream);
-/* srk_conv3x3_wgrad_bf16 with y stored pixel-shuffled by r (the gradient of a conv + PixelShuffle(r) output, Cs stored channels) */
+/* srk_conv3x3_wgrad_bf16 with y stored pixel-shuffled by r (the gradient of a conv + PixelShuffle(r) output, Cs stored channels):
+ * y bf16 [B][H*r][W*r][Cs], row n = (i*r + j)*Cs + c of dw takes y[b][h*r + i][w*r + j][c].  SRK_E_SHAPE unless B, H, W > 0, r >= 1,
+ * Cs % 8 == 0 and N == r*r*Cs (and N % 64 == 0, CinP % 64 == 0); SRK_E_ALIGN unless y and x are 16-byte aligned. */
 int srk_conv3x3_wgrad_ps_bf16(const uint16_t* y, const uint16_t* x, float* dw, float* db, int B, int H, int W, int CinP, int N, int r, int Cs,
                               srk_stream_t stream);
 /* srk_mlp_fused_fwd that also stores u = xn W1^T + b1 and h = gelu(u) (bf16 [M][384]) for a backward pass */

@@ -164,6 +164,91 @@ def test_gemm_ex_refuses_bad_argument_blocks_without_a_gpu(lib):
     assert h.srk_gemm_ex(None, None) == E_NULL
 
 
+def test_weight_gradient_entry_points_refuse_bad_arguments_without_a_gpu(lib):
+    """The weight-gradient family returns on the host, before any launch, for the shapes, strides and alignments its kernels cannot
+    honour (include/srk.h states each rule at its entry point).  The addresses are dummies that are never dereferenced: every call here
+    differs from a valid one in exactly the argument under test, and is rejected."""
+    h = lib.lib()
+    P = 4096                                                     # a non-null, 16-byte aligned address; never read or written
+    E_SHAPE, E_NULL, E_ALIGN = -1, -2, -5
+
+    def refused(rc, code):
+        assert rc == code, (rc, code, h.srk_last_error())
+        assert h.srk_last_error(), "no message"
+
+    def variants(base, changes):
+        """base: name -> valid value (in argument order); changes: (name, bad value, code)."""
+        for name, bad, code in changes:
+            yield [bad if k == name else v for k, v in base.items()], code, name
+
+    # srk_linear_wgrad_bf16(y, x, dw, db, M, N, K, stream)
+    base = dict(y=P, x=P, dw=P, db=None, M=64, N=64, K=64)
+    for a, code, _ in variants(base, [("y", None, E_NULL), ("x", None, E_NULL), ("dw", None, E_NULL), ("y", P + 2, E_ALIGN), ("x", P + 8, E_ALIGN),
+                                      ("M", 0, E_SHAPE), ("M", -64, E_SHAPE), ("N", 96, E_SHAPE), ("K", 100, E_SHAPE)]):
+        refused(h.srk_linear_wgrad_bf16(*a, None), code)
+
+    # srk_linear_wgrad_multi_bf16(problems, count, M, stream)
+    def problems(n=2, **kw):
+        arr = (lib.WgradProblem * 4)()
+        for i in range(4):
+            arr[i].y, arr[i].x, arr[i].dw, arr[i].db = P, P, P, None
+            arr[i].N, arr[i].K, arr[i].ldy, arr[i].ldx = 192, 64, 256, 128
+        for k, v in kw.items():
+            setattr(arr[n - 1], k, v)                            # the LAST problem of the list carries the fault
+        return arr
+
+    refused(h.srk_linear_wgrad_multi_bf16(None, 1, 64, None), E_NULL)
+    for count in (0, -1, 5):
+        refused(h.srk_linear_wgrad_multi_bf16(problems(), count, 64, None), E_SHAPE)
+    for M in (0, -64):
+        refused(h.srk_linear_wgrad_multi_bf16(problems(), 2, M, None), E_SHAPE)
+    for n in (1, 2, 3, 4):
+        for kw, code in ((dict(N=100), E_SHAPE), (dict(K=32), E_SHAPE), (dict(N=0), E_SHAPE), (dict(ldy=128), E_SHAPE), (dict(ldx=56), E_SHAPE),
+                         (dict(ldy=196), E_ALIGN), (dict(ldx=68), E_ALIGN), (dict(ldy=193), E_ALIGN), (dict(y=None), E_NULL), (dict(x=None), E_NULL),
+                         (dict(dw=None), E_NULL), (dict(y=P + 4), E_ALIGN), (dict(x=P + 8), E_ALIGN)):
+            refused(h.srk_linear_wgrad_multi_bf16(problems(n, **kw), n, 64, None), code)
+    assert b"multiples of 8" in (h.srk_linear_wgrad_multi_bf16(problems(1, ldx=68), 1, 64, None), h.srk_last_error())[1]
+
+    # srk_conv3x3_wgrad_bf16(y, x, dw, db, B, H, W, CinP, N, stream)  /  srk_conv3x3_wgrad_ps_bf16(..., N, r, Cs, stream)
+    base = dict(y=P, x=P, dw=P, db=None, B=2, H=4, W=8, CinP=64, N=64)
+    for a, code, _ in variants(base, [("y", None, E_NULL), ("x", None, E_NULL), ("dw", None, E_NULL), ("y", P + 2, E_ALIGN), ("x", P + 8, E_ALIGN),
+                                      ("B", 0, E_SHAPE), ("H", -4, E_SHAPE), ("W", 0, E_SHAPE), ("CinP", 60, E_SHAPE), ("N", 16, E_SHAPE)]):
+        refused(h.srk_conv3x3_wgrad_bf16(*a, None), code)
+    base = dict(y=P, x=P, dw=P, db=None, B=2, H=4, W=8, CinP=64, N=256, r=2, Cs=64)
+    for a, code, _ in variants(base, [("y", None, E_NULL), ("x", None, E_NULL), ("dw", None, E_NULL), ("y", P + 2, E_ALIGN), ("x", P + 8, E_ALIGN),
+                                      ("B", 0, E_SHAPE), ("H", 0, E_SHAPE), ("W", -8, E_SHAPE), ("CinP", 60, E_SHAPE), ("N", 192, E_SHAPE),
+                                      ("r", 0, E_SHAPE), ("r", 3, E_SHAPE), ("Cs", 32, E_SHAPE), ("Cs", 0, E_SHAPE)]):
+        refused(h.srk_conv3x3_wgrad_ps_bf16(*a, None), code)
+    refused(h.srk_conv3x3_wgrad_ps_bf16(P, P, P, None, 2, 4, 8, 64, 64, 4, 4, None), E_SHAPE)       # N == r*r*Cs but Cs % 8 != 0
+
+    # srk_img_grad_prep(d_pred, gy, B, Cimg, Hc, Wc, H, W, r, CoP, inv_range, stream)
+    base = dict(d_pred=P, gy=P, B=2, Cimg=3, Hc=8, Wc=16, H=4, W=8, r=2, CoP=16, inv_range=1.0)
+    for a, code, _ in variants(base, [("d_pred", None, E_NULL), ("gy", None, E_NULL), ("B", 0, E_SHAPE), ("H", 0, E_SHAPE), ("W", -1, E_SHAPE),
+                                      ("r", 0, E_SHAPE), ("r", 3, E_SHAPE), ("Cimg", 0, E_SHAPE), ("Cimg", 5, E_SHAPE), ("CoP", 8, E_SHAPE),
+                                      ("CoP", 4, E_SHAPE), ("Hc", 9, E_SHAPE), ("Wc", 17, E_SHAPE), ("Hc", 0, E_SHAPE), ("Wc", 0, E_SHAPE)]):
+        refused(h.srk_img_grad_prep(*a, None), code)
+
+    # srk_smallconv_wgrad(x, gy, dw, db, B, H, W, Cin, CinP, Co, CoP, stream)  /  srk_smallconv_dgrad(gy, weight, dx, B, ..., stream)
+    shape_faults = [("B", 0, E_SHAPE), ("H", 0, E_SHAPE), ("W", -3, E_SHAPE), ("Co", 5, E_SHAPE), ("Co", 0, E_SHAPE), ("CoP", 8, E_SHAPE),
+                    ("CoP", 32, E_SHAPE), ("Cin", 65, E_SHAPE), ("Cin", 0, E_SHAPE), ("CinP", 60, E_SHAPE), ("CinP", 320, E_SHAPE)]
+    base = dict(x=P, gy=P, dw=P, db=P, B=1, H=4, W=8, Cin=60, CinP=64, Co=3, CoP=4)
+    for a, code, _ in variants(base, shape_faults + [("x", None, E_NULL), ("gy", None, E_NULL), ("dw", None, E_NULL), ("db", None, E_NULL),
+                                                     ("x", P + 2, E_ALIGN), ("gy", P + 4, E_ALIGN)]):
+        refused(h.srk_smallconv_wgrad(*a, None), code)
+    base = dict(gy=P, weight=P, dx=P, B=1, H=4, W=8, Cin=60, CinP=64, Co=3, CoP=4)
+    for a, code, _ in variants(base, shape_faults + [("gy", None, E_NULL), ("weight", None, E_NULL), ("dx", None, E_NULL), ("gy", P + 4, E_ALIGN),
+                                                     ("dx", P + 8, E_ALIGN)]):
+        refused(h.srk_smallconv_dgrad(*a, None), code)
+
+    # srk_stem_wgrad(img4, gy, dw, db, B, H, W, Cin, C, CP, stream)
+    base = dict(img4=P, gy=P, dw=P, db=P, B=1, H=4, W=8, Cin=3, C=60, CP=64)
+    for a, code, _ in variants(base, [("img4", None, E_NULL), ("gy", None, E_NULL), ("dw", None, E_NULL), ("db", None, E_NULL), ("img4", P + 4, E_ALIGN),
+                                      ("gy", P + 8, E_ALIGN), ("B", 0, E_SHAPE), ("H", 0, E_SHAPE), ("W", 0, E_SHAPE), ("Cin", 5, E_SHAPE),
+                                      ("Cin", 0, E_SHAPE), ("C", 65, E_SHAPE), ("C", 0, E_SHAPE), ("CP", 62, E_SHAPE)]):
+        refused(h.srk_stem_wgrad(*a, None), code)
+    refused(h.srk_stem_wgrad(P, P, P, P, 1, 4, 8, 3, 260, 320, None), E_SHAPE)                      # C > 256: one thread per channel
+
+
 def test_options_are_process_wide_with_per_plan_values():
     """SURVEY 8b 're-entrant': srk_set_option writes ONE process-wide value per option (every thread sees it -- the autograd engine runs
     the backward on its own thread); a plan carries its own values (srk_swinir_plan_set_option), applied in a thread-private copy of the

@@ -254,6 +254,13 @@ int srk_linear_wgrad_multi_bf16(const srk_wgrad_problem* problems, int count, in
   for (int i = 0; i < count; ++i) {
     const srk_wgrad_problem& q = problems[i];
     REQ_PTR(q.y); REQ_PTR(q.x); REQ_PTR(q.dw); REQ_ALIGN(q.y); REQ_ALIGN(q.x);
+    SRK_REQUIRE(q.N > 0 && q.K > 0 && q.N % 64 == 0 && q.K % 64 == 0, SRK_E_SHAPE, "linear_wgrad_multi: problem %d: N=%d K=%d (multiples of 64)", i,
+                q.N, q.K);
+    SRK_REQUIRE((q.ldy <= 0 || q.ldy >= q.N) && (q.ldx <= 0 || q.ldx >= q.K), SRK_E_SHAPE, "linear_wgrad_multi: problem %d: ldy=%d < N or ldx=%d < K",
+                i, q.ldy, q.ldx);
+    // the kernels read 16-byte pieces at y + m * ldy and x + m * ldx
+    SRK_REQUIRE((q.ldy <= 0 || q.ldy % 8 == 0) && (q.ldx <= 0 || q.ldx % 8 == 0), SRK_E_ALIGN,
+                "linear_wgrad_multi: problem %d: ldy=%d / ldx=%d must be multiples of 8 elements", i, q.ldy, q.ldx);
     ps[i].Y = static_cast<const bf16_t*>(q.y); ps[i].ldy = q.ldy > 0 ? q.ldy : q.N;
     ps[i].X = static_cast<const bf16_t*>(q.x); ps[i].ldx = q.ldx > 0 ? q.ldx : q.K;
     ps[i].M = M; ps[i].N = q.N; ps[i].K = q.K; ps[i].dW = q.dw; ps[i].ldw = q.K; ps[i].db = q.db;
@@ -273,6 +280,7 @@ int srk_conv3x3_bf16(const uint16_t* x, const uint16_t* w, const float* bias, ui
 int srk_conv3x3_wgrad_bf16(const uint16_t* y, const uint16_t* x, float* dw, float* db, int B, int H, int W, int CinP, int N,
                            srk_stream_t stream) {
   REQ_PTR(y); REQ_PTR(x); REQ_PTR(dw); REQ_ALIGN(y); REQ_ALIGN(x);
+  SRK_REQUIRE(B > 0 && H > 0 && W > 0 && (long long)B * H * W < (1ll << 31), SRK_E_SHAPE, "conv3x3_wgrad: B=%d H=%d W=%d", B, H, W);
   WgradParams p = {};
   p.Y = y; p.ldy = N; p.X = x; p.ldx = CinP; p.M = B * H * W; p.N = N; p.K = CinP; p.dW = dw; p.ldw = 9 * CinP; p.db = db;
   p.conv = 1; p.B = B; p.H = H; p.W = W; p.r = 1;

@@ -236,32 +236,59 @@ int srk_rowscale_bf16(const uint16_t* src, uint16_t* dst, const float* f, int64_
   return srk_check_launch("rowscale_bf16");
 }
 
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 int srk_img_grad_prep(const float* d_pred, float* gy, int B, int Cimg, int Hc, int Wc, int H, int W, int r, int CoP, float inv_range,
                       srk_stream_t stream) {
   SRK_REQUIRE(d_pred && gy, SRK_E_NULL, "img_grad_prep: null pointer");
+  SRK_REQUIRE(B > 0 && H > 0 && W > 0 && r >= 1, SRK_E_SHAPE, "img_grad_prep: B=%d H=%d W=%d r=%d", B, H, W, r);
+  SRK_REQUIRE((CoP == 4 || CoP == 16) && Cimg >= 1 && Cimg * r * r <= CoP, SRK_E_SHAPE, "img_grad_prep: Cimg=%d r=%d CoP=%d (CoP 4 or 16, Cimg*r*r <= CoP)",
+              Cimg, r, CoP);
+  SRK_REQUIRE(Hc > 0 && Wc > 0 && Hc <= H * r && Wc <= W * r, SRK_E_SHAPE, "img_grad_prep: crop %dx%d outside the %dx%d image", Hc, Wc, H * r, W * r);
   return srk_launch_img_grad_prep(d_pred, gy, B, Cimg, Hc, Wc, H, W, r, CoP, inv_range, (hipStream_t)stream);
+}
+
+// shape rules shared by the two image-head gradients
+static int smallconv_check(const char* fn, int B, int H, int W, int Cin, int CinP, int Co, int CoP) {
+  SRK_REQUIRE(B > 0 && H > 0 && W > 0, SRK_E_SHAPE, "%s: B=%d H=%d W=%d", fn, B, H, W);
+  SRK_REQUIRE((CoP == 4 || CoP == 16) && Co >= 1 && Co <= CoP, SRK_E_SHAPE, "%s: Co=%d CoP=%d (CoP 4 or 16, Co <= CoP)", fn, Co, CoP);
+  SRK_REQUIRE(Cin >= 1 && Cin <= CinP && CinP % 64 == 0 && CinP <= 256, SRK_E_SHAPE, "%s: Cin=%d CinP=%d (Cin <= CinP, CinP a multiple of 64, <= 256)", fn,
+              Cin, CinP);
+  return SRK_OK;
 }
 
 int srk_smallconv_wgrad(const uint16_t* x, const float* gy, float* dw, float* db, int B, int H, int W, int Cin, int CinP, int Co, int CoP,
                         srk_stream_t stream) {
   SRK_REQUIRE(x && gy && dw && db, SRK_E_NULL, "smallconv_wgrad: null pointer");
+  if (int rc = smallconv_check("smallconv_wgrad", B, H, W, Cin, CinP, Co, CoP)) return rc;
+  SRK_REQUIRE(aligned16(x) && aligned16(gy), SRK_E_ALIGN, "smallconv_wgrad: x and gy must be 16-byte aligned");
   return srk_launch_smallconv_wgrad(x, gy, dw, db, B, H, W, Cin, CinP, Co, CoP, (hipStream_t)stream);
 }
 
 int srk_smallconv_dgrad(const float* gy, const float* weight, uint16_t* dx, int B, int H, int W, int Cin, int CinP, int Co, int CoP,
                         srk_stream_t stream) {
   SRK_REQUIRE(gy && weight && dx, SRK_E_NULL, "smallconv_dgrad: null pointer");
+  if (int rc = smallconv_check("smallconv_dgrad", B, H, W, Cin, CinP, Co, CoP)) return rc;
+  SRK_REQUIRE(aligned16(gy) && aligned16(dx), SRK_E_ALIGN, "smallconv_dgrad: gy and dx must be 16-byte aligned");
   return srk_launch_smallconv_dgrad(gy, weight, dx, B, H, W, Cin, CinP, Co, CoP, (hipStream_t)stream);
 }
 
 int srk_stem_wgrad(const float* img4, const float* gy, float* dw, float* db, int B, int H, int W, int Cin, int C, int CP, srk_stream_t stream) {
   SRK_REQUIRE(img4 && gy && dw && db, SRK_E_NULL, "stem_wgrad: null pointer");
+  SRK_REQUIRE(B > 0 && H > 0 && W > 0, SRK_E_SHAPE, "stem_wgrad: B=%d H=%d W=%d", B, H, W);
+  SRK_REQUIRE(Cin >= 1 && Cin <= 4 && C >= 1 && C <= CP && C <= 256 && CP % 4 == 0, SRK_E_SHAPE,
+              "stem_wgrad: Cin=%d C=%d CP=%d (Cin <= 4, C <= CP, C <= 256, CP a multiple of 4)", Cin, C, CP);
+  SRK_REQUIRE(aligned16(img4) && aligned16(gy), SRK_E_ALIGN, "stem_wgrad: img4 and gy must be 16-byte aligned");
   return srk_launch_stem_wgrad(img4, gy, dw, db, B, H, W, Cin, C, CP, (hipStream_t)stream);
 }
 
 int srk_conv3x3_wgrad_ps_bf16(const uint16_t* y, const uint16_t* x, float* dw, float* db, int B, int H, int W, int CinP, int N, int r, int Cs,
                               srk_stream_t stream) {
   SRK_REQUIRE(y && x && dw, SRK_E_NULL, "conv3x3_wgrad_ps: null pointer");
+  SRK_REQUIRE(aligned16(y) && aligned16(x), SRK_E_ALIGN, "conv3x3_wgrad_ps: y and x must be 16-byte aligned");
+  SRK_REQUIRE(B > 0 && H > 0 && W > 0 && (long long)B * H * W < (1ll << 31), SRK_E_SHAPE, "conv3x3_wgrad_ps: B=%d H=%d W=%d", B, H, W);
+  SRK_REQUIRE(r >= 1 && Cs > 0 && Cs % 8 == 0 && N == r * r * Cs, SRK_E_SHAPE, "conv3x3_wgrad_ps: N=%d r=%d Cs=%d (N == r*r*Cs, Cs a multiple of 8)", N, r,
+              Cs);
   WgradParams p = {};
   p.Y = y; p.ldy = N; p.X = x; p.ldx = CinP; p.M = B * H * W; p.N = N; p.K = CinP; p.dW = dw; p.ldw = 9 * CinP; p.db = db;
   p.conv = 1; p.B = B; p.H = H; p.W = W; p.r = r; p.Cs = Cs;
