@@ -427,6 +427,14 @@ int srk_rowscale_bf16(const uint16_t* src, uint16_t* dst, const float* f, int64_
  * (dat_arch.py:310-314, :463-467); act 0 none / 1 GELU; mul (optional) is SGFN's x1 in x1 * DWconv(LN(x2)) (:48-54). */
 int srk_dwconv3x3(const uint16_t* x, int ldx, const float* w, const float* scale, const float* shift, const uint16_t* mul, int ldm, uint16_t* out,
                   int ldo, int B, int H, int W, int C8, int act, srk_stream_t stream);
+/* The DW-conv branch of a DAT block with its BatchNorm FROZEN (eval mode inside a training step), ONE token pass with two outputs:
+ * pre = bf16(conv(x) + bias)  (what the backward and the weight gradient read; bit-equal to srk_dwconv3x3 with scale = 1, shift = bias,
+ * act 0) and out = bf16(gelu(pre * bn_scale + bn_shift)) evaluated on the rounded pre (bn_scale / bn_shift fp32 [C8*8]: rows 0 / 1 of
+ * srk_bn_frozen_coeffs).  Replaces srk_dwconv3x3 + srk_chan_stats + srk_affine_act_bf16 of the batch-statistics path.
+ * srk_dwconv3x3_bn_act_launches: launches of it in this process so far (tests assert that the path was taken). */
+int srk_dwconv3x3_bn_act(const uint16_t* x, int ldx, const float* w, const float* bias, const float* bn_scale, const float* bn_shift, uint16_t* pre,
+                         int ldpre, uint16_t* out, int ldo, int B, int H, int W, int C8, srk_stream_t stream);
+long long srk_dwconv3x3_bn_act_launches(void);
 /* LayerNorm (eps 1e-5) over C channels of a bf16 row slice -> bf16 [rows][ldo], columns C..CP_out written as zero (SpatialGate.norm :46) */
 int srk_rowln_bf16(const uint16_t* x, int ldx, const float* gamma, const float* beta, uint16_t* out, int ldo, int64_t rows, int C, int CP_out,
                    srk_stream_t stream);
@@ -487,6 +495,14 @@ int srk_bn_train_coeffs(const float* partial, int R, int row_stride, int ld, int
                         float* running_mean, float* running_var, float momentum, const int* real_of, srk_stream_t stream);
 int srk_bn_train_bwd_coeffs(const float* partial, int R, int row_stride, int ld, int C, float n, const float* fwd_coef, float* coef,
                             srk_stream_t stream);
+/* nn.BatchNorm2d in EVAL mode inside a training step (frozen statistics), one launch each:
+ *   srk_bn_frozen_coeffs: coef [4][ld] = scale (gamma rstd), shift (beta - mean scale), mean, rstd of channels 0..C-1 from the module's
+ *     running buffers (real_of as above; padding channels all zero); gamma / beta in the padded layout.  Nothing is written but coef.
+ *   srk_bn_frozen_bwd_coeffs: partial rows (sum dz, sum dz x) + that coef -> coef [5][ld] = A = scale, B = 0, C = 0,
+ *     d gamma = rstd (sum dz x - mean sum dz), d beta = sum dz: the contract of srk_bn_train_bwd_coeffs. */
+int srk_bn_frozen_coeffs(int ld, int C, const float* gamma, const float* beta, float eps, const float* running_mean, const float* running_var,
+                         const int* real_of, float* coef, srk_stream_t stream);
+int srk_bn_frozen_bwd_coeffs(const float* partial, int R, int row_stride, int ld, int C, const float* fwd_coef, float* coef, srk_stream_t stream);
 /* out = act(x * scale[i][c] + shift[i][c]); i = row / rows_per_sample (rows_per_sample 0: one vector for all rows); act 1 = GELU */
 int srk_affine_act_bf16(const uint16_t* x, int ldx, const float* scale, const float* shift, uint16_t* out, int ldo, int64_t rows, int C8,
                         int rows_per_sample, int act, srk_stream_t stream);
@@ -551,6 +567,17 @@ int srk_channel_interaction_bwd(const float* pm, const float* dcgate, int ldg, f
                                 const float* b1, const float* gamma, const float* beta, float eps, const float* W2, const float* b2,
                                 float* dW1, float* db1, float* dgamma, float* dbeta, float* dW2, float* db2, float* dpool, int B, int C, int S,
                                 int CA, srk_stream_t stream);
+/* srk_channel_interaction_frozen_fwd / _bwd: the same function with the BatchNorm in eval mode: normalised with running_mean / running_var
+ * [S] (read only), no statistic over the batch, so B = 1 is valid (srk_channel_interaction_frozen_covered: B >= 1, S <= 64, 150 KB). */
+int srk_channel_interaction_frozen_covered(int B, int C, int S);
+int srk_channel_interaction_frozen_fwd(const float* pooled, int ldp, float inv_hw, const int* pad_of, const float* W1, const float* b1,
+                                       const float* gamma, const float* beta, float eps, const float* W2, const float* b2,
+                                       const float* running_mean, const float* running_var, float* pm_out, float* cgate, int B, int C, int S,
+                                       int CA, srk_stream_t stream);
+int srk_channel_interaction_frozen_bwd(const float* pm, const float* dcgate, int ldg, float inv_hw, const int* pad_of, const float* W1,
+                                       const float* b1, const float* gamma, const float* beta, float eps, const float* W2, const float* b2,
+                                       const float* running_mean, const float* running_var, float* dW1, float* db1, float* dgamma,
+                                       float* dbeta, float* dW2, float* db2, float* dpool, int B, int C, int S, int CA, srk_stream_t stream);
 int srk_chan_attn_matrix_fwd(const float* partial, int nchunk, const float* temperature, float* gram, float* A, int B, int num_heads, int dh,
                              srk_stream_t stream);
 int srk_chan_attn_matrix_bwd(const float* dpartial, int nchunk, const float* gram, const float* A, const float* temperature, float* dG, float* dGt,

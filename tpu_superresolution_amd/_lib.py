@@ -138,6 +138,13 @@ _SIGNATURES = {
     "srk_channel_gate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _i, _vp]),
     "srk_channel_gate_act": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "srk_dwconv3x3": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "srk_dwconv3x3_bn_act": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
+    "srk_dwconv3x3_bn_act_launches": (C.c_longlong, []),
+    "srk_bn_frozen_coeffs": (_i, [_i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
+    "srk_bn_frozen_bwd_coeffs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "srk_channel_interaction_frozen_covered": (_i, [_i, _i, _i]),
+    "srk_channel_interaction_frozen_fwd": (_i, [_vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "srk_channel_interaction_frozen_bwd": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp] + [_vp] * 7 + [_i, _i, _i, _i, _vp]),
     "srk_rowln_bf16": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i64, _i, _i, _vp]),
     "srk_spatial_gate": (_i, [_vp, _i, _vp, _vp, _vp, _f, _i, _vp, _i64, _i, _vp]),
     "srk_spatial_gate_dev": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _vp]),

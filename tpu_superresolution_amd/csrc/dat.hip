@@ -12,6 +12,8 @@
 //                           temperature, softmax, applied to v -- Gram partials per 256-token chunk, fixed-order finish
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -45,10 +47,25 @@ constexpr int DT_PIECES = DT_HH * DT_HW * 8;                 // 16-byte pieces o
 constexpr int DT_FILL = (DT_PIECES + 255) / 256;             // DMA instructions per wave
 __device__ uint4 g_dw_zero[1];                               // 16 zero bytes: DMA source outside the image / beyond the channels
 
+// DUAL (the frozen-BatchNorm training forward of the DW-conv branch, srk_dwconv3x3_bn_act): TWO outputs from the one token pass --
+// pre = bf16(conv(x) + shift) (shift = the conv bias, scale is not read: c_pre, what the backward and the weight gradient read) and
+// out = bf16(gelu(pre * scale2 + shift2)) from the ROUNDED pre (scale2 / shift2 = the BatchNorm's running-statistics affine), so that
+// the backward's recomputation from the stored pre sees the forward's argument.  DUAL = false carries an empty struct and is the
+// kernel it was.
+template <bool DUAL>
+struct DwDual {};
+template <>
+struct DwDual<true> {
+  bf16_t* pre;
+  int ldpre;
+  const float *scale2, *shift2;
+};
+
+template <bool DUAL>
 __global__ __launch_bounds__(256) void dwconv3x3_tile_kernel(const bf16_t* __restrict__ x, int ldx, const float* __restrict__ w,
                                                              const float* __restrict__ scale, const float* __restrict__ shift,
                                                              const bf16_t* __restrict__ mul, int ldm, bf16_t* __restrict__ out, int ldo, int B,
-                                                             int H, int W, int C, int act, int tilesx, int tilesy) {
+                                                             int H, int W, int C, int act, int tilesx, int tilesy, const DwDual<DUAL> dual) {
   __shared__ __attribute__((aligned(16))) unsigned char tile[DT_FILL * 256 * 16];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -80,6 +97,14 @@ __global__ __launch_bounds__(256) void dwconv3x3_tile_kernel(const bf16_t* __res
     for (int t = 0; t < 9; ++t) wr[t][h] = srk_f32x2_t{w[ca * 9 + t], w[cb * 9 + t]};
     sc[h] = srk_f32x2_t{scale[ca], scale[cb]};
     sh[h] = srk_f32x2_t{shift[ca], shift[cb]};
+  }
+  float s2[4] = {0.f, 0.f, 0.f, 0.f}, t2[4] = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (DUAL) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      s2[e] = dual.scale2[live ? c + e : 0];
+      t2[e] = dual.shift2[live ? c + e : 0];
+    }
   }
   uint2 mraw[DT_H];
   const long long pix0 = ((long long)(b * H + y0) * W + x0 + col);
@@ -115,9 +140,19 @@ __global__ __launch_bounds__(256) void dwconv3x3_tile_kernel(const bf16_t* __res
     float v[4];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const srk_f32x2_t a = __builtin_elementwise_fma(acc[h], sc[h], sh[h]);
+      srk_f32x2_t a;
+      if constexpr (DUAL) a = acc[h] + sh[h];      // = fma(acc, 1, bias) bit for bit: what srk_dwconv3x3 gives with a scale vector of ones
+      else a = __builtin_elementwise_fma(acc[h], sc[h], sh[h]);
       v[2 * h] = a[0];
       v[2 * h + 1] = a[1];
+    }
+    if constexpr (DUAL) {
+      const unsigned p01 = pack_bf2(v[0], v[1]), p23 = pack_bf2(v[2], v[3]);
+      if (live && y0 + it < H) *reinterpret_cast<uint2*>(dual.pre + (pix0 + (long long)it * W) * dual.ldpre + c) = make_uint2(p01, p23);
+      unpack_bf2(p01, v[0], v[1]);
+      unpack_bf2(p23, v[2], v[3]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = gelu_f(v[e] * s2[e] + t2[e]);
     }
     if (act == 1) {
 #pragma unroll
@@ -407,9 +442,31 @@ int srk_dwconv3x3(const uint16_t* x, int ldx, const float* w, const float* scale
   const int tilesx = (W + DT_W - 1) / DT_W, tilesy = (H + DT_H - 1) / DT_H;       // any H, W: edges are predicated
   const long long nb = (long long)B * tilesx * tilesy;
   SRK_REQUIRE(nb < (1LL << 31), SRK_E_SHAPE, "dwconv3x3: too many tiles");
-  hipLaunchKernelGGL(dwconv3x3_tile_kernel, dim3((unsigned)nb, (unsigned)((8 * C8 + DT_CB - 1) / DT_CB)), dim3(256), 0, (hipStream_t)stream, x, ldx, w,
-                     scale, shift, mul, ldm, out, ldo, B, H, W, 8 * C8, act, tilesx, tilesy);
+  hipLaunchKernelGGL(dwconv3x3_tile_kernel<false>, dim3((unsigned)nb, (unsigned)((8 * C8 + DT_CB - 1) / DT_CB)), dim3(256), 0, (hipStream_t)stream, x,
+                     ldx, w, scale, shift, mul, ldm, out, ldo, B, H, W, 8 * C8, act, tilesx, tilesy, DwDual<false>{});
   return srk_check_launch("dwconv3x3");
+}
+
+static std::atomic<long long> g_dwconv_bn_act_launches{0};
+
+long long srk_dwconv3x3_bn_act_launches(void) { return g_dwconv_bn_act_launches.load(); }
+
+int srk_dwconv3x3_bn_act(const uint16_t* x, int ldx, const float* w, const float* bias, const float* bn_scale, const float* bn_shift, uint16_t* pre,
+                         int ldpre, uint16_t* out, int ldo, int B, int H, int W, int C8, srk_stream_t stream) {
+  SRK_REQUIRE(x && w && bias && bn_scale && bn_shift && pre && out, SRK_E_NULL, "dwconv3x3_bn_act: null pointer");
+  SRK_REQUIRE(B > 0 && H > 0 && W > 0 && C8 > 0 && ldx >= 8 * C8 && ldo >= 8 * C8 && ldpre >= 8 * C8 && ldx % 8 == 0 && ldo % 8 == 0 && ldpre % 8 == 0,
+              SRK_E_SHAPE, "dwconv3x3_bn_act: bad shape / strides (16-byte pieces)");
+  SRK_REQUIRE(C8 <= 64, SRK_E_SHAPE, "dwconv3x3_bn_act: at most 512 channels (got %d)", 8 * C8);
+  SRK_REQUIRE(pre != out, SRK_E_SHAPE, "dwconv3x3_bn_act: pre and out must be two buffers");
+  const int tilesx = (W + DT_W - 1) / DT_W, tilesy = (H + DT_H - 1) / DT_H;
+  const long long nb = (long long)B * tilesx * tilesy;
+  SRK_REQUIRE(nb < (1LL << 31), SRK_E_SHAPE, "dwconv3x3_bn_act: too many tiles");
+  DwDual<true> d{reinterpret_cast<bf16_t*>(pre), ldpre, bn_scale, bn_shift};
+  hipLaunchKernelGGL(dwconv3x3_tile_kernel<true>, dim3((unsigned)nb, (unsigned)((8 * C8 + DT_CB - 1) / DT_CB)), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const bf16_t*>(x), ldx, w, bias, bias, (const bf16_t*)nullptr, 0, reinterpret_cast<bf16_t*>(out), ldo, B, H, W,
+                     8 * C8, 0, tilesx, tilesy, d);
+  g_dwconv_bn_act_launches.fetch_add(1);
+  return srk_check_launch("dwconv3x3_bn_act");
 }
 
 int srk_rowln_bf16(const uint16_t* x, int ldx, const float* gamma, const float* beta, uint16_t* out, int ldo, int64_t rows, int C, int CP_out,

@@ -90,6 +90,131 @@ __device__ void ci_forward_part(const CiParams& p, const float* pm_src, const Ci
   __syncthreads();
 }
 
+// The same with FROZEN statistics (the BatchNorm in eval mode): mean / rstd from the running buffers, nothing over the batch -- valid for
+// B = 1 -- and no buffer written.  Leaves what ci_forward_part leaves (var is not used).
+__device__ void ci_forward_part_frozen(const CiParams& p, const float* pm_src, const float* __restrict__ running_mean,
+                                       const float* __restrict__ running_var, const CiLds& l) {
+  const int tid = threadIdx.x, B = p.B, C = p.C, S = p.S;
+  for (int i = tid; i < S * C; i += CI_THREADS) {
+    l.W1[i] = p.W1[i];
+    l.W2[i] = p.W2[i];
+  }
+  for (int i = tid; i < B * C; i += CI_THREADS) {
+    const int b = i / C, c = i - b * C;
+    l.pm[i] = pm_src ? pm_src[i] : p.pooled[(long long)b * p.ldp + p.pad_of[c]] * p.inv_hw;
+  }
+  if (tid < S) {
+    l.mean[tid] = running_mean[tid];
+    l.rstd[tid] = 1.0f / sqrtf(running_var[tid] + p.eps);
+  }
+  __syncthreads();
+  for (int i = tid; i < B * S; i += CI_THREADS) {
+    const int b = i / S, s = i - b * S;
+    float acc = p.b1[s];
+    const float* w = l.W1 + s * C;
+    const float* x = l.pm + b * C;
+    for (int c = 0; c < C; ++c) acc = fmaf(x[c], w[c], acc);
+    const float z = (acc - l.mean[s]) * l.rstd[s];
+    l.zh[i] = z;
+    l.a[i] = gelu_f(fmaf(z, p.gamma[s], p.beta[s]));
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(CI_THREADS) void channel_interaction_frozen_fwd_kernel(const CiParams p, const float* __restrict__ running_mean,
+                                                                                    const float* __restrict__ running_var,
+                                                                                    float* __restrict__ pm_out, float* __restrict__ cgate) {
+  extern __shared__ __attribute__((aligned(16))) float ci_smem[];
+  const CiLds l = ci_carve(ci_smem, p.B, p.C, p.S);
+  const int tid = threadIdx.x, B = p.B, C = p.C, S = p.S;
+  for (int i = tid; i < B * p.CA; i += CI_THREADS) cgate[i] = 0.f;   // the padding channels of the gate
+  ci_forward_part_frozen(p, nullptr, running_mean, running_var, l);
+  for (int i = tid; i < B * C; i += CI_THREADS) {
+    const int b = i / C, c = i - b * C;
+    float acc = p.b2[c];
+    const float* w = l.W2 + c * S;
+    const float* x = l.a + b * S;
+    for (int s = 0; s < S; ++s) acc = fmaf(x[s], w[s], acc);
+    pm_out[i] = l.pm[i];
+    cgate[(long long)b * p.CA + p.pad_of[c]] = sigmoid_f(acc);
+  }
+}
+
+// backward with frozen statistics: d y = gamma rstd d(BatchNorm output) (no batch terms), d gamma = sum d(out) zh, d beta = sum d(out)
+__global__ __launch_bounds__(CI_THREADS) void channel_interaction_frozen_bwd_kernel(const CiParams p, const float* __restrict__ running_mean,
+                                                                                    const float* __restrict__ running_var,
+                                                                                    const float* __restrict__ pm_in, const float* __restrict__ dcg,
+                                                                                    int ldg, float* __restrict__ dW1, float* __restrict__ db1,
+                                                                                    float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                                    float* __restrict__ dW2, float* __restrict__ db2,
+                                                                                    float* __restrict__ dpool) {
+  extern __shared__ __attribute__((aligned(16))) float ci_smem[];
+  const CiLds l = ci_carve(ci_smem, p.B, p.C, p.S);
+  const int tid = threadIdx.x, B = p.B, C = p.C, S = p.S;
+  for (int i = tid; i < B * p.CA; i += CI_THREADS) dpool[i] = 0.f;
+  ci_forward_part_frozen(p, pm_in, running_mean, running_var, l);
+  for (int i = tid; i < B * C; i += CI_THREADS) {                     // d(pre-sigmoid) = d cgate * o (1 - o)
+    const int b = i / C, c = i - b * C;
+    float acc = p.b2[c];
+    const float* w = l.W2 + c * S;
+    const float* x = l.a + b * S;
+    for (int s = 0; s < S; ++s) acc = fmaf(x[s], w[s], acc);
+    const float o = sigmoid_f(acc);
+    l.dpre[i] = dcg[(long long)b * ldg + p.pad_of[c]] * o * (1.0f - o);
+  }
+  __syncthreads();
+  for (int i = tid; i < C * S; i += CI_THREADS) {                     // d W2 [C][S]
+    const int c = i / S, s = i - c * S;
+    float acc = 0.f;
+    for (int b = 0; b < B; ++b) acc = fmaf(l.dpre[b * C + c], l.a[b * S + s], acc);
+    dW2[i] = acc;
+  }
+  for (int c = tid; c < C; c += CI_THREADS) {
+    float acc = 0.f;
+    for (int b = 0; b < B; ++b) acc += l.dpre[b * C + c];
+    db2[c] = acc;
+  }
+  for (int i = tid; i < B * S; i += CI_THREADS) {                     // d a -> d(BatchNorm output) through GELU
+    const int b = i / S, s = i - b * S;
+    float acc = 0.f;
+    for (int c = 0; c < C; ++c) acc = fmaf(l.dpre[b * C + c], l.W2[c * S + s], acc);
+    l.dy[i] = acc * dgelu_shared_exp(fmaf(l.zh[i], p.gamma[s], p.beta[s]));
+  }
+  __syncthreads();
+  if (tid < S) {
+    float g = 0.f, bsum = 0.f;
+    for (int b = 0; b < B; ++b) {
+      g = fmaf(l.dy[b * S + tid], l.zh[b * S + tid], g);
+      bsum += l.dy[b * S + tid];
+    }
+    dgamma[tid] = g;
+    dbeta[tid] = bsum;
+  }
+  __syncthreads();
+  for (int i = tid; i < B * S; i += CI_THREADS) {                     // through the fixed affine map: d y
+    const int s = i % S;
+    l.dy[i] = p.gamma[s] * l.rstd[s] * l.dy[i];
+  }
+  __syncthreads();
+  for (int i = tid; i < S * C; i += CI_THREADS) {                     // d W1 [S][C]
+    const int s = i / C, c = i - s * C;
+    float acc = 0.f;
+    for (int b = 0; b < B; ++b) acc = fmaf(l.dy[b * S + s], l.pm[b * C + c], acc);
+    dW1[i] = acc;
+  }
+  if (tid < S) {
+    float acc = 0.f;
+    for (int b = 0; b < B; ++b) acc += l.dy[b * S + tid];
+    db1[tid] = acc;
+  }
+  for (int i = tid; i < B * C; i += CI_THREADS) {                     // d pm -> d pooled (/ HW), head-padded
+    const int b = i / C, c = i - b * C;
+    float acc = 0.f;
+    for (int s = 0; s < S; ++s) acc = fmaf(l.dy[b * S + s], l.W1[s * C + c], acc);
+    dpool[(long long)b * p.CA + p.pad_of[c]] = acc * p.inv_hw;
+  }
+}
+
 __global__ __launch_bounds__(CI_THREADS) void channel_interaction_fwd_kernel(const CiParams p, float* __restrict__ pm_out,
                                                                              float* __restrict__ cgate, float* __restrict__ running_mean,
                                                                              float* __restrict__ running_var, float momentum) {
@@ -364,6 +489,49 @@ int srk_channel_interaction_bwd(const float* pm, const float* dcgate, int ldg, f
   hipLaunchKernelGGL(channel_interaction_bwd_kernel, dim3(1), dim3(CI_THREADS), lds, (hipStream_t)stream, p, pm, dcgate, ldg, dW1, db1, dgamma,
                      dbeta, dW2, db2, dpool);
   return srk_check_launch("channel_interaction_bwd");
+}
+
+/* 1 when srk_channel_interaction_frozen_fwd / _bwd cover the shape: as above, and B = 1 is valid (no statistic is taken over the batch) */
+int srk_channel_interaction_frozen_covered(int B, int C, int S) {
+  return B > 0 && C > 0 && S > 0 && S <= 64 && ci_lds_floats(B, C, S, true) * 4 <= (size_t)CI_MAX_LDS;
+}
+
+int srk_channel_interaction_frozen_fwd(const float* pooled, int ldp, float inv_hw, const int* pad_of, const float* W1, const float* b1,
+                                       const float* gamma, const float* beta, float eps, const float* W2, const float* b2,
+                                       const float* running_mean, const float* running_var, float* pm_out, float* cgate, int B, int C, int S,
+                                       int CA, srk_stream_t stream) {
+  SRK_REQUIRE(pooled && pad_of && W1 && b1 && gamma && beta && W2 && b2 && running_mean && running_var && pm_out && cgate, SRK_E_NULL,
+              "channel_interaction_frozen_fwd: null pointer");
+  REQS(srk_channel_interaction_frozen_covered(B, C, S) && CA >= C && ldp >= CA,
+       "channel_interaction_frozen_fwd: B=%d C=%d S=%d CA=%d ldp=%d (S <= 64; CA >= C; ldp >= CA; the arrays must fit %d bytes of LDS)", B, C, S, CA,
+       ldp, CI_MAX_LDS);
+  static SrkPerDevice<int> st_pd;
+  const size_t lds = ci_lds_floats(B, C, S, false) * 4;
+  const int rc = ci_configure(reinterpret_cast<const void*>(&channel_interaction_frozen_fwd_kernel), lds, &st_pd.here());
+  if (rc) return rc;
+  CiParams p{pooled, ldp, inv_hw, pad_of, W1, b1, gamma, beta, W2, b2, eps, B, C, S, CA};
+  hipLaunchKernelGGL(channel_interaction_frozen_fwd_kernel, dim3(1), dim3(CI_THREADS), lds, (hipStream_t)stream, p, running_mean, running_var,
+                     pm_out, cgate);
+  return srk_check_launch("channel_interaction_frozen_fwd");
+}
+
+int srk_channel_interaction_frozen_bwd(const float* pm, const float* dcgate, int ldg, float inv_hw, const int* pad_of, const float* W1,
+                                       const float* b1, const float* gamma, const float* beta, float eps, const float* W2, const float* b2,
+                                       const float* running_mean, const float* running_var, float* dW1, float* db1, float* dgamma,
+                                       float* dbeta, float* dW2, float* db2, float* dpool, int B, int C, int S, int CA, srk_stream_t stream) {
+  SRK_REQUIRE(pm && dcgate && pad_of && W1 && b1 && gamma && beta && W2 && b2 && running_mean && running_var && dW1 && db1 && dgamma && dbeta &&
+                  dW2 && db2 && dpool,
+              SRK_E_NULL, "channel_interaction_frozen_bwd: null pointer");
+  REQS(srk_channel_interaction_frozen_covered(B, C, S) && CA >= C && ldg >= CA, "channel_interaction_frozen_bwd: B=%d C=%d S=%d CA=%d ldg=%d", B, C,
+       S, CA, ldg);
+  static SrkPerDevice<int> st_pd;
+  const size_t lds = ci_lds_floats(B, C, S, true) * 4;
+  const int rc = ci_configure(reinterpret_cast<const void*>(&channel_interaction_frozen_bwd_kernel), lds, &st_pd.here());
+  if (rc) return rc;
+  CiParams p{nullptr, 0, inv_hw, pad_of, W1, b1, gamma, beta, W2, b2, eps, B, C, S, CA};
+  hipLaunchKernelGGL(channel_interaction_frozen_bwd_kernel, dim3(1), dim3(CI_THREADS), lds, (hipStream_t)stream, p, running_mean, running_var, pm,
+                     dcgate, ldg, dW1, db1, dgamma, dbeta, dW2, db2, dpool);
+  return srk_check_launch("channel_interaction_frozen_bwd");
 }
 
 int srk_chan_attn_matrix_fwd(const float* partial, int nchunk, const float* temperature, float* gram, float* A, int B, int num_heads, int dh,

@@ -176,6 +176,44 @@ __global__ __launch_bounds__(256) void bn_train_bwd_coeffs_kernel(const float* _
   coef[4 * ld + c] = S1;
 }
 
+// BatchNorm with FROZEN statistics (the module in eval mode): the same coef [4][ld] = scale, shift, mean, rstd from the module's running
+// buffers instead of the batch -- no token pass in front of it, no buffer written.  gamma / beta in the padded layout, running_mean /
+// running_var in the module's own order (real_of as above; padding channels get scale = shift = mean = rstd = 0).
+__global__ __launch_bounds__(256) void bn_frozen_coeffs_kernel(int ld, int Cn, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                               float eps, const float* __restrict__ running_mean,
+                                                               const float* __restrict__ running_var, const int* __restrict__ real_of,
+                                                               float* __restrict__ coef) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= Cn) return;
+  const int rc = real_of ? real_of[c] : c;
+  float sc = 0.f, sh = 0.f, mean = 0.f, rstd = 0.f;
+  if (rc >= 0) {
+    mean = running_mean[rc];
+    rstd = 1.0f / sqrtf(running_var[rc] + eps);
+    sc = gamma[c] * rstd;
+    sh = beta[c] - mean * sc;
+  }
+  coef[c] = sc;
+  coef[ld + c] = sh;
+  coef[2 * ld + c] = mean;
+  coef[3 * ld + c] = rstd;
+}
+
+// ... and its backward: the statistics are constants, so d x = scale dz (B = C = 0); d gamma = rstd (S2 - mean S1), d beta = S1.  The
+// same coef [5][ld] contract as bn_train_bwd_coeffs_kernel: the token passes behind it run unchanged.
+__global__ __launch_bounds__(256) void bn_frozen_bwd_coeffs_kernel(const float* __restrict__ partial, int R, int rs, int ld, int Cn,
+                                                                   const float* __restrict__ fwd_coef, float* __restrict__ coef) {
+  float S1, S2;
+  const int c = bn_sum_rows(partial, R, rs, ld, Cn, S1, S2);
+  if (c < 0) return;
+  const float sc = fwd_coef[c], mean = fwd_coef[2 * ld + c], rstd = fwd_coef[3 * ld + c];
+  coef[c] = sc;
+  coef[ld + c] = 0.f;
+  coef[2 * ld + c] = 0.f;
+  coef[3 * ld + c] = rstd * (S2 - mean * S1);
+  coef[4 * ld + c] = S1;
+}
+
 // coefficient index of row t, channel c: (rps > 0 ? t / rps : 0) * CP + c
 // The GELU-derivative pass (mode 1) keeps the one-piece-per-thread grid-stride form: it is VALU-bound (erf + exp per element), and with
 // the row-walking mapping below it lost occupancy (37 -> 49 us with four rows per lane, 113 us with one).
@@ -858,6 +896,23 @@ int srk_bn_train_bwd_coeffs(const float* partial, int R, int row_stride, int ld,
   hipLaunchKernelGGL(bn_train_bwd_coeffs_kernel, dim3((C + 63) / 64), dim3(256), 0, (hipStream_t)stream, partial, R, row_stride, ld, C, n, fwd_coef,
                      coef);
   return srk_check_launch("bn_train_bwd_coeffs");
+}
+
+int srk_bn_frozen_coeffs(int ld, int C, const float* gamma, const float* beta, float eps, const float* running_mean, const float* running_var,
+                         const int* real_of, float* coef, srk_stream_t stream) {
+  SRK_REQUIRE(gamma && beta && running_mean && running_var && coef, SRK_E_NULL, "bn_frozen_coeffs: null pointer");
+  REQP(C > 0 && C <= ld && eps > 0.f, "bn_frozen_coeffs: bad shape (C=%d ld=%d eps=%g)", C, ld, (double)eps);
+  hipLaunchKernelGGL(bn_frozen_coeffs_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, ld, C, gamma, beta, eps, running_mean,
+                     running_var, real_of, coef);
+  return srk_check_launch("bn_frozen_coeffs");
+}
+
+int srk_bn_frozen_bwd_coeffs(const float* partial, int R, int row_stride, int ld, int C, const float* fwd_coef, float* coef, srk_stream_t stream) {
+  SRK_REQUIRE(partial && fwd_coef && coef, SRK_E_NULL, "bn_frozen_bwd_coeffs: null pointer");
+  REQP(R > 0 && C > 0 && C <= ld && row_stride >= 2 * ld, "bn_frozen_bwd_coeffs: bad shape");
+  hipLaunchKernelGGL(bn_frozen_bwd_coeffs_kernel, dim3((C + 63) / 64), dim3(256), 0, (hipStream_t)stream, partial, R, row_stride, ld, C, fwd_coef,
+                     coef);
+  return srk_check_launch("bn_frozen_bwd_coeffs");
 }
 
 int64_t srk_chan_stats_chunks(int64_t rows) { return rows <= 0 ? 0 : (rows + ST_ROWS - 1) / ST_ROWS; }

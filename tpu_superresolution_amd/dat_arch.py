@@ -412,15 +412,20 @@ class DAT(nn.Module):
         if p0.device != x.device:
             raise RuntimeError(f"input is on {x.device} but the model is on {p0.device}")
         _lib.claim_device(x.device.index if x.device.index is not None else torch.cuda.current_device())
-        if self.training:
-            # train mode: BatchNorm normalises with the batch's statistics and moves its running estimates, DropPath factors are drawn
-            # here (dat_arch.py:562-563) and passed to the kernels as data; with grad enabled the whole model is ONE autograd node whose
-            # backward is dat_train.dat_backward
+        want_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if self.training or want_grad:
+            # Every BatchNorm follows its OWN ``training`` flag (nn.BatchNorm2d's rule, read at every forward): in training mode it normalises
+            # with the batch's statistics and moves its running estimates, in eval mode ("frozen") it normalises with its running estimates
+            # and writes nothing -- so model.eval() with grad enabled is the fine-tuning step with frozen statistics.  DropPath follows
+            # self.training: the factors are drawn here (dat_arch.py:562-563) and passed to the kernels as data.  With grad enabled the whole
+            # model is ONE autograd node whose backward is dat_train.dat_backward
             from .dat_train import DATFunction, dat_forward_train, pack_train
-            drop = getattr(self, "_drop_override", None)          # training.GraphedTrainStep draws the factors outside its graph
-            if drop is None:
-                drop = self.draw_drop_path(x.shape[0], x.device)
-            if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            drop = None
+            if self.training:
+                drop = getattr(self, "_drop_override", None)          # training.GraphedTrainStep draws the factors outside its graph
+                if drop is None:
+                    drop = self.draw_drop_path(x.shape[0], x.device)
+            if want_grad:
                 return DATFunction.apply(self, x, drop, *[p for _, p in self.named_parameters()])
             with torch.no_grad(), torch.cuda.device(x.device):
                 return dat_forward_train(self, x.contiguous().float(), self._pack(x.device, True), pack_train(self, x.device), drop)[0]

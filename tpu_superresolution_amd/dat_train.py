@@ -1,5 +1,5 @@
-"""DAT training on MI355X: the forward that keeps what the backward needs (BatchNorm in training mode: batch statistics, running
-statistics updated) and the backward pass, as host-side sequences of C-ABI calls (include/srk.h) -- the training-mode counterpart
+"""DAT training on MI355X: the forward that keeps what the backward needs (every BatchNorm as its own ``training`` flag says: batch
+statistics and running statistics updated, or -- the module in eval mode, "frozen" -- its running statistics and no buffer written) and the backward pass, as host-side sequences of C-ABI calls (include/srk.h) -- the training-mode counterpart
 of ``dat_arch._dat_forward``, in the manner of ``hat_train``.
 
 Reference: dat_arch.py:366-446 (Adaptive_Spatial_Attention.forward), :481-528 (Adaptive_Channel_Attention.forward), :74-90 (SGFN),
@@ -17,6 +17,11 @@ BatchNorm (training) for a channel with n values x: mu = sum x / n, var = sum x^
 z = x * s + t with s = gamma * rstd, t = beta - mu * s.  Backward with S1 = sum dz, S2 = sum dz * x:
 d beta = S1, d gamma = rstd * (S2 - mu * S1), d x = A dz + B x + C with A = s, B = -s * rstd * d gamma / n,
 C = (s / n) * (mu * rstd * d gamma - S1).  The running estimates move by momentum 0.1 (unbiased variance), as nn.BatchNorm2d.
+
+BatchNorm (frozen: ``not bn.training`` and running buffers present, nn.BatchNorm2d's own rule, read per module at every forward): mu / var
+are the running buffers, constants of the step: s, t as above, d beta = S1, d gamma = rstd * (S2 - mu * S1), d x = s dz (B = C = 0).  No
+statistics pass runs in front of it (srk_bn_frozen_coeffs reads the buffers), the depth-wise-conv branch is ONE token pass
+(srk_dwconv3x3_bn_act), channel_interaction is valid at batch size 1, and no buffer is written.
 """
 from __future__ import annotations
 
@@ -86,6 +91,20 @@ def _bn_forward(L, st, part: torch.Tensor, R: int, row_stride: int, ld: int, Cn:
     return coef
 
 
+def _bn_live(bn) -> bool:
+    """nn.BatchNorm2d's rule: batch statistics (and moving buffers) iff the module is in training mode or has no running buffers"""
+    return bool(bn.training) or bn.running_mean is None
+
+
+def _bn_frozen(L, st, ld: int, Cn: int, gamma: torch.Tensor, beta: torch.Tensor, bn, real_of: Optional[torch.Tensor]) -> torch.Tensor:
+    """running buffers -> coef [4][ld] = scale, shift, mean, rstd in ONE launch (srk_bn_frozen_coeffs); no buffer is written"""
+    coef = torch.empty(4, ld, dtype=torch.float32, device=gamma.device)
+    rm, rv = bn.running_mean.float(), bn.running_var.float()
+    check(L.srk_bn_frozen_coeffs(ld, Cn, gamma.data_ptr(), beta.data_ptr(), float(bn.eps), rm.data_ptr(), rv.data_ptr(),
+                                 None if real_of is None else real_of.data_ptr(), coef.data_ptr(), st))
+    return coef
+
+
 def real_of_inverse(real_of: torch.Tensor) -> torch.Tensor:
     """padded position of every real channel (the positions where real_of >= 0, ordered by the real index)"""
     pos = torch.nonzero(real_of >= 0).flatten()
@@ -102,9 +121,13 @@ def _bn_update(bn: nn.BatchNorm2d, mean: torch.Tensor, var: torch.Tensor, n: int
     bn.running_var.mul_(1.0 - mom).add_((var * (n / max(n - 1, 1))).to(bn.running_var.dtype), alpha=mom)
 
 
-def _channel_interaction(pm: torch.Tensor, ci: nn.Sequential, stats: Optional[dict] = None) -> torch.Tensor:
-    """pooled mean [B][C] -> sigmoid(channel map) [B][C]  (dat_arch.py:315-321 on a 1 x 1 map, BatchNorm over the batch)"""
+def _channel_interaction(pm: torch.Tensor, ci: nn.Sequential, stats: Optional[dict] = None, frozen: bool = False) -> torch.Tensor:
+    """pooled mean [B][C] -> sigmoid(channel map) [B][C]  (dat_arch.py:315-321 on a 1 x 1 map, BatchNorm over the batch; frozen: with the
+    module's running statistics, any batch size)"""
     y = F.linear(pm, ci[1].weight.flatten(1), ci[1].bias)
+    if frozen:
+        y = (y - ci[2].running_mean.float()) * torch.rsqrt(ci[2].running_var.float() + ci[2].eps) * ci[2].weight + ci[2].bias
+        return torch.sigmoid(F.linear(F.gelu(y), ci[4].weight.flatten(1), ci[4].bias))
     n = y.shape[0]
     if n <= 1:
         raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(y.shape) + (1, 1)}")
@@ -130,6 +153,13 @@ def _ci_fused_ok(B: int, C: int, S: int, ci: nn.Sequential) -> bool:
     bn = ci[2]
     return (bool(lib().srk_channel_interaction_covered(B, C, S)) and bn.affine and ci[1].weight.dtype == torch.float32
             and (not bn.track_running_stats or bn.running_mean is None or (bn.momentum is not None and bn.running_mean.dtype == torch.float32)))
+
+
+def _ci_frozen_ok(B: int, C: int, S: int, ci: nn.Sequential) -> bool:
+    """srk_channel_interaction_frozen_fwd / _bwd cover this shape (B >= 1) and the buffers are fp32"""
+    bn = ci[2]
+    return (bool(lib().srk_channel_interaction_frozen_covered(B, C, S)) and bn.affine and ci[1].weight.dtype == torch.float32
+            and bn.running_mean.dtype == torch.float32 and bn.running_var.dtype == torch.float32)
 
 
 def _hm32(hm: torch.Tensor) -> torch.Tensor:
@@ -336,16 +366,23 @@ def dat_forward_train(m, x: torch.Tensor, P: Dict[str, torch.Tensor], PT: Dict[s
             v_ptr = qkv.data_ptr() + 2 * CA * 2
             # DW-conv branch on v (:418 / :508): conv (+ bias), BatchNorm with the batch's statistics, GELU
             c_pre, conv = torch.empty(T, CA, **b16), torch.empty(T, CA, **b16)
-            check(L.srk_dwconv3x3(v_ptr, 3 * CA, P[pre + "dw_w"].data_ptr(), ones.data_ptr(), PT[pre + "dw_b"].data_ptr(), None, 0, c_pre.data_ptr(),
-                                  CA, B, H, W, CA // 8, 0, st))
-            part = torch.empty(B, n_chunks, 2, CA, **f32)
-            check(L.srk_chan_stats(c_pre.data_ptr(), CA, c_pre.data_ptr(), CA, part.data_ptr(), B, HW, CA // 8, st))
             real_of = ha._cached_map(("real_of", nH, dh, str(dev)), lambda: torch.full((CA,), -1, dtype=torch.int32, device=dev).scatter_(
                 0, hm, torch.arange(C_, dtype=torch.int32, device=dev)))
-            dw_coef = _bn_forward(L, st, part, B * n_chunks, 2 * CA, CA, CA, T, PT[pre + "dw_gam"], PT[pre + "dw_bet"], at.dwconv[1], real_of)
-            dw_s, dw_t = dw_coef[0], dw_coef[1]
-            check(L.srk_affine_act_bf16(c_pre.data_ptr(), CA, dw_s.data_ptr(), dw_t.data_ptr(), conv.data_ptr(), CA, T, CA // 8, 0, 1, st))
-            bk.update(dw_s=dw_s, dw_t=dw_t, dw_coef=dw_coef)
+            dw_live = _bn_live(at.dwconv[1])
+            if dw_live:
+                check(L.srk_dwconv3x3(v_ptr, 3 * CA, P[pre + "dw_w"].data_ptr(), ones.data_ptr(), PT[pre + "dw_b"].data_ptr(), None, 0, c_pre.data_ptr(),
+                                      CA, B, H, W, CA // 8, 0, st))
+                part = torch.empty(B, n_chunks, 2, CA, **f32)
+                check(L.srk_chan_stats(c_pre.data_ptr(), CA, c_pre.data_ptr(), CA, part.data_ptr(), B, HW, CA // 8, st))
+                dw_coef = _bn_forward(L, st, part, B * n_chunks, 2 * CA, CA, CA, T, PT[pre + "dw_gam"], PT[pre + "dw_bet"], at.dwconv[1], real_of)
+                dw_s, dw_t = dw_coef[0], dw_coef[1]
+                check(L.srk_affine_act_bf16(c_pre.data_ptr(), CA, dw_s.data_ptr(), dw_t.data_ptr(), conv.data_ptr(), CA, T, CA // 8, 0, 1, st))
+            else:       # frozen: coefficients from the running buffers, then conv + bias -> c_pre and gelu(BatchNorm) -> conv in ONE token pass
+                dw_coef = _bn_frozen(L, st, CA, CA, PT[pre + "dw_gam"], PT[pre + "dw_bet"], at.dwconv[1], real_of)
+                dw_s, dw_t = dw_coef[0], dw_coef[1]
+                check(L.srk_dwconv3x3_bn_act(v_ptr, 3 * CA, P[pre + "dw_w"].data_ptr(), PT[pre + "dw_b"].data_ptr(), dw_s.data_ptr(), dw_t.data_ptr(),
+                                             c_pre.data_ptr(), CA, conv.data_ptr(), CA, B, H, W, CA // 8, st))
+            bk.update(dw_s=dw_s, dw_t=dw_t, dw_coef=dw_coef, dw_live=dw_live)
             att = torch.empty(T, CA, **b16)
             if bk["spatial"]:
                 biases = []
@@ -373,7 +410,20 @@ def dat_forward_train(m, x: torch.Tensor, P: Dict[str, torch.Tensor], PT: Dict[s
             pooled, _ = token_sums(gate_src.data_ptr(), CA, gate_src.data_ptr(), CA, CA // 8, per_sample=True)
             ci = at.channel_interaction
             S1 = ci[1].weight.shape[0]
-            if _ci_fused_ok(B, C_, S1, ci):
+            ci_live = _bn_live(ci[2])
+            bk["ci_live"] = ci_live
+            if not ci_live and _ci_frozen_ok(B, C_, S1, ci):
+                pm, cgate = torch.empty(B, C_, **f32), torch.empty(B, CA, **f32)
+                bnc = ci[2]
+                check(L.srk_channel_interaction_frozen_fwd(pooled.data_ptr(), pooled.stride(0), 1.0 / HW, _hm32(hm).data_ptr(), ci[1].weight.data_ptr(),
+                                                           ci[1].bias.data_ptr(), bnc.weight.data_ptr(), bnc.bias.data_ptr(), float(bnc.eps),
+                                                           ci[4].weight.data_ptr(), ci[4].bias.data_ptr(), bnc.running_mean.data_ptr(),
+                                                           bnc.running_var.data_ptr(), pm.data_ptr(), cgate.data_ptr(), B, C_, S1, CA, st))
+            elif not ci_live:
+                pm = (pooled / HW)[:, hm].contiguous()
+                cgate = torch.zeros(B, CA, **f32)
+                cgate[:, hm] = _channel_interaction(pm, ci, frozen=True)
+            elif _ci_fused_ok(B, C_, S1, ci):
                 pm, cgate = torch.empty(B, C_, **f32), torch.empty(B, CA, **f32)
                 bnc = ci[2]
                 track = bnc.track_running_stats and bnc.running_mean is not None
@@ -395,11 +445,16 @@ def dat_forward_train(m, x: torch.Tensor, P: Dict[str, torch.Tensor], PT: Dict[s
             si = at.spatial_interaction
             S2 = si[0].weight.shape[0]
             nblk = (T + 255) // 256
-            part = torch.empty(nblk, 2, 16, **f32)
             w0raw, b0raw = PT[pre + "si_w0raw"], si[0].bias.float().contiguous()
-            check(L.srk_spatial_gate_train(0, tok_src.data_ptr(), CA, w0raw.data_ptr(), b0raw.data_ptr(), None, None, None, None, None, None, None,
-                                           None, 0, 0, part.data_ptr(), T, CA, S2, st))
-            si_coef = _bn_forward(L, st, part, nblk, 32, 16, S2, T, si[1].weight.float(), si[1].bias.float(), si[1], None)
+            si_live = _bn_live(si[1])
+            bk["si_live"] = si_live
+            if si_live:
+                part = torch.empty(nblk, 2, 16, **f32)
+                check(L.srk_spatial_gate_train(0, tok_src.data_ptr(), CA, w0raw.data_ptr(), b0raw.data_ptr(), None, None, None, None, None, None, None,
+                                               None, 0, 0, part.data_ptr(), T, CA, S2, st))
+                si_coef = _bn_forward(L, st, part, nblk, 32, 16, S2, T, si[1].weight.float(), si[1].bias.float(), si[1], None)
+            else:       # frozen: no statistics pass over the tokens
+                si_coef = _bn_frozen(L, st, 16, S2, si[1].weight.float(), si[1].bias.float(), si[1], None)
             si_s, si_t = si_coef[0, :S2], si_coef[1, :S2]
             tgate = torch.empty(T, **f32)
             w3 = si[3].weight.float().reshape(S2).contiguous()
@@ -667,7 +722,18 @@ def dat_backward(m, S: dict, dy: torch.Tensor, hook=None) -> Dict[str, torch.Ten
             ci = at.channel_interaction
             ci_params = [ci[1].weight, ci[1].bias, ci[2].weight, ci[2].bias, ci[4].weight, ci[4].bias]
             S1 = ci[1].weight.shape[0]
-            if _ci_fused_ok(B, C_, S1, ci):
+            if not bk["ci_live"] and _ci_frozen_ok(B, C_, S1, ci):
+                dcg = _sum_rows(dcg_part, B, nck)                                       # [B][CA], head-padded
+                gci = [torch.empty(p_.shape, **f32) for p_ in ci_params]
+                dpool = torch.empty(B, CA, **f32)
+                check(L.srk_channel_interaction_frozen_bwd(bk["pm"].data_ptr(), dcg.data_ptr(), CA, 1.0 / HW, _hm32(hm).data_ptr(), ci[1].weight.data_ptr(),
+                                                           ci[1].bias.data_ptr(), ci[2].weight.data_ptr(), ci[2].bias.data_ptr(), float(ci[2].eps),
+                                                           ci[4].weight.data_ptr(), ci[4].bias.data_ptr(), ci[2].running_mean.data_ptr(),
+                                                           ci[2].running_var.data_ptr(), gci[0].data_ptr(), gci[1].data_ptr(), gci[2].data_ptr(),
+                                                           gci[3].data_ptr(), gci[4].data_ptr(), gci[5].data_ptr(), dpool.data_ptr(), B, C_, S1, CA, st))
+                for p_, g_ in zip(ci_params, gci):
+                    G[pname(p_)] = g_
+            elif _ci_fused_ok(B, C_, S1, ci) and bk["ci_live"]:
                 dcg = _sum_rows(dcg_part, B, nck)                                       # [B][CA], head-padded
                 gci = [torch.empty(p_.shape, **f32) for p_ in ci_params]
                 dpool = torch.empty(B, CA, **f32)
@@ -681,7 +747,7 @@ def dat_backward(m, S: dict, dy: torch.Tensor, hook=None) -> Dict[str, torch.Ten
             else:
                 with torch.enable_grad():
                     pm = bk["pm"].detach().requires_grad_(True)
-                    cg = _channel_interaction(pm, ci)
+                    cg = _channel_interaction(pm, ci, frozen=not bk["ci_live"])
                     grads = torch.autograd.grad(cg, [pm] + ci_params, dcg_part.sum(1)[:, hm])
                 for p_, g_ in zip(ci_params, grads[1:]):
                     put(p_, g_)
@@ -701,7 +767,10 @@ def dat_backward(m, S: dict, dy: torch.Tensor, hook=None) -> Dict[str, torch.Ten
                                            dsmap.data_ptr(), None, None, None, None, 0, 0, part.data_ptr(), T, CA, S2, st))
             ps = _sum_rows(part, 1, nblk).view(4, 16)
             bc = torch.empty(5, 16, **f32)
-            check(L.srk_bn_train_bwd_coeffs(part.data_ptr(), nblk, 64, 16, S2, float(T), si_coef.data_ptr(), bc.data_ptr(), st))
+            if bk["si_live"]:
+                check(L.srk_bn_train_bwd_coeffs(part.data_ptr(), nblk, 64, 16, S2, float(T), si_coef.data_ptr(), bc.data_ptr(), st))
+            else:
+                check(L.srk_bn_frozen_bwd_coeffs(part.data_ptr(), nblk, 64, 16, S2, si_coef.data_ptr(), bc.data_ptr(), st))
             cA, cB, cC = bc[0], bc[1], bc[2]
             put(si[1].weight, bc[3, :S2])
             put(si[1].bias, bc[4, :S2])
@@ -723,13 +792,19 @@ def dat_backward(m, S: dict, dy: torch.Tensor, hook=None) -> Dict[str, torch.Ten
             part = torch.empty(B, n_chunks, 2, CA, **f32)
             check(L.srk_chan_stats(dz.data_ptr(), CA, c_pre.data_ptr(), CA, part.data_ptr(), B, HW, CA // 8, st))
             bc = torch.empty(5, CA, **f32)
-            check(L.srk_bn_train_bwd_coeffs(part.data_ptr(), B * n_chunks, 2 * CA, CA, CA, float(T), bk["dw_coef"].data_ptr(), bc.data_ptr(), st))
+            if bk["dw_live"]:
+                check(L.srk_bn_train_bwd_coeffs(part.data_ptr(), B * n_chunks, 2 * CA, CA, CA, float(T), bk["dw_coef"].data_ptr(), bc.data_ptr(), st))
+            else:
+                check(L.srk_bn_frozen_bwd_coeffs(part.data_ptr(), B * n_chunks, 2 * CA, CA, CA, bk["dw_coef"].data_ptr(), bc.data_ptr(), st))
             cA, cB, cC = bc[0], bc[1], bc[2]
             put(at.dwconv[1].weight, bc[3][hm])
             put(at.dwconv[1].bias, bc[4][hm])
             dcpre = d_conv                                          # (re-used buffer)
-            check(L.srk_lincomb2_bf16(dz.data_ptr(), CA, c_pre.data_ptr(), CA, cA.data_ptr(), cB.data_ptr(), cC.data_ptr(), dcpre.data_ptr(), CA, T,
-                                      CA // 8, 0, 0, st))
+            if bk["dw_live"]:
+                check(L.srk_lincomb2_bf16(dz.data_ptr(), CA, c_pre.data_ptr(), CA, cA.data_ptr(), cB.data_ptr(), cC.data_ptr(), dcpre.data_ptr(), CA, T,
+                                          CA // 8, 0, 0, st))
+            else:       # frozen: d x = A dz, c_pre is not read
+                check(L.srk_lincomb2_bf16(dz.data_ptr(), CA, None, 0, cA.data_ptr(), None, None, dcpre.data_ptr(), CA, T, CA // 8, 0, 0, st))
             dwconv_grads(dcpre.data_ptr(), CA, v_ptr, 3 * CA, CA, at.dwconv[0], hm)
             dv_conv = dz                                            # (re-used buffer)
             check(L.srk_dwconv3x3(dcpre.data_ptr(), CA, PT[pre + "dw_wf"].data_ptr(), ones.data_ptr(), zeros.data_ptr(), None, 0, dv_conv.data_ptr(), CA,
@@ -799,8 +874,8 @@ def dat_backward(m, S: dict, dy: torch.Tensor, hook=None) -> Dict[str, torch.Ten
 
 
 class DATFunction(torch.autograd.Function):
-    """One autograd node for the whole model (as HATFunction): forward keeps the activations and updates the BatchNorm running
-    statistics, backward returns every parameter's gradient.  The input image gets no gradient."""
+    """One autograd node for the whole model (as HATFunction): forward keeps the activations and updates the running statistics of
+    the BatchNorms that are in training mode, backward returns every parameter's gradient.  The input image gets no gradient."""
 
     @staticmethod
     def forward(ctx, model, x, drop, *params):

@@ -32,7 +32,7 @@ from . import SwinIR
 from .distributed import DataParallelSwinIR, init_from_env
 from .optim import FusedAdamW
 from .sr_datasets import PairTransformTrain, PairTransformValid, Shuffled2DPaired
-from .training import assert_finite_step, l1_loss, train_step
+from .training import assert_finite_step, freeze_batchnorm, l1_loss, train_step
 
 
 def fmt(seconds: float) -> str:
@@ -94,9 +94,13 @@ class DevicePoolLoader:
             yield self.pool.sample(mine[b * self.batch_size:(b + 1) * self.batch_size])
 
 
-def train_one_epoch(model, loader, optimizer, device, sync=None, check_finite=True, graphed=None):
-    """graphed: a training.GraphedTrainStep over (model, optimizer) that runs the step instead of train_step (--graph)."""
+def train_one_epoch(model, loader, optimizer, device, sync=None, check_finite=True, graphed=None, freeze_bn=False):
+    """graphed: a training.GraphedTrainStep over (model, optimizer) that runs the step instead of train_step (--graph).
+    freeze_bn: every BatchNorm stays in eval mode (running statistics, no buffer moves): re-applied here because model.train() switches
+    them all back on, and before the first graphed step captures the launch sequence."""
     model.train()
+    if freeze_bn:
+        freeze_batchnorm(model)
     total, n, t0 = 0.0, 0, time.time()
     for lr, hr in loader:
         lr, hr = lr.to(device, non_blocking=True), hr.to(device, non_blocking=True)
@@ -189,6 +193,9 @@ def main(argv=None):
                     help="additive: the model to fine-tune (build_sr_model)")
     ap.add_argument("--graph", action="store_true",
                     help="additive, --arch hat|dat, one process: capture the train step into a hipGraph and replay it")
+    ap.add_argument("--freeze_bn", action="store_true",
+                    help="additive, --arch dat: fine-tune with every BatchNorm in eval mode (running statistics, no buffer moves; "
+                         "allows --batch_size 1); swinir / hat have no BatchNorm")
     ap.add_argument("--ema_decay", type=float, default=0.0,
                     help="additive: keep an exponential moving average of the weights inside the fused optimizer step (0 = off; "
                          "published recipes use 0.999); validation runs on it and checkpoints gain 'params_ema'")
@@ -248,6 +255,11 @@ def main(argv=None):
                 froze += 1
         if rank == 0:
             print(f"[freeze] regex='{args.freeze_regex}', froze_params={froze}")
+    if args.freeze_bn:
+        n_bn = freeze_batchnorm(model)          # train_one_epoch re-applies it after every model.train()
+    if args.freeze_bn and rank == 0:
+        print(f"[freeze_bn] {n_bn} BatchNorm layers use their running statistics" if n_bn else
+              f"[freeze_bn] --arch {args.arch} has no BatchNorm layer: nothing to freeze")
     if rank == 0:
         n_train = sum(1 for p in model.parameters() if p.requires_grad)
         print(f"[params] trainable tensors: {n_train} / total: {len(list(model.parameters()))}")
@@ -283,7 +295,8 @@ def main(argv=None):
     for epoch in range(1, args.epochs + 1):
         if sampler is not None:
             sampler.set_epoch(epoch)
-        tr_loss, tr_t = train_one_epoch(model, train_loader, opt, device, dp if world > 1 else None, graphed=graphed)
+        tr_loss, tr_t = train_one_epoch(model, train_loader, opt, device, dp if world > 1 else None, graphed=graphed,
+                                        freeze_bn=args.freeze_bn)
         if args.ema_decay:          # validate what gets shipped: the averaged weights (ranks hold identical averages)
             with opt.swap_ema():
                 val_loss, val_psnr, val_t = validate(model, valid_loader, device)

@@ -51,6 +51,25 @@ def train_step(model, optimizer, lr_img: torch.Tensor, hr_img: torch.Tensor, syn
     return loss.detach(), bad
 
 
+def freeze_batchnorm(model) -> int:
+    """Put every nn.BatchNorm* of the model into eval mode -- it then normalises with its running statistics and writes no buffer, also
+    inside a training step (DAT reads the flag per module at every forward) -- and return how many there are.  ``model.train()``
+    switches them all back on: call this again after it."""
+    n = 0
+    for mod in model.modules():
+        if isinstance(mod, torch.nn.modules.batchnorm._BatchNorm):
+            mod.eval()
+            n += 1
+    return n
+
+
+def batchnorm_state(model) -> Tuple[bool, Tuple[bool, ...]]:
+    """(model.training, the ``training`` flag of every nn.BatchNorm* in module order): what decides a host-orchestrated model's launch
+    sequence besides the shapes"""
+    return bool(model.training), tuple(bool(mod.training) for mod in model.modules()
+                                       if isinstance(mod, torch.nn.modules.batchnorm._BatchNorm))
+
+
 def assert_finite_step(loss: torch.Tensor, bad: torch.Tensor) -> None:
     """Host-side check with the reference's error behaviour (RuntimeError on non-finite output / loss)."""
     nb = int(bad)
@@ -73,7 +92,9 @@ class GraphedTrainStep:
     (world size 1: collectives stay outside graphs here), nothing in the step that reads a device value on the host.  The first call
     runs ``warmup`` eager steps (kernel attributes, caches and workspaces get set up outside the capture), then captures.  DropPath
     factors are drawn OUTSIDE the graph, before every replay, into a static buffer the captured forward reads (``model.draw_drop_path``
-    / ``model._drop_override``): a fresh draw per step does not depend on how the graph-captured generator advances.
+    / ``model._drop_override``): a fresh draw per step does not depend on how the graph-captured generator advances.  The captured
+    launch sequence depends on ``model.training`` and on every BatchNorm's ``training`` flag (batch or running statistics,
+    ``freeze_batchnorm``): they are recorded at capture, and a replay under another state raises ``ValueError``.
 
     With an ``optim.FusedAdamW`` the step is the project's own: no ``clip_grad_norm_`` (the optimizer's ``max_grad_norm`` clips on the
     device; the ``max_grad_norm`` argument here is not used) and ``opt.step(nonfinite=bad)``, so a non-finite prediction inside a replay
@@ -92,6 +113,7 @@ class GraphedTrainStep:
             raise ValueError("GraphedTrainStep is for host-orchestrated models (HAT / DAT); SwinIR's step is one C call per pass already")
         self.graph = None
         self.x = self.t = self.loss = self.bad = self.drop = None
+        self.bn_state = None
 
     def _eager(self, x, t):
         self.opt.zero_grad(set_to_none=True)
@@ -119,11 +141,22 @@ class GraphedTrainStep:
                 for _ in range(max(self.warmup, 1)):
                     self._eager(self.x, self.t)
             torch.cuda.current_stream(lr_img.device).wait_stream(side)
+            self.bn_state = batchnorm_state(self.model)
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
                 self.loss, self.bad = self._eager(self.x, self.t)
         elif lr_img.shape != self.x.shape or hr_img.shape != self.t.shape:
             raise ValueError(f"GraphedTrainStep was captured for {tuple(self.x.shape)} -> {tuple(self.t.shape)}")
+        now = batchnorm_state(self.model)
+        if now != self.bn_state:
+            (tr0, bn0), (tr1, bn1) = self.bn_state, now
+            diff = [i for i, (a, b) in enumerate(zip(bn0, bn1)) if a != b]
+            what = [f"model.training {tr0} -> {tr1}"] if tr0 != tr1 else []
+            if diff or len(bn0) != len(bn1):
+                what.append(f"{len(diff)} of {len(bn0)} BatchNorm training flags differ (first: BatchNorm #{diff[0] if diff else min(len(bn0), len(bn1))}, "
+                            f"{sum(bn0)} in training mode at capture, {sum(bn1)} now)")
+            raise ValueError("GraphedTrainStep: the captured launch sequence depends on the train / eval state it was captured in; "
+                             + "; ".join(what) + " -- restore the state (freeze_batchnorm after model.train()) or build a new GraphedTrainStep")
         self.x.copy_(lr_img)
         self.t.copy_(hr_img)
         if self.drop is not None:
