@@ -354,6 +354,18 @@ int srk_win_attention_fwd_padded(const uint16_t* qkv, int ldq, int CA, const flo
  * SRK_E_UNSUPPORTED outside 2 <= ws <= 7, SRK_E_SHAPE when H or W is not a multiple of ws. */
 int srk_win_small_attention_fwd(const uint16_t* qkv, int ldq, int CA, const float* table, uint16_t* out, int ldo, int B, int H, int W,
                                 int ws, int shift, int num_heads, float scale, srk_stream_t stream);
+/* Gradient of srk_win_small_attention_fwd (csrc/attn_small_bwd.hip; WindowAttention.forward network_swinir.py:114-145 and the roll /
+ * partition / reverse of SwinTransformerBlock.forward :240-279 backwards), same conventions: qkv as the forward read it; d_out bf16
+ * [T][ldo] raster = gradient of the attention output (head h at columns 32 h, ldo % 8 == 0); d_qkv bf16 [T][ldq] in the layout of
+ * qkv (q gradient w.r.t. the UNSCALED q, as qkv holds it) is WRITTEN: every element of rows 0 .. T - 1, columns 0 .. 3 CA - 1, nothing
+ * else (no pre-zeroing; columns head_dim .. 31 of a head come out 0 when they are 0 in qkv and d_out); d_table fp32
+ * [(2 ws - 1)^2][num_heads] is ACCUMULATED.  Padded queries and padded keys contribute exactly nothing.  scratch:
+ * srk_win_small_attention_bwd_scratch bytes, 16-byte aligned, fully written before it is read (needs no zeroing).
+ * SRK_E_UNSUPPORTED outside 2 <= ws <= 7, SRK_E_SHAPE when H or W is not a multiple of ws or shift is outside [0, ws). */
+size_t srk_win_small_attention_bwd_scratch(int B, int H, int W, int ws, int num_heads);
+int srk_win_small_attention_bwd(const uint16_t* qkv, int ldq, int CA, const float* table, const uint16_t* d_out, int ldo,
+                                uint16_t* d_qkv, float* d_table, void* scratch, int B, int H, int W, int ws, int shift,
+                                int num_heads, float scale, srk_stream_t stream);
 /* ChannelAttention gate of CAB (:41-57): gate[b][c] = out_scale * sigmoid(W2 relu(W1 mean_b + b1) + b2), mean over the HW tokens
  * of x bf16 [B*HW][CP]; w1 [S][C], w2 [C][S] fp32 (the 1x1 convs).  workspace: srk_channel_gate_workspace bytes. */
 size_t srk_channel_gate_workspace(int B, int HW, int CP);

@@ -65,7 +65,7 @@ def _load_state(path: str, param_key: str = "auto"):
     return ckpt, "[ckpt] loaded raw state_dict"
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=str, choices=["X2", "X4"], required=True, help="dataset configuration")
     ap.add_argument("--data_root", type=str, default="DeepRockSR-2D")
@@ -82,7 +82,15 @@ def main(argv=None):
     ap.add_argument("--param_key", type=str, choices=["auto", *PARAM_KEYS], default="auto",
                     help="additive: which envelope of the checkpoint to load (auto: model, then params, then params_ema)")
     ap.add_argument("--device", type=str, default=None, help="additive: force 'cpu' / 'cuda' (default: cuda if available)")
+    ap.add_argument("--window_size", type=int, default=8, help="additive, --arch swinir: SwinIR(window_size=N), N in 2..8")
     args = ap.parse_args(argv)
+    if not 2 <= args.window_size <= 8 or (args.window_size != 8 and args.arch != "swinir"):
+        ap.error(f"--window_size must be in 2..8 and is an option of --arch swinir (got {args.window_size} with --arch {args.arch})")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
 
     device = torch.device(args.device) if args.device else torch.device("cuda" if torch.cuda.is_available() else "cpu")
     print("[device]", device, torch.cuda.get_device_name(0) if device.type == "cuda" else "-")
@@ -126,7 +134,7 @@ def main(argv=None):
 
     if swin:
         from .finetune_swinir import build_sr_model
-        model = build_sr_model(args.arch, scale_int, drop_path_rate=0.0)
+        model = build_sr_model(args.arch, scale_int, drop_path_rate=0.0, window_size=args.window_size)
     else:
         model = MS_ResUNet()
     state, msg = _load_state(args.ckpt, args.param_key)

@@ -140,19 +140,24 @@ def validate(model, loader, device):
     return total / max(1, n), sum_psnr / max(1, n_imgs), time.time() - t0
 
 
-def build_model(scale_int: int, drop_path_rate: float = 0.1) -> SwinIR:
-    """finetune_swinir.py:269-281."""
-    return SwinIR(upscale=scale_int, in_chans=3, img_size=64, window_size=8, img_range=1.0, depths=[6] * 6, embed_dim=180,
+def build_model(scale_int: int, drop_path_rate: float = 0.1, window_size: int = 8) -> SwinIR:
+    """finetune_swinir.py:269-281; window_size (additive): 8 as the script has it, or 2..7 (7: the published JPEG-artifact models).
+    img_size -- which only sizes the attn_mask buffers of the state_dict -- is 64 rounded down to a multiple of the window (63 at
+    window 7: the reference's constructor cannot build its masks otherwise)."""
+    return SwinIR(upscale=scale_int, in_chans=3, img_size=64 // window_size * window_size, window_size=window_size, img_range=1.0,
+                  depths=[6] * 6, embed_dim=180,
                   num_heads=[6] * 6, mlp_ratio=2, upsampler="pixelshuffle", resi_connection="1conv",
                   drop_path_rate=drop_path_rate)
 
 
-def build_sr_model(arch: str, scale_int: int, drop_path_rate: float = 0.1):
+def build_sr_model(arch: str, scale_int: int, drop_path_rate: float = 0.1, window_size: int = 8):
     """The transformer SR models of modules/ at their published x2 / x4 hyper-parameters, on the HIP path: 'swinir'
     (finetune_swinir.py:269-281), 'hat' (HAT-SRx4 configuration of hat_arch.py's constructor defaults: window 16, overlap 0.5, CAB),
     'dat' (official DAT configuration: split [8, 32], expansion 4; dat_arch.py:721-741).  Used by train.py / evaluate.py --arch."""
     if arch == "swinir":
-        return build_model(scale_int, drop_path_rate)
+        return build_model(scale_int, drop_path_rate, window_size)
+    if window_size != 8:
+        raise ValueError(f"window_size={window_size} is an option of arch 'swinir' ('{arch}' has its published window)")
     if arch == "hat":
         from .hat_arch import HAT
         return HAT(upscale=scale_int, in_chans=3, img_size=64, window_size=16, compress_ratio=3, squeeze_factor=30, conv_scale=0.01,
@@ -165,7 +170,7 @@ def build_sr_model(arch: str, scale_int: int, drop_path_rate: float = 0.1):
     raise ValueError(f"unknown arch {arch!r}")
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--data_root", type=str, required=True)
     ap.add_argument("--scale", type=str, choices=["X2", "X4"], required=True)
@@ -199,12 +204,24 @@ def main(argv=None):
     ap.add_argument("--ema_decay", type=float, default=0.0,
                     help="additive: keep an exponential moving average of the weights inside the fused optimizer step (0 = off; "
                          "published recipes use 0.999); validation runs on it and checkpoints gain 'params_ema'")
+    ap.add_argument("--window_size", type=int, default=8,
+                    help="additive, --arch swinir: build SwinIR(window_size=N); 2..7 train through enable_small_window_training() "
+                         "(7 is the window of the published JPEG-artifact models) and allow --graph")
     args = ap.parse_args(argv)
     if not 0.0 <= args.ema_decay < 1.0:          # also refuses NaN
         ap.error(f"--ema_decay must be in [0, 1) (got {args.ema_decay})")
-    if args.graph and args.arch == "swinir":
-        ap.error("--graph captures the host-orchestrated train step of --arch hat / dat (SwinIR's step is one C call already)")
+    if not 2 <= args.window_size <= 8:
+        ap.error(f"--window_size must be in 2..8 (got {args.window_size})")
+    if args.window_size != 8 and args.arch != "swinir":
+        ap.error("--window_size is an option of --arch swinir")
+    if args.graph and args.arch == "swinir" and args.window_size == 8:
+        ap.error("--graph captures the host-orchestrated train step of --arch hat / dat and of --arch swinir --window_size 2..7 "
+                 "(the window-8 SwinIR step is one C call already)")
+    return args
 
+
+def main(argv=None):
+    args = parse_args(argv)
     rank, world, local = init_from_env()
     if args.graph and world > 1:
         raise SystemExit("--graph is for one process (gradient all-reduce stays outside graphs)")
@@ -236,7 +253,11 @@ def main(argv=None):
     valid_loader = make_loader(valid_ds, max(1, args.batch_size // 2), args.workers, pin=not args.no_pin, shuffle=False,
                                drop_last=False, persistent=not args.no_persistent)
 
-    model = build_model(scale_int, args.drop_path_rate) if args.arch == "swinir" else build_sr_model(args.arch, scale_int, args.drop_path_rate)
+    model = (build_model(scale_int, args.drop_path_rate, args.window_size) if args.arch == "swinir" else
+             build_sr_model(args.arch, scale_int, args.drop_path_rate))
+    small = args.arch == "swinir" and args.window_size < 8
+    if small:
+        model.enable_small_window_training()          # before the optimizer is constructed: the model steps on the multi-tensor path
     if args.weights:
         ckpt = torch.load(args.weights, map_location="cpu", weights_only=True)
         state = ckpt
@@ -264,13 +285,13 @@ def main(argv=None):
         n_train = sum(1 for p in model.parameters() if p.requires_grad)
         print(f"[params] trainable tensors: {n_train} / total: {len(list(model.parameters()))}")
 
-    if args.arch == "swinir":
+    if args.arch == "swinir" and not small:
         dp = DataParallelSwinIR(model)
         dp.attach(device)                 # weights are now identical on every rank (broadcast from rank 0)
     else:
         dp = None
         if world > 1:
-            # HAT / DAT: separate parameter tensors.  Same weights (and BatchNorm statistics) everywhere, then per-segment gradient
+            # HAT / DAT / small-window SwinIR: separate parameter tensors.  Same weights (and BatchNorm statistics) everywhere, then per-segment gradient
             # SUMS overlapped with the backward (hat_train / dat_train call model.grad_sync); the optimizer divides by the world size
             import torch.distributed as dist
             from .distributed import ListGradSynchronizer

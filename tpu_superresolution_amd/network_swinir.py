@@ -390,6 +390,30 @@ class SwinIR(nn.Module):
             if p.requires_grad and p.grad is None:
                 p.grad = gv[name]
 
+    # -- training at window sizes 2..7 (opt-in) ------------------------------------------------------------------
+    def enable_small_window_training(self):
+        """Opt in to training at window_size 2..7: afterwards a grad-enabled forward in train mode is ONE autograd node whose
+        forward / backward are the host-orchestrated C-ABI sequences of ``swinir_small_train.py`` (the small-window attention
+        backward of csrc/attn_small_bwd.hip), and ``loss.backward()`` fills ``.grad`` of every parameter.  Eval / no_grad forwards
+        are unchanged.  Covers what the small-window inference covers (heads 'pixelshuffle', 'pixelshuffledirect', ''; '1conv'; no
+        ape; patch_norm; no dropout; use_checkpoint=False; img_size > window_size); anything else raises SrkUnsupported here, not in
+        the middle of a step.  Call it BEFORE constructing ``optim.FusedAdamW`` (an enabled model steps on the multi-tensor path,
+        with EMA / params_ema; a model that has not been enabled is classified as an engine model).  Returns self."""
+        from . import swinir_small_train
+        why = swinir_small_train.unsupported_reason(self)
+        if why:
+            raise SrkUnsupported(f"enable_small_window_training: the MI355X HIP path does not cover {why}; no fallback path exists "
+                                 "in this package")
+        self._small_window_training = True
+        return self
+
+    def draw_drop_path(self, B: int, device) -> Optional[torch.Tensor]:
+        """DropPath factors [n_blocks][2][B] of an enabled small-window model in train mode (``_drop_scale``), else None;
+        ``training.GraphedTrainStep`` draws them outside its graph into ``_drop_override``."""
+        if not getattr(self, "_small_window_training", False):
+            return None
+        return self._drop_scale(B, device)
+
     # -- forward ----------------------------------------------------------------------------------------------
     def forward_features(self, x):
         """network_swinir.py:790-803 as a callable: x = conv_first's output [B, embed_dim, H, W] (H, W multiples of the
@@ -423,8 +447,12 @@ class SwinIR(nn.Module):
             return swinir_w16.forward(self, x)
         if self.window_size < 8:          # windows of <= 49 tokens: the same host-orchestrated sequence with the small-window attention
             if torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters()):
+                if getattr(self, "_small_window_training", False):      # opted in: one autograd node (swinir_small_train.py)
+                    from . import swinir_small_train
+                    return swinir_small_train.train_forward(self, x)
                 raise SrkUnsupported(f"SwinIR(window_size={self.window_size}) on the HIP path is inference-only: call model.eval() / "
-                                     "torch.no_grad() (training runs with window_size 8)")
+                                     "torch.no_grad() (training runs with window_size 8, or here after "
+                                     "model.enable_small_window_training())")
             from . import swinir_w16
             return swinir_w16.forward(self, x)
         eng = self._bind(x.device)

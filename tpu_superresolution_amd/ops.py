@@ -162,6 +162,31 @@ def window_attention_small_fwd(qkv: torch.Tensor, table: torch.Tensor, B: int, H
     return out
 
 
+def window_attention_small_bwd(qkv: torch.Tensor, table: torch.Tensor, d_out: torch.Tensor, B: int, H: int, W: int, window_size: int,
+                               shift: int, num_heads: int, scale: float, d_table: Optional[torch.Tensor] = None):
+    """Gradient of window_attention_small_fwd.  qkv, table as the forward took them; d_out bf16 [B*H*W, num_heads*32]
+    -> (d_qkv bf16 [B*H*W, 3*CA], written in full; d_table fp32 [(2 ws - 1)^2, num_heads]).  A d_table that is passed in is
+    ACCUMULATED into, otherwise a zeroed one is made."""
+    T, ldq = qkv.shape
+    if T != B * H * W or ldq % 3 or qkv.dtype != torch.bfloat16:
+        raise ValueError(f"qkv must be bf16 [B*H*W = {B * H * W}, 3*CA], got {qkv.dtype} {tuple(qkv.shape)}")
+    if d_out.dtype != torch.bfloat16 or d_out.dim() != 2 or d_out.shape[0] != T or d_out.shape[1] < num_heads * 32:
+        raise ValueError(f"d_out must be bf16 [{T}, >= {num_heads * 32}], got {d_out.dtype} {tuple(d_out.shape)}")
+    if 2 <= window_size <= 7:
+        want = ((2 * window_size - 1) ** 2, num_heads)
+        for name, t in (("table", table), ("d_table", d_table)):
+            if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != want):
+                raise ValueError(f"{name} must be fp32 {list(want)}, got {t.dtype} {tuple(t.shape)}")
+    d_qkv = torch.empty((T, ldq), dtype=torch.bfloat16, device=qkv.device)
+    if d_table is None:
+        d_table = torch.zeros_like(table)
+    scratch = torch.empty(max(16, int(lib().srk_win_small_attention_bwd_scratch(B, H, W, window_size, num_heads))), dtype=torch.uint8,
+                          device=qkv.device)
+    check(lib().srk_win_small_attention_bwd(_p(qkv), ldq, ldq // 3, _p(table), _p(d_out), d_out.shape[1], _p(d_qkv), _p(d_table),
+                                            _p(scratch), B, H, W, window_size, shift, num_heads, float(scale), _stream()))
+    return d_qkv, d_table
+
+
 def rel_pos_bias_expand(table: torch.Tensor) -> torch.Tensor:
     nH = table.shape[1]
     out = torch.empty((nH, 64, 64), dtype=torch.float32, device=table.device)

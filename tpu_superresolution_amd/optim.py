@@ -34,6 +34,12 @@ def _stream(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def trains_through_engine(model) -> bool:
+    """A SwinIR that trains through the C++ engine (flat parameter buffer): every SwinIR but one on which
+    ``enable_small_window_training()`` has been called -- call that BEFORE constructing the optimizer."""
+    return isinstance(model, SwinIR) and not getattr(model, "_small_window_training", False)
+
+
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, model: torch.nn.Module, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, max_grad_norm: Optional[float] = None, grad_div: float = 1.0,
@@ -55,7 +61,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self._engine_id = None
         # every model but SwinIR: separate parameter tensors, moments in self.state[p] (torch's own layout, so that
         # Optimizer.state_dict / load_state_dict carry them), one pointer table per set of parameters that have a gradient
-        self._flat = isinstance(model, SwinIR)
+        self._flat = trains_through_engine(model)          # an enabled small-window SwinIR is host-orchestrated: list path
         self._hyper: Optional[torch.Tensor] = None          # device {lr, 1 - beta1^step, sqrt(1 - beta2^step)} for captured steps
         self._table: Optional[ops.TensorTable] = None
         self._table_key = None
@@ -203,6 +209,9 @@ class FusedAdamW(torch.optim.Optimizer):
             raise RuntimeError("FusedAdamW.step() inside swap_ema(): the weights hold the average")
         if not self._flat:
             return self._step_list(nonfinite)
+        if not trains_through_engine(self.model):
+            raise RuntimeError("FusedAdamW: enable_small_window_training() was called on the model after this optimizer was constructed "
+                               "(it was classified as an engine model); enable first, then construct the optimizer")
         eng = self._prepare()
         g = eng.ensure_grad()
         grp = self.param_groups[0]
