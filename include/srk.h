@@ -153,7 +153,11 @@ int srk_probe_end(double* total_ms, double* flops, double* bytes, int* launches)
  *   register-staged one (both in csrc/wgrad.hip).
  *   "conv_wgrad_taps" 2 (default) / 1 / 0: all-taps conv weight gradient with the LDS-DMA ring / register-staged
  *   (csrc/convwgrad.hip, incl. the MFMA image-head kernels), or the per-tap tiles of wgrad.hip + the VALU image head.
- *   "wgrad_stream_rows" 32 (default) / 64: rows per ring stage of that kernel (6 or 3 stages in the 144 KB ring);
+ *   "conv_wgrad_roll" 1 (default) / 0: with conv_wgrad_taps = 2, the LDS-DMA kernel keeps a rolling window of X image rows in
+ *   LDS (one new row per 64-pixel run; W = 64 and W = 128, other widths run the per-run staging) or stages a fresh
+ *   3 x 66-pixel halo for every run.  At W = 64 both give the same dW bits.  The MFMA image-head kernel (srk_smallconv_wgrad)
+ *   follows the same option: X rows and the fp32 dY by LDS-DMA into rings, or both staged through registers.
+ *   "wgrad_stream_rows" 32 (default) / 64: rows per ring stage of the linear kernel (6 or 3 stages in the 144 KB ring);
  *   "wgrad_stream_nt" 1 (default) / 0: streaming cache policy on its operand DMAs.
  *   "wgrad_partials" 1 (default) / 0: the streaming weight-gradient kernels write their per-split partial tiles to the
  *   caller's workspace (srk_set_wgrad_workspace; the model executor uses a region of its own workspace) and a reduce

@@ -30,7 +30,7 @@ int srk_device_cus();         // multiProcessorCount of the current device (cach
 enum SrkOptId {
   OPT_MLP_FUSED, OPT_MLP_BWD_FUSED, OPT_GEMM_STREAM, OPT_TUNE_BM, OPT_TUNE_KS2, OPT_TUNE_SPLIT, OPT_TUNE_NB, OPT_ATTN_BWD_FUSED,
   OPT_ATTN_FUSED, OPT_BLOCK_LIGHT, OPT_TAPS_ENABLED, OPT_TAPS_DMA, OPT_WGRAD_STREAM, OPT_WGRAD_ROWS, OPT_WGRAD_NT, OPT_WGRAD_W8,
-  OPT_WGRAD_PARTIALS, OPT_MLP_DGELU_STORE, SRK_NUM_OPTS
+  OPT_WGRAD_PARTIALS, OPT_MLP_DGELU_STORE, OPT_TAPS_ROLL, SRK_NUM_OPTS
 };
 struct SrkOptTls {
   int v[SRK_NUM_OPTS];

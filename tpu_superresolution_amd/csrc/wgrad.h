@@ -82,6 +82,8 @@ int srk_launch_wgrad(const WgradParams& p, hipStream_t stream);
 int srk_launch_conv_wgrad_taps(const WgradParams& p, hipStream_t stream);
 void srk_conv_wgrad_taps_enable(int on);
 int srk_conv_wgrad_taps_mode();
+void srk_conv_wgrad_roll_enable(int on);   // rolling X-row window of the all-taps DMA kernel and the image-head kernel
+int srk_conv_wgrad_roll_enabled();
 int srk_launch_smallconv_wgrad_mfma(const bf16_t* x, const float* gy, float* dW, float* db, int B, int H, int W, int Cin, int CinP, int Co,
                                     int CoP, hipStream_t stream);
 int srk_launch_imghead_dgrad_mfma(const float* gy, const float* wgt, bf16_t* dx, int B, int H, int W, int Cin, int CinP, int Co, int CoP,
