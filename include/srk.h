@@ -196,6 +196,17 @@ int srk_set_wgrad_workspace(void* workspace, int64_t bytes);
  * value = u8 / 255 in IEEE fp32, a gray image is repeated into three channels: bit-identical to the host transform. */
 int srk_paired_crop_u8(const uint8_t* pool, const int64_t* lr_desc, const int64_t* hr_desc, float* lr_out, float* hr_out, int B,
                        int lr_patch, int scale, srk_stream_t stream);
+/* D4 transform of a batch of fp32 NCHW images (flip / rot90 augmentation of a training batch, the forward and inverse transforms of
+ * the x8 self-ensemble).  op in 0..7: bit 0 = horizontal flip (x -> W-1-x), bit 1 = vertical flip (y -> H-1-y), bit 2 = transpose,
+ * applied in that order: T_op = Tr^b2 . V^b1 . H^b0.
+ * in [B][C][H][W]; out [B][C][Ho][Wo], (Ho, Wo) = (W, H) when bit 2 is set, else (H, W).
+ * ops: DEVICE int32 [B] (one code per sample; only the low three bits are read) or null = op_all for every sample.
+ * With ops != null the geometry must not depend on the codes: H == W is required (SRK_E_SHAPE otherwise).
+ * accumulate == 0: out = alpha * T(in); accumulate == 1: out += alpha * T(in).  in and out must not overlap (SRK_E_SHAPE).
+ * op_all outside 0..7, B / C / H / W < 1: SRK_E_SHAPE.  Nothing outside out[0 .. B*C*H*W) is written.  With alpha == 1 and
+ * accumulate == 0 the values are moved, not multiplied: every bit pattern (NaN payloads included) arrives unchanged. */
+int srk_dihedral_f32(const float* in, float* out, const int32_t* ops, int op_all, int B, int C, int H, int W, float alpha,
+                     int accumulate, srk_stream_t stream);
 /* Validation metrics of one batch in one pass (first slice): per-image PSNR of the images clamped to [0, 1]
  * (batch_psnr, finetune_swinir.py:69-74: 20 log10(max_val / sqrt(mse + 1e-8)), mse over the per_image = C*H*W elements of an
  * image) and the sum of |pred - target| over the batch for the validation L1 (F.l1_loss, :66-67, used by validate :181-207).

@@ -462,6 +462,20 @@ int srk_paired_crop_u8(const uint8_t* pool, const int64_t* lr_desc, const int64_
   return srk_launch_crop_u8(pool, reinterpret_cast<const long long*>(hr_desc), hr_out, B, lr_patch * scale, (hipStream_t)stream);
 }
 
+int srk_dihedral_f32(const float* in, float* out, const int32_t* ops, int op_all, int B, int C, int H, int W, float alpha,
+                     int accumulate, srk_stream_t stream) {
+  REQ_PTR(in); REQ_PTR(out);
+  SRK_REQUIRE(B >= 1 && C >= 1 && H >= 1 && W >= 1, SRK_E_SHAPE, "dihedral: B=%d C=%d H=%d W=%d must all be >= 1", B, C, H, W);
+  SRK_REQUIRE(accumulate == 0 || accumulate == 1, SRK_E_SHAPE, "dihedral: accumulate must be 0 or 1 (got %d)", accumulate);
+  if (ops) SRK_REQUIRE(H == W, SRK_E_SHAPE, "dihedral: per-sample op codes need square images (got %d x %d)", H, W);
+  else SRK_REQUIRE(op_all >= 0 && op_all <= 7, SRK_E_SHAPE, "dihedral: op must be in 0..7 (got %d)", op_all);
+  const double bytes = 4.0 * B * C * H * W;
+  SRK_REQUIRE(bytes < 9.0e18, SRK_E_SHAPE, "dihedral: B=%d C=%d H=%d W=%d is too large", B, C, H, W);
+  const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out), n = (uintptr_t)bytes;
+  SRK_REQUIRE(a + n <= b || b + n <= a, SRK_E_SHAPE, "dihedral: in and out overlap (the transform is not done in place)");
+  return srk_launch_dihedral_f32(in, out, reinterpret_cast<const int*>(ops), op_all, B, C, H, W, alpha, accumulate, (hipStream_t)stream);
+}
+
 int64_t srk_batch_psnr_workspace(int64_t per_image, int B) {
   if (per_image <= 0 || B <= 0) return 0;
   return (int64_t)2 * sizeof(float) * B * srk_batch_psnr_chunks(per_image);

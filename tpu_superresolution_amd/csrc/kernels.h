@@ -55,6 +55,9 @@ inline int srk_batch_psnr_chunks(long long per_image) {
   return (int)(c < 1 ? 1 : (c > 64 ? 64 : c));
 }
 int srk_launch_crop_u8(const unsigned char* pool, const long long* desc, float* out, int B, int patch, hipStream_t stream);
+// dihedral.hip: the eight symmetries of the square on fp32 NCHW batches (arguments checked by srk_dihedral_f32)
+int srk_launch_dihedral_f32(const float* in, float* out, const int* ops, int op_all, int B, int C, int H, int W, float alpha,
+                            int accumulate, hipStream_t stream);
 int srk_launch_batch_psnr(const float* pred, const float* target, float* partial, int B, long long per_image, float max_val,
                           float* psnr, float* psnr_sum, float* abs_sum, hipStream_t stream);
 int srk_launch_zero_f32(float* p, long long n, hipStream_t stream);      // graph-safe zero fill (misc.hip)

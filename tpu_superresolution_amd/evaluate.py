@@ -11,7 +11,8 @@ by --save_n (:199-225) -> summary (:229-234).
 
 BASELINE config 1 runs this on the CPU with stock torch operators (MS_ResUNet has no kernel in scope).
 Additive: ``--arch swinir | hat | dat`` evaluates the MI355X SwinIR / HAT / DAT path (finetune_swinir.py model, RGB un-upscaled LR input, needs a
-GPU + libsrk); ``main(argv)`` is callable from tests.  SSIM is ``metrics.ssim`` (restated, parity unpinned).
+GPU + libsrk); ``--self_ensemble`` averages the eight flipped / rotated predictions (any --arch); ``main(argv)`` is callable from
+tests.  SSIM is ``metrics.ssim`` (restated, parity unpinned).
 """
 from __future__ import annotations
 
@@ -83,6 +84,9 @@ def parse_args(argv=None):
                     help="additive: which envelope of the checkpoint to load (auto: model, then params, then params_ema)")
     ap.add_argument("--device", type=str, default=None, help="additive: force 'cpu' / 'cuda' (default: cuda if available)")
     ap.add_argument("--window_size", type=int, default=8, help="additive, --arch swinir: SwinIR(window_size=N), N in 2..8")
+    ap.add_argument("--self_ensemble", action="store_true",
+                    help="additive: predict with the x8 self-ensemble (the '+' of SwinIR+ / HAT+ / DAT+): the mean of the eight "
+                         "inverse-transformed predictions on the flipped / rotated inputs (augment.self_ensemble)")
     args = ap.parse_args(argv)
     if not 2 <= args.window_size <= 8 or (args.window_size != 8 and args.arch != "swinir"):
         ap.error(f"--window_size must be in 2..8 and is an option of --arch swinir (got {args.window_size} with --arch {args.arch})")
@@ -141,6 +145,13 @@ def main(argv=None):
     model.load_state_dict(state, strict=True)
     print(msg)
     model = model.to(device).eval()
+    predict = model
+    if args.self_ensemble:
+        from functools import partial
+
+        from .augment import self_ensemble
+        predict = partial(self_ensemble, model)
+        print("[self_ensemble] x8")
 
     t0 = time.time()
     psnr_vals, ssim_vals = [], []
@@ -161,7 +172,7 @@ def main(argv=None):
         for lr, hr in test_loader:
             lr, hr = lr.to(device, non_blocking=True), hr.to(device, non_blocking=True)
             with torch.amp.autocast("cuda", enabled=(device.type == "cuda" and not swin)):
-                pred = model(lr)
+                pred = predict(lr)
                 if not torch.isfinite(pred).all():
                     bad = (~torch.isfinite(pred)).float().mean().item()
                     raise RuntimeError(f"Pred has non-finite values: share={bad:.6f}, min={torch.nanmin(pred).item():.4g}, "

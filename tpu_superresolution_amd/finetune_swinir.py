@@ -8,7 +8,8 @@ Same flags, same model configuration (:269-281), same checkpoint envelopes in ({
 out ("best_swinir_finetune_<scale>.pt", "bestpsnr_swinir_finetune_<scale>.pt" with key "model", :345-371),
 same epoch print line (:337-342).  Differences, all additive: bf16 MFMA is built into the kernels (no autocast
 context), the step uses the fused L1 / clip / AdamW kernels, `--weights` may be omitted (random init) and
-`--drop_path_rate` exposes the constructor default (0.1) that the reference leaves implicit.
+`--drop_path_rate` exposes the constructor default (0.1) that the reference leaves implicit.  `--augment flip|d4` (default none) trains
+on flipped / rotated patches (augment.py; on the device with `--gpu_data`).
 
 Also additive: `--arch hat|dat` fine-tunes HAT / DAT (build_sr_model) through the same loop -- the fused, device-gated clip + AdamW step
 over their parameter lists (optim.FusedAdamW, csrc/optim_multi.hip), checkpoints "best_<arch>_finetune_<scale>.pt" /
@@ -207,6 +208,12 @@ def parse_args(argv=None):
     ap.add_argument("--window_size", type=int, default=8,
                     help="additive, --arch swinir: build SwinIR(window_size=N); 2..7 train through enable_small_window_training() "
                          "(7 is the window of the published JPEG-artifact models) and allow --graph")
+    ap.add_argument("--augment", type=str, choices=["none", "flip", "d4"], default="none",
+                    help="additive: training augmentation by the symmetries of the square, one drawn per sample after its crop corners "
+                         "and applied to LR and HR alike (validation is never augmented).  flip: horizontal and vertical flip, each "
+                         "with p = 0.5 -- the distribution of the reference's PairFlips, drawn from `random` and not from its "
+                         "torch.rand stream; d4: the flips and the 90-degree rotations (all eight symmetries).  With --gpu_data the "
+                         "transform is one kernel launch per batch side")
     args = ap.parse_args(argv)
     if not 0.0 <= args.ema_decay < 1.0:          # also refuses NaN
         ap.error(f"--ema_decay must be in [0, 1) (got {args.ema_decay})")
@@ -237,7 +244,8 @@ def main(argv=None):
         print("[device]", device, torch.cuda.get_device_name(local), f"world={world}")
     scale_int = 2 if args.scale.upper() == "X2" else 4
 
-    train_ds = Shuffled2DPaired(args.data_root, split="train", scale=args.scale, transform_pair=PairTransformTrain(args.lr_patch, scale_int))
+    train_ds = Shuffled2DPaired(args.data_root, split="train", scale=args.scale,
+                                transform_pair=PairTransformTrain(args.lr_patch, scale_int, args.augment))
     valid_ds = Shuffled2DPaired(args.data_root, split="valid", scale=args.scale, transform_pair=PairTransformValid(scale_int))
     sampler = DistributedSampler(train_ds, num_replicas=world, rank=rank, shuffle=True, seed=args.seed) if world > 1 else None
     train_loader = make_loader(train_ds, args.batch_size, args.workers, pin=not args.no_pin, shuffle=True, drop_last=True,
@@ -246,7 +254,7 @@ def main(argv=None):
         from .sr_datasets import DevicePairPool
         raw = Shuffled2DPaired(args.data_root, split="train", scale=args.scale, transform_pair=None)
         pool = DevicePairPool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, device=device,
-                              shard_bytes=(args.gpu_data_shard_mb << 20) or None)
+                              shard_bytes=(args.gpu_data_shard_mb << 20) or None, augment=args.augment)
         train_loader = sampler = DevicePoolLoader(pool, args.batch_size, rank, world, args.seed)
         if rank == 0:
             print(f"[gpu_data] {len(pool)} pairs in {pool.num_shards} shard(s), {sum(t.numel() for t in pool._host) / 2**20:.1f} MiB decoded")

@@ -17,6 +17,8 @@ import torch
 from PIL import Image
 from torch.utils.data import Dataset
 
+from .augment import AUGMENT_MODES, apply_op_host, draw_op
+
 
 def _dirs(root: str, split: str, scale: str) -> Tuple[Path, Path]:
     base = Path(root) / "shuffled2D"
@@ -66,7 +68,7 @@ class Shuffled2DPaired(Dataset):
         return lr, hr
 
 
-# ---- minimal paired transforms of finetune_swinir.py:80-131 (no augmentation) -----------------------
+# ---- minimal paired transforms of finetune_swinir.py:80-131 (augmentation: opt-in, augment.py) ------
 def pil_to_tensor01(img: Image.Image) -> torch.Tensor:
     """uint8 PIL -> float32 [C,H,W] in [0,1] (torchvision ToImage + ToDtype(scale=True) for 8-bit inputs)."""
     a = np.asarray(img)
@@ -99,12 +101,19 @@ def paired_random_crop(lr_t: torch.Tensor, hr_t: torch.Tensor, lr_patch: int, sc
 
 
 class PairTransformTrain:
-    def __init__(self, lr_patch: int, scale: int):
-        self.lr_patch, self.scale = lr_patch, scale
+    """Paired random crop, then (augment 'flip' / 'd4') one D4 transform drawn after the crop corners and applied to both patches.
+    'none' (the default) draws nothing and returns the crops as they are."""
+
+    def __init__(self, lr_patch: int, scale: int, augment: str = "none"):
+        if augment not in AUGMENT_MODES:
+            raise ValueError(f"augment must be one of {AUGMENT_MODES} (got {augment!r})")
+        self.lr_patch, self.scale, self.augment = lr_patch, scale, augment
 
     def __call__(self, lr_pil, hr_pil):
         lr, hr = ensure_3ch(pil_to_tensor01(lr_pil)), ensure_3ch(pil_to_tensor01(hr_pil))
-        return paired_random_crop(lr, hr, self.lr_patch, self.scale)
+        lr, hr = paired_random_crop(lr, hr, self.lr_patch, self.scale)
+        k = draw_op(self.augment)
+        return apply_op_host(lr, k), apply_op_host(hr, k)
 
 
 class PairTransformValid:
@@ -126,10 +135,17 @@ class DevicePairPool:
     live on the device: ``prefetch(s)`` starts the asynchronous copy of shard s on a side stream, ``sample`` of an index in a
     shard that is not resident switches to it (joining its copy) and prefetches the next one -- the host->device transfer of
     shard s+1 overlaps the training steps on shard s.  ``shard_of(i)`` tells a sampler which shard an image
-    lives in, so that epochs can be ordered shard by shard."""
+    lives in, so that epochs can be ordered shard by shard.
 
-    def __init__(self, pairs, lr_patch: int, scale: int, device="cuda", shard_bytes: Optional[int] = None):
+    ``augment`` ('none' | 'flip' | 'd4', augment.draw_op): `sample` draws one D4 code per sample right after its crop corners -- the
+    order PairTransformTrain draws in, so the two paths still agree from the same `random` state -- and, when any code is non-zero,
+    transforms the LR and the HR batch with one `srk_dihedral_f32` launch each (per-sample codes; patches are square)."""
+
+    def __init__(self, pairs, lr_patch: int, scale: int, device="cuda", shard_bytes: Optional[int] = None, augment: str = "none"):
         """pairs: iterable of (lr, hr) PIL images or uint8 / uint16 arrays [H,W] / [H,W,1|3]."""
+        if augment not in AUGMENT_MODES:
+            raise ValueError(f"augment must be one of {AUGMENT_MODES} (got {augment!r})")
+        self.augment = augment
         self.lr_patch, self.scale, self.device = int(lr_patch), int(scale), torch.device(device)
         shards, chunks, self.meta, off = [], [], [], 0
         for lr, hr in pairs:
@@ -218,7 +234,7 @@ class DevicePairPool:
         """-> (lr [B,3,P,P], hr [B,3,P*s,P*s]) fp32 on the device; advances the global `random` state like the host transform."""
         from ._lib import check, lib
         P, s = self.lr_patch, self.scale
-        ld, hd = [], []
+        ld, hd, codes = [], [], []
         shard_ids = {self.meta[int(i)][0] for i in indices}
         if len(shard_ids) != 1:
             raise ValueError("a batch must come from one shard (order the epoch with shard_of())")
@@ -228,6 +244,7 @@ class DevicePairPool:
             top, left = random.randint(0, lh - P), random.randint(0, lw - P)
             ld.append((lo, lh, lw, lc, top, left))
             hd.append((ho, hh, hw, hc, top * s, left * s))
+            codes.append(draw_op(self.augment))
         B = len(ld)
         desc = torch.tensor(ld + hd, dtype=torch.int64).to(self.device)
         lr = torch.empty(B, 3, P, P, dtype=torch.float32, device=self.device)
@@ -235,4 +252,8 @@ class DevicePairPool:
         st = torch.cuda.current_stream(self.device).cuda_stream
         check(lib().srk_paired_crop_u8(pool.data_ptr(), desc[:B].data_ptr(), desc[B:].data_ptr(), lr.data_ptr(), hr.data_ptr(),
                                        B, P, s, st))
+        if any(codes):
+            from .augment import dihedral
+            ops = torch.tensor(codes, dtype=torch.int32).to(self.device)
+            lr, hr = dihedral(lr, ops), dihedral(hr, ops)
         return lr, hr
