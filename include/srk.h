@@ -178,6 +178,31 @@ int srk_get_option(const char* name, int* value);
  * (zero them first); d_pred may be null; grad_scale multiplies d_pred (1.0 for a plain backward). */
 int srk_l1_loss_fwd_bwd(const float* pred, const float* target, float* d_pred, float* loss, uint32_t* nonfinite,
                         int64_t n, float grad_scale, srk_stream_t stream);
+/* The pixel objectives of SR fine-tuning with the semantics of the L1 entry above (csrc/loss.hip): kind SRK_LOSS_L1 = mean |d|,
+ * SRK_LOSS_MSE = mean d^2, SRK_LOSS_CHARBONNIER = mean sqrt(d^2 + eps^2) (eps > 0; other kinds do not read eps), d = pred - target
+ * over n fp32 elements.  loss[0] += the mean (weight 1: srk_ssim_loss_fwd_bwd can add its term to the same scalar); nonfinite
+ * (uint32, may be null) += the number of non-finite pred values; d_pred (may be null) = grad_scale * d loss / d pred, stored when
+ * accumulate == 0 and added to what d_pred holds when accumulate == 1.  Unlike the L1 entry the loss sum is formed in a FIXED order
+ * (per-workgroup partials in `workspace`, srk_pixel_loss_workspace(n) bytes owned by the caller, plus one finishing workgroup): two
+ * calls give the same bits.  SRK_E_NULL: null pred / target / loss / workspace; SRK_E_SHAPE: n <= 0, unknown kind, Charbonnier with
+ * eps <= 0, accumulate not 0 / 1. */
+#define SRK_LOSS_L1 0
+#define SRK_LOSS_MSE 1
+#define SRK_LOSS_CHARBONNIER 2
+int64_t srk_pixel_loss_workspace(int64_t n);
+int srk_pixel_loss_fwd_bwd(const float* pred, const float* target, float* d_pred, float* loss, uint32_t* nonfinite, int64_t n, int kind,
+                           float eps, float grad_scale, int accumulate, void* workspace, srk_stream_t stream);
+/* SSIM as a training term: S = srk_ssim's batch mean of x against y (fp32 [B][C][H][W]; the same 11-tap Gaussian, K constants and
+ * VALID filter; the taps are normalised in fp64 here, which moves S by up to ~3e-6 against srk_ssim's fp32-normalised taps).
+ * ssim_mean[0] = S (may be null); loss[0] += alpha * (1 - S) (may be null); d_x (fp32 [B][C][H][W], may be null) receives
+ * -alpha * dS/dx, stored when accumulate == 0 and added when accumulate == 1; there is no gradient for y.  One fused kernel per
+ * 32 x 32 tile of input pixels (no per-pixel intermediates in HBM), fixed-order sums, no float atomics: reproducible.  Nothing
+ * outside d_x[0 .. B*C*H*W) and the two scalars is written.  workspace: srk_ssim_loss_workspace(B, C, H, W) bytes.
+ * SRK_E_UNSUPPORTED: H or W < 11; SRK_E_SHAPE: B, C outside srk_ssim's limits (B <= 1024, B*C < 65536), data_range <= 0, d_x
+ * overlapping x or y; SRK_E_NULL: null x / y / workspace. */
+int64_t srk_ssim_loss_workspace(int B, int C, int H, int W);
+int srk_ssim_loss_fwd_bwd(const float* x, const float* y, void* workspace, int B, int C, int H, int W, float data_range, float alpha,
+                          float* d_x, int accumulate, float* ssim_mean, float* loss, srk_stream_t stream);
 /* Optional workspace of the stand-alone weight-gradient entry points (srk_linear_wgrad_bf16, srk_conv3x3_wgrad_bf16):
  * srk_wgrad_workspace_bytes() bytes of device memory owned by the caller, registered for the CALLING THREAD until replaced
  * (null / 0 unregisters).  With it the row-splits of a weight-gradient tile are summed in a fixed order (reproducible dW);

@@ -58,6 +58,9 @@ LD_ROWS, LD_CONV3, LD_CONV3_PS = 0, 1, 2
 EP_BF16, EP_GELU, EP_RES, EP_LRELU, EP_PS, EP_IMG, EP_PS_IMG, EP_RES_BF16 = 0, 3, 4, 6, 7, 8, 9, 10
 EP_DGELU, EP_DLRELU, EP_F32_BF16, EP_LNBWD = 5, 11, 12, 13
 
+LOSS_L1, LOSS_MSE, LOSS_CHARBONNIER = 0, 1, 2          # SRK_LOSS_* (include/srk.h)
+LOSS_KINDS = {"l1": LOSS_L1, "mse": LOSS_MSE, "charbonnier": LOSS_CHARBONNIER}
+
 UPSAMPLER_PIXELSHUFFLE = 1
 UPSAMPLER_PIXELSHUFFLEDIRECT = 2
 UPSAMPLER_NEAREST_CONV = 3
@@ -95,6 +98,10 @@ _SIGNATURES = {
     "srk_probe_begin": (_i, [_i, _i]),
     "srk_probe_end": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
     "srk_l1_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _f, _vp]),
+    "srk_pixel_loss_workspace": (_i64, [_i64]),
+    "srk_pixel_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _f, _i, _vp, _vp]),
+    "srk_ssim_loss_workspace": (_i64, [_i, _i, _i, _i]),
+    "srk_ssim_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _i, _vp, _vp, _vp]),
     "srk_wgrad_workspace_bytes": (_i64, []),
     "srk_set_wgrad_workspace": (_i, [_vp, _i64]),
     "srk_paired_crop_u8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -71,6 +71,16 @@ int srk_launch_nn2x_bf16(const bf16_t* in, bf16_t* out, int B, int h, int w, int
 int srk_launch_nn2x_sum_dlrelu(const bf16_t* g, const bf16_t* act, bf16_t* out, int B, int h, int w, int C, float slope, hipStream_t stream);
 int srk_launch_nchw_tokens(const float* src, float* dst, int B, int C, int CP, int HW, int to_tokens, hipStream_t stream);
 int srk_launch_l1_loss(const float* pred, const float* target, float* dpred, float* loss_sum, unsigned* nonfinite, long long n, float grad_scale, hipStream_t stream);
+// loss.hip: pixel losses and the SSIM term with fixed-order sums (arguments checked by srk_pixel_loss_fwd_bwd / srk_ssim_loss_fwd_bwd)
+// workgroups of the pixel-loss pass: 256 elements each, at most 2048 (then a grid-stride loop)
+inline int srk_pixel_loss_blocks(long long n) {
+  const long long b = (n + 255) / 256;
+  return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
+}
+int srk_launch_pixel_loss(const float* pred, const float* target, float* dpred, float* loss, unsigned* nonfinite, long long n, int kind,
+                          float eps, float grad_scale, int accumulate, float* partial, hipStream_t stream);
+int srk_launch_ssim_loss(const float* x, const float* y, float* partial, int B, int C, int H, int W, float data_range, float alpha, float* d_x,
+                         int accumulate, float* ssim_mean, float* loss, hipStream_t stream);
 int srk_launch_sumsq(const float* g, long long n, float* out, hipStream_t stream);
 int srk_launch_adamw(float* p, const float* g, float* m, float* v, long long n, const float* sumsq, const int* nonfinite, float max_norm, float grad_div, float lr, float beta1, float beta2, float eps, float wd, int step, hipStream_t stream);
 int srk_launch_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, long long n, const float* sumsq, const int* nonfinite, float max_norm, float grad_div, float lr, float beta1, float beta2, float eps, float wd, int step, float ema_decay, hipStream_t stream);

@@ -9,7 +9,9 @@ out ("best_swinir_finetune_<scale>.pt", "bestpsnr_swinir_finetune_<scale>.pt" wi
 same epoch print line (:337-342).  Differences, all additive: bf16 MFMA is built into the kernels (no autocast
 context), the step uses the fused L1 / clip / AdamW kernels, `--weights` may be omitted (random init) and
 `--drop_path_rate` exposes the constructor default (0.1) that the reference leaves implicit.  `--augment flip|d4` (default none) trains
-on flipped / rotated patches (augment.py; on the device with `--gpu_data`).
+on flipped / rotated patches (augment.py; on the device with `--gpu_data`).  `--loss l1|mse|charbonnier` (default l1) and
+`--ssim_weight W` (default 0) choose the objective: the pixel loss plus W * (1 - SSIM), value and gradient from the fused kernels of
+csrc/loss.hip (training.make_loss); with W > 0 validation also reports the mean per-image SSIM and checkpoints gain 'val_ssim'.
 
 Also additive: `--arch hat|dat` fine-tunes HAT / DAT (build_sr_model) through the same loop -- the fused, device-gated clip + AdamW step
 over their parameter lists (optim.FusedAdamW, csrc/optim_multi.hip), checkpoints "best_<arch>_finetune_<scale>.pt" /
@@ -33,7 +35,7 @@ from . import SwinIR
 from .distributed import DataParallelSwinIR, init_from_env
 from .optim import FusedAdamW
 from .sr_datasets import PairTransformTrain, PairTransformValid, Shuffled2DPaired
-from .training import assert_finite_step, freeze_batchnorm, l1_loss, train_step
+from .training import assert_finite_step, freeze_batchnorm, l1_loss, loss_name, make_loss, train_step
 
 
 def fmt(seconds: float) -> str:
@@ -95,8 +97,9 @@ class DevicePoolLoader:
             yield self.pool.sample(mine[b * self.batch_size:(b + 1) * self.batch_size])
 
 
-def train_one_epoch(model, loader, optimizer, device, sync=None, check_finite=True, graphed=None, freeze_bn=False):
-    """graphed: a training.GraphedTrainStep over (model, optimizer) that runs the step instead of train_step (--graph).
+def train_one_epoch(model, loader, optimizer, device, sync=None, check_finite=True, graphed=None, freeze_bn=False, loss_fn=None):
+    """loss_fn: the objective of train_step (training.make_loss; None = L1).
+    graphed: a training.GraphedTrainStep over (model, optimizer) that runs the step instead of train_step (--graph).
     freeze_bn: every BatchNorm stays in eval mode (running statistics, no buffer moves): re-applied here because model.train() switches
     them all back on, and before the first graphed step captures the launch sequence."""
     model.train()
@@ -105,7 +108,7 @@ def train_one_epoch(model, loader, optimizer, device, sync=None, check_finite=Tr
     total, n, t0 = 0.0, 0, time.time()
     for lr, hr in loader:
         lr, hr = lr.to(device, non_blocking=True), hr.to(device, non_blocking=True)
-        loss, bad = graphed(lr, hr) if graphed is not None else train_step(model, optimizer, lr, hr, sync)
+        loss, bad = graphed(lr, hr) if graphed is not None else train_step(model, optimizer, lr, hr, sync, loss_fn)
         if check_finite:
             assert_finite_step(loss, bad)          # RuntimeError like finetune_swinir.py:133-143
         total += float(loss)
@@ -114,9 +117,12 @@ def train_one_epoch(model, loader, optimizer, device, sync=None, check_finite=Tr
 
 
 @torch.no_grad()
-def validate(model, loader, device):
+def validate(model, loader, device, with_ssim=False):
+    """-> (mean L1 over batches, mean per-image PSNR, seconds); with_ssim (device only): also the mean per-image SSIM (ops.ssim,
+    data_range 1), inserted before the seconds."""
     model.eval()
     total, n, sum_psnr, n_imgs, t0 = 0.0, 0, 0.0, 0, time.time()
+    ssim_acc = torch.zeros(1, dtype=torch.float32, device=device) if with_ssim else None
     on_gpu = torch.device(device).type == "cuda"
     if on_gpu:
         # fused L1 + per-image PSNR pass (csrc/misc.hip psnr_*_kernel); the sums stay on the device until the loop ends
@@ -131,6 +137,8 @@ def validate(model, loader, device):
             batch_abs = torch.zeros(1, dtype=torch.float32, device=device)
             ops.batch_psnr(out.float(), hr.float(), 1.0, psnr_sum=psnr_acc, abs_sum=batch_abs)
             l1_acc += batch_abs / out.numel()          # mean over the batch, like F.l1_loss; batches may differ in size
+            if with_ssim:
+                ssim_acc += ops.ssim(out.float(), hr.float(), 1.0)[0].sum()
         else:
             total += float(l1_loss(out, hr))
             sum_psnr += float(batch_psnr(out, hr).sum())
@@ -138,6 +146,8 @@ def validate(model, loader, device):
         n_imgs += lr.size(0)
     if on_gpu:
         total, sum_psnr = float(l1_acc), float(psnr_acc)
+    if with_ssim:
+        return total / max(1, n), sum_psnr / max(1, n_imgs), float(ssim_acc) / max(1, n_imgs), time.time() - t0
     return total / max(1, n), sum_psnr / max(1, n_imgs), time.time() - t0
 
 
@@ -214,7 +224,21 @@ def parse_args(argv=None):
                          "with p = 0.5 -- the distribution of the reference's PairFlips, drawn from `random` and not from its "
                          "torch.rand stream; d4: the flips and the 90-degree rotations (all eight symmetries).  With --gpu_data the "
                          "transform is one kernel launch per batch side")
+    ap.add_argument("--loss", type=str, choices=["l1", "mse", "charbonnier"], default="l1",
+                    help="additive: the pixel objective (training.make_loss): l1 as the reference, mse, or charbonnier = "
+                         "mean sqrt(d^2 + eps^2)")
+    ap.add_argument("--charbonnier_eps", type=float, default=1e-3, help="additive: the eps of --loss charbonnier")
+    ap.add_argument("--ssim_weight", type=float, default=0.0,
+                    help="additive: add ssim_weight * (1 - SSIM(pred, hr)) to the objective (0 = off; needs HR patches of at least "
+                         "11 x 11); validation then also reports the SSIM and checkpoints gain 'val_ssim'")
     args = ap.parse_args(argv)
+    if not 0.0 <= args.ssim_weight < float("inf"):          # also refuses NaN
+        ap.error(f"--ssim_weight must be a finite number >= 0 (got {args.ssim_weight})")
+    if not args.charbonnier_eps > 0.0:
+        ap.error(f"--charbonnier_eps must be > 0 (got {args.charbonnier_eps})")
+    if args.ssim_weight > 0 and args.lr_patch * (2 if args.scale.upper() == "X2" else 4) < 11:
+        ap.error(f"--ssim_weight needs HR patches of at least 11 x 11 (lr_patch * scale = "
+                 f"{args.lr_patch * (2 if args.scale.upper() == 'X2' else 4)})")
     if not 0.0 <= args.ema_decay < 1.0:          # also refuses NaN
         ap.error(f"--ema_decay must be in [0, 1) (got {args.ema_decay})")
     if not 2 <= args.window_size <= 8:
@@ -315,32 +339,42 @@ def main(argv=None):
                      ema_decay=args.ema_decay or None)
     sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=args.epochs, eta_min=args.min_lr) if args.scheduler == "Cosine" else None
 
+    custom = args.loss != "l1" or args.ssim_weight > 0          # at the defaults: the L1 step, lines and files of ever
+    loss_fn = make_loss(args.loss, args.charbonnier_eps, args.ssim_weight) if custom else None
+    with_ssim = args.ssim_weight > 0
     graphed = None
     if args.graph:
         from .training import GraphedTrainStep
-        graphed = GraphedTrainStep(model, opt)          # drop_last=True keeps the batch shape fixed
+        graphed = GraphedTrainStep(model, opt, loss_fn=loss_fn)          # drop_last=True keeps the batch shape fixed
 
     best_loss, best_psnr, t_all = float("inf"), -float("inf"), time.time()
     for epoch in range(1, args.epochs + 1):
         if sampler is not None:
             sampler.set_epoch(epoch)
         tr_loss, tr_t = train_one_epoch(model, train_loader, opt, device, dp if world > 1 else None, graphed=graphed,
-                                        freeze_bn=args.freeze_bn)
+                                        freeze_bn=args.freeze_bn, loss_fn=loss_fn)
         if args.ema_decay:          # validate what gets shipped: the averaged weights (ranks hold identical averages)
             with opt.swap_ema():
-                val_loss, val_psnr, val_t = validate(model, valid_loader, device)
+                val = validate(model, valid_loader, device, with_ssim)
         else:
-            val_loss, val_psnr, val_t = validate(model, valid_loader, device)
+            val = validate(model, valid_loader, device, with_ssim)
+        val_loss, val_psnr, val_t = val[0], val[1], val[-1]
         if sched is not None:
             sched.step()
         if rank != 0:
             continue
+        train_name = f"loss[{loss_name(args.loss, args.ssim_weight)}]" if custom else "L1"
+        val_more = f", SSIM={val[2]:.4f}" if with_ssim else ""
         print(f"[{args.scale}] epoch {epoch:03d}/{args.epochs} | lr={opt.param_groups[0]['lr']:.2e} | "
-              f"train L1={tr_loss:.6f} ({tr_t:.1f}s) | val L1={val_loss:.6f}, PSNR={val_psnr:.2f}dB ({val_t:.1f}s)")
+              f"train {train_name}={tr_loss:.6f} ({tr_t:.1f}s) | val L1={val_loss:.6f}, PSNR={val_psnr:.2f}dB{val_more} ({val_t:.1f}s)")
         sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}     # un-prefixed keys, like the reference
         # with --ema_decay: the average next to the raw weights, under the key of the published checkpoints; without: the files as ever
         more = {"params_ema": opt.ema_state_dict()} if args.ema_decay else {}
-        saved_args = {k: v for k, v in vars(args).items() if k != "ema_decay" or args.ema_decay}
+        if with_ssim:
+            more["val_ssim"] = val[2]
+        at_default = {"ema_decay": not args.ema_decay, "loss": args.loss == "l1", "charbonnier_eps": args.charbonnier_eps == 1e-3,
+                      "ssim_weight": args.ssim_weight == 0}          # additive flags leave no trace in the files at their defaults
+        saved_args = {k: v for k, v in vars(args).items() if not at_default.get(k, False)}
         if val_loss < best_loss:
             best_loss = val_loss
             torch.save({"model": sd, **more, "epoch": epoch, "best_val_loss": best_loss, "val_psnr": val_psnr, "args": saved_args},

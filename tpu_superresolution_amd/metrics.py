@@ -82,11 +82,33 @@ def ssim_torch(X: torch.Tensor, Y: torch.Tensor, data_range: float = 255.0, size
     return per_channel.mean() if size_average else per_channel.mean(1)
 
 
+class _SsimMean(torch.autograd.Function):
+    """Batch-mean SSIM that carries a gradient for X (csrc/loss.hip: value and dS/dX from one fused kernel); none for Y."""
+
+    @staticmethod
+    def forward(ctx, X, Y, data_range):
+        from . import ops
+        mean, d_x, _ = ops.ssim_loss_fwd_bwd(X.contiguous(), Y.detach().contiguous(), data_range, alpha=-1.0)      # d_x = +dS/dX
+        ctx.save_for_backward(d_x)
+        return mean.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (d_x,) = ctx.saved_tensors
+        return d_x * g, None, None
+
+
 def ssim(X: torch.Tensor, Y: torch.Tensor, data_range: float = 255.0, size_average: bool = True, **kw) -> torch.Tensor:
-    """``pytorch_msssim.ssim`` signature (data_range default 255, as published)."""
+    """``pytorch_msssim.ssim`` signature (data_range default 255, as published).  On the device path the batch mean
+    (size_average=True) of an X that requires grad is differentiable in X (``1 - ssim(model(x), hr)`` trains); Y gets no gradient.
+    The per-image form (size_average=False) of such an X goes through the torch operators."""
     if (_on_device(X, Y) and not kw and X.ndim == 4 and X.shape == Y.shape and X.shape[2] >= 11 and X.shape[3] >= 11 and X.size(0) <= 1024
             and X.size(0) * X.size(1) < 65536):
         from . import ops
+        if torch.is_grad_enabled() and X.requires_grad:
+            if size_average:
+                return _SsimMean.apply(X, Y, float(data_range))
+            return ssim_torch(X, Y, data_range=data_range, size_average=False)
         per, mean = ops.ssim(X.detach(), Y.detach(), data_range)
         return mean.reshape(()) if size_average else per
     return ssim_torch(X, Y, data_range=data_range, size_average=size_average, **kw)

@@ -469,3 +469,50 @@ def l1_loss_fwd_bwd(pred: torch.Tensor, target: torch.Tensor, want_grad: bool = 
     d = torch.empty_like(pred) if want_grad else None
     check(lib().srk_l1_loss_fwd_bwd(_p(pred), _p(target), _p(d), _p(loss), _p(bad), pred.numel(), float(grad_scale), _stream()))
     return loss, d, bad
+
+
+def pixel_loss_fwd_bwd(pred: torch.Tensor, target: torch.Tensor, kind: str = "l1", eps: float = 1e-3, want_grad: bool = True,
+                       grad_scale: float = 1.0, d_pred: Optional[torch.Tensor] = None, accumulate: bool = False,
+                       loss: Optional[torch.Tensor] = None, bad: Optional[torch.Tensor] = None):
+    """mean |d| ('l1'), mean d^2 ('mse') or mean sqrt(d^2 + eps^2) ('charbonnier'), d = pred - target (csrc/loss.hip, fixed-order sums)
+    -> (loss fp32 [1], d_pred | None, nonfinite int32 [1]).  `loss` / `bad` that are passed in are ACCUMULATED into; a `d_pred` that is
+    passed in is overwritten, or added to with accumulate=True.  No host read: capturable."""
+    if kind not in _lib.LOSS_KINDS:
+        raise ValueError(f"pixel loss kind must be one of {sorted(_lib.LOSS_KINDS)} (got {kind!r})")
+    if pred.shape != target.shape or pred.dtype != torch.float32 or target.dtype != torch.float32:
+        raise ValueError(f"pixel loss: pred / target must be fp32 of one shape (got {pred.dtype} {tuple(pred.shape)}, "
+                         f"{target.dtype} {tuple(target.shape)})")
+    if loss is None:
+        loss = torch.zeros(1, dtype=torch.float32, device=pred.device)
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int32, device=pred.device)
+    if d_pred is None and want_grad:
+        if accumulate:
+            raise ValueError("pixel loss: accumulate=True needs the d_pred to add to")
+        d_pred = torch.empty_like(pred)
+    n = pred.numel()
+    ws = torch.empty(max(4, int(lib().srk_pixel_loss_workspace(n))), dtype=torch.uint8, device=pred.device)
+    check(lib().srk_pixel_loss_fwd_bwd(_p(pred), _p(target), _p(d_pred), _p(loss), _p(bad), n, _lib.LOSS_KINDS[kind], float(eps),
+                                       float(grad_scale), int(bool(accumulate)), _p(ws), _stream()))
+    return loss, d_pred, bad
+
+
+def ssim_loss_fwd_bwd(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0, alpha: float = 1.0, want_grad: bool = True,
+                      d_x: Optional[torch.Tensor] = None, accumulate: bool = False, loss: Optional[torch.Tensor] = None):
+    """The SSIM training term (csrc/loss.hip): S = ssim(x, y)'s batch mean -> (S fp32 [1], d_x | None, loss | None) with
+    d_x = -alpha dS/dx (stored, or added to a given d_x with accumulate=True) and, when `loss` is given, loss[0] += alpha (1 - S).
+    One fused kernel, fixed-order sums, no host read: capturable."""
+    if x.shape != y.shape or x.ndim != 4 or x.dtype != torch.float32 or y.dtype != torch.float32:
+        raise ValueError(f"ssim loss: x / y must be fp32 [B, C, H, W] of one shape (got {x.dtype} {tuple(x.shape)}, {y.dtype} {tuple(y.shape)})")
+    B, Cc, H, W = x.shape
+    if d_x is None and want_grad:
+        if accumulate:
+            raise ValueError("ssim loss: accumulate=True needs the d_x to add to")
+        d_x = torch.empty_like(x)
+    if d_x is not None and (d_x.shape != x.shape or d_x.dtype != torch.float32):
+        raise ValueError(f"ssim loss: d_x must be fp32 {tuple(x.shape)} (got {d_x.dtype} {tuple(d_x.shape)})")
+    ws = torch.empty(max(4, int(lib().srk_ssim_loss_workspace(B, Cc, H, W))), dtype=torch.uint8, device=x.device)
+    mean = torch.empty(1, dtype=torch.float32, device=x.device)
+    check(lib().srk_ssim_loss_fwd_bwd(_p(x), _p(y), _p(ws), B, Cc, H, W, float(data_range), float(alpha), _p(d_x), int(bool(accumulate)),
+                                      _p(mean), _p(loss), _stream()))
+    return mean, d_x, loss

@@ -1,5 +1,5 @@
 """Training-step pieces of finetune_swinir.py:148-179 on the HIP path: fused L1 loss (+ finite check),
-one-call train step."""
+one-call train step; make_loss: MSE / Charbonnier and an optional SSIM term through the same interface."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -35,12 +35,67 @@ def l1_loss_checked(pred: torch.Tensor, target: torch.Tensor) -> Tuple[torch.Ten
     return _L1Loss.apply(pred, target)
 
 
-def train_step(model, optimizer, lr_img: torch.Tensor, hr_img: torch.Tensor, sync=None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """One step of the reference loop (finetune_swinir.py:154-176): zero_grad, forward, L1, backward,
+LOSS_KINDS = ("l1", "mse", "charbonnier")
+
+
+def loss_name(kind: str = "l1", ssim_weight: float = 0.0) -> str:
+    """'l1', 'charbonnier+0.2*(1-ssim)', ...: how the scripts name the objective"""
+    return kind + (f"+{ssim_weight:g}*(1-ssim)" if ssim_weight else "")
+
+
+def make_loss(kind: str = "l1", charbonnier_eps: float = 1e-3, ssim_weight: float = 0.0, data_range: float = 1.0):
+    """-> callable (pred, target) -> (loss, nonfinite_count), both device tensors, for train_step / GraphedTrainStep(loss_fn=...).
+
+    kind 'l1' | 'mse' | 'charbonnier' (mean sqrt(d^2 + charbonnier_eps^2)); ssim_weight > 0 adds ssim_weight * (1 - SSIM(pred, target))
+    with the SSIM of metrics.ssim at `data_range` (4-D batches, H, W >= 11).  One autograd Function: its forward runs the pixel kernel
+    and then the SSIM kernel, which accumulates into the same loss scalar and the same d(pred) (csrc/loss.hip: fixed-order sums, no host
+    read, capturable); the non-finite counter is the one optim.FusedAdamW.step(nonfinite=...) gates on.  The target gets no gradient.
+    kind 'l1' without an SSIM term returns l1_loss_checked itself."""
+    if kind not in LOSS_KINDS:
+        raise ValueError(f"loss kind must be one of {LOSS_KINDS} (got {kind!r})")
+    eps, w, dr = float(charbonnier_eps), float(ssim_weight), float(data_range)
+    if not w >= 0.0 or w == float("inf"):          # also refuses NaN
+        raise ValueError(f"ssim_weight must be a finite number >= 0 (got {ssim_weight!r})")
+    if kind == "charbonnier" and not eps > 0.0:
+        raise ValueError(f"charbonnier_eps must be > 0 (got {charbonnier_eps!r})")
+    if not dr > 0.0:
+        raise ValueError(f"data_range must be > 0 (got {data_range!r})")
+    if kind == "l1" and w == 0.0:
+        return l1_loss_checked
+
+    class _Loss(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, pred, target):
+            p, t = pred.contiguous().float(), target.contiguous().float()
+            loss, d_pred, bad = ops.pixel_loss_fwd_bwd(p, t, kind, eps, want_grad=True)
+            if w > 0.0:
+                ops.ssim_loss_fwd_bwd(p, t, dr, alpha=w, d_x=d_pred, accumulate=True, loss=loss)
+            ctx.save_for_backward(d_pred)
+            ctx.mark_non_differentiable(bad)
+            return loss.reshape(()), bad
+
+        @staticmethod
+        def backward(ctx, g_loss, _g_bad):
+            (d_pred,) = ctx.saved_tensors
+            return d_pred * g_loss, None
+
+    def loss_fn(pred: torch.Tensor, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        if target.requires_grad:
+            raise ValueError("make_loss: the target gets no gradient (detach it)")
+        if w > 0.0 and (pred.ndim != 4 or pred.shape[2] < 11 or pred.shape[3] < 11):
+            raise ValueError(f"make_loss: the SSIM term needs [B, C, H, W] batches with H, W >= 11 (got {tuple(pred.shape)})")
+        return _Loss.apply(pred, target)
+
+    loss_fn.__name__ = loss_fn.__qualname__ = f"loss[{loss_name(kind, w)}]"
+    return loss_fn
+
+
+def train_step(model, optimizer, lr_img: torch.Tensor, hr_img: torch.Tensor, sync=None, loss_fn=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One step of the reference loop (finetune_swinir.py:154-176): zero_grad, forward, L1 (or `loss_fn`, see make_loss), backward,
     [gradient all-reduce], clip + AdamW.  Returns (loss, nonfinite_count) as device tensors (no host sync)."""
     optimizer.zero_grad(set_to_none=True)
     out = model(lr_img)
-    loss, bad = l1_loss_checked(out, hr_img)
+    loss, bad = (loss_fn or l1_loss_checked)(out, hr_img)
     loss.backward()
     if sync is not None:
         sync.finish()
@@ -104,10 +159,11 @@ class GraphedTrainStep:
 
         step = GraphedTrainStep(model, FusedAdamW(model, lr=2e-5, max_grad_norm=1.0))"""
 
-    def __init__(self, model, optimizer, max_grad_norm: float = 1.0, warmup: int = 2):
+    def __init__(self, model, optimizer, max_grad_norm: float = 1.0, warmup: int = 2, loss_fn=None):
         if getattr(model, "grad_sync", None) is not None:
             raise ValueError("GraphedTrainStep: detach the gradient synchronizer (graph capture is for single-process steps)")
         self.model, self.opt, self.max_grad_norm, self.warmup = model, optimizer, float(max_grad_norm), int(warmup)
+        self.loss_fn = loss_fn or l1_loss_checked              # (pred, target) -> (loss, nonfinite): make_loss; captured with the step
         self.fused = hasattr(optimizer, "begin_replay")          # optim.FusedAdamW
         if self.fused and getattr(optimizer, "_flat", False):
             raise ValueError("GraphedTrainStep is for host-orchestrated models (HAT / DAT); SwinIR's step is one C call per pass already")
@@ -117,7 +173,7 @@ class GraphedTrainStep:
 
     def _eager(self, x, t):
         self.opt.zero_grad(set_to_none=True)
-        loss, bad = l1_loss_checked(self.model(x), t)
+        loss, bad = self.loss_fn(self.model(x), t)
         loss.backward()
         if self.fused:
             self.opt.step(nonfinite=bad)          # clip + AdamW, gated on the device by the non-finite counter
