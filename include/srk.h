@@ -232,6 +232,29 @@ int srk_paired_crop_u8(const uint8_t* pool, const int64_t* lr_desc, const int64_
  * accumulate == 0 the values are moved, not multiplied: every bit pattern (NaN payloads included) arrives unchanged. */
 int srk_dihedral_f32(const float* in, float* out, const int32_t* ops, int op_all, int B, int C, int H, int W, float alpha,
                      int accumulate, srk_stream_t stream);
+/* Tiled inference (csrc/tile.hip): crop a chunk of overlapping tiles out of an fp32 NCHW batch, run a model on them as a batch of
+ * n * B, and merge the chunk's outputs into the output image.
+ * Tile grid, per axis with extent N, tile t (1 <= t <= N) and stride s (1 <= s <= t; overlap = t - s): k = ceil((N - t) / s) + 1
+ * tiles, origin o_i = min(i * s, N - t) -- range(0, N - t, s) + [N - t], the last tile pulled back to the border.  The 2-D grid is
+ * row-major, tile index iy * kx + ix; a chunk is the tiles t0 .. t0 + n - 1.
+ * srk_tile_gather_f32: tiles [n][B][C][th][tw] <- the crops of x [B][C][H][W].
+ * srk_tile_merge_f32: tiles [n][B][C][th][tw] -> out [B][C][Ho][Wo], every extent in OUTPUT pixels.  Chunks must be merged in
+ * ascending order and together cover the grid once.
+ *   SRK_TILE_MEAN: out[p] = (((0 + y_a[p]) + y_b[p]) + ...) / count over the tiles covering p in ascending tile index, sequential
+ *     fp32 adds and one correctly rounded fp32 division by the integer count.  A launch starts a pixel from 0 when its first covering
+ *     tile is in the chunk and from out[p] otherwise, adds the chunk's covering tiles, and divides iff the last covering tile is in
+ *     the chunk: out may start uninitialised, and the bits do not depend on how the grid is cut into chunks.
+ *   SRK_TILE_CENTER: out[p] is copied (bit pattern kept) from one tile: per axis the covering tile that maximises
+ *     min(p - o, o + t - 1 - p), ties to the lower index; written in the chunk that holds that tile.
+ * A launch writes no pixel that no tile of its chunk covers and nothing outside out[0 .. B*C*Ho*Wo) / tiles[0 .. n*B*C*th*tw).
+ * SRK_E_SHAPE, before any launch: a non-positive extent or n, t0 < 0, th > H, tw > W, a stride outside 1..t, t0 + n > ky * kx, an
+ * unknown mode, a grid that does not fit one launch, tiles overlapping x / out. */
+#define SRK_TILE_MEAN 0
+#define SRK_TILE_CENTER 1
+int srk_tile_gather_f32(const float* x, float* tiles, int t0, int n, int B, int C, int H, int W, int th, int tw, int sy, int sx,
+                        srk_stream_t stream);
+int srk_tile_merge_f32(const float* tiles, float* out, int t0, int n, int B, int C, int Ho, int Wo, int th, int tw, int sy, int sx,
+                       int mode, srk_stream_t stream);
 /* Validation metrics of one batch in one pass (first slice): per-image PSNR of the images clamped to [0, 1]
  * (batch_psnr, finetune_swinir.py:69-74: 20 log10(max_val / sqrt(mse + 1e-8)), mse over the per_image = C*H*W elements of an
  * image) and the sum of |pred - target| over the batch for the validation L1 (F.l1_loss, :66-67, used by validate :181-207).

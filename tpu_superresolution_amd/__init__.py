@@ -9,5 +9,6 @@ from .dat_arch import DAT  # noqa: F401
 from .hat_arch import HAT  # noqa: F401
 from .ms_resunet import MS_ResUNet, MSResUNet  # noqa: F401
 from .network_swinir import SwinIR, window_partition, window_reverse  # noqa: F401
+from .tiling import tile_origins, tiled_forward  # noqa: F401
 
-__all__ = ["SwinIR", "window_partition", "window_reverse", "MS_ResUNet", "MSResUNet", "HAT", "DAT"]
+__all__ = ["SwinIR", "window_partition", "window_reverse", "MS_ResUNet", "MSResUNet", "HAT", "DAT", "tile_origins", "tiled_forward"]

@@ -476,6 +476,47 @@ int srk_dihedral_f32(const float* in, float* out, const int32_t* ops, int op_all
   return srk_launch_dihedral_f32(in, out, reinterpret_cast<const int*>(ops), op_all, B, C, H, W, alpha, accumulate, (hipStream_t)stream);
 }
 
+// the checks srk_tile_gather_f32 and srk_tile_merge_f32 share; img is x or out, whichever the tiles must not overlap
+static int tile_args(const char* fn, const float* tiles, const float* img, int t0, int n, int B, int C, int H, int W, int th, int tw,
+                     int sy, int sx, TileAxis* ay, TileAxis* ax) {
+  SRK_REQUIRE(B >= 1 && C >= 1 && H >= 1 && W >= 1 && th >= 1 && tw >= 1, SRK_E_SHAPE, "%s: B=%d C=%d H=%d W=%d th=%d tw=%d must all be >= 1",
+              fn, B, C, H, W, th, tw);
+  SRK_REQUIRE(th <= H && tw <= W, SRK_E_SHAPE, "%s: a %d x %d tile is larger than the %d x %d image", fn, th, tw, H, W);
+  SRK_REQUIRE(sy >= 1 && sy <= th && sx >= 1 && sx <= tw, SRK_E_SHAPE, "%s: the stride must be in 1..tile (got %d for th=%d, %d for tw=%d)",
+              fn, sy, th, sx, tw);
+  *ay = srk_tile_axis(H, th, sy);
+  *ax = srk_tile_axis(W, tw, sx);
+  const long long grid = (long long)ay->k * ax->k;
+  SRK_REQUIRE(t0 >= 0 && n >= 1 && (long long)t0 + n <= grid && grid <= 2147483647LL, SRK_E_SHAPE,
+              "%s: the chunk [%d, %d + %d) is outside the grid of %d x %d tiles", fn, t0, t0, n, ay->k, ax->k);
+  const double planes = (double)B * C, tb = 4.0 * n * planes * th * tw, ib = 4.0 * planes * H * W;
+  SRK_REQUIRE(planes <= 2147483647.0 && tb < 9.0e18 && ib < 9.0e18, SRK_E_SHAPE, "%s: n=%d B=%d C=%d H=%d W=%d th=%d tw=%d is too large", fn, n,
+              B, C, H, W, th, tw);
+  const uintptr_t a = reinterpret_cast<uintptr_t>(tiles), b = reinterpret_cast<uintptr_t>(img);
+  SRK_REQUIRE(a + (uintptr_t)tb <= b || b + (uintptr_t)ib <= a, SRK_E_SHAPE, "%s: the tiles and the image overlap", fn);
+  return SRK_OK;
+}
+
+int srk_tile_gather_f32(const float* x, float* tiles, int t0, int n, int B, int C, int H, int W, int th, int tw, int sy, int sx,
+                        srk_stream_t stream) {
+  REQ_PTR(x); REQ_PTR(tiles);
+  TileAxis ay, ax;
+  const int rc = tile_args("tile_gather", tiles, x, t0, n, B, C, H, W, th, tw, sy, sx, &ay, &ax);
+  if (rc) return rc;
+  return srk_launch_tile_gather_f32(x, tiles, t0, n, B * C, ay, ax, (hipStream_t)stream);
+}
+
+int srk_tile_merge_f32(const float* tiles, float* out, int t0, int n, int B, int C, int Ho, int Wo, int th, int tw, int sy, int sx,
+                       int mode, srk_stream_t stream) {
+  REQ_PTR(tiles); REQ_PTR(out);
+  SRK_REQUIRE(mode == SRK_TILE_MEAN || mode == SRK_TILE_CENTER, SRK_E_SHAPE, "tile_merge: mode must be SRK_TILE_MEAN or SRK_TILE_CENTER (got %d)",
+              mode);
+  TileAxis ay, ax;
+  const int rc = tile_args("tile_merge", tiles, out, t0, n, B, C, Ho, Wo, th, tw, sy, sx, &ay, &ax);
+  if (rc) return rc;
+  return srk_launch_tile_merge_f32(tiles, out, t0, n, B * C, ay, ax, mode, (hipStream_t)stream);
+}
+
 int64_t srk_batch_psnr_workspace(int64_t per_image, int B) {
   if (per_image <= 0 || B <= 0) return 0;
   return (int64_t)2 * sizeof(float) * B * srk_batch_psnr_chunks(per_image);

@@ -58,6 +58,14 @@ int srk_launch_crop_u8(const unsigned char* pool, const long long* desc, float* 
 // dihedral.hip: the eight symmetries of the square on fp32 NCHW batches (arguments checked by srk_dihedral_f32)
 int srk_launch_dihedral_f32(const float* in, float* out, const int* ops, int op_all, int B, int C, int H, int W, float alpha,
                             int accumulate, hipStream_t stream);
+// tile.hip: tiled inference (arguments checked by srk_tile_gather_f32 / srk_tile_merge_f32).  One axis of the tile grid: extent n,
+// tile t (1 <= t <= n), stride s (1 <= s <= t), k = ceil((n - t) / s) + 1 tiles, origin o_i = min(i * s, n - t)
+struct TileAxis { int n, t, s, k; };
+inline TileAxis srk_tile_axis(int n, int t, int s) { return TileAxis{n, t, s, (n - t + s - 1) / s + 1}; }
+inline int srk_tile_origin(const TileAxis& a, int i) { const long long o = (long long)i * a.s; return o < a.n - a.t ? (int)o : a.n - a.t; }
+int srk_launch_tile_gather_f32(const float* x, float* tiles, int t0, int n, int planes, TileAxis ay, TileAxis ax, hipStream_t stream);
+int srk_launch_tile_merge_f32(const float* tiles, float* out, int t0, int n, int planes, TileAxis ay, TileAxis ax, int mode,
+                              hipStream_t stream);
 int srk_launch_batch_psnr(const float* pred, const float* target, float* partial, int B, long long per_image, float max_val,
                           float* psnr, float* psnr_sum, float* abs_sum, hipStream_t stream);
 int srk_launch_zero_f32(float* p, long long n, hipStream_t stream);      // graph-safe zero fill (misc.hip)

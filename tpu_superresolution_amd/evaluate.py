@@ -11,8 +11,9 @@ by --save_n (:199-225) -> summary (:229-234).
 
 BASELINE config 1 runs this on the CPU with stock torch operators (MS_ResUNet has no kernel in scope).
 Additive: ``--arch swinir | hat | dat`` evaluates the MI355X SwinIR / HAT / DAT path (finetune_swinir.py model, RGB un-upscaled LR input, needs a
-GPU + libsrk); ``--self_ensemble`` averages the eight flipped / rotated predictions (any --arch); ``main(argv)`` is callable from
-tests.  SSIM is ``metrics.ssim`` (restated, parity unpinned).
+GPU + libsrk); ``--self_ensemble`` averages the eight flipped / rotated predictions (any --arch); ``--tile N`` predicts on overlapping
+N x N tiles of the model's input and merges them (tiling.tiled_forward; any --arch; inside the self-ensemble when both are given);
+``main(argv)`` is callable from tests.  SSIM is ``metrics.ssim`` (restated, parity unpinned).
 """
 from __future__ import annotations
 
@@ -87,7 +88,18 @@ def parse_args(argv=None):
     ap.add_argument("--self_ensemble", action="store_true",
                     help="additive: predict with the x8 self-ensemble (the '+' of SwinIR+ / HAT+ / DAT+): the mean of the eight "
                          "inverse-transformed predictions on the flipped / rotated inputs (augment.self_ensemble)")
+    ap.add_argument("--tile", type=int, default=0,
+                    help="additive: predict on overlapping tiles of N x N input pixels and merge them (tiling.tiled_forward; 0 = off, "
+                         "the whole image in one call; a tile at least as large as the image is the whole image too)")
+    ap.add_argument("--tile_overlap", type=int, default=32, help="additive, with --tile: input pixels two neighbouring tiles share")
+    ap.add_argument("--tile_batch", type=int, default=1, help="additive, with --tile: tiles per model call")
+    ap.add_argument("--tile_blend", type=str, choices=["mean", "center"], default="mean",
+                    help="additive, with --tile: mean = average the tiles covering a pixel (SwinIR's test script), center = take each "
+                         "pixel from the tile whose border is farthest (what the tile_pad of the HAT / DAT scripts aims at)")
     args = ap.parse_args(argv)
+    if args.tile < 0 or args.tile_batch < 1 or args.tile_overlap < 0 or (args.tile and args.tile_overlap >= args.tile):
+        ap.error(f"--tile must be >= 0, --tile_batch >= 1 and 0 <= --tile_overlap < --tile (got --tile {args.tile} "
+                 f"--tile_overlap {args.tile_overlap} --tile_batch {args.tile_batch})")
     if not 2 <= args.window_size <= 8 or (args.window_size != 8 and args.arch != "swinir"):
         ap.error(f"--window_size must be in 2..8 and is an option of --arch swinir (got {args.window_size} with --arch {args.arch})")
     return args
@@ -146,11 +158,17 @@ def main(argv=None):
     print(msg)
     model = model.to(device).eval()
     predict = model
+    if args.tile:
+        from functools import partial
+
+        from .tiling import tiled_forward
+        predict = partial(tiled_forward, model, tile=args.tile, overlap=args.tile_overlap, tile_batch=args.tile_batch, blend=args.tile_blend)
+        print(f"[tile] {args.tile} overlap {args.tile_overlap} batch {args.tile_batch} blend {args.tile_blend}")
     if args.self_ensemble:
         from functools import partial
 
         from .augment import self_ensemble
-        predict = partial(self_ensemble, model)
+        predict = partial(self_ensemble, predict)
         print("[self_ensemble] x8")
 
     t0 = time.time()

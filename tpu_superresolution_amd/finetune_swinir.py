@@ -12,6 +12,7 @@ context), the step uses the fused L1 / clip / AdamW kernels, `--weights` may be 
 on flipped / rotated patches (augment.py; on the device with `--gpu_data`).  `--loss l1|mse|charbonnier` (default l1) and
 `--ssim_weight W` (default 0) choose the objective: the pixel loss plus W * (1 - SSIM), value and gradient from the fused kernels of
 csrc/loss.hip (training.make_loss); with W > 0 validation also reports the mean per-image SSIM and checkpoints gain 'val_ssim'.
+`--val_tile N` (default 0 = whole images) validates on overlapping N x N LR tiles merged on the device (tiling.tiled_forward).
 
 Also additive: `--arch hat|dat` fine-tunes HAT / DAT (build_sr_model) through the same loop -- the fused, device-gated clip + AdamW step
 over their parameter lists (optim.FusedAdamW, csrc/optim_multi.hip), checkpoints "best_<arch>_finetune_<scale>.pt" /
@@ -117,10 +118,12 @@ def train_one_epoch(model, loader, optimizer, device, sync=None, check_finite=Tr
 
 
 @torch.no_grad()
-def validate(model, loader, device, with_ssim=False):
+def validate(model, loader, device, with_ssim=False, predict=None):
     """-> (mean L1 over batches, mean per-image PSNR, seconds); with_ssim (device only): also the mean per-image SSIM (ops.ssim,
-    data_range 1), inserted before the seconds."""
+    data_range 1), inserted before the seconds.  predict: what maps an LR batch to the prediction instead of the model itself
+    (--val_tile: tiling.tiled_forward around the model)."""
     model.eval()
+    predict = model if predict is None else predict
     total, n, sum_psnr, n_imgs, t0 = 0.0, 0, 0.0, 0, time.time()
     ssim_acc = torch.zeros(1, dtype=torch.float32, device=device) if with_ssim else None
     on_gpu = torch.device(device).type == "cuda"
@@ -132,7 +135,7 @@ def validate(model, loader, device, with_ssim=False):
         l1_acc = torch.zeros(1, dtype=torch.float32, device=device)
     for lr, hr in loader:
         lr, hr = lr.to(device, non_blocking=True), hr.to(device, non_blocking=True)
-        out = model(lr)
+        out = predict(lr)
         if on_gpu:
             batch_abs = torch.zeros(1, dtype=torch.float32, device=device)
             ops.batch_psnr(out.float(), hr.float(), 1.0, psnr_sum=psnr_acc, abs_sum=batch_abs)
@@ -231,7 +234,14 @@ def parse_args(argv=None):
     ap.add_argument("--ssim_weight", type=float, default=0.0,
                     help="additive: add ssim_weight * (1 - SSIM(pred, hr)) to the objective (0 = off; needs HR patches of at least "
                          "11 x 11); validation then also reports the SSIM and checkpoints gain 'val_ssim'")
+    ap.add_argument("--val_tile", type=int, default=0,
+                    help="additive: validate on overlapping tiles of N x N LR pixels merged by their mean (tiling.tiled_forward; 0 = "
+                         "off, the whole image in one call)")
+    ap.add_argument("--val_tile_overlap", type=int, default=32, help="additive, with --val_tile: LR pixels two neighbouring tiles share")
     args = ap.parse_args(argv)
+    if args.val_tile < 0 or args.val_tile_overlap < 0 or (args.val_tile and args.val_tile_overlap >= args.val_tile):
+        ap.error(f"--val_tile must be >= 0 and 0 <= --val_tile_overlap < --val_tile (got --val_tile {args.val_tile} "
+                 f"--val_tile_overlap {args.val_tile_overlap})")
     if not 0.0 <= args.ssim_weight < float("inf"):          # also refuses NaN
         ap.error(f"--ssim_weight must be a finite number >= 0 (got {args.ssim_weight})")
     if not args.charbonnier_eps > 0.0:
@@ -347,6 +357,15 @@ def main(argv=None):
         from .training import GraphedTrainStep
         graphed = GraphedTrainStep(model, opt, loss_fn=loss_fn)          # drop_last=True keeps the batch shape fixed
 
+    predict = None
+    if args.val_tile:
+        from functools import partial
+
+        from .tiling import tiled_forward
+        predict = partial(tiled_forward, model, tile=args.val_tile, overlap=args.val_tile_overlap)
+        if rank == 0:
+            print(f"[val_tile] {args.val_tile} overlap {args.val_tile_overlap}")
+
     best_loss, best_psnr, t_all = float("inf"), -float("inf"), time.time()
     for epoch in range(1, args.epochs + 1):
         if sampler is not None:
@@ -355,9 +374,9 @@ def main(argv=None):
                                         freeze_bn=args.freeze_bn, loss_fn=loss_fn)
         if args.ema_decay:          # validate what gets shipped: the averaged weights (ranks hold identical averages)
             with opt.swap_ema():
-                val = validate(model, valid_loader, device, with_ssim)
+                val = validate(model, valid_loader, device, with_ssim, predict)
         else:
-            val = validate(model, valid_loader, device, with_ssim)
+            val = validate(model, valid_loader, device, with_ssim, predict)
         val_loss, val_psnr, val_t = val[0], val[1], val[-1]
         if sched is not None:
             sched.step()
@@ -373,7 +392,8 @@ def main(argv=None):
         if with_ssim:
             more["val_ssim"] = val[2]
         at_default = {"ema_decay": not args.ema_decay, "loss": args.loss == "l1", "charbonnier_eps": args.charbonnier_eps == 1e-3,
-                      "ssim_weight": args.ssim_weight == 0}          # additive flags leave no trace in the files at their defaults
+                      "ssim_weight": args.ssim_weight == 0, "val_tile": args.val_tile == 0,
+                      "val_tile_overlap": args.val_tile == 0 or args.val_tile_overlap == 32}          # additive flags leave no trace in the files at their defaults
         saved_args = {k: v for k, v in vars(args).items() if not at_default.get(k, False)}
         if val_loss < best_loss:
             best_loss = val_loss
