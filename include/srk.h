@@ -232,6 +232,29 @@ int srk_paired_crop_u8(const uint8_t* pool, const int64_t* lr_desc, const int64_
  * accumulate == 0 the values are moved, not multiplied: every bit pattern (NaN payloads included) arrives unchanged. */
 int srk_dihedral_f32(const float* in, float* out, const int32_t* ops, int op_all, int B, int C, int H, int W, float alpha,
                      int accumulate, srk_stream_t stream);
+/* Antialiased bicubic resampling (csrc/resize.hip): the Keys cubic with a = -0.5 in the convention of PIL's Image.BICUBIC and of
+ * F.interpolate(mode='bicubic', antialias=True, align_corners=False).  Per axis n_in -> n_out with scale = n_in / n_out (fp64):
+ * support = 2 max(scale, 1); output i has centre c = scale (i + 0.5) and taps [lo, hi) = [max(int(c - support + 0.5), 0),
+ * min(int(c + support + 0.5), n_in)) with w_j = k((j + lo - c + 0.5) / max(scale, 1)) divided by their sum: taps outside the image are
+ * dropped and the rest renormalised, nothing is clamped or mirrored.  The weights are evaluated in fp64 and rounded once to fp32; the
+ * horizontal pass runs first, then the vertical pass, each an ascending-tap chain of fp32 fused multiply-adds starting from 0.
+ * x fp32 [B][C][H][W] -> out fp32 [B][C][Ho][Wo], up or down.  quant_bits == 0: the filtered value; quant_bits == 8:
+ * (float)rint(clamp(v, 0, 1) * 255) / 255.0f, what an 8-bit image file of the result decodes to.  An output is NaN exactly when a tap of
+ * its footprint (zero weights included) is.  One launch, no device allocation, the horizontal-pass result stays in LDS; nothing
+ * outside out[0 .. B*C*Ho*Wo) is written.  SRK_E_NULL: null x / out; SRK_E_SHAPE: a non-positive extent, quant_bits other than 0 / 8,
+ * x and out overlapping, a size that does not fit one launch; SRK_E_UNSUPPORTED: an axis shrinking by more than 8x (more than 33 taps). */
+int srk_resize_aa_f32(const float* x, float* out, int B, int C, int H, int W, int Ho, int Wo, int quant_bits, srk_stream_t stream);
+/* Training pairs from HR images only: the HR patch of srk_paired_crop_u8 and its antialiased bicubic degradation in ONE launch.
+ * pool / hr_desc: as srk_paired_crop_u8 -- B descriptors {byte offset, H, W, C | (wide << 8), top, left} in DEVICE memory; top and left
+ * are in HR pixels, multiples of scale (2..4), and top / scale + P <= H / scale, left / scale + P <= W / scale (the caller checks; the
+ * kernel does not, it only keeps its loads inside the image).  hr_out: fp32 [B][3][P*scale][P*scale], bit-identical to what
+ * srk_paired_crop_u8 writes for the descriptor.  lr_out: fp32 [B][3][P][P] = rows top / scale .. and columns left / scale .. of the
+ * (H / scale, W / scale) downscale of the image's top-left (H - H % scale, W - W % scale) region: taps are bounded by that region, not
+ * by the patch, so the patch is BIT-IDENTICAL to the same window of srk_resize_aa_f32 on the whole converted region (the two entries
+ * share their device routines).  A gray source is filtered once and written to three channels.  quant_bits as above (LR only).
+ * SRK_E_NULL: a null pointer; SRK_E_SHAPE: B outside 1..65535, lr_patch outside 1..2048, scale outside 2..4, quant_bits other than 0 / 8. */
+int srk_crop_degrade_u8(const uint8_t* pool, const int64_t* hr_desc, float* lr_out, float* hr_out, int B, int lr_patch, int scale,
+                        int quant_bits, srk_stream_t stream);
 /* Tiled inference (csrc/tile.hip): crop a chunk of overlapping tiles out of an fp32 NCHW batch, run a model on them as a batch of
  * n * B, and merge the chunk's outputs into the output image.
  * Tile grid, per axis with extent N, tile t (1 <= t <= N) and stride s (1 <= s <= t; overlap = t - s): k = ceil((N - t) / s) + 1

@@ -476,6 +476,31 @@ int srk_dihedral_f32(const float* in, float* out, const int32_t* ops, int op_all
   return srk_launch_dihedral_f32(in, out, reinterpret_cast<const int*>(ops), op_all, B, C, H, W, alpha, accumulate, (hipStream_t)stream);
 }
 
+int srk_resize_aa_f32(const float* x, float* out, int B, int C, int H, int W, int Ho, int Wo, int quant_bits, srk_stream_t stream) {
+  REQ_PTR(x); REQ_PTR(out);
+  SRK_REQUIRE(B >= 1 && C >= 1 && H >= 1 && W >= 1 && Ho >= 1 && Wo >= 1, SRK_E_SHAPE, "resize_aa: B=%d C=%d H=%d W=%d Ho=%d Wo=%d must all be >= 1",
+              B, C, H, W, Ho, Wo);
+  SRK_REQUIRE(quant_bits == 0 || quant_bits == 8, SRK_E_SHAPE, "resize_aa: quant_bits must be 0 or 8 (got %d)", quant_bits);
+  const double planes = (double)B * C, ib = 4.0 * planes * H * W, ob = 4.0 * planes * Ho * Wo;
+  SRK_REQUIRE(planes <= 2147483647.0 && ib < 9.0e18 && ob < 9.0e18, SRK_E_SHAPE, "resize_aa: B=%d C=%d H=%d W=%d Ho=%d Wo=%d is too large", B, C, H,
+              W, Ho, Wo);
+  const uintptr_t a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(out);
+  SRK_REQUIRE(a + (uintptr_t)ib <= b || b + (uintptr_t)ob <= a, SRK_E_SHAPE, "resize_aa: x and out overlap (the resize is not done in place)");
+  SRK_REQUIRE((long long)H <= 8LL * Ho && (long long)W <= 8LL * Wo, SRK_E_UNSUPPORTED,
+              "resize_aa: %d x %d -> %d x %d shrinks an axis by more than 8x (more than 33 taps)", H, W, Ho, Wo);
+  return srk_launch_resize_aa_f32(x, out, B * C, H, W, Ho, Wo, quant_bits, (hipStream_t)stream);
+}
+
+int srk_crop_degrade_u8(const uint8_t* pool, const int64_t* hr_desc, float* lr_out, float* hr_out, int B, int lr_patch, int scale,
+                        int quant_bits, srk_stream_t stream) {
+  REQ_PTR(pool); REQ_PTR(hr_desc); REQ_PTR(lr_out); REQ_PTR(hr_out);
+  SRK_REQUIRE(B > 0 && B <= 65535 && lr_patch > 0 && lr_patch <= 2048 && scale >= 2 && scale <= 4, SRK_E_SHAPE,
+              "crop_degrade: B=%d (1..65535) patch=%d (1..2048) scale=%d (2..4)", B, lr_patch, scale);
+  SRK_REQUIRE(quant_bits == 0 || quant_bits == 8, SRK_E_SHAPE, "crop_degrade: quant_bits must be 0 or 8 (got %d)", quant_bits);
+  return srk_launch_crop_degrade_u8(pool, reinterpret_cast<const long long*>(hr_desc), lr_out, hr_out, B, lr_patch, scale, quant_bits,
+                                    (hipStream_t)stream);
+}
+
 // the checks srk_tile_gather_f32 and srk_tile_merge_f32 share; img is x or out, whichever the tiles must not overlap
 static int tile_args(const char* fn, const float* tiles, const float* img, int t0, int n, int B, int C, int H, int W, int th, int tw,
                      int sy, int sx, TileAxis* ay, TileAxis* ax) {

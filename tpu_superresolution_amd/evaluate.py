@@ -13,7 +13,8 @@ BASELINE config 1 runs this on the CPU with stock torch operators (MS_ResUNet ha
 Additive: ``--arch swinir | hat | dat`` evaluates the MI355X SwinIR / HAT / DAT path (finetune_swinir.py model, RGB un-upscaled LR input, needs a
 GPU + libsrk); ``--self_ensemble`` averages the eight flipped / rotated predictions (any --arch); ``--tile N`` predicts on overlapping
 N x N tiles of the model's input and merges them (tiling.tiled_forward; any --arch; inside the self-ensemble when both are given);
-``main(argv)`` is callable from tests.  SSIM is ``metrics.ssim`` (restated, parity unpinned).
+``--synth_lr [--synth_lr_bits 0|8]`` (--arch swinir | hat | dat) needs only the HR directory of the test split: LR is its antialiased
+bicubic downscale, formed on the device (ops.resize_aa); ``main(argv)`` is callable from tests.  SSIM is ``metrics.ssim`` (restated, parity unpinned).
 """
 from __future__ import annotations
 
@@ -96,7 +97,14 @@ def parse_args(argv=None):
     ap.add_argument("--tile_blend", type=str, choices=["mean", "center"], default="mean",
                     help="additive, with --tile: mean = average the tiles covering a pixel (SwinIR's test script), center = take each "
                          "pixel from the tile whose border is farthest (what the tile_pad of the HAT / DAT scripts aims at)")
+    ap.add_argument("--synth_lr", action="store_true",
+                    help="additive, --arch swinir|hat|dat: evaluate from the HR directory of the test split alone; LR is its antialiased "
+                         "bicubic (PIL BICUBIC convention) downscale, formed on the device (ops.resize_aa)")
+    ap.add_argument("--synth_lr_bits", type=int, choices=[0, 8], default=8,
+                    help="additive, with --synth_lr: 8 = LR rounded to k / 255 as an 8-bit LR file would hold it, 0 = the filtered values")
     args = ap.parse_args(argv)
+    if args.synth_lr and args.arch == "ms_resunet":
+        ap.error("--synth_lr is an option of --arch swinir | hat | dat (MS_ResUNet takes the pre-upscaled LR of the eval transform)")
     if args.tile < 0 or args.tile_batch < 1 or args.tile_overlap < 0 or (args.tile and args.tile_overlap >= args.tile):
         ap.error(f"--tile must be >= 0, --tile_batch >= 1 and 0 <= --tile_overlap < --tile (got --tile {args.tile} "
                  f"--tile_overlap {args.tile_overlap} --tile_batch {args.tile_batch})")
@@ -120,9 +128,16 @@ def main(argv=None):
         tf_test = PairTransformValid(scale_int)
     else:
         tf_test = build_pair_transform_eval()
-    test_ds = Shuffled2DPaired(args.data_root, split="test", scale=args.scale, transform_pair=tf_test)
+    if args.synth_lr:
+        from .sr_datasets import Shuffled2DHR, SynthLRBatches, hr_to_tensor3
+        test_ds = Shuffled2DHR(args.data_root, split="test", transform=hr_to_tensor3)
+    else:
+        test_ds = Shuffled2DPaired(args.data_root, split="test", scale=args.scale, transform_pair=tf_test)
     test_loader = DataLoader(test_ds, batch_size=args.batch_size, shuffle=False, num_workers=args.workers,
                              pin_memory=(device.type == "cuda"), persistent_workers=False)
+    if args.synth_lr:          # (lr, hr) batches formed on the device, before the peek, the baseline and the prediction loop
+        test_loader = SynthLRBatches(test_loader, scale_int, args.synth_lr_bits, device)
+        print(f"[synth_lr] LR = antialiased bicubic /{scale_int} of HR on the device, {args.synth_lr_bits or 'no'}-bit rounding")
     print(f"[data] test samples: {len(test_ds)} | steps: {len(test_loader)}")
 
     def upscaled(lr, hr):

@@ -13,6 +13,8 @@ on flipped / rotated patches (augment.py; on the device with `--gpu_data`).  `--
 `--ssim_weight W` (default 0) choose the objective: the pixel loss plus W * (1 - SSIM), value and gradient from the fused kernels of
 csrc/loss.hip (training.make_loss); with W > 0 validation also reports the mean per-image SSIM and checkpoints gain 'val_ssim'.
 `--val_tile N` (default 0 = whole images) validates on overlapping N x N LR tiles merged on the device (tiling.tiled_forward).
+`--gpu_data --synth_lr [--synth_lr_bits 0|8]` trains and validates from the HR directories alone: every LR patch is the antialiased
+bicubic downscale of its HR image, made on the device (sr_datasets.DeviceHRPool, csrc/resize.hip); no LR directory is read.
 
 Also additive: `--arch hat|dat` fine-tunes HAT / DAT (build_sr_model) through the same loop -- the fused, device-gated clip + AdamW step
 over their parameter lists (optim.FusedAdamW, csrc/optim_multi.hip), checkpoints "best_<arch>_finetune_<scale>.pt" /
@@ -238,7 +240,16 @@ def parse_args(argv=None):
                     help="additive: validate on overlapping tiles of N x N LR pixels merged by their mean (tiling.tiled_forward; 0 = "
                          "off, the whole image in one call)")
     ap.add_argument("--val_tile_overlap", type=int, default=32, help="additive, with --val_tile: LR pixels two neighbouring tiles share")
+    ap.add_argument("--synth_lr", action="store_true",
+                    help="additive, with --gpu_data: train and validate from the HR directories alone -- every LR patch is the "
+                         "antialiased bicubic (PIL BICUBIC convention) downscale of its HR image, computed on the device in the launch "
+                         "that crops the HR patch (sr_datasets.DeviceHRPool); no LR directory is required or read")
+    ap.add_argument("--synth_lr_bits", type=int, choices=[0, 8], default=8,
+                    help="additive, with --synth_lr: 8 = round the LR values to k / 255, as an 8-bit LR file would hold them; 0 = keep "
+                         "the filtered fp32 values")
     args = ap.parse_args(argv)
+    if args.synth_lr and not args.gpu_data:
+        ap.error("--synth_lr forms the LR patches on the device: it needs --gpu_data")
     if args.val_tile < 0 or args.val_tile_overlap < 0 or (args.val_tile and args.val_tile_overlap >= args.val_tile):
         ap.error(f"--val_tile must be >= 0 and 0 <= --val_tile_overlap < --val_tile (got --val_tile {args.val_tile} "
                  f"--val_tile_overlap {args.val_tile_overlap})")
@@ -278,13 +289,24 @@ def main(argv=None):
         print("[device]", device, torch.cuda.get_device_name(local), f"world={world}")
     scale_int = 2 if args.scale.upper() == "X2" else 4
 
-    train_ds = Shuffled2DPaired(args.data_root, split="train", scale=args.scale,
-                                transform_pair=PairTransformTrain(args.lr_patch, scale_int, args.augment))
-    valid_ds = Shuffled2DPaired(args.data_root, split="valid", scale=args.scale, transform_pair=PairTransformValid(scale_int))
-    sampler = DistributedSampler(train_ds, num_replicas=world, rank=rank, shuffle=True, seed=args.seed) if world > 1 else None
-    train_loader = make_loader(train_ds, args.batch_size, args.workers, pin=not args.no_pin, shuffle=True, drop_last=True,
-                               persistent=not args.no_persistent, sampler=sampler)
-    if args.gpu_data:
+    if args.synth_lr:
+        from .sr_datasets import DeviceHRPool, Shuffled2DHR, SynthLRBatches, hr_to_tensor3
+        raw = Shuffled2DHR(args.data_root, split="train")
+        pool = DeviceHRPool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, device=device,
+                            shard_bytes=(args.gpu_data_shard_mb << 20) or None, augment=args.augment, quant_bits=args.synth_lr_bits)
+        train_loader = sampler = DevicePoolLoader(pool, args.batch_size, rank, world, args.seed)
+        valid_ds = Shuffled2DHR(args.data_root, split="valid", transform=hr_to_tensor3)
+        if rank == 0:
+            print(f"[synth_lr] {len(pool)} HR images in {pool.num_shards} shard(s), {sum(t.numel() for t in pool._host) / 2**20:.1f} MiB "
+                  f"decoded; LR = antialiased bicubic /{scale_int} on the device, {args.synth_lr_bits or 'no'}-bit rounding")
+    else:
+        train_ds = Shuffled2DPaired(args.data_root, split="train", scale=args.scale,
+                                    transform_pair=PairTransformTrain(args.lr_patch, scale_int, args.augment))
+        valid_ds = Shuffled2DPaired(args.data_root, split="valid", scale=args.scale, transform_pair=PairTransformValid(scale_int))
+        sampler = DistributedSampler(train_ds, num_replicas=world, rank=rank, shuffle=True, seed=args.seed) if world > 1 else None
+        train_loader = make_loader(train_ds, args.batch_size, args.workers, pin=not args.no_pin, shuffle=True, drop_last=True,
+                                   persistent=not args.no_persistent, sampler=sampler)
+    if args.gpu_data and not args.synth_lr:
         from .sr_datasets import DevicePairPool
         raw = Shuffled2DPaired(args.data_root, split="train", scale=args.scale, transform_pair=None)
         pool = DevicePairPool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, device=device,
@@ -294,6 +316,8 @@ def main(argv=None):
             print(f"[gpu_data] {len(pool)} pairs in {pool.num_shards} shard(s), {sum(t.numel() for t in pool._host) / 2**20:.1f} MiB decoded")
     valid_loader = make_loader(valid_ds, max(1, args.batch_size // 2), args.workers, pin=not args.no_pin, shuffle=False,
                                drop_last=False, persistent=not args.no_persistent)
+    if args.synth_lr:
+        valid_loader = SynthLRBatches(valid_loader, scale_int, args.synth_lr_bits, device)
 
     model = (build_model(scale_int, args.drop_path_rate, args.window_size) if args.arch == "swinir" else
              build_sr_model(args.arch, scale_int, args.drop_path_rate))
@@ -393,7 +417,8 @@ def main(argv=None):
             more["val_ssim"] = val[2]
         at_default = {"ema_decay": not args.ema_decay, "loss": args.loss == "l1", "charbonnier_eps": args.charbonnier_eps == 1e-3,
                       "ssim_weight": args.ssim_weight == 0, "val_tile": args.val_tile == 0,
-                      "val_tile_overlap": args.val_tile == 0 or args.val_tile_overlap == 32}          # additive flags leave no trace in the files at their defaults
+                      "val_tile_overlap": args.val_tile == 0 or args.val_tile_overlap == 32, "synth_lr": not args.synth_lr,
+                      "synth_lr_bits": not args.synth_lr or args.synth_lr_bits == 8}          # additive flags leave no trace in the files at their defaults
         saved_args = {k: v for k, v in vars(args).items() if not at_default.get(k, False)}
         if val_loss < best_loss:
             best_loss = val_loss

@@ -516,3 +516,39 @@ def ssim_loss_fwd_bwd(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0,
     check(lib().srk_ssim_loss_fwd_bwd(_p(x), _p(y), _p(ws), B, Cc, H, W, float(data_range), float(alpha), _p(d_x), int(bool(accumulate)),
                                       _p(mean), _p(loss), _stream()))
     return mean, d_x, loss
+
+
+def resize_aa(x: torch.Tensor, size, quant_bits: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Antialiased bicubic resize of a CUDA fp32 batch x [B,C,H,W] to size = (Ho, Wo), up or down (csrc/resize.hip,
+    srk_resize_aa_f32): the Keys cubic with a = -0.5 in the convention of PIL's Image.BICUBIC and of
+    F.interpolate(mode='bicubic', antialias=True, align_corners=False) -- fp64 weights rounded once to fp32, border taps dropped and
+    renormalised, horizontal pass first.  quant_bits 8 rounds the result to k / 255 (what an 8-bit file of it would decode to);
+    0 keeps the filtered values.  `out` must not alias `x`; it is allocated when absent.  One launch, no host read: capturable.
+    An axis shrinking by more than 8x raises SrkUnsupported."""
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError(f"resize_aa takes fp32 [B,C,H,W] (got {x.dtype} {tuple(x.shape)})")
+    try:
+        Ho, Wo = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"resize_aa: size must be (Ho, Wo) (got {size!r})") from None
+    if Ho < 1 or Wo < 1 or min(x.shape) < 1:
+        raise ValueError(f"resize_aa: every extent must be >= 1 (got {tuple(x.shape)} -> {(Ho, Wo)})")
+    if quant_bits not in (0, 8):
+        raise ValueError(f"resize_aa: quant_bits must be 0 or 8 (got {quant_bits!r})")
+    B, Cc, H, W = x.shape
+    shape = (B, Cc, Ho, Wo)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != x.device:
+        raise ValueError(f"out must be fp32 {shape} on {x.device} (got {out.dtype} {tuple(out.shape)} on {out.device})")
+    check(lib().srk_resize_aa_f32(_p(x), _p(out), B, Cc, H, W, Ho, Wo, int(quant_bits), _stream()))
+    return out
+
+
+def degrade_aa(hr: torch.Tensor, scale: int, quant_bits: int = 8) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(lr, hr_cropped) of `--synth_lr` validation / evaluation: hr [B,C,H,W] cropped to its top-left (H - H % s, W - W % s) region and
+    that region's (H // s, W // s) antialiased bicubic downscale -- what DeviceHRPool's training patches are windows of."""
+    H, W = hr.shape[-2:]
+    s = int(scale)
+    hr = hr[..., :H - H % s, :W - W % s].float().contiguous()
+    return resize_aa(hr, (H // s, W // s), quant_bits), hr

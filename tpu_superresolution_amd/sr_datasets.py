@@ -68,6 +68,33 @@ class Shuffled2DPaired(Dataset):
         return lr, hr
 
 
+class Shuffled2DHR(Dataset):
+    """The HR images of a split alone (`--synth_lr`): lists <root>/shuffled2D/shuffled2D_<split>_HR; no LR directory is required or
+    read.  ``transform(hr_pil) -> tensor``; without one the PIL image is returned."""
+
+    def __init__(self, root: str, split: str = "train", exts: Tuple[str, ...] = (".png", ".jpg", ".jpeg", ".tif", ".tiff"),
+                 transform: Optional[Callable] = None):
+        self.hr_dir = Path(root) / "shuffled2D" / f"shuffled2D_{split}_HR"
+        if not self.hr_dir.exists():
+            raise FileNotFoundError(f"HR directory not found for split={split} under {self.hr_dir.parent}")
+        self.transform = transform
+        self.files = [p for p in sorted(self.hr_dir.iterdir()) if p.suffix.lower() in exts]
+        if not self.files:
+            raise RuntimeError(f"no HR files in {self.hr_dir}")
+
+    def __len__(self):
+        return len(self.files)
+
+    def __getitem__(self, idx: int):
+        hr = Shuffled2DPaired._open(self.files[idx])
+        return self.transform(hr) if self.transform is not None else hr
+
+
+def hr_to_tensor3(hr_pil) -> torch.Tensor:
+    """HR PIL image -> float32 [3,H,W] in [0,1]: the HR half of PairTransformValid."""
+    return ensure_3ch(pil_to_tensor01(hr_pil))
+
+
 # ---- minimal paired transforms of finetune_swinir.py:80-131 (augmentation: opt-in, augment.py) ------
 def pil_to_tensor01(img: Image.Image) -> torch.Tensor:
     """uint8 PIL -> float32 [C,H,W] in [0,1] (torchvision ToImage + ToDtype(scale=True) for 8-bit inputs)."""
@@ -125,38 +152,26 @@ class PairTransformValid:
 
 
 # ---- device-resident training set (first slice) ---------------------------------------------------------
-class DevicePairPool:
-    """Pre-decoded 8-bit LR/HR pairs in GPU memory + the paired train transform as one kernel pair per batch
-    (`srk_paired_crop_u8`).  `sample(indices)` draws the crop corners with the same two `random.randint` calls per sample, in
-    the same order, as `paired_random_crop` (finetune_swinir.py:96-110), so a host pipeline and this pool produce identical
-    batches from the same `random` state.  8-bit and 16-bit (uint16 -> value / 65535, as pil_to_tensor01) images, mixed freely.
+class _DeviceImagePool:
+    """What DevicePairPool and DeviceHRPool share: groups of pre-decoded 8- / 16-bit images (a pair, or one HR image) packed back to
+    back into one byte pool, optionally cut into pinned host shards of which two live on the device.  ``meta[i]`` = (shard, one
+    (byte offset, H, W, C | wide << 8) per image of group i); ``_check_group(*entries)`` refuses a group the pool cannot sample."""
 
-    ``shard_bytes``: when the decoded set is larger than this, it stays in PINNED host memory as shards and only two shards
-    live on the device: ``prefetch(s)`` starts the asynchronous copy of shard s on a side stream, ``sample`` of an index in a
-    shard that is not resident switches to it (joining its copy) and prefetches the next one -- the host->device transfer of
-    shard s+1 overlaps the training steps on shard s (SURVEY 8 row f-3).  ``shard_of(i)`` tells a sampler which shard an image
-    lives in, so that epochs can be ordered shard by shard.
+    def _check_group(self, *entries) -> None:
+        raise NotImplementedError
 
-    ``augment`` ('none' | 'flip' | 'd4', augment.draw_op): `sample` draws one D4 code per sample right after its crop corners -- the
-    order PairTransformTrain draws in, so the two paths still agree from the same `random` state -- and, when any code is non-zero,
-    transforms the LR and the HR batch with one `srk_dihedral_f32` launch each (per-sample codes; patches are square)."""
-
-    def __init__(self, pairs, lr_patch: int, scale: int, device="cuda", shard_bytes: Optional[int] = None, augment: str = "none"):
-        """pairs: iterable of (lr, hr) PIL images or uint8 / uint16 arrays [H,W] / [H,W,1|3]."""
-        if augment not in AUGMENT_MODES:
-            raise ValueError(f"augment must be one of {AUGMENT_MODES} (got {augment!r})")
-        self.augment = augment
-        self.lr_patch, self.scale, self.device = int(lr_patch), int(scale), torch.device(device)
+    def _pack(self, groups, shard_bytes: Optional[int]) -> None:
+        name = type(self).__name__
         shards, chunks, self.meta, off = [], [], [], 0
-        for lr, hr in pairs:
+        for group in groups:
             entry, pieces, size = [], [], 0
-            for img in (lr, hr):
+            for img in group:
                 a = np.asarray(img)
                 if a.dtype.byteorder == ">":
                     a = a.astype(a.dtype.newbyteorder("="))
                 a = np.ascontiguousarray(a)
                 if a.dtype not in (np.uint8, np.uint16):
-                    raise ValueError(f"DevicePairPool holds 8-bit and 16-bit unsigned images, got {a.dtype}")
+                    raise ValueError(f"{name} holds 8-bit and 16-bit unsigned images, got {a.dtype}")
                 if a.ndim == 2:
                     a = a[:, :, None]
                 if a.ndim != 3 or a.shape[2] not in (1, 3):
@@ -166,11 +181,7 @@ class DevicePairPool:
                 entry.append([size, a.shape[0], a.shape[1], a.shape[2] | (wide << 8)])
                 pieces.append((size, a.view(np.uint8).reshape(-1)))
                 size += a.nbytes
-            (_, lh, lw, _), (_, hh, hw, _) = entry
-            if lh < self.lr_patch or lw < self.lr_patch:
-                raise ValueError(f"LR image too small for patch {self.lr_patch}: lr_size=({lh},{lw})")
-            if hh < lh * self.scale or hw < lw * self.scale:
-                raise ValueError(f"HR image ({hh},{hw}) smaller than scale x LR ({lh},{lw})")
+            self._check_group(*entry)
             off += off & 1
             if shard_bytes and chunks and off + size > shard_bytes:
                 shards.append((chunks, off))
@@ -181,7 +192,7 @@ class DevicePairPool:
             self.meta.append((len(shards),) + tuple(tuple(e) for e in entry))
             off += size
         if not self.meta:
-            raise ValueError("DevicePairPool: no images")
+            raise ValueError(f"{name}: no images")
         shards.append((chunks, off))
         self._host = []
         for sh_chunks, total in shards:
@@ -230,15 +241,51 @@ class DevicePairPool:
         self.pool = dev
         return dev
 
+    def _batch_pool(self, indices) -> torch.Tensor:
+        """The device tensor of the one shard a batch comes from (switching to it, and prefetching the next, when needed)."""
+        shard_ids = {self.meta[int(i)][0] for i in indices}
+        if len(shard_ids) != 1:
+            raise ValueError("a batch must come from one shard (order the epoch with shard_of())")
+        return self._use(shard_ids.pop())
+
+
+class DevicePairPool(_DeviceImagePool):
+    """Pre-decoded 8-bit LR/HR pairs in GPU memory + the paired train transform as one kernel pair per batch
+    (`srk_paired_crop_u8`).  `sample(indices)` draws the crop corners with the same two `random.randint` calls per sample, in
+    the same order, as `paired_random_crop` (finetune_swinir.py:96-110), so a host pipeline and this pool produce identical
+    batches from the same `random` state.  8-bit and 16-bit (uint16 -> value / 65535, as pil_to_tensor01) images, mixed freely.
+
+    ``shard_bytes``: when the decoded set is larger than this, it stays in PINNED host memory as shards and only two shards
+    live on the device: ``prefetch(s)`` starts the asynchronous copy of shard s on a side stream, ``sample`` of an index in a
+    shard that is not resident switches to it (joining its copy) and prefetches the next one -- the host->device transfer of
+    shard s+1 overlaps the training steps on shard s (SURVEY 8 row f-3).  ``shard_of(i)`` tells a sampler which shard an image
+    lives in, so that epochs can be ordered shard by shard.
+
+    ``augment`` ('none' | 'flip' | 'd4', augment.draw_op): `sample` draws one D4 code per sample right after its crop corners -- the
+    order PairTransformTrain draws in, so the two paths still agree from the same `random` state -- and, when any code is non-zero,
+    transforms the LR and the HR batch with one `srk_dihedral_f32` launch each (per-sample codes; patches are square)."""
+
+    def __init__(self, pairs, lr_patch: int, scale: int, device="cuda", shard_bytes: Optional[int] = None, augment: str = "none"):
+        """pairs: iterable of (lr, hr) PIL images or uint8 / uint16 arrays [H,W] / [H,W,1|3]."""
+        if augment not in AUGMENT_MODES:
+            raise ValueError(f"augment must be one of {AUGMENT_MODES} (got {augment!r})")
+        self.augment = augment
+        self.lr_patch, self.scale, self.device = int(lr_patch), int(scale), torch.device(device)
+        self._pack(pairs, shard_bytes)
+
+    def _check_group(self, lr, hr) -> None:
+        (_, lh, lw, _), (_, hh, hw, _) = lr, hr
+        if lh < self.lr_patch or lw < self.lr_patch:
+            raise ValueError(f"LR image too small for patch {self.lr_patch}: lr_size=({lh},{lw})")
+        if hh < lh * self.scale or hw < lw * self.scale:
+            raise ValueError(f"HR image ({hh},{hw}) smaller than scale x LR ({lh},{lw})")
+
     def sample(self, indices):
         """-> (lr [B,3,P,P], hr [B,3,P*s,P*s]) fp32 on the device; advances the global `random` state like the host transform."""
         from ._lib import check, lib
         P, s = self.lr_patch, self.scale
         ld, hd, codes = [], [], []
-        shard_ids = {self.meta[int(i)][0] for i in indices}
-        if len(shard_ids) != 1:
-            raise ValueError("a batch must come from one shard (order the epoch with shard_of())")
-        pool = self._use(shard_ids.pop())
+        pool = self._batch_pool(indices)
         for i in indices:
             _, (lo, lh, lw, lc), (ho, hh, hw, hc) = self.meta[int(i)]
             top, left = random.randint(0, lh - P), random.randint(0, lw - P)
@@ -257,3 +304,79 @@ class DevicePairPool:
             ops = torch.tensor(codes, dtype=torch.int32).to(self.device)
             lr, hr = dihedral(lr, ops), dihedral(hr, ops)
         return lr, hr
+
+
+class DeviceHRPool(_DeviceImagePool):
+    """Training pairs from HR images only (`--synth_lr`): the pool holds the decoded HR images -- half the device memory of a
+    DevicePairPool at x2, no LR files to keep in sync -- and `sample` makes the HR patch AND its antialiased bicubic degradation
+    (PIL's BICUBIC convention) in one launch (`srk_crop_degrade_u8`, csrc/resize.hip).  The LR patch is exactly the window of the
+    (H // s, W // s) downscale of the image's top-left (H - H % s, W - W % s) region: the taps reach past the patch into the image.
+
+    Same surface as DevicePairPool (shards, prefetch, augment), and `sample` draws `random.randint(0, H // s - P)`,
+    `random.randint(0, W // s - P)` and the D4 code per sample -- DevicePairPool's order and ranges, so from one `random` state
+    both pools cut the same HR patches.  ``quant_bits`` 8 (default): LR values are rounded to k / 255 as an 8-bit LR file would hold
+    them; 0: the filtered fp32 values."""
+
+    def __init__(self, images, lr_patch: int, scale: int, device="cuda", shard_bytes: Optional[int] = None, augment: str = "none",
+                 quant_bits: int = 8):
+        """images: iterable of HR PIL images or uint8 / uint16 arrays [H,W] / [H,W,1|3]."""
+        if augment not in AUGMENT_MODES:
+            raise ValueError(f"augment must be one of {AUGMENT_MODES} (got {augment!r})")
+        if quant_bits not in (0, 8):
+            raise ValueError(f"quant_bits must be 0 or 8 (got {quant_bits!r})")
+        if not 2 <= int(scale) <= 4:
+            raise ValueError(f"DeviceHRPool degrades by an integer factor in 2..4 (got {scale!r})")
+        self.augment, self.quant_bits = augment, int(quant_bits)
+        self.lr_patch, self.scale, self.device = int(lr_patch), int(scale), torch.device(device)
+        self._pack(((img,) for img in images), shard_bytes)
+
+    def _check_group(self, hr) -> None:
+        _, hh, hw, _ = hr
+        if hh // self.scale < self.lr_patch or hw // self.scale < self.lr_patch:
+            raise ValueError(f"HR image ({hh},{hw}) too small for LR patch {self.lr_patch} at scale {self.scale}")
+
+    def draw(self, indices):
+        """-> (HR descriptors, D4 codes) of a batch; advances the global `random` state exactly as DevicePairPool.sample does."""
+        P, s = self.lr_patch, self.scale
+        hd, codes = [], []
+        for i in indices:
+            _, (ho, hh, hw, hc) = self.meta[int(i)]
+            top, left = random.randint(0, hh // s - P), random.randint(0, hw // s - P)
+            hd.append((ho, hh, hw, hc, top * s, left * s))
+            codes.append(draw_op(self.augment))
+        return hd, codes
+
+    def sample(self, indices):
+        """-> (lr [B,3,P,P], hr [B,3,P*s,P*s]) fp32 on the device."""
+        from ._lib import check, lib
+        P, s = self.lr_patch, self.scale
+        pool = self._batch_pool(indices)
+        hd, codes = self.draw(indices)
+        B = len(hd)
+        desc = torch.tensor(hd, dtype=torch.int64).to(self.device)
+        lr = torch.empty(B, 3, P, P, dtype=torch.float32, device=self.device)
+        hr = torch.empty(B, 3, P * s, P * s, dtype=torch.float32, device=self.device)
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        check(lib().srk_crop_degrade_u8(pool.data_ptr(), desc.data_ptr(), lr.data_ptr(), hr.data_ptr(), B, P, s, self.quant_bits, st))
+        if any(codes):
+            from .augment import dihedral
+            ops = torch.tensor(codes, dtype=torch.int32).to(self.device)
+            lr, hr = dihedral(lr, ops), dihedral(hr, ops)
+        return lr, hr
+
+
+class SynthLRBatches:
+    """Wraps a loader of HR batches [B,3,H,W] into the (lr, hr) batches of `--synth_lr` validation / evaluation: each HR batch goes to
+    the device, is cropped to a multiple of the factor and degraded there (ops.degrade_aa) -- the whole-image form of what
+    DeviceHRPool's training patches are windows of."""
+
+    def __init__(self, loader, scale: int, quant_bits: int, device):
+        self.loader, self.scale, self.quant_bits, self.device = loader, int(scale), int(quant_bits), torch.device(device)
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        from .ops import degrade_aa
+        for hr in self.loader:
+            yield degrade_aa(hr.to(self.device, dtype=torch.float32), self.scale, self.quant_bits)
