@@ -112,6 +112,8 @@ int srk_conv3x3_bf16(const uint16_t* x, const uint16_t* w, const float* bias, ui
  * 16-byte aligned (else SRK_E_ALIGN). */
 int srk_conv3x3_wgrad_bf16(const uint16_t* y, const uint16_t* x, float* dw, float* db, int B, int H, int W, int CinP, int N,
                            srk_stream_t stream);
+/* y[i] = bf16(x[i]), round to nearest even, NaN stays NaN (one packed conversion per pair; fp32 subnormals are converted like every other
+ * value, not flushed).  SRK_E_NULL: null x / y; SRK_E_SHAPE: n <= 0 or n % 4 != 0; SRK_E_ALIGN: x not 16-byte or y not 8-byte aligned. */
 int srk_cast_f32_bf16(const float* x, uint16_t* y, int64_t n, srk_stream_t stream);
 /* on-device check of the ds_read_b64_tr_b16 contract the kernels rely on: in u16 [64][16], out u16 [64][8] */
 int srk_probe_trread(const uint16_t* in, uint16_t* out, srk_stream_t stream);
@@ -408,7 +410,13 @@ int srk_swin_block_fwd(const float* x, float* y, uint16_t* y_bf16, const float* 
                        const float* norm2_b, const uint16_t* wqkv, const float* bqkv, const uint16_t* wproj, const float* bproj,
                        const uint16_t* w1, const float* b1, const uint16_t* w2, const float* b2, const float* bias_dense, float scale,
                        int C, int num_heads, int head_dim, int hidden, int B, int H, int W, int shift, srk_stream_t stream);
-/* image -> padded, normalised NHWC4 (check_image_size + (x - mean) * range, hat_arch.py:963-975) and conv_first (fp32 VALU) */
+/* image -> padded, normalised NHWC4 (check_image_size + (x - mean) * range, hat_arch.py:963-975) and conv_first (fp32 VALU).
+ * srk_img_prep: x fp32 NCHW [B][Cimg][H0][W0] -> out fp32 [B][H][W][4], 'reflect' padding at the bottom / right, one IEEE subtract and one
+ * IEEE multiply per value, channels >= Cimg are +0.  SRK_E_NULL: null x / out / mean3; SRK_E_SHAPE unless B > 0, 1 <= Cimg <= 3,
+ * H0 <= H < 2 H0, W0 <= W < 2 W0 (reflection needs pad <= extent - 1); SRK_E_ALIGN unless out is 16-byte aligned.
+ * srk_stem_conv: img4 fp32 [B][H][W][4], weight fp32 [C][Cin][3][3], bias fp32 [C] -> out fp32 [B*H*W][CP], columns C..CP-1 are +0.
+ * SRK_E_NULL for any null pointer; SRK_E_SHAPE unless B, H, W > 0, 1 <= Cin <= 4, 1 <= C <= CP, CP % 4 == 0, CP <= 256 (the kernel stages
+ * (36 CP + 576) floats in LDS); SRK_E_ALIGN unless img4 and out are 16-byte aligned.  All checked on the host before any launch. */
 int srk_img_prep(const float* x, float* out, int B, int Cimg, int H0, int W0, int H, int W, float range, const float* mean3, srk_stream_t stream);
 int srk_stem_conv(const float* img4, const float* weight, const float* bias, float* out, int B, int H, int W, int Cin, int C, int CP,
                   srk_stream_t stream);
@@ -482,10 +490,17 @@ int srk_cab_bwd(const uint16_t* conv, const float* g, const float* gate, void* w
                 const float* b2, float out_scale, float* dw1, float* db1, float* dw2, float* db2, float* dmean, uint16_t* d_conv, int B, int HW,
                 int C, int CP, int S, srk_stream_t stream);
 /* LayerNorm backward over C of CP columns: dy bf16 [rows][CP]; x, mean, rstd as srk_layernorm_fwd saw / produced them;
- * gx fp32 [rows][CP] = (accumulate ? gx : 0) + dx; gx_bf16 (optional) = bf16(gx); dgamma / dbeta fp32 [C] ACCUMULATED. */
+ * gx fp32 [rows][CP] = (accumulate ? gx : 0) + dx; gx_bf16 (optional) = bf16(gx); dgamma / dbeta fp32 [C] ACCUMULATED (elements >= C are
+ * not touched).  Pad columns C..CP-1: dx is 0 there, so with accumulate == 0 gx and gx_bf16 receive +0, and with accumulate == 1 gx keeps
+ * the value it held (0 + old; a -0 becomes +0) and gx_bf16 receives bf16 of it -- a caller that wants zero pads under accumulate == 1 must
+ * hand in a gx whose pads are zero.  SRK_E_NULL: a null pointer other than gx_bf16; SRK_E_SHAPE unless rows > 0, 1 <= C <= CP,
+ * CP % 64 == 0, CP <= 256; SRK_E_ALIGN unless x and gx are 16-byte and dy and gx_bf16 8-byte aligned. */
 int srk_layernorm_bwd(const uint16_t* dy, const float* x, const float* mean, const float* rstd, const float* gamma, float* gx,
                       uint16_t* gx_bf16, float* dgamma, float* dbeta, int rows, int C, int CP, int accumulate, srk_stream_t stream);
-/* element-wise helpers of a backward pass: a += b and ab_bf16 = bf16(a); a += float(b); out = a + b   (n % 4 == 0) */
+/* element-wise helpers of a backward pass: a += b and ab_bf16 = bf16(a); a += float(b); out = a + b.  Each is a fixed sequence of IEEE
+ * fp32 operations (one add; one round-to-nearest-even conversion where bf16 is stored, NaN stays NaN; fp32 subnormals are neither
+ * flushed on input nor on output).  SRK_E_NULL: a null pointer; SRK_E_SHAPE: n not a positive multiple of 4; SRK_E_ALIGN: an fp32 array
+ * not 16-byte or a bf16 array not 8-byte aligned (float4 / four-bf16 accesses). */
 int srk_add_f32_bf16(float* a, const float* b, uint16_t* ab_bf16, int64_t n, srk_stream_t stream);
 int srk_add_bf16_into_f32(float* a, const uint16_t* b, int64_t n, srk_stream_t stream);
 int srk_add_f32(float* out, const float* a, const float* b, int64_t n, srk_stream_t stream);
@@ -516,7 +531,9 @@ int srk_mlp_fused_fwd_train(const uint16_t* xn, const uint16_t* w1, const float*
                             float* out, uint16_t* out_bf16, uint16_t* u_out, uint16_t* h_out, uint16_t* xn_next, float* xn_mean,
                             float* xn_rstd, const float* xn_gamma, const float* xn_beta, int xn_C, const float* rowscale, int rows_per_sample,
                             int M, srk_stream_t stream);
-/* dst[m][c] = bf16(float(src[m][c]) * f[m / rows_per_sample])  (a DropPath factor on a bf16 gradient copy; dst may alias src) */
+/* dst[m][c] = bf16(float(src[m][c]) * f[m / rows_per_sample])  (a DropPath factor on a bf16 gradient copy; dst may alias src; rows need
+ * not be a multiple of rows_per_sample; one IEEE multiply, one round-to-nearest-even conversion).  SRK_E_NULL: a null pointer;
+ * SRK_E_SHAPE unless rows > 0, rows_per_sample > 0 and CP is a positive multiple of 4; SRK_E_ALIGN unless src and dst are 8-byte aligned. */
 int srk_rowscale_bf16(const uint16_t* src, uint16_t* dst, const float* f, int64_t rows, int rows_per_sample, int CP, srk_stream_t stream);
 
 /* ---- DAT (reference dat_arch.py), inference pieces; token-major bf16 [T][ld], channels padded per head to 32 -------------------------

@@ -249,6 +249,72 @@ def test_weight_gradient_entry_points_refuse_bad_arguments_without_a_gpu(lib):
     refused(h.srk_stem_wgrad(P, P, P, P, 1, 4, 8, 3, 260, 320, None), E_SHAPE)                      # C > 256: one thread per channel
 
 
+def test_glue_entry_points_refuse_bad_arguments_without_a_gpu(lib):
+    """LayerNorm, the image stem and the element-wise helpers of the host-orchestrated training paths return on the host, before any
+    launch, for null pointers (SRK_E_NULL), shapes their kernels cannot honour (SRK_E_SHAPE) and addresses that their float4 / four-bf16
+    accesses cannot take (SRK_E_ALIGN); include/srk.h states each rule at its entry point.  The addresses are dummies that are never
+    dereferenced; every call differs from a valid one in exactly the argument under test."""
+    h = lib.lib()
+    P = 4096
+    E_SHAPE, E_NULL, E_ALIGN = -1, -2, -5
+
+    def sweep(fn, base, changes, tail=(None,)):
+        for name, bad, code in changes:
+            assert name in base, name
+            args = [bad if k == name else v for k, v in base.items()]
+            rc = fn(*args, *tail)
+            assert rc == code, (fn.__name__, name, bad, rc, code, h.srk_last_error())
+            assert h.srk_last_error(), "no message"
+
+    # srk_layernorm_fwd(x, gamma, beta, y_bf16, y_f32, mean, rstd, rows, C, CP, geom, stream)
+    base = dict(x=P, gamma=P, beta=P, y_bf16=P, y_f32=P, mean=P, rstd=P, rows=16, C=60, CP=64)
+    sweep(h.srk_layernorm_fwd, base, [("CP", 320, E_SHAPE), ("CP", 96, E_SHAPE), ("C", 65, E_SHAPE), ("C", 0, E_SHAPE), ("rows", 0, E_SHAPE),
+                                      ("mean", None, E_NULL), ("rstd", None, E_NULL), ("x", P + 4, E_ALIGN), ("x", None, E_NULL),
+                                      ("gamma", None, E_NULL), ("beta", None, E_NULL)], tail=(None, None))
+    assert h.srk_layernorm_fwd(P, P, P, None, None, P, P, 16, 60, 64, None, None) == E_NULL           # no output at all
+
+    # srk_layernorm_bwd(dy, x, mean, rstd, gamma, gx, gx_bf16, dgamma, dbeta, rows, C, CP, accumulate, stream)
+    base = dict(dy=P, x=P, mean=P, rstd=P, gamma=P, gx=P, gx_bf16=P, dgamma=P, dbeta=P, rows=16, C=60, CP=64, accumulate=0)
+    sweep(h.srk_layernorm_bwd, base, [("CP", 320, E_SHAPE), ("CP", 100, E_SHAPE), ("C", 65, E_SHAPE), ("C", 0, E_SHAPE), ("rows", 0, E_SHAPE),
+                                      ("rows", -16, E_SHAPE), ("dy", None, E_NULL), ("x", None, E_NULL), ("mean", None, E_NULL),
+                                      ("rstd", None, E_NULL), ("gamma", None, E_NULL), ("gx", None, E_NULL), ("dgamma", None, E_NULL),
+                                      ("dbeta", None, E_NULL), ("x", P + 4, E_ALIGN), ("gx", P + 8, E_ALIGN), ("dy", P + 2, E_ALIGN),
+                                      ("dy", P + 4, E_ALIGN), ("gx_bf16", P + 2, E_ALIGN), ("gx_bf16", P + 12, E_ALIGN)])
+
+    # srk_stem_conv(img4, weight, bias, out, B, H, W, Cin, C, CP, stream)
+    base = dict(img4=P, weight=P, bias=P, out=P, B=1, H=4, W=8, Cin=3, C=60, CP=64)
+    sweep(h.srk_stem_conv, base, [("img4", None, E_NULL), ("weight", None, E_NULL), ("bias", None, E_NULL), ("out", None, E_NULL),
+                                  ("B", 0, E_SHAPE), ("H", 0, E_SHAPE), ("W", 0, E_SHAPE), ("W", -8, E_SHAPE), ("Cin", 0, E_SHAPE),
+                                  ("Cin", 5, E_SHAPE), ("C", 0, E_SHAPE), ("C", 65, E_SHAPE), ("CP", 62, E_SHAPE), ("img4", P + 4, E_ALIGN),
+                                  ("out", P + 8, E_ALIGN)])
+    assert h.srk_stem_conv(P, P, P, P, 1, 4, 8, 3, 260, 320, None) == E_SHAPE                          # CP > 256: the LDS the kernel stages
+    assert h.srk_stem_conv(P, P, P, P, 1, 4, 8, 3, 256, 260, None) == E_SHAPE
+
+    # srk_img_prep(x, out, B, Cimg, H0, W0, H, W, range, mean3, stream)
+    mean3 = (C.c_float * 3)(0.4488, 0.4371, 0.4040)
+    base = dict(x=P, out=P, B=2, Cimg=3, H0=9, W0=9, H=17, W=16, range=1.0, mean3=C.byref(mean3))
+    sweep(h.srk_img_prep, base, [("H", 18, E_SHAPE), ("W", 18, E_SHAPE), ("H", 8, E_SHAPE), ("Cimg", 4, E_SHAPE), ("Cimg", 0, E_SHAPE),
+                                 ("B", 0, E_SHAPE), ("x", None, E_NULL), ("out", None, E_NULL), ("mean3", None, E_NULL),
+                                 ("out", P + 4, E_ALIGN)])
+
+    # srk_cast_f32_bf16(x, y, n, stream)
+    sweep(h.srk_cast_f32_bf16, dict(x=P, y=P, n=64), [("x", None, E_NULL), ("y", None, E_NULL), ("n", 0, E_SHAPE), ("n", -4, E_SHAPE),
+                                                      ("n", 66, E_SHAPE), ("x", P + 8, E_ALIGN), ("y", P + 4, E_ALIGN), ("y", P + 2, E_ALIGN)])
+    # srk_add_f32_bf16(a, b, ab_bf16, n, stream)
+    sweep(h.srk_add_f32_bf16, dict(a=P, b=P, ab=P, n=64), [("a", None, E_NULL), ("b", None, E_NULL), ("ab", None, E_NULL), ("n", 0, E_SHAPE),
+                                                           ("n", 6, E_SHAPE), ("a", P + 4, E_ALIGN), ("b", P + 8, E_ALIGN), ("ab", P + 4, E_ALIGN)])
+    # srk_add_bf16_into_f32(a, b, n, stream)
+    sweep(h.srk_add_bf16_into_f32, dict(a=P, b=P, n=64), [("a", None, E_NULL), ("b", None, E_NULL), ("n", 0, E_SHAPE), ("n", 2, E_SHAPE),
+                                                          ("a", P + 8, E_ALIGN), ("b", P + 2, E_ALIGN), ("b", P + 4, E_ALIGN)])
+    # srk_add_f32(out, a, b, n, stream)
+    sweep(h.srk_add_f32, dict(out=P, a=P, b=P, n=64), [("out", None, E_NULL), ("a", None, E_NULL), ("b", None, E_NULL), ("n", -64, E_SHAPE),
+                                                       ("n", 65, E_SHAPE), ("out", P + 4, E_ALIGN), ("a", P + 8, E_ALIGN), ("b", P + 12, E_ALIGN)])
+    # srk_rowscale_bf16(src, dst, f, rows, rows_per_sample, CP, stream)
+    sweep(h.srk_rowscale_bf16, dict(src=P, dst=P, f=P, rows=100, rps=50, CP=64),
+          [("src", None, E_NULL), ("dst", None, E_NULL), ("f", None, E_NULL), ("rows", 0, E_SHAPE), ("rps", 0, E_SHAPE), ("CP", 0, E_SHAPE),
+           ("CP", 62, E_SHAPE), ("CP", -64, E_SHAPE), ("src", P + 2, E_ALIGN), ("dst", P + 4, E_ALIGN)])
+
+
 def test_options_are_process_wide_with_per_plan_values():
     """SURVEY 8b 're-entrant': srk_set_option writes ONE process-wide value per option (every thread sees it -- the autograd engine runs
     the backward on its own thread); a plan carries its own values (srk_swinir_plan_set_option), applied in a thread-private copy of the

@@ -289,6 +289,9 @@ int srk_conv3x3_wgrad_bf16(const uint16_t* y, const uint16_t* x, float* dw, floa
 
 int srk_cast_f32_bf16(const float* x, uint16_t* y, int64_t n, srk_stream_t stream) {
   REQ_PTR(x); REQ_PTR(y);
+  SRK_REQUIRE(n > 0 && n % 4 == 0, SRK_E_SHAPE, "cast_f32_bf16: n=%lld must be a positive multiple of 4", (long long)n);
+  REQ_ALIGN(x);
+  SRK_REQUIRE((reinterpret_cast<uintptr_t>(y) & 7) == 0, SRK_E_ALIGN, "cast_f32_bf16: 'y' is not 8-byte aligned");
   return srk_launch_cast_f32_bf16(x, y, n, (hipStream_t)stream);
 }
 

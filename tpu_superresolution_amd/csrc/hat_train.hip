@@ -202,26 +202,38 @@ int srk_win256_attention_bwd(const uint16_t* qkv, int ldq, int CA, const float* 
                                     scale, overlap, (hipStream_t)stream);
 }
 
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
 int srk_layernorm_bwd(const uint16_t* dy, const float* x, const float* mean, const float* rstd, const float* gamma, float* gx,
                       uint16_t* gx_bf16, float* dgamma, float* dbeta, int rows, int C, int CP, int accumulate, srk_stream_t stream) {
   SRK_REQUIRE(dy && x && mean && rstd && gamma && gx && dgamma && dbeta, SRK_E_NULL, "layernorm_bwd: null pointer");
   SRK_REQUIRE(rows > 0 && C > 0 && C <= CP && CP % 64 == 0 && CP <= 256, SRK_E_SHAPE, "layernorm_bwd: rows=%d C=%d CP=%d", rows, C, CP);
+  // float4 accesses of x / gx, uint2 (four bf16) accesses of dy / gx_bf16
+  SRK_REQUIRE(aligned16(x) && aligned16(gx) && aligned8(dy) && aligned8(gx_bf16), SRK_E_ALIGN,
+              "layernorm_bwd: x / gx not 16-byte or dy / gx_bf16 not 8-byte aligned");
   return srk_launch_ln_bwd(dy, x, mean, rstd, gamma, gx, gx_bf16, dgamma, dbeta, rows, C, CP, nullptr, 0, 0, 0, accumulate, nullptr, rows,
                            (hipStream_t)stream);
 }
 
 int srk_add_f32_bf16(float* a, const float* b, uint16_t* ab_bf16, int64_t n, srk_stream_t stream) {
-  SRK_REQUIRE(a && b && ab_bf16 && n > 0 && n % 4 == 0, SRK_E_SHAPE, "add_f32_bf16: bad arguments");
+  SRK_REQUIRE(a && b && ab_bf16, SRK_E_NULL, "add_f32_bf16: null pointer");
+  SRK_REQUIRE(n > 0 && n % 4 == 0, SRK_E_SHAPE, "add_f32_bf16: n=%lld must be a positive multiple of 4", (long long)n);
+  SRK_REQUIRE(aligned16(a) && aligned16(b) && aligned8(ab_bf16), SRK_E_ALIGN, "add_f32_bf16: a / b not 16-byte or ab_bf16 not 8-byte aligned");
   return srk_launch_add_f32_bf16(a, b, ab_bf16, n, (hipStream_t)stream);
 }
 
 int srk_add_bf16_into_f32(float* a, const uint16_t* b, int64_t n, srk_stream_t stream) {
-  SRK_REQUIRE(a && b && n > 0 && n % 4 == 0, SRK_E_SHAPE, "add_bf16_into_f32: bad arguments");
+  SRK_REQUIRE(a && b, SRK_E_NULL, "add_bf16_into_f32: null pointer");
+  SRK_REQUIRE(n > 0 && n % 4 == 0, SRK_E_SHAPE, "add_bf16_into_f32: n=%lld must be a positive multiple of 4", (long long)n);
+  SRK_REQUIRE(aligned16(a) && aligned8(b), SRK_E_ALIGN, "add_bf16_into_f32: a not 16-byte or b not 8-byte aligned");
   return srk_launch_add_bf16_into_f32(a, b, n, (hipStream_t)stream);
 }
 
 int srk_add_f32(float* out, const float* a, const float* b, int64_t n, srk_stream_t stream) {
-  SRK_REQUIRE(out && a && b && n > 0 && n % 4 == 0, SRK_E_SHAPE, "add_f32: bad arguments");
+  SRK_REQUIRE(out && a && b, SRK_E_NULL, "add_f32: null pointer");
+  SRK_REQUIRE(n > 0 && n % 4 == 0, SRK_E_SHAPE, "add_f32: n=%lld must be a positive multiple of 4", (long long)n);
+  SRK_REQUIRE(aligned16(out) && aligned16(a) && aligned16(b), SRK_E_ALIGN, "add_f32: out / a / b not 16-byte aligned");
   const long long n4 = n / 4;
   const int grid = (int)((n4 + 255) / 256 < 16384 ? (n4 + 255) / 256 : 16384);
   hipLaunchKernelGGL(add3_f32_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, a, b, n4);
@@ -229,14 +241,15 @@ int srk_add_f32(float* out, const float* a, const float* b, int64_t n, srk_strea
 }
 
 int srk_rowscale_bf16(const uint16_t* src, uint16_t* dst, const float* f, int64_t rows, int rows_per_sample, int CP, srk_stream_t stream) {
-  SRK_REQUIRE(src && dst && f && rows > 0 && rows_per_sample > 0 && CP % 4 == 0, SRK_E_SHAPE, "rowscale_bf16: bad arguments");
+  SRK_REQUIRE(src && dst && f, SRK_E_NULL, "rowscale_bf16: null pointer");
+  SRK_REQUIRE(rows > 0 && rows_per_sample > 0 && CP > 0 && CP % 4 == 0, SRK_E_SHAPE, "rowscale_bf16: rows=%lld rows_per_sample=%d CP=%d",
+              (long long)rows, rows_per_sample, CP);
+  SRK_REQUIRE(aligned8(src) && aligned8(dst), SRK_E_ALIGN, "rowscale_bf16: src / dst not 8-byte aligned");
   const long long n4 = rows * (CP / 4);
   const int grid = (int)((n4 + 255) / 256 < 16384 ? (n4 + 255) / 256 : 16384);
   hipLaunchKernelGGL(rowscale_bf16_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, dst, f, (long long)rows, rows_per_sample, CP);
   return srk_check_launch("rowscale_bf16");
 }
-
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 int srk_img_grad_prep(const float* d_pred, float* gy, int B, int Cimg, int Hc, int Wc, int H, int W, int r, int CoP, float inv_range,
                       srk_stream_t stream) {
