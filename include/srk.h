@@ -578,6 +578,56 @@ int srk_mlp_fused_bwd(const uint16_t* g, const uint16_t* w2t, const uint16_t* u,
                       const float* ln_mean, const float* ln_rstd, const float* ln_gamma, float* gx, uint16_t* gxb, const float* rowscale,
                       int rows_per_sample, float* d_gamma, float* d_beta, int C, int M, srk_stream_t stream);
 
+/* ---- the fused per-block Swin kernels in the form the SwinIR executor launches them (csrc/hat_train.hip; for parity tests and
+ * host-orchestrated models).  Every buffer 16-byte aligned (else SRK_E_ALIGN); a srk_win_geom needs H, W multiples of 8, shift 0 or 4
+ * and a row count that is a multiple of H*W (else SRK_E_SHAPE); "not covered" is SRK_E_UNSUPPORTED with a message, nothing written. */
+/* srk_mlp_fused_fwd_train plus: u_out / h_out may BOTH be null (inference); u_dgelu != 0: u_out receives bf16(gelu'(u)) of the unrounded
+ * u instead of bf16(u) (needs u_out; what srk_mlp_fused_bwd_ex reads with u_is_dgelu); xn_geom non-null: xn_next / xn_mean / xn_rstd rows
+ * are in WINDOW order of that geometry (the next block's norm1 with its roll + window partition), null: token order. */
+int srk_mlp_fused_fwd_ex(const uint16_t* xn, const uint16_t* w1, const float* b1, const uint16_t* w2, const float* b2, const float* res,
+                         float* out, uint16_t* out_bf16, uint16_t* u_out, uint16_t* h_out, int u_dgelu, uint16_t* xn_next, float* xn_mean,
+                         float* xn_rstd, const float* xn_gamma, const float* xn_beta, int xn_C, const srk_win_geom* xn_geom,
+                         const float* rowscale, int rows_per_sample, int M, srk_stream_t stream);
+/* srk_mlp_fused_bwd plus: u_is_dgelu != 0: u holds gelu'(u) (d u = bf16((g W2) * u)); out_geom non-null: row t of the bf16 copy gxb is
+ * stored at its WINDOW-order row of that geometry (gx, ln_x, the statistics and rowscale stay in token order). */
+int srk_mlp_fused_bwd_ex(const uint16_t* g, const uint16_t* w2t, const uint16_t* u, int u_is_dgelu, uint16_t* du_out, const uint16_t* w1t,
+                         const float* ln_x, const float* ln_mean, const float* ln_rstd, const float* ln_gamma, float* gx, uint16_t* gxb,
+                         const srk_win_geom* out_geom, const float* rowscale, int rows_per_sample, float* d_gamma, float* d_beta, int C, int M,
+                         srk_stream_t stream);
+/* launches of the fused MLP kernels in this process so far, per (backward, u holds gelu'(u)) variant */
+long long srk_mlp_fused_launches(int backward, int u_dgelu);
+/* qkv projection + window attention forward as one kernel per window (csrc/attn_fused.hip; network_swinir.py:121-142), whichever kernel
+ * option "attn_fused" selects (2: three 4-wave workgroups per CU, falling back to 1: one 8-wave workgroup per CU, when its configuration
+ * fails; 0 and every shape the kernels do not cover -- nH != 6, B_ < #CUs -- is SRK_E_UNSUPPORTED).  xn bf16 [B_*64][lda] norm1 output in
+ * window order, w_qkv bf16 [576][192] / b_qkv fp32 [576] or null (q rows first, heads padded 30 -> 32), qkv_out bf16 [3][B_][6][64][32]
+ * or null, out bf16 [B_*64][192].  bias_dense fp32 [6][64][64]: the kernels rebuild the 225-entry relative-position table from it (offset
+ * (dy, dx) is read at query (max(dy,0), max(dx,0)), key (max(-dy,0), max(-dx,0))), so it must be table[relative_position_index] as
+ * srk_rel_pos_bias_expand writes it -- an arbitrary dense bias is NOT supported.  srk_qkv_attn_fwd3_launches / ..._fwd8_launches:
+ * launches of the 4-wave / 8-wave kernel in this process so far (tests assert which one ran). */
+int srk_qkv_window_attention_fwd(const uint16_t* xn, int lda, const uint16_t* w_qkv, const float* b_qkv, float scale, uint16_t* qkv_out,
+                                 const float* bias_dense, uint16_t* out, int64_t B_, int nH, const srk_win_geom* geom, srk_stream_t stream);
+long long srk_qkv_attn_fwd3_launches(void);
+long long srk_qkv_attn_fwd8_launches(void);
+/* attention output projection + window reverse + un-roll + residual (+ DropPath factor, + norm2 of the new row) (network_swinir.py:143,
+ * :265-277): with t = token(geom, m), out[t] = res[t] + rowscale[t / rows_per_sample] * (ao[m] . w_proj^T + b_proj); xn_out non-null:
+ * xn_out[t] = bf16(LayerNorm(out[t]) over xn_C), xn_mean[t], xn_rstd[t].  ao bf16 [B_*64][192] window order, w_proj bf16 [192][192],
+ * res / out fp32 [T][192] token order (not aliased), rowscale fp32 [T / rows_per_sample] or null.  Streaming or tile kernel as srk_gemm_ex
+ * picks them; with a rowscale the streaming kernel serves rows_per_sample == H*W only (a sample is an image, as in the model: it takes a
+ * window-ordered tile's sample from its image), any other rows_per_sample dividing T runs on the tile kernel.
+ * srk_gemm_stream_launches: launches of the streaming GEMM kernels in this process so far (tests assert which path ran). */
+int srk_proj_residual_fwd(const uint16_t* ao, const uint16_t* w_proj, const float* b_proj, const float* res, float* out, const float* rowscale,
+                          int rows_per_sample, uint16_t* xn_out, float* xn_mean, float* xn_rstd, const float* xn_gamma, const float* xn_beta,
+                          int xn_C, int64_t B_, const srk_win_geom* geom, srk_stream_t stream);
+long long srk_gemm_stream_launches(void);
+/* d xn1 = d_qkv . w_qkv_t^T with norm1's backward, the window reverse and the un-roll in its epilogue: row m (window order; ln_mean /
+ * ln_rstd indexed by m) belongs to token t = token(geom, m); gx[t] += d x (fp32, in place), gxb[t] = bf16(gx[t] * rowscale[t /
+ * rows_per_sample]) or null, d_gamma / d_beta ACCUMULATED.  ln_skip non-null (the RSTB skip fold): the row result is gx[t] + d x +
+ * ln_skip[t], stored to ln_skip[t] (gx untouched), gxb its scaled bf16 copy.  d_qkv bf16 [B_*64][576], w_qkv_t bf16 [192][576],
+ * ln_x / gx / ln_skip fp32 [T][192] token order; rowscale and kernel choice as above. */
+int srk_qkv_dgrad_lnbwd(const uint16_t* d_qkv, const uint16_t* w_qkv_t, const float* ln_x, const float* ln_mean, const float* ln_rstd,
+                        const float* ln_gamma, float* gx, uint16_t* gxb, const float* rowscale, int rows_per_sample, float* ln_skip,
+                        float* d_gamma, float* d_beta, int C, int64_t B_, const srk_win_geom* geom, srk_stream_t stream);
+
 /* ---- DAT training pieces (csrc/dat_train.hip, csrc/attn_rect_bwd.hip) -----------------------------------------------------------
  * Token-sized work and token reductions only: the per-channel / per-sample functions in between (train-mode BatchNorm coefficients
  * dat_arch.py:301-313 / :464-476, channel_interaction on the pooled [B][C] vector, the d x d channel-attention matrices :497-503,

@@ -167,6 +167,15 @@ _SIGNATURES = {
     "srk_channel_attention_fwd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "srk_linear_wgrad_multi_bf16": (_i, [C.POINTER(WgradProblem), _i, _i, _vp]),
     "srk_mlp_fused_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
+    "srk_mlp_fused_fwd_ex": (_i, [_vp] * 10 + [_i] + [_vp] * 5 + [_i, _geom_p, _vp, _i, _i, _vp]),
+    "srk_mlp_fused_bwd_ex": (_i, [_vp, _vp, _vp, _i] + [_vp] * 8 + [_geom_p, _vp, _i, _vp, _vp, _i, _i, _vp]),
+    "srk_mlp_fused_launches": (C.c_longlong, [_i, _i]),
+    "srk_qkv_window_attention_fwd": (_i, [_vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _i64, _i, _geom_p, _vp]),
+    "srk_qkv_attn_fwd3_launches": (C.c_longlong, []),
+    "srk_qkv_attn_fwd8_launches": (C.c_longlong, []),
+    "srk_gemm_stream_launches": (C.c_longlong, []),
+    "srk_proj_residual_fwd": (_i, [_vp] * 6 + [_i] + [_vp] * 5 + [_i, _i64, _geom_p, _vp]),
+    "srk_qkv_dgrad_lnbwd": (_i, [_vp] * 9 + [_i] + [_vp] * 3 + [_i, _i64, _geom_p, _vp]),
     "srk_win_attention_bwd_padded_scratch": (_sz, [_i, _i, _i, _i, _i, _i]),
     "srk_win_attention_bwd_padded": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp]),
     "srk_bn_train_coeffs": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp, _f, _vp, _vp, _vp, _f, _vp, _vp]),

@@ -24,6 +24,7 @@
 //   loading     wave 7 never stores: it issues the LDS-DMA of the next window's 64 x 192 bf16 rows (swizzled on the source
 //               address, 2-slot ring) right after the first barrier, and its vmcnt(0) before the next one is "landed".
 // Three raw barriers per window.  The ao tile aliases the ring slot that the window's projection has just consumed.
+#include <atomic>
 #include <type_traits>
 
 #include "kernels.h"
@@ -483,6 +484,11 @@ SrkOpt g_attn_fused{OPT_ATTN_FUSED, SRK_ATTN_FUSED_DEFAULT};            // 0 sep
 
 }  // namespace
 
+// launches of the two kernels in this process so far (tests assert which one ran: mode 2 falls back to the 8-wave kernel silently)
+static std::atomic<long long> g_attn_fwd8_launches{0}, g_attn_fwd3_launches{0};
+extern "C" long long srk_qkv_attn_fwd8_launches(void) { return g_attn_fwd8_launches.load(); }
+extern "C" long long srk_qkv_attn_fwd3_launches(void) { return g_attn_fwd3_launches.load(); }
+
 void srk_attn_fused_enable(int on) { g_attn_fused = on < 0 ? 0 : (on > 2 ? 2 : on); }
 int srk_attn_fused_mode() { return g_attn_fused; }
 
@@ -527,8 +533,10 @@ int srk_launch_qkv_attn_fwd(const bf16_t* xn, int lda, const bf16_t* Wt, const f
     long long ngrp = g_fused_cus / 8;                       // 24 workgroups per group of 8 windows in flight: 3 per CU
     if (ngrp * 8 > B_) ngrp = (B_ + 7) / 8;
     hipLaunchKernelGGL(qkv_attn_fwd3_kernel, dim3((unsigned)(24 * ngrp)), dim3(256), G_LDS, stream, fp, (int)ngrp);
+    g_attn_fwd3_launches.fetch_add(1);
     return srk_check_launch("qkv+attention (3 per CU)");
   }
   hipLaunchKernelGGL(qkv_attn_fwd_kernel, dim3(g_fused_cus), dim3(512), F_LDS, stream, fp);
+  g_attn_fwd8_launches.fetch_add(1);
   return srk_check_launch("qkv+attention");
 }

@@ -32,6 +32,8 @@
 // writes lane-linear (wave-uniform base + 16 * lane), so the swizzle is applied on the per-lane SOURCE address.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+
 #include "gemm.h"
 #include "gemm_rowep.h"
 
@@ -1359,6 +1361,11 @@ void srk_gemm_stream_tune_get(int* bm, int* ks2, int* split, int* nb) {
   *bm = g_tune_bm; *ks2 = g_tune_ks2; *split = g_tune_split; *nb = g_tune_nb;
 }
 
+// launches of the streaming kernels through srk_launch_gemm_stream in this process so far (tests assert which GEMM path ran)
+static std::atomic<long long> g_gemm_stream_launches{0};
+extern "C" long long srk_gemm_stream_launches(void) { return g_gemm_stream_launches.load(); }
+static int stream_dispatch(int epilogue, const GemmParams& p, hipStream_t stream);
+
 // Returns SRK_NOT_COVERED when the streaming kernel does not cover this problem (the caller then uses the tile kernel).
 int srk_launch_gemm_stream(int epilogue, const GemmParams& p, hipStream_t stream) {
   if (g_stream_enabled < 0) {
@@ -1372,6 +1379,16 @@ int srk_launch_gemm_stream(int epilogue, const GemmParams& p, hipStream_t stream
   if (p.M < 64 * g_num_cus) return SRK_NOT_COVERED;            // too few tiles to fill the persistent grid
   if (p.rowscale && (p.rows_per_sample <= 0 || p.rows_per_sample % 64 != 0)) return SRK_NOT_COVERED;   // a tile lies inside one sample
   if (p.M >= (1 << 24)) return SRK_NOT_COVERED;                // row / token indices go through fdiv24
+  // window-ordered rows: stream_issue_tile takes a tile's sample from its image (tokbase / rows_per_sample), which is the sample of
+  // its tokens only where a sample IS an image; anything else goes to the tile kernel (token / rows_per_sample per row)
+  if (p.rowscale && (epilogue == EP_PROJ_RES || (epilogue == EP_LNBWD && p.ln_rows_window)) && p.rows_per_sample != p.geom.H * p.geom.W)
+    return SRK_NOT_COVERED;
+  const int rc_stream = stream_dispatch(epilogue, p, stream);
+  if (rc_stream == SRK_OK) g_gemm_stream_launches.fetch_add(1);
+  return rc_stream;
+}
+
+static int stream_dispatch(int epilogue, const GemmParams& p, hipStream_t stream) {
   switch (epilogue) {
     case EP_BF16: return dispatch_k<EP_BF16>(p, stream, {32, false, true}, {32, false, true});
     case EP_QKV: return dispatch_k<EP_QKV>(p, stream, {64, false, false}, {32, false, true});   // front-bound when split: 3 slices share A
@@ -1386,6 +1403,10 @@ int srk_launch_gemm_stream(int epilogue, const GemmParams& p, hipStream_t stream
     default: return SRK_NOT_COVERED;
   }
 }
+
+// launches of the four fused MLP kernels in this process so far: [backward][u holds gelu'(u)] (tests assert which variant ran)
+static std::atomic<long long> g_mlp_fused_launches[2][2];
+extern "C" long long srk_mlp_fused_launches(int backward, int u_dgelu) { return g_mlp_fused_launches[backward ? 1 : 0][u_dgelu ? 1 : 0].load(); }
 
 void srk_mlp_fused_enable(int on) { g_mlp_fused_enabled = on ? 1 : 0; }
 int srk_mlp_fused_enabled() { return g_mlp_fused_enabled; }
@@ -1413,6 +1434,7 @@ int srk_launch_mlp_fused(const GemmParams& p, hipStream_t stream) {
   if (p.u_dgelu) hipLaunchKernelGGL(mlp_fused_fwd_kernel<true>, dim3(g_num_cus), dim3(512), MlpCfg::LDS, stream, p, g_num_cus / 8);
   else hipLaunchKernelGGL(mlp_fused_fwd_kernel<false>, dim3(g_num_cus), dim3(512), MlpCfg::LDS, stream, p, g_num_cus / 8);
   srk_probe_post(FAM_GEMM_LINEAR, stream);
+  g_mlp_fused_launches[0][p.u_dgelu ? 1 : 0].fetch_add(1);
   return srk_check_launch("mlp_fused");
 }
 
@@ -1447,5 +1469,6 @@ int srk_launch_mlp_fused_bwd(const GemmParams& p, hipStream_t stream) {
   if (p.u_dgelu) hipLaunchKernelGGL(mlp_fused_bwd_kernel<true>, dim3(g_num_cus), dim3(512), MlpBwdCfg::LDS, stream, p, g_num_cus / 8);
   else hipLaunchKernelGGL(mlp_fused_bwd_kernel<false>, dim3(g_num_cus), dim3(512), MlpBwdCfg::LDS, stream, p, g_num_cus / 8);
   srk_probe_post(FAM_GEMM_LINEAR, stream);
+  g_mlp_fused_launches[1][p.u_dgelu ? 1 : 0].fetch_add(1);
   return srk_check_launch("mlp_fused_bwd");
 }

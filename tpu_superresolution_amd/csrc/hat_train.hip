@@ -354,4 +354,150 @@ int srk_mlp_fused_bwd(const uint16_t* g, const uint16_t* w2t, const uint16_t* u,
   return rc;
 }
 
+// ---- the fused per-block Swin kernels exactly as the SwinIR executor (csrc/swinir.hip) launches them -------------------------------
+// Thin wrappers: they fill GemmParams / the fused-attention arguments the way forward_body / the backward do, so that a test reaches
+// the production form of each kernel (window-ordered LayerNorm outputs, the gelu'(u) hand-over, DropPath factors, the RSTB skip fold).
+
+static int block_geom(const srk_win_geom* g, WinGeom* out, long long rows, const char* fn) {
+  SRK_REQUIRE(g->H > 0 && g->W > 0 && g->H % 8 == 0 && g->W % 8 == 0, SRK_E_SHAPE, "%s: H,W must be multiples of 8 (got %d,%d)", fn, g->H, g->W);
+  SRK_REQUIRE(g->shift == 0 || g->shift == 4, SRK_E_SHAPE, "%s: shift must be 0 or 4 (got %d)", fn, g->shift);
+  SRK_REQUIRE(rows % ((long long)g->H * g->W) == 0, SRK_E_SHAPE, "%s: %lld rows are not a multiple of H*W = %d", fn, rows, g->H * g->W);
+  out->H = g->H; out->W = g->W; out->nWw = g->W / 8; out->nW = (g->H / 8) * (g->W / 8); out->shift = g->shift;
+  return SRK_OK;
+}
+
+static int block_rowscale(const float* rowscale, int rows_per_sample, long long rows, const char* fn) {
+  SRK_REQUIRE(!rowscale || (rows_per_sample > 0 && rows % rows_per_sample == 0), SRK_E_SHAPE,
+              "%s: a rowscale needs rows_per_sample > 0 dividing the %lld rows (got %d)", fn, rows, rows_per_sample);
+  return SRK_OK;
+}
+
+#define BLOCK_ALIGNED(fn, ...)                                                                                      \
+  do {                                                                                                              \
+    const void* ptrs_[] = {__VA_ARGS__};                                                                            \
+    for (const void* q_ : ptrs_) SRK_REQUIRE(aligned16(q_), SRK_E_ALIGN, fn ": every buffer must be 16-byte aligned"); \
+  } while (0)
+
+int srk_mlp_fused_fwd_ex(const uint16_t* xn, const uint16_t* w1, const float* b1, const uint16_t* w2, const float* b2, const float* res,
+                         float* out, uint16_t* out_bf16, uint16_t* u_out, uint16_t* h_out, int u_dgelu, uint16_t* xn_next, float* xn_mean,
+                         float* xn_rstd, const float* xn_gamma, const float* xn_beta, int xn_C, const srk_win_geom* xn_geom,
+                         const float* rowscale, int rows_per_sample, int M, srk_stream_t stream) {
+  SRK_REQUIRE(xn && w1 && w2 && res && out, SRK_E_NULL, "mlp_fused_fwd_ex: null pointer");
+  SRK_REQUIRE((u_out != nullptr) == (h_out != nullptr), SRK_E_NULL, "mlp_fused_fwd_ex: u_out and h_out go together (both or neither)");
+  SRK_REQUIRE(M > 0, SRK_E_SHAPE, "mlp_fused_fwd_ex: M=%d", M);
+  BLOCK_ALIGNED("mlp_fused_fwd_ex", xn, w1, b1, w2, b2, res, out, out_bf16, u_out, h_out, xn_next, xn_gamma, xn_beta);
+  if (int rc = block_rowscale(rowscale, rows_per_sample, M, "mlp_fused_fwd_ex")) return rc;
+  GemmParams p = {};
+  p.A = xn; p.lda = 192; p.Wt = w1; p.K = 192; p.bias = b1; p.W2 = w2; p.bias2 = b2; p.HP = 384; p.M = M; p.N = 192; p.ldo = 192;
+  p.res = res; p.outf = out; p.outb = out_bf16; p.u_out = u_out; p.h_out = h_out; p.u_dgelu = u_dgelu ? 1 : 0;
+  p.rowscale = rowscale; p.rows_per_sample = rows_per_sample;
+  if (xn_next) {
+    SRK_REQUIRE(xn_mean && xn_rstd && xn_gamma && xn_beta, SRK_E_NULL, "mlp_fused_fwd_ex: fused LayerNorm needs mean / rstd / gamma / beta");
+    SRK_REQUIRE(xn_C > 0 && xn_C <= 192, SRK_E_SHAPE, "mlp_fused_fwd_ex: xn_C=%d", xn_C);
+    p.xn_out = xn_next; p.xn_mean = xn_mean; p.xn_rstd = xn_rstd; p.xn_gamma = xn_gamma; p.xn_beta = xn_beta; p.xn_C = xn_C;
+    if (xn_geom) {
+      if (int rc = block_geom(xn_geom, &p.xn_geom, M, "mlp_fused_fwd_ex")) return rc;
+      p.xn_window = 1;
+    }
+  } else {
+    SRK_REQUIRE(!xn_geom, SRK_E_NULL, "mlp_fused_fwd_ex: xn_geom without xn_next");
+  }
+  p.flops = 4.0 * M * 180.0 * 360.0;
+  const int rc = srk_launch_mlp_fused(p, (hipStream_t)stream);
+  if (rc == SRK_NOT_COVERED) {
+    srk_set_error("mlp_fused_fwd_ex: not covered (needs options gemm_stream / mlp_fused on, M %% 64 == 0, M >= 64 * (#CUs & ~7), "
+                  "rows_per_sample %% 64 == 0 with a rowscale, u_out with u_dgelu; got M=%d rows_per_sample=%d u_dgelu=%d)", M,
+                  rows_per_sample, u_dgelu);
+    return SRK_E_UNSUPPORTED;
+  }
+  return rc;
+}
+
+int srk_mlp_fused_bwd_ex(const uint16_t* g, const uint16_t* w2t, const uint16_t* u, int u_is_dgelu, uint16_t* du_out, const uint16_t* w1t,
+                         const float* ln_x, const float* ln_mean, const float* ln_rstd, const float* ln_gamma, float* gx, uint16_t* gxb,
+                         const srk_win_geom* out_geom, const float* rowscale, int rows_per_sample, float* d_gamma, float* d_beta, int C, int M,
+                         srk_stream_t stream) {
+  SRK_REQUIRE(g && w2t && u && du_out && w1t && ln_x && ln_mean && ln_rstd && ln_gamma && gx && d_gamma && d_beta, SRK_E_NULL,
+              "mlp_fused_bwd_ex: null pointer");
+  SRK_REQUIRE(M > 0 && C > 0 && C <= 192, SRK_E_SHAPE, "mlp_fused_bwd_ex: M=%d C=%d", M, C);
+  BLOCK_ALIGNED("mlp_fused_bwd_ex", g, w2t, u, du_out, w1t, ln_x, gx, gxb);
+  if (int rc = block_rowscale(rowscale, rows_per_sample, M, "mlp_fused_bwd_ex")) return rc;
+  GemmParams p = {};
+  p.A = g; p.lda = 192; p.Wt = w2t; p.K = 192; p.HP = 384; p.aux = u; p.u_out = du_out; p.W2 = w1t; p.M = M; p.N = 192; p.ldo = 192;
+  p.outf = gx; p.outb = gxb; p.rowscale = rowscale; p.rows_per_sample = rows_per_sample;
+  p.ln_x = ln_x; p.ln_mean = ln_mean; p.ln_rstd = ln_rstd; p.ln_gamma = ln_gamma; p.ln_dgamma = d_gamma; p.ln_dbeta = d_beta; p.ln_C = C;
+  p.ln_rows_window = 0; p.ln_stats_by_m = 0; p.ln_out_window = 0;
+  p.u_dgelu = u_is_dgelu ? 1 : 0;
+  if (out_geom) {
+    SRK_REQUIRE(gxb, SRK_E_NULL, "mlp_fused_bwd_ex: out_geom without gxb");
+    if (int rc = block_geom(out_geom, &p.geom, M, "mlp_fused_bwd_ex")) return rc;
+    p.ln_out_window = 1;
+  }
+  p.flops = 8.0 * M * 180.0 * 360.0;
+  const int rc = srk_launch_mlp_fused_bwd(p, (hipStream_t)stream);
+  if (rc == SRK_NOT_COVERED) {
+    srk_set_error("mlp_fused_bwd_ex: not covered (needs options gemm_stream / mlp_bwd_fused on, M %% 64 == 0, M >= 64 * (#CUs & ~7), "
+                  "rows_per_sample %% 64 == 0 with a rowscale; got M=%d rows_per_sample=%d)", M, rows_per_sample);
+    return SRK_E_UNSUPPORTED;
+  }
+  return rc;
+}
+
+int srk_qkv_window_attention_fwd(const uint16_t* xn, int lda, const uint16_t* w_qkv, const float* b_qkv, float scale, uint16_t* qkv_out,
+                                 const float* bias_dense, uint16_t* out, int64_t B_, int nH, const srk_win_geom* geom, srk_stream_t stream) {
+  SRK_REQUIRE(xn && w_qkv && bias_dense && out && geom, SRK_E_NULL, "qkv_window_attention_fwd: null pointer");
+  BLOCK_ALIGNED("qkv_window_attention_fwd", xn, w_qkv, b_qkv, qkv_out, bias_dense, out);
+  SRK_REQUIRE(B_ > 0 && B_ < (1ll << 24) && lda >= 192 && lda % 8 == 0, SRK_E_SHAPE, "qkv_window_attention_fwd: B_=%lld lda=%d (lda >= 192, a multiple of 8)",
+              (long long)B_, lda);
+  WinGeom wg;
+  if (int rc = block_geom(geom, &wg, (long long)B_ * 64, "qkv_window_attention_fwd")) return rc;
+  const int rc = srk_launch_qkv_attn_fwd(xn, lda, w_qkv, b_qkv, scale, qkv_out, bias_dense, out, B_, nH, nH * 32, 192, wg, (hipStream_t)stream);
+  if (rc == SRK_NOT_COVERED) {
+    srk_set_error("qkv_window_attention_fwd: not covered (needs option attn_fused 1 or 2, 6 heads x 32, C padded to 192 and at least one "
+                  "window per CU; got nH=%d B_=%lld attn_fused=%d)", nH, (long long)B_, srk_attn_fused_mode());
+    return SRK_E_UNSUPPORTED;
+  }
+  return rc;
+}
+
+int srk_proj_residual_fwd(const uint16_t* ao, const uint16_t* w_proj, const float* b_proj, const float* res, float* out, const float* rowscale,
+                          int rows_per_sample, uint16_t* xn_out, float* xn_mean, float* xn_rstd, const float* xn_gamma, const float* xn_beta,
+                          int xn_C, int64_t B_, const srk_win_geom* geom, srk_stream_t stream) {
+  SRK_REQUIRE(ao && w_proj && res && out && geom, SRK_E_NULL, "proj_residual_fwd: null pointer");
+  SRK_REQUIRE(res != out, SRK_E_SHAPE, "proj_residual_fwd: out must not alias res (rows are read and written in different orders)");
+  BLOCK_ALIGNED("proj_residual_fwd", ao, w_proj, b_proj, res, out, xn_out, xn_gamma, xn_beta);
+  SRK_REQUIRE(B_ > 0 && B_ < (1ll << 24), SRK_E_SHAPE, "proj_residual_fwd: B_=%lld", (long long)B_);
+  const long long T = (long long)B_ * 64;
+  GemmParams p = {};
+  if (int rc = block_geom(geom, &p.geom, T, "proj_residual_fwd")) return rc;
+  if (int rc = block_rowscale(rowscale, rows_per_sample, T, "proj_residual_fwd")) return rc;
+  p.A = ao; p.lda = 192; p.Wt = w_proj; p.M = (int)T; p.N = 192; p.K = 192; p.bias = b_proj; p.res = res; p.outf = out; p.ldo = 192;
+  p.rowscale = rowscale; p.rows_per_sample = rows_per_sample; p.flops = 2.0 * T * 180.0 * 180.0;
+  if (xn_out) {
+    SRK_REQUIRE(xn_mean && xn_rstd && xn_gamma && xn_beta, SRK_E_NULL, "proj_residual_fwd: fused LayerNorm needs mean / rstd / gamma / beta");
+    SRK_REQUIRE(xn_C > 0 && xn_C <= 192, SRK_E_SHAPE, "proj_residual_fwd: xn_C=%d", xn_C);
+    p.xn_out = xn_out; p.xn_mean = xn_mean; p.xn_rstd = xn_rstd; p.xn_gamma = xn_gamma; p.xn_beta = xn_beta; p.xn_C = xn_C; p.xn_window = 0;
+  }
+  return srk_launch_gemm(LD_ROWS, EP_PROJ_RES, p, (hipStream_t)stream);
+}
+
+int srk_qkv_dgrad_lnbwd(const uint16_t* d_qkv, const uint16_t* w_qkv_t, const float* ln_x, const float* ln_mean, const float* ln_rstd,
+                        const float* ln_gamma, float* gx, uint16_t* gxb, const float* rowscale, int rows_per_sample, float* ln_skip,
+                        float* d_gamma, float* d_beta, int C, int64_t B_, const srk_win_geom* geom, srk_stream_t stream) {
+  SRK_REQUIRE(d_qkv && w_qkv_t && ln_x && ln_mean && ln_rstd && ln_gamma && gx && d_gamma && d_beta && geom, SRK_E_NULL,
+              "qkv_dgrad_lnbwd: null pointer");
+  SRK_REQUIRE(ln_skip != gx, SRK_E_SHAPE, "qkv_dgrad_lnbwd: ln_skip must not alias gx");
+  BLOCK_ALIGNED("qkv_dgrad_lnbwd", d_qkv, w_qkv_t, ln_x, gx, gxb, ln_skip);
+  SRK_REQUIRE(B_ > 0 && B_ < (1ll << 24) && C > 0 && C <= 192, SRK_E_SHAPE, "qkv_dgrad_lnbwd: B_=%lld C=%d", (long long)B_, C);
+  const long long T = (long long)B_ * 64;
+  GemmParams p = {};
+  if (int rc = block_geom(geom, &p.geom, T, "qkv_dgrad_lnbwd")) return rc;
+  if (int rc = block_rowscale(rowscale, rows_per_sample, T, "qkv_dgrad_lnbwd")) return rc;
+  p.A = d_qkv; p.lda = 576; p.Wt = w_qkv_t; p.M = (int)T; p.N = 192; p.K = 576; p.ldo = 192; p.flops = 2.0 * T * 540.0 * 180.0;
+  p.outf = gx; p.outb = gxb; p.rowscale = rowscale; p.rows_per_sample = rows_per_sample; p.ln_skip = ln_skip;
+  p.ln_x = ln_x; p.ln_mean = ln_mean; p.ln_rstd = ln_rstd; p.ln_gamma = ln_gamma; p.ln_dgamma = d_gamma; p.ln_dbeta = d_beta; p.ln_C = C;
+  p.ln_rows_window = 1; p.ln_stats_by_m = 1; p.ln_out_window = 0;
+  return srk_launch_gemm(LD_ROWS, EP_LNBWD, p, (hipStream_t)stream);
+}
+
 }  // extern "C"
