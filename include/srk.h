@@ -68,7 +68,9 @@ int srk_layernorm_fwd(const float* x, const float* gamma, const float* beta, uin
 int srk_window_attention_fwd(const uint16_t* qkv, const float* bias_dense, uint16_t* out, int64_t B_, int nH,
                              const srk_win_geom* geom, srk_stream_t stream);
 /* gradient of the above.  d_out bf16 [B_*64][nH*32]; d_qkv bf16 [B_*64][3*nH*32] (columns which,h,d);
- * d_table fp32 [225][nH] is ACCUMULATED; slab = scratch of srk_window_attention_bwd_scratch() bytes. */
+ * d_table fp32 [225][nH] is ACCUMULATED; slab = scratch of srk_window_attention_bwd_scratch() bytes, fully written before it is
+ * read (needs no zeroing).  Every element of d_qkv is written (columns head_dim .. 31 of a head come out 0 when they are 0 in qkv
+ * and d_out). */
 int srk_window_attention_bwd(const uint16_t* qkv, const float* bias_dense, const uint16_t* d_out, uint16_t* d_qkv,
                              float* d_table, void* slab, int64_t B_, int nH, float scale, const srk_win_geom* geom,
                              srk_stream_t stream);
@@ -477,7 +479,10 @@ int srk_cab_add_ln(float* x, const uint16_t* conv, const float* gate, const floa
  * OCAB.forward :403-439 backwards).  d_out bf16 [T][ldo] raster = gradient of the attention output; d_qkv bf16 [T][ldq] in the
  * layout of qkv (q gradient w.r.t. the UNSCALED q, as qkv holds it); d_table fp32 [table_rows][num_heads] is ACCUMULATED (the
  * negative relative_position_index_OCA entries wrap, :911-918); scratch: srk_win256_attention_bwd_scratch bytes.  In the
- * overlapping form the key / value gradients of a token are summed over the (up to four) key windows that hold it. */
+ * overlapping form the key / value gradients of a token are summed over the (up to four) key windows that hold it.  shift_y and
+ * shift_x are independent, any 0 <= shift < 16 (the mask comes from the region labels of the slices (0, -16), (-16, -shift),
+ * (-shift, end) per axis; the overlapping form takes no shift).  Every element of rows 0 .. T - 1, columns 0 .. 3 CA - 1 of d_qkv is
+ * written; the scratch is fully written before it is read (needs no zeroing). */
 size_t srk_win256_attention_bwd_scratch(int B, int H, int W, int num_heads, int CA, int table_rows, int overlap);
 int srk_win256_attention_bwd(const uint16_t* qkv, int ldq, int CA, const float* table, int table_rows, const uint16_t* d_out, int ldo,
                              uint16_t* d_qkv, float* d_table, void* scratch, int B, int H, int W, int shift_y, int shift_x, int num_heads,
@@ -636,7 +641,9 @@ int srk_qkv_dgrad_lnbwd(const uint16_t* d_qkv, const uint16_t* w_qkv_t, const fl
 /* backward of srk_win_attention_fwd_padded with a dense bias: d_qkv (q | k | v slices of the heads of this launch) and d_bias
  * [heads][N][N] ACCUMULATED (zero it first) over the windows.  scratch: null (d_bias by float atomics) or
  * srk_win_attention_bwd_padded_scratch bytes (per-window dS tiles + a reduction kernel, and a transposed copy of the bias for the
- * key-major pass: the fast path) */
+ * key-major pass: the fast path; fully written before it is read, needs no zeroing).  d_bias is added to whatever it holds.  Only
+ * the q | k | v column blocks of heads 0 .. num_heads - 1 of rows 0 .. T - 1 are written (a wider CA holds another launch's heads);
+ * shift_y < wh and shift_x < ww are independent; padded queries and the d k / d v of padded keys contribute nothing. */
 size_t srk_win_attention_bwd_padded_scratch(int B, int Hp, int Wp, int wh, int ww, int num_heads);
 int srk_win_attention_bwd_padded(const uint16_t* qkv, int ldq, int CA, const float* bias, const uint16_t* d_out, int ldo, uint16_t* d_qkv,
                                  float* d_bias, void* scratch, int B, int H, int W, int Hp, int Wp, int wh, int ww, int shift_y, int shift_x,
