@@ -555,7 +555,10 @@ int srk_dwconv3x3(const uint16_t* x, int ldx, const float* w, const float* scale
 int srk_dwconv3x3_bn_act(const uint16_t* x, int ldx, const float* w, const float* bias, const float* bn_scale, const float* bn_shift, uint16_t* pre,
                          int ldpre, uint16_t* out, int ldo, int B, int H, int W, int C8, srk_stream_t stream);
 long long srk_dwconv3x3_bn_act_launches(void);
-/* LayerNorm (eps 1e-5) over C channels of a bf16 row slice -> bf16 [rows][ldo], columns C..CP_out written as zero (SpatialGate.norm :46) */
+/* LayerNorm (eps 1e-5) over C channels of a bf16 row slice -> bf16 [rows][ldo], columns C..CP_out-1 written as +0 (SpatialGate.norm :46).
+ * Two-pass statistics (the variance from x - mean).  Columns C..CP_out-1 of x are never used (they may hold anything, NaN included);
+ * columns >= CP_out of out are not written.  ldx >= the 8-column pieces that cover C and ldo >= CP_out are the caller's to keep: the
+ * launcher checks only that both are multiples of 8. */
 int srk_rowln_bf16(const uint16_t* x, int ldx, const float* gamma, const float* beta, uint16_t* out, int ldo, int64_t rows, int C, int CP_out,
                    srk_stream_t stream);
 /* spatial_interaction (:322-327, :475-480): gate[t] = sigmoid(b3 + w3 . gelu(W0 x_t + b0)); W0 fp32 [S][CP] (BatchNorm folded, zero at pads) */
@@ -565,7 +568,8 @@ int srk_spatial_gate(const uint16_t* x, int ldx, const float* W0, const float* b
 int srk_spatial_gate_dev(const uint16_t* x, int ldx, const float* W0, const float* b0, const float* w3, const float* b3, int S, float* gate,
                          int64_t rows, int CP, srk_stream_t stream);
 /* out = a * ga + b * gb with one gate per token (tgate [rows]) and one per (sample, channel) (cgate [B][CP]); tok_gate_on_a selects
- * which operand takes the token gate (:430-436 spatial block: 0; :518-524 channel block: 1).  Gates are post-sigmoid. */
+ * which operand takes the token gate (:430-436 spatial block: 0; :518-524 channel block: 1).  Gates are post-sigmoid.
+ * a, b and out are contiguous [rows][CP]: the entry point takes no row stride. */
 int srk_dual_gate_combine(const uint16_t* a, const uint16_t* b, const float* cgate, const float* tgate, uint16_t* out, int64_t rows,
                           int rows_per_sample, int CP, int tok_gate_on_a, srk_stream_t stream);
 /* Adaptive_Channel_Attention core (:481-505): per sample and head, q / k columns L2-normalised over the N tokens, logits
@@ -649,7 +653,9 @@ int srk_win_attention_bwd_padded(const uint16_t* qkv, int ldq, int CA, const flo
                                  float* d_bias, void* scratch, int B, int H, int W, int Hp, int Wp, int wh, int ww, int shift_y, int shift_x,
                                  int num_heads, float scale, srk_stream_t stream);
 /* partial [samples][chunks][2][8 C8]: per 256-row chunk of a sample, sum_t p[t][c] and sum_t p[t][c] q[t][c] (fixed order; the caller
- * sums the chunks).  BatchNorm batch statistics (q = p), its backward sums (p = dz, q = x), the pooled mean (samples = B). */
+ * sums the chunks).  BatchNorm batch statistics (q = p), its backward sums (p = dz, q = x), the pooled mean (samples = B).
+ * Every element of partial is written (it needs no zeroing); ldp, ldq >= 8 C8 are the caller's to keep (only their divisibility by 8
+ * is checked). */
 int64_t srk_chan_stats_chunks(int64_t rows_per_sample);
 int srk_chan_stats(const uint16_t* p, int ldp, const uint16_t* q, int ldq, float* partial, int samples, int64_t rows_per_sample, int C8,
                    srk_stream_t stream);
@@ -657,7 +663,8 @@ int srk_chan_stats(const uint16_t* p, int ldp, const uint16_t* q, int ldq, float
  *   srk_bn_train_coeffs: the R partial rows (row_stride floats apart; sum x at + 0, sum x^2 at + ld; from srk_chan_stats or
  *     srk_spatial_gate_train what 0) summed in a fixed order -> coef [4][ld] = scale (gamma rstd), shift (beta - mean scale), mean, rstd over n values per channel; running_mean / running_var
  *     (or null) move in place by `momentum` with the unbiased variance; real_of[c] = index of channel c in the module's un-padded buffers,
- *     -1 for padding (null: identity).
+ *     -1 for padding (null: identity).  Only columns 0..C-1 of each coefficient row are written; a channel whose variance comes out
+ *     negative in fp32 is clamped at 0.
  *   srk_bn_train_bwd_coeffs: partial rows (sum dz, sum dz x) + the forward's coef -> coef [5][ld] = A, B, C of d x = A dz + B x + C,
  *     d gamma, d beta. */
 /* out[o][i] = sum over r < R of in[o][r][i] (in: fp32 [outer][R][n] contiguous), rows added in a fixed order: the finishing sum of the
@@ -675,42 +682,55 @@ int srk_bn_train_bwd_coeffs(const float* partial, int R, int row_stride, int ld,
 int srk_bn_frozen_coeffs(int ld, int C, const float* gamma, const float* beta, float eps, const float* running_mean, const float* running_var,
                          const int* real_of, float* coef, srk_stream_t stream);
 int srk_bn_frozen_bwd_coeffs(const float* partial, int R, int row_stride, int ld, int C, const float* fwd_coef, float* coef, srk_stream_t stream);
-/* out = act(x * scale[i][c] + shift[i][c]); i = row / rows_per_sample (rows_per_sample 0: one vector for all rows); act 1 = GELU */
+/* out = act(x * scale[i][c] + shift[i][c]); i = row / rows_per_sample (rows_per_sample 0: one vector for all rows); act 1 = GELU.
+ * x * scale + shift is one fused multiply-add.  For this and the three entry points below: scale / shift / A / B / C are contiguous
+ * [samples][8 C8]; only the 8 C8 columns of the slice are read and written; the row strides must be >= 8 C8 (not checked beyond their
+ * divisibility by 8); rows * C8 < 2^31. */
 int srk_affine_act_bf16(const uint16_t* x, int ldx, const float* scale, const float* shift, uint16_t* out, int ldo, int64_t rows, int C8,
                         int rows_per_sample, int act, srk_stream_t stream);
 /* out = dy * gelu'(x * scale[c] + shift[c]) */
 int srk_dgelu_affine_bf16(const uint16_t* dy, int lddy, const uint16_t* x, int ldx, const float* scale, const float* shift, uint16_t* out,
                           int ldo, int64_t rows, int C8, srk_stream_t stream);
-/* out (+)= A[i][c] p + B[i][c] q + C[i][c]   (null A / B: coefficient 1; null p / q: no such term; accumulate: out is read first) */
+/* out (+)= A[i][c] p + B[i][c] q + C[i][c]   (null A / B: coefficient 1; null p / q: no such term; accumulate: out is read first).
+ * Evaluated as ((old + A p) + B q) + C in fp32 with one bf16 rounding, so the one-term forms (copy, A p, old + p, old + C) are the
+ * correctly rounded result; a -0 input is copied as +0. */
 int srk_lincomb2_bf16(const uint16_t* p, int ldp, const uint16_t* q, int ldq, const float* A, const float* Bc, const float* Cc, uint16_t* out,
                       int ldo, int64_t rows, int C8, int rows_per_sample, int accumulate, srk_stream_t stream);
 /* d a = dy * b, d b = dy * a  (SpatialGate's x1 * x2, dat_arch.py:54) */
 int srk_mul_bwd_bf16(const uint16_t* dy, int lddy, const uint16_t* a, int lda, const uint16_t* b, int ldb, uint16_t* da, int ldda, uint16_t* db,
                      int lddb, int64_t rows, int C8, srk_stream_t stream);
-/* depth-wise 3x3 (pad 1): partial [B][srk_dwconv3x3_wgrad_chunks(H)][10][8 C8]; rows 0..8 the taps' weight gradient, row 9 the bias gradient */
+/* depth-wise 3x3 (pad 1): partial [B][srk_dwconv3x3_wgrad_chunks(H)][10][8 C8]; rows 0..8 the taps' weight gradient, row 9 the bias gradient
+ * of one band of 8 image rows.  Every element of partial is written (no zeroing); lddy, ldx >= 8 C8 (only divisibility by 8 is checked). */
 int srk_dwconv3x3_wgrad_chunks(int H);
 int srk_dwconv3x3_wgrad(const uint16_t* dy, int lddy, const uint16_t* x, int ldx, float* partial, int B, int H, int W, int C8,
                         srk_stream_t stream);
 /* backward of srk_dual_gate_combine, out = a_chan * cgate[b][c] + a_tok * tgate[t]:  d_chan = d * cgate, d_tok = d * tgate,
  * dcg_partial [B][ceil(HW / 64)][CA] = chunk sums of d * a_chan  (gradient w.r.t. the post-sigmoid channel gate),
- * dsmap [B * HW] = (sum_c d * a_tok) * tgate (1 - tgate)   (gradient w.r.t. the PRE-sigmoid spatial map) */
+ * dsmap [B * HW] = (sum_c d * a_tok) * tgate (1 - tgate)   (gradient w.r.t. the PRE-sigmoid spatial map).
+ * All bf16 operands contiguous [B * HW][CA] (no row stride), CA <= 256; dcg_partial and dsmap are fully written (no zeroing). */
 int srk_dual_gate_bwd(const uint16_t* dcomb, const uint16_t* a_chan, const uint16_t* a_tok, const float* cgate, const float* tgate,
                       uint16_t* d_chan, uint16_t* d_tok, float* dcg_partial, float* dsmap, int B, int HW, int CA, srk_stream_t stream);
 /* spatial_interaction in training (:318-323 / :475-480): y1 = W0 x + b0 (S <= 16), z = y1 * bn_scale + bn_shift, smap = w3 . gelu(z) + b3.
  *   what 0: partial [blocks][2][16]  = sums of y1, y1^2 over each 256-row block (BatchNorm batch statistics)
  *   what 1: partial [blocks][4][16]  = sums of dz, dz * y1, dsmap * gelu(z), dsmap (in slot 0) with dz = dsmap * w3 * gelu'(z)
  *   what 2: dy1 = cA * dz + cB * y1 + cC (the BatchNorm backward, coefficients from the caller); dx (+)= W0^T dy1;
- *           partial [blocks][16][C + 1] = the block's d W0 [s][c] (first 16 C floats) and d b0 [s] (last 16) */
+ *           partial [blocks][16][C + 1] = the block's d W0 [s][c] (first 16 C floats) and d b0 [s] (last 16)
+ * blocks = ceil(rows / 256); every element of partial is written, slots s >= S as 0 (no zeroing); C in {64, 128, 192, 256}; only the C
+ * columns of dx are written; ldx, lddx >= C (only divisibility by 8 is checked). */
 int srk_spatial_gate_train(int what, const uint16_t* x, int ldx, const float* W0, const float* b0, const float* bn_scale, const float* bn_shift,
                            const float* w3, const float* dsmap, const float* cA, const float* cB, const float* cC, uint16_t* dx, int lddx,
                            int accumulate, float* partial, int64_t rows, int C, int S, srk_stream_t stream);
-/* LayerNorm (eps 1e-5) backward on bf16 rows (SpatialGate.norm): dx bf16 (columns C..CP_out zero); partial [blocks][2][C] with the
- * workgroups' d gamma / d beta sums, blocks = srk_rowln_bwd_blocks(rows); CP_out <= 512 */
+/* LayerNorm (eps 1e-5) backward on bf16 rows (SpatialGate.norm): dx bf16 (columns C..CP_out-1 written as +0, columns >= CP_out not
+ * written); partial [blocks][2][C] with the workgroups' d gamma / d beta sums (row m goes to block (m / 16) % blocks), blocks =
+ * srk_rowln_bwd_blocks(rows) = min(1024, ceil(rows / 16)); every element of partial is written (no zeroing); CP_out <= 512.  The row
+ * statistics are recomputed as the forward forms them (two passes: the variance from x - mean).  Columns C..CP_out-1 of x and dy are
+ * never used (they may hold anything, NaN included). */
 int64_t srk_rowln_bwd_blocks(int64_t rows);
 int srk_rowln_bwd_bf16(const uint16_t* dy, int lddy, const uint16_t* x, int ldx, const float* gamma, uint16_t* dx, int lddx, float* partial,
                        int64_t rows, int C, int CP_out, srk_stream_t stream);
 /* channel attention (:497-508): partial [B][heads][ceil(N / 256)][1088] = per chunk G[i][j] = sum_n x[n][32 h + i] y[n][32 h + j] (1024),
- * sum_n x[n][i]^2 (32), sum_n y[n][j]^2 (32); srk_chan_gram_floats = the partial's size in floats */
+ * sum_n x[n][i]^2 (32), sum_n y[n][j]^2 (32); srk_chan_gram_floats = the partial's size in floats.  All 32 columns of every head are read
+ * (the layout's padding must be finite; zero in the models); every element of partial is written (no zeroing). */
 int64_t srk_chan_gram_floats(int B, int N, int num_heads);
 int srk_chan_gram(const uint16_t* x, int ldx, const uint16_t* y, int ldy, float* partial, int B, int N, int num_heads, srk_stream_t stream);
 /* out[n][32 h + i] (+)= sum_j M[b][h][i][j] src[n][32 h + j] + diag[b][h][i] src2[n][32 h + i]   (M fp32 [B][heads][32][32]; diag optional) */

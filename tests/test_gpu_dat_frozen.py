@@ -159,7 +159,7 @@ class _Slice:
         self.ptr, self.ld = self.buf[pad:, off:].data_ptr(), ld
 
 
-@pytest.mark.parametrize("B,H,W,C", [(2, 11, 21, 40), (1, 16, 32, 192), (3, 8, 16, 64)])
+@pytest.mark.parametrize("B,H,W,C", [(2, 11, 21, 40), (1, 16, 32, 192), (3, 8, 16, 64), (2, 9, 17, 72)])   # 72: C8 = 9, a second channel block
 def test_dwconv_bn_act_single_pass_vs_the_three_pass_kernels(B, H, W, C):
     """srk_dwconv3x3_bn_act against srk_dwconv3x3 (scale 1, shift = bias) + srk_affine_act_bf16 (GELU) on the same inputs: c_pre bit-equal,
     conv equal up to one bf16 rounding (2^-8 relative).  Input in a NaN frame (rows around it, columns beside the slice), outputs in

@@ -747,7 +747,7 @@ __global__ __launch_bounds__(256) void rowln_bwd_kernel(const bf16_t* __restrict
     }
   for (long long m = ((long long)blockIdx.x * 4 + wave) * 4 + sub; m < rows; m += (long long)gridDim.x * 16) {
     float xv[K][8], dv[K][8];
-    float s = 0.f, q = 0.f;
+    float s = 0.f;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const int c0 = (j + 16 * k) * 8;
@@ -762,18 +762,26 @@ __global__ __launch_bounds__(256) void rowln_bwd_kernel(const bf16_t* __restrict
       for (int e = 0; e < 8; ++e) {
         if (c0 + e >= C) xv[k][e] = dv[k][e] = 0.f;
         s += xv[k][e];
-        q += xv[k][e] * xv[k][e];
       }
     }
+    // the variance from x - mean, as the forward (rowln_bf16_kernel) forms it: E[x^2] - mean^2 in fp32 loses the spread of a row whose
+    // mean is large against it (rstd off by 3e-3 at mean 200 / std 1, and by more on a constant row, where the difference is all rounding)
     const float mean = wave_sum16(s) * invC;
-    const float var = fmaxf(wave_sum16(q) * invC - mean * mean, 0.f);
-    const float rstd = rsqrtf(var + 1e-5f);
+    float q = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        xv[k][e] = (j + 16 * k) * 8 + e < C ? xv[k][e] - mean : 0.f;
+        q += xv[k][e] * xv[k][e];
+      }
+    const float rstd = rsqrtf(wave_sum16(q) * invC + 1e-5f);
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int k = 0; k < K; ++k)
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        xv[k][e] = (j + 16 * k) * 8 + e < C ? (xv[k][e] - mean) * rstd : 0.f;         // x hat
+        xv[k][e] *= rstd;                                                             // x hat (0 beyond C)
         const float t = dv[k][e] * gm[k][e];
         s1 += t;
         s2 += t * xv[k][e];
