@@ -259,6 +259,38 @@ int srk_resize_aa_f32(const float* x, float* out, int B, int C, int H, int W, in
  * SRK_E_NULL: a null pointer; SRK_E_SHAPE: B outside 1..65535, lr_patch outside 1..2048, scale outside 2..4, quant_bits other than 0 / 8. */
 int srk_crop_degrade_u8(const uint8_t* pool, const int64_t* hr_desc, float* lr_out, float* hr_out, int B, int lr_patch, int scale,
                         int quant_bits, srk_stream_t stream);
+/* Blind degradation (csrc/degrade.hip): the antialiased bicubic downscale above behind a per-sample Gaussian blur, plus per-sample noise.
+ * Parameters, four int64 slots per sample (slots 6..9 of a ten-slot descriptor, or one row of par4):
+ *   [6] fp32 bits of sigma_y (low word) and sigma_x (high word), HR pixels, each in [0, 2.5]
+ *   [7] fp32 bits of sigma_n (low word) and gain (high word), image units, each in [0, 1]
+ *   [8] noise_id, 64 bits        [9] flags: bit 0 = gray noise (one draw for all channels)
+ * Blur: an axis-aligned anisotropic Gaussian.  Per axis R = ceil(3 sigma) (<= 8), g[d] = exp(-d^2 / (2 sigma^2)), d = -R..R, normalised
+ * in fp64, composed with the cubic taps (lo_c, w_c[j]) of the resize -- the fp64 values before their rounding -- into one table per
+ * output i: W[m] = sum_j w_c[j] g[m - lo_c - j] for m in [max(lo_c - R, 0), min(hi_c + R, n_in)), divided by its sum (mass outside the
+ * image is dropped and the rest renormalised, the border rule of the resize); fp64 with contraction off, rounded once to fp32.  At
+ * factors 2 / 3 / 4 that is at most 8 + 16, 12 + 16 and 16 + 16 taps; the two passes of the resize run unchanged on the composed
+ * tables (horizontal first, ascending-tap fmaf chains from 0).  An axis with sigma == 0 takes the cubic table itself.
+ * Noise, on the filtered fp32 value v and before the 8-bit rounding: v + sqrtf(sigma_n^2 + gain * fmaxf(v, 0)) * z, in fp32 without
+ * contraction.  z = sqrtf(-2 logf(u1)) * cospif(2 u2), u1 = ((r0 >> 8) + 1) * 2^-24, u2 = (r1 >> 8) * 2^-24, (r0, r1) the first two
+ * words of Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85) on the counter (x, y, ch, 0) under
+ * the key (low word, high word of noise_id): x, y are the output's coordinates in the WHOLE downscaled image, ch its channel, or 0
+ * with gray noise -- which a one-channel image always gets.  sigma_n == 0 && gain == 0: nothing is added, the bits of v pass through.
+ * With both sigmas 0 and no noise the outputs are BIT-IDENTICAL to srk_resize_aa_f32 / srk_crop_degrade_u8.
+ * The host checks the ranges; for ANY bit pattern the kernels clamp R to 0..8 (sigma <= 0 or NaN: no blur) and sigma_n, gain to
+ * [0, 16] (NaN: 0), and stay inside their tables and their output.  One launch, no device allocation.
+ *
+ * srk_degrade_blind_f32: x fp32 [B][C][H][W] -> out fp32 [B][C][H/scale][W/scale]; par4 DEVICE int64 [B][4] = slots 6..9.
+ * SRK_E_NULL: a null pointer; SRK_E_SHAPE: a non-positive extent, scale outside 2..4 or not dividing H and W, quant_bits other than
+ * 0 / 8, x and out overlapping, a size that does not fit one launch. */
+int srk_degrade_blind_f32(const float* x, float* out, const int64_t* par4, int B, int C, int H, int W, int scale, int quant_bits,
+                          srk_stream_t stream);
+/* srk_crop_degrade_u8 with the blind degradation: desc10 = B descriptors of TEN int64 in DEVICE memory, [0..5] the six of
+ * srk_crop_degrade_u8, [6..9] as above.  hr_out is never blurred or noised: bit-identical to srk_crop_degrade_u8's.  lr_out is
+ * BIT-IDENTICAL to the window of srk_degrade_blind_f32 on the whole converted region with the same four slots (the counter takes image
+ * coordinates; the two entries share their device routines).  A gray source is filtered once, gets one draw and is written to three
+ * channels.  Errors as srk_crop_degrade_u8. */
+int srk_crop_degrade_blind_u8(const uint8_t* pool, const int64_t* desc10, float* lr_out, float* hr_out, int B, int lr_patch, int scale,
+                              int quant_bits, srk_stream_t stream);
 /* Tiled inference (csrc/tile.hip): crop a chunk of overlapping tiles out of an fp32 NCHW batch, run a model on them as a batch of
  * n * B, and merge the chunk's outputs into the output image.
  * Tile grid, per axis with extent N, tile t (1 <= t <= N) and stride s (1 <= s <= t; overlap = t - s): k = ceil((N - t) / s) + 1

@@ -504,6 +504,30 @@ int srk_crop_degrade_u8(const uint8_t* pool, const int64_t* hr_desc, float* lr_o
                                     (hipStream_t)stream);
 }
 
+int srk_crop_degrade_blind_u8(const uint8_t* pool, const int64_t* desc10, float* lr_out, float* hr_out, int B, int lr_patch, int scale,
+                              int quant_bits, srk_stream_t stream) {
+  REQ_PTR(pool); REQ_PTR(desc10); REQ_PTR(lr_out); REQ_PTR(hr_out);
+  SRK_REQUIRE(B > 0 && B <= 65535 && lr_patch > 0 && lr_patch <= 2048 && scale >= 2 && scale <= 4, SRK_E_SHAPE,
+              "crop_degrade_blind: B=%d (1..65535) patch=%d (1..2048) scale=%d (2..4)", B, lr_patch, scale);
+  SRK_REQUIRE(quant_bits == 0 || quant_bits == 8, SRK_E_SHAPE, "crop_degrade_blind: quant_bits must be 0 or 8 (got %d)", quant_bits);
+  return srk_launch_crop_degrade_blind_u8(pool, reinterpret_cast<const long long*>(desc10), lr_out, hr_out, B, lr_patch, scale, quant_bits,
+                                          (hipStream_t)stream);
+}
+
+int srk_degrade_blind_f32(const float* x, float* out, const int64_t* par4, int B, int C, int H, int W, int scale, int quant_bits,
+                          srk_stream_t stream) {
+  REQ_PTR(x); REQ_PTR(out); REQ_PTR(par4);
+  SRK_REQUIRE(B >= 1 && C >= 1 && H >= 1 && W >= 1, SRK_E_SHAPE, "degrade_blind: B=%d C=%d H=%d W=%d must all be >= 1", B, C, H, W);
+  SRK_REQUIRE(scale >= 2 && scale <= 4 && H % scale == 0 && W % scale == 0, SRK_E_SHAPE,
+              "degrade_blind: scale=%d must be in 2..4 and divide H=%d and W=%d", scale, H, W);
+  SRK_REQUIRE(quant_bits == 0 || quant_bits == 8, SRK_E_SHAPE, "degrade_blind: quant_bits must be 0 or 8 (got %d)", quant_bits);
+  const double planes = (double)B * C, ib = 4.0 * planes * H * W, ob = ib / ((double)scale * scale);
+  SRK_REQUIRE(planes <= 2147483647.0 && ib < 9.0e18, SRK_E_SHAPE, "degrade_blind: B=%d C=%d H=%d W=%d is too large", B, C, H, W);
+  const uintptr_t a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(out);
+  SRK_REQUIRE(a + (uintptr_t)ib <= b || b + (uintptr_t)ob <= a, SRK_E_SHAPE, "degrade_blind: x and out overlap (the filter is not run in place)");
+  return srk_launch_degrade_blind_f32(x, out, reinterpret_cast<const long long*>(par4), B, C, H, W, scale, quant_bits, (hipStream_t)stream);
+}
+
 // the checks srk_tile_gather_f32 and srk_tile_merge_f32 share; img is x or out, whichever the tiles must not overlap
 static int tile_args(const char* fn, const float* tiles, const float* img, int t0, int n, int B, int C, int H, int W, int th, int tw,
                      int sy, int sx, TileAxis* ay, TileAxis* ax) {

@@ -63,6 +63,12 @@ int srk_launch_dihedral_f32(const float* in, float* out, const int* ops, int op_
 int srk_launch_resize_aa_f32(const float* x, float* out, int planes, int H, int W, int Ho, int Wo, int quant_bits, hipStream_t stream);
 int srk_launch_crop_degrade_u8(const unsigned char* pool, const long long* desc, float* lr_out, float* hr_out, int B, int P, int scale,
                                int quant_bits, hipStream_t stream);
+// degrade.hip: the same two behind a per-sample Gaussian blur and with per-sample noise (arguments checked by srk_degrade_blind_f32 /
+// srk_crop_degrade_blind_u8)
+int srk_launch_degrade_blind_f32(const float* x, float* out, const long long* par, int B, int C, int H, int W, int scale, int quant_bits,
+                                 hipStream_t stream);
+int srk_launch_crop_degrade_blind_u8(const unsigned char* pool, const long long* desc, float* lr_out, float* hr_out, int B, int P, int scale,
+                                     int quant_bits, hipStream_t stream);
 // tile.hip: tiled inference (arguments checked by srk_tile_gather_f32 / srk_tile_merge_f32).  One axis of the tile grid: extent n,
 // tile t (1 <= t <= n), stride s (1 <= s <= t), k = ceil((n - t) / s) + 1 tiles, origin o_i = min(i * s, n - t)
 struct TileAxis { int n, t, s, k; };

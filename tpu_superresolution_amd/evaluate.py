@@ -14,7 +14,8 @@ Additive: ``--arch swinir | hat | dat`` evaluates the MI355X SwinIR / HAT / DAT 
 GPU + libsrk); ``--self_ensemble`` averages the eight flipped / rotated predictions (any --arch); ``--tile N`` predicts on overlapping
 N x N tiles of the model's input and merges them (tiling.tiled_forward; any --arch; inside the self-ensemble when both are given);
 ``--synth_lr [--synth_lr_bits 0|8]`` (--arch swinir | hat | dat) needs only the HR directory of the test split: LR is its antialiased
-bicubic downscale, formed on the device (ops.resize_aa); ``main(argv)`` is callable from tests.  SSIM is ``metrics.ssim`` (restated, parity unpinned).
+bicubic downscale, formed on the device (ops.resize_aa), with ``--degrade blind --blur_sigma SY SX --noise_sigma N --noise_gain G`` blurred and
+noised there with fixed parameters (ops.degrade_blind); ``main(argv)`` is callable from tests.  SSIM is ``metrics.ssim`` (restated, parity unpinned).
 """
 from __future__ import annotations
 
@@ -102,9 +103,24 @@ def parse_args(argv=None):
                          "bicubic (PIL BICUBIC convention) downscale, formed on the device (ops.resize_aa)")
     ap.add_argument("--synth_lr_bits", type=int, choices=[0, 8], default=8,
                     help="additive, with --synth_lr: 8 = LR rounded to k / 255 as an 8-bit LR file would hold it, 0 = the filtered values")
+    ap.add_argument("--degrade", type=str, choices=["bicubic", "blind"], default="bicubic",
+                    help="additive, with --synth_lr: blind = LR is blurred and noised with the fixed parameters below (ops.degrade_blind; "
+                         "the noise id of an image is its index in the split)")
+    ap.add_argument("--blur_sigma", type=float, nargs=2, default=[1.1, 1.1], metavar=("SY", "SX"),
+                    help="additive, with --degrade blind: sigma of the Gaussian blur in HR pixels along y and x, within [0, 2.5]")
+    ap.add_argument("--noise_sigma", type=float, default=5.0, help="additive, with --degrade blind: noise sigma in 8-bit levels")
+    ap.add_argument("--noise_gain", type=float, default=0.0, help="additive, with --degrade blind: gain of the signal-dependent noise")
     args = ap.parse_args(argv)
     if args.synth_lr and args.arch == "ms_resunet":
         ap.error("--synth_lr is an option of --arch swinir | hat | dat (MS_ResUNet takes the pre-upscaled LR of the eval transform)")
+    if args.degrade == "blind":
+        if not args.synth_lr:
+            ap.error("--degrade blind degrades the HR images on the device: it needs --synth_lr")
+        try:
+            from .ops import pack_degrade_params
+            pack_degrade_params(args.blur_sigma, (args.noise_sigma / 255.0, args.noise_gain), 0, False)
+        except ValueError as e:
+            ap.error(f"--degrade blind: {e}")
     if args.tile < 0 or args.tile_batch < 1 or args.tile_overlap < 0 or (args.tile and args.tile_overlap >= args.tile):
         ap.error(f"--tile must be >= 0, --tile_batch >= 1 and 0 <= --tile_overlap < --tile (got --tile {args.tile} "
                  f"--tile_overlap {args.tile_overlap} --tile_batch {args.tile_batch})")
@@ -136,8 +152,15 @@ def main(argv=None):
     test_loader = DataLoader(test_ds, batch_size=args.batch_size, shuffle=False, num_workers=args.workers,
                              pin_memory=(device.type == "cuda"), persistent_workers=False)
     if args.synth_lr:          # (lr, hr) batches formed on the device, before the peek, the baseline and the prediction loop
-        test_loader = SynthLRBatches(test_loader, scale_int, args.synth_lr_bits, device)
+        fixed = None
+        if args.degrade == "blind":
+            from .sr_datasets import FixedDegrade
+            fixed = FixedDegrade(tuple(args.blur_sigma), (args.noise_sigma / 255.0, args.noise_gain))
+        test_loader = SynthLRBatches(test_loader, scale_int, args.synth_lr_bits, device, degrade=fixed)
         print(f"[synth_lr] LR = antialiased bicubic /{scale_int} of HR on the device, {args.synth_lr_bits or 'no'}-bit rounding")
+        if fixed is not None:
+            print(f"[degrade] blind: blur sigma=({fixed.blur[0]:.4g}, {fixed.blur[1]:.4g}) HR px, noise sigma={args.noise_sigma:.4g} / 255 "
+                  f"gain={args.noise_gain:.4g}, noise id = image index")
     print(f"[data] test samples: {len(test_ds)} | steps: {len(test_loader)}")
 
     def upscaled(lr, hr):

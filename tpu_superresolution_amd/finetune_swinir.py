@@ -15,6 +15,8 @@ csrc/loss.hip (training.make_loss); with W > 0 validation also reports the mean 
 `--val_tile N` (default 0 = whole images) validates on overlapping N x N LR tiles merged on the device (tiling.tiled_forward).
 `--gpu_data --synth_lr [--synth_lr_bits 0|8]` trains and validates from the HR directories alone: every LR patch is the antialiased
 bicubic downscale of its HR image, made on the device (sr_datasets.DeviceHRPool, csrc/resize.hip); no LR directory is read.
+`--degrade blind [--blur_sigma LO HI --noise_sigma LO HI ...]` blurs and noises every such patch with random parameters in the same
+launch (csrc/degrade.hip); validation uses the midpoints of the ranges and the same noise every epoch.
 
 Also additive: `--arch hat|dat` fine-tunes HAT / DAT (build_sr_model) through the same loop -- the fused, device-gated clip + AdamW step
 over their parameter lists (optim.FusedAdamW, csrc/optim_multi.hip), checkpoints "best_<arch>_finetune_<scale>.pt" /
@@ -247,9 +249,32 @@ def parse_args(argv=None):
     ap.add_argument("--synth_lr_bits", type=int, choices=[0, 8], default=8,
                     help="additive, with --synth_lr: 8 = round the LR values to k / 255, as an 8-bit LR file would hold them; 0 = keep "
                          "the filtered fp32 values")
+    ap.add_argument("--degrade", type=str, choices=["bicubic", "blind"], default="bicubic",
+                    help="additive, with --synth_lr: blind = every LR training patch is blurred (Gaussian, composed into the bicubic "
+                         "taps) and noised with random per-sample parameters on the device (sr_datasets.DegradeSpec, csrc/degrade.hip); "
+                         "validation uses the midpoints of the ranges and fixed noise, the same LR images every epoch")
+    ap.add_argument("--blur_sigma", type=float, nargs=2, default=[0.2, 2.0], metavar=("LO", "HI"),
+                    help="additive, with --degrade blind: range of the blur sigma in HR pixels, within [0, 2.5]")
+    ap.add_argument("--blur_aniso_p", type=float, default=0.5,
+                    help="additive, with --degrade blind: probability of an independent sigma_x (otherwise sigma_x = sigma_y)")
+    ap.add_argument("--noise_sigma", type=float, nargs=2, default=[0.0, 10.0], metavar=("LO", "HI"),
+                    help="additive, with --degrade blind: range of the signal-independent noise sigma in 8-bit levels (divided by 255)")
+    ap.add_argument("--noise_gain", type=float, nargs=2, default=[0.0, 0.0], metavar=("LO", "HI"),
+                    help="additive, with --degrade blind: range of the gain of the signal-dependent (Poisson-like) noise variance gain * v")
+    ap.add_argument("--gray_noise_p", type=float, default=0.4,
+                    help="additive, with --degrade blind: probability that a colour image gets one noise draw for its three channels")
+    ap.add_argument("--degrade_seed", type=int, default=0,
+                    help="additive, with --degrade blind: seed of the degradation parameters' own generator (+ rank)")
     args = ap.parse_args(argv)
     if args.synth_lr and not args.gpu_data:
         ap.error("--synth_lr forms the LR patches on the device: it needs --gpu_data")
+    if args.degrade == "blind":
+        if not args.synth_lr:
+            ap.error("--degrade blind degrades HR patches on the device: it needs --synth_lr")
+        try:
+            degrade_spec(args)
+        except ValueError as e:
+            ap.error(f"--degrade blind: {e}")
     if args.val_tile < 0 or args.val_tile_overlap < 0 or (args.val_tile and args.val_tile_overlap >= args.val_tile):
         ap.error(f"--val_tile must be >= 0 and 0 <= --val_tile_overlap < --val_tile (got --val_tile {args.val_tile} "
                  f"--val_tile_overlap {args.val_tile_overlap})")
@@ -270,6 +295,15 @@ def parse_args(argv=None):
         ap.error("--graph captures the host-orchestrated train step of --arch hat / dat and of --arch swinir --window_size 2..7 "
                  "(the window-8 SwinIR step is one C call already)")
     return args
+
+
+def degrade_spec(args):
+    """The DegradeSpec of the command line (None for --degrade bicubic); --noise_sigma is given in 8-bit levels."""
+    if args.degrade != "blind":
+        return None
+    from .sr_datasets import DegradeSpec
+    return DegradeSpec(blur_sigma=tuple(args.blur_sigma), blur_aniso_p=args.blur_aniso_p, noise_sigma=tuple(v / 255.0 for v in args.noise_sigma),
+                       noise_gain=tuple(args.noise_gain), gray_noise_p=args.gray_noise_p, seed=args.degrade_seed)
 
 
 def main(argv=None):
@@ -293,12 +327,19 @@ def main(argv=None):
         from .sr_datasets import DeviceHRPool, Shuffled2DHR, SynthLRBatches, hr_to_tensor3
         raw = Shuffled2DHR(args.data_root, split="train")
         pool = DeviceHRPool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, device=device,
-                            shard_bytes=(args.gpu_data_shard_mb << 20) or None, augment=args.augment, quant_bits=args.synth_lr_bits)
+                            shard_bytes=(args.gpu_data_shard_mb << 20) or None, augment=args.augment, quant_bits=args.synth_lr_bits,
+                            degrade=degrade_spec(args), rank=rank)
         train_loader = sampler = DevicePoolLoader(pool, args.batch_size, rank, world, args.seed)
         valid_ds = Shuffled2DHR(args.data_root, split="valid", transform=hr_to_tensor3)
         if rank == 0:
             print(f"[synth_lr] {len(pool)} HR images in {pool.num_shards} shard(s), {sum(t.numel() for t in pool._host) / 2**20:.1f} MiB "
                   f"decoded; LR = antialiased bicubic /{scale_int} on the device, {args.synth_lr_bits or 'no'}-bit rounding")
+            if args.degrade == "blind":
+                fx = degrade_spec(args).fixed()
+                print(f"[degrade] blind: blur sigma in {args.blur_sigma} HR px (aniso p={args.blur_aniso_p}), noise sigma in "
+                      f"{args.noise_sigma} / 255, gain in {args.noise_gain}, gray p={args.gray_noise_p}, seed {args.degrade_seed}; "
+                      f"validation: sigma=({fx.blur[0]:.4g}, {fx.blur[1]:.4g}) noise sigma={fx.noise[0] * 255.0:.4g} / 255 "
+                      f"gain={fx.noise[1]:.4g}, noise id = image index")
     else:
         train_ds = Shuffled2DPaired(args.data_root, split="train", scale=args.scale,
                                     transform_pair=PairTransformTrain(args.lr_patch, scale_int, args.augment))
@@ -317,7 +358,7 @@ def main(argv=None):
     valid_loader = make_loader(valid_ds, max(1, args.batch_size // 2), args.workers, pin=not args.no_pin, shuffle=False,
                                drop_last=False, persistent=not args.no_persistent)
     if args.synth_lr:
-        valid_loader = SynthLRBatches(valid_loader, scale_int, args.synth_lr_bits, device)
+        valid_loader = SynthLRBatches(valid_loader, scale_int, args.synth_lr_bits, device, degrade=degrade_spec(args))
 
     model = (build_model(scale_int, args.drop_path_rate, args.window_size) if args.arch == "swinir" else
              build_sr_model(args.arch, scale_int, args.drop_path_rate))
@@ -418,7 +459,11 @@ def main(argv=None):
         at_default = {"ema_decay": not args.ema_decay, "loss": args.loss == "l1", "charbonnier_eps": args.charbonnier_eps == 1e-3,
                       "ssim_weight": args.ssim_weight == 0, "val_tile": args.val_tile == 0,
                       "val_tile_overlap": args.val_tile == 0 or args.val_tile_overlap == 32, "synth_lr": not args.synth_lr,
-                      "synth_lr_bits": not args.synth_lr or args.synth_lr_bits == 8}          # additive flags leave no trace in the files at their defaults
+                      "synth_lr_bits": not args.synth_lr or args.synth_lr_bits == 8, "degrade": args.degrade == "bicubic",
+                      "blur_sigma": args.blur_sigma == [0.2, 2.0], "blur_aniso_p": args.blur_aniso_p == 0.5,
+                      "noise_sigma": args.noise_sigma == [0.0, 10.0], "noise_gain": args.noise_gain == [0.0, 0.0],
+                      "gray_noise_p": args.gray_noise_p == 0.4,
+                      "degrade_seed": args.degrade_seed == 0}          # additive flags leave no trace in the files at their defaults
         saved_args = {k: v for k, v in vars(args).items() if not at_default.get(k, False)}
         if val_loss < best_loss:
             best_loss = val_loss

@@ -7,6 +7,7 @@ missing library raises.
 from __future__ import annotations
 
 import ctypes as C
+import struct
 from typing import Optional, Tuple
 
 import threading
@@ -552,3 +553,63 @@ def degrade_aa(hr: torch.Tensor, scale: int, quant_bits: int = 8) -> Tuple[torch
     s = int(scale)
     hr = hr[..., :H - H % s, :W - W % s].float().contiguous()
     return resize_aa(hr, (H // s, W // s), quant_bits), hr
+
+
+BLUR_SIGMA_MAX = 2.5          # R = ceil(3 sigma) <= 8 taps on either side: what the 33-tap rows of csrc/resize.h hold at factors 2..4
+
+
+def _f32_bits(v: float) -> int:
+    return struct.unpack("<I", struct.pack("<f", v))[0]
+
+
+def pack_degrade_params(blur, noise, noise_id: int, gray_noise: bool):
+    """Slots 6..9 of a `srk_crop_degrade_blind_u8` descriptor / one row of `srk_degrade_blind_f32`'s table, as four signed 64-bit
+    integers: fp32 bits of (sigma_y | sigma_x << 32), of (sigma_n | gain << 32), the noise id, the flags (bit 0 = gray noise).
+    The one place that packs them; the ranges are checked here: sigmas in [0, 2.5] HR pixels, sigma_n and gain in [0, 1]."""
+    (sy, sx), (sn, gain) = (float(v) for v in blur), (float(v) for v in noise)
+    if not (0.0 <= sy <= BLUR_SIGMA_MAX and 0.0 <= sx <= BLUR_SIGMA_MAX):          # also refuses NaN
+        raise ValueError(f"blur sigmas must be in [0, {BLUR_SIGMA_MAX}] HR pixels (got {(sy, sx)})")
+    if not (0.0 <= sn <= 1.0 and 0.0 <= gain <= 1.0):
+        raise ValueError(f"noise sigma and gain must be in [0, 1] (got {(sn, gain)})")
+    noise_id = int(noise_id)
+    if not -(1 << 63) <= noise_id < (1 << 64):
+        raise ValueError(f"noise id must fit 64 bits (got {noise_id})")
+    signed = lambda v: v - (1 << 64) if v >> 63 else v          # noqa: E731
+    return [signed(_f32_bits(sy) | _f32_bits(sx) << 32), signed(_f32_bits(sn) | _f32_bits(gain) << 32),
+            signed(noise_id & 0xFFFFFFFFFFFFFFFF), int(bool(gray_noise))]
+
+
+def _per_sample(v, B: int, width: int, what: str):
+    rows = [list(r) for r in v] if (len(v) and hasattr(v[0], "__len__")) else [list(v)] * B
+    if len(rows) != B or any(len(r) != width for r in rows):
+        raise ValueError(f"degrade_blind: {what} must be {width} numbers or one such row per sample (B={B}; got {v!r})")
+    return rows
+
+
+def degrade_blind(hr: torch.Tensor, scale: int, blur, noise, noise_ids, gray_noise=False, quant_bits: int = 8) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(lr, hr_cropped) like `degrade_aa`, with a Gaussian blur (sigma_y, sigma_x) in HR pixels composed into the bicubic tables and
+    noise `v + sqrt(sigma_n^2 + gain max(v, 0)) z` added before the rounding (csrc/degrade.hip, srk_degrade_blind_f32): what
+    DeviceHRPool's blind training patches are windows of.  blur = (sigma_y, sigma_x) and noise = (sigma_n, gain): one pair or one per
+    sample; noise_ids: B integers (the Philox key; the same id and coordinates give the same draw); gray_noise: a bool or B of them --
+    one draw for all channels (always so for C == 1).  hr [B,C,H,W] is cropped to a multiple of the factor (2..4).  One launch after one
+    small upload; sigmas and amplitudes out of range raise ValueError."""
+    if hr.dim() != 4 or not hr.is_cuda:
+        raise ValueError(f"degrade_blind takes a CUDA [B,C,H,W] batch (got {tuple(hr.shape)} on {hr.device})")
+    s = int(scale)
+    if not 2 <= s <= 4:
+        raise ValueError(f"degrade_blind: the factor must be in 2..4 (got {scale!r})")
+    if quant_bits not in (0, 8):
+        raise ValueError(f"degrade_blind: quant_bits must be 0 or 8 (got {quant_bits!r})")
+    B, Cc, H, W = hr.shape
+    if H < s or W < s or B < 1 or Cc < 1:
+        raise ValueError(f"degrade_blind: {tuple(hr.shape)} is smaller than one output pixel at factor {s}")
+    ids = [int(v) for v in noise_ids]
+    grays = [bool(gray_noise)] * B if isinstance(gray_noise, (bool, int)) else [bool(v) for v in gray_noise]
+    if len(ids) != B or len(grays) != B:
+        raise ValueError(f"degrade_blind: one noise id and one gray flag per sample (B={B}; got {len(ids)} ids, {len(grays)} flags)")
+    rows = [pack_degrade_params(b, n, i, g) for b, n, i, g in zip(_per_sample(blur, B, 2, "blur"), _per_sample(noise, B, 2, "noise"), ids, grays)]
+    hr = hr[..., :H - H % s, :W - W % s].float().contiguous()
+    par = torch.tensor(rows, dtype=torch.int64).to(hr.device)
+    lr = torch.empty(B, Cc, H // s, W // s, dtype=torch.float32, device=hr.device)
+    check(lib().srk_degrade_blind_f32(_p(hr), _p(lr), _p(par), B, Cc, H - H % s, W - W % s, s, int(quant_bits), _stream()))
+    return lr, hr

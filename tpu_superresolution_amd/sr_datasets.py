@@ -9,8 +9,9 @@ from __future__ import annotations
 
 import random
 import re
+from dataclasses import dataclass
 from pathlib import Path
-from typing import Callable, Optional, Tuple
+from typing import Callable, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -306,6 +307,64 @@ class DevicePairPool(_DeviceImagePool):
         return lr, hr
 
 
+class FixedDegrade(NamedTuple):
+    """One fixed blind degradation (validation, evaluation): blur = (sigma_y, sigma_x) in HR pixels, noise = (sigma_n, gain) in [0, 1]
+    units, gray_noise = one draw for the three channels of a colour image (a gray image always gets one)."""
+    blur: Tuple[float, float]
+    noise: Tuple[float, float]
+    gray_noise: bool = False
+
+
+def _check_range(name: str, r, hi: float) -> Tuple[float, float]:
+    try:
+        a, b = (float(v) for v in r)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be two numbers LO HI (got {r!r})") from None
+    if not 0.0 <= a <= b <= hi:          # also refuses NaN
+        raise ValueError(f"{name} must satisfy 0 <= LO <= HI <= {hi:g} (got {a} {b})")
+    return a, b
+
+
+@dataclass(frozen=True)
+class DegradeSpec:
+    """The random first-order degradation of `--degrade blind`: per training sample a Gaussian blur with sigma_y uniform in
+    `blur_sigma` HR pixels and, with probability `blur_aniso_p`, an independent sigma_x (else sigma_x = sigma_y); noise
+    `sqrt(sigma_n^2 + gain v) z` with sigma_n uniform in `noise_sigma` and gain uniform in `noise_gain` (image units, [0, 1]); for a
+    colour image one draw for all channels with probability `gray_noise_p`; a 64-bit noise id.  Everything comes from the spec's OWN
+    generator `random.Random(seed + rank)`: the global `random` state, which places the crops, never sees it."""
+    blur_sigma: Tuple[float, float] = (0.2, 2.0)
+    blur_aniso_p: float = 0.5
+    noise_sigma: Tuple[float, float] = (0.0, 10.0 / 255.0)
+    noise_gain: Tuple[float, float] = (0.0, 0.0)
+    gray_noise_p: float = 0.4
+    seed: int = 0
+
+    def __post_init__(self):
+        from .ops import BLUR_SIGMA_MAX
+        object.__setattr__(self, "blur_sigma", _check_range("blur_sigma", self.blur_sigma, BLUR_SIGMA_MAX))
+        object.__setattr__(self, "noise_sigma", _check_range("noise_sigma", self.noise_sigma, 1.0))
+        object.__setattr__(self, "noise_gain", _check_range("noise_gain", self.noise_gain, 1.0))
+        for name in ("blur_aniso_p", "gray_noise_p"):
+            if not 0.0 <= float(getattr(self, name)) <= 1.0:
+                raise ValueError(f"{name} must be a probability (got {getattr(self, name)!r})")
+
+    def rng(self, rank: int = 0) -> random.Random:
+        return random.Random(int(self.seed) + int(rank))
+
+    def draw(self, rng: random.Random, colour: bool):
+        """-> (blur, noise, noise_id, gray_noise) of one sample; always the same seven variates, whatever they decide."""
+        sy, sx = rng.uniform(*self.blur_sigma), rng.uniform(*self.blur_sigma)
+        aniso = rng.random() < self.blur_aniso_p
+        noise = (rng.uniform(*self.noise_sigma), rng.uniform(*self.noise_gain))
+        gray = rng.random() < self.gray_noise_p
+        return (sy, sx if aniso else sy), noise, rng.getrandbits(64), gray or not colour
+
+    def fixed(self) -> FixedDegrade:
+        """The midpoints of the ranges: what validation scores, every epoch and every run."""
+        mid = lambda r: 0.5 * (r[0] + r[1])          # noqa: E731
+        return FixedDegrade((mid(self.blur_sigma),) * 2, (mid(self.noise_sigma), mid(self.noise_gain)), self.gray_noise_p >= 0.5)
+
+
 class DeviceHRPool(_DeviceImagePool):
     """Training pairs from HR images only (`--synth_lr`): the pool holds the decoded HR images -- half the device memory of a
     DevicePairPool at x2, no LR files to keep in sync -- and `sample` makes the HR patch AND its antialiased bicubic degradation
@@ -315,10 +374,14 @@ class DeviceHRPool(_DeviceImagePool):
     Same surface as DevicePairPool (shards, prefetch, augment), and `sample` draws `random.randint(0, H // s - P)`,
     `random.randint(0, W // s - P)` and the D4 code per sample -- DevicePairPool's order and ranges, so from one `random` state
     both pools cut the same HR patches.  ``quant_bits`` 8 (default): LR values are rounded to k / 255 as an 8-bit LR file would hold
-    them; 0: the filtered fp32 values."""
+    them; 0: the filtered fp32 values.
+
+    ``degrade`` (a DegradeSpec; None = the clean downscale, today's launch): every sample is blurred and noised with parameters drawn
+    from the spec's own generator (seed + ``rank``), in one `srk_crop_degrade_blind_u8` launch on ten-slot descriptors.  `draw`, and
+    with it the global `random` state, the HR patches and the D4 codes, is the same with and without a spec."""
 
     def __init__(self, images, lr_patch: int, scale: int, device="cuda", shard_bytes: Optional[int] = None, augment: str = "none",
-                 quant_bits: int = 8):
+                 quant_bits: int = 8, degrade: Optional[DegradeSpec] = None, rank: int = 0):
         """images: iterable of HR PIL images or uint8 / uint16 arrays [H,W] / [H,W,1|3]."""
         if augment not in AUGMENT_MODES:
             raise ValueError(f"augment must be one of {AUGMENT_MODES} (got {augment!r})")
@@ -326,7 +389,10 @@ class DeviceHRPool(_DeviceImagePool):
             raise ValueError(f"quant_bits must be 0 or 8 (got {quant_bits!r})")
         if not 2 <= int(scale) <= 4:
             raise ValueError(f"DeviceHRPool degrades by an integer factor in 2..4 (got {scale!r})")
+        if degrade is not None and not isinstance(degrade, DegradeSpec):
+            raise ValueError(f"degrade must be a DegradeSpec or None (got {type(degrade).__name__})")
         self.augment, self.quant_bits = augment, int(quant_bits)
+        self.degrade, self._degrade_rng = degrade, (degrade.rng(rank) if degrade is not None else None)
         self.lr_patch, self.scale, self.device = int(lr_patch), int(scale), torch.device(device)
         self._pack(((img,) for img in images), shard_bytes)
 
@@ -346,6 +412,12 @@ class DeviceHRPool(_DeviceImagePool):
             codes.append(draw_op(self.augment))
         return hd, codes
 
+    def draw_degrade(self, hd):
+        """The ten-slot descriptors of a batch: `draw`'s six plus the packed parameters of one `DegradeSpec.draw` per sample, from the
+        spec's generator alone (the global `random` state is not touched)."""
+        from .ops import pack_degrade_params
+        return [tuple(d) + tuple(pack_degrade_params(*self.degrade.draw(self._degrade_rng, colour=(d[3] & 0xff) == 3))) for d in hd]
+
     def sample(self, indices):
         """-> (lr [B,3,P,P], hr [B,3,P*s,P*s]) fp32 on the device."""
         from ._lib import check, lib
@@ -353,11 +425,12 @@ class DeviceHRPool(_DeviceImagePool):
         pool = self._batch_pool(indices)
         hd, codes = self.draw(indices)
         B = len(hd)
-        desc = torch.tensor(hd, dtype=torch.int64).to(self.device)
+        desc = torch.tensor(hd if self.degrade is None else self.draw_degrade(hd), dtype=torch.int64).to(self.device)
         lr = torch.empty(B, 3, P, P, dtype=torch.float32, device=self.device)
         hr = torch.empty(B, 3, P * s, P * s, dtype=torch.float32, device=self.device)
         st = torch.cuda.current_stream(self.device).cuda_stream
-        check(lib().srk_crop_degrade_u8(pool.data_ptr(), desc.data_ptr(), lr.data_ptr(), hr.data_ptr(), B, P, s, self.quant_bits, st))
+        entry = lib().srk_crop_degrade_u8 if self.degrade is None else lib().srk_crop_degrade_blind_u8
+        check(entry(pool.data_ptr(), desc.data_ptr(), lr.data_ptr(), hr.data_ptr(), B, P, s, self.quant_bits, st))
         if any(codes):
             from .augment import dihedral
             ops = torch.tensor(codes, dtype=torch.int32).to(self.device)
@@ -368,15 +441,33 @@ class DeviceHRPool(_DeviceImagePool):
 class SynthLRBatches:
     """Wraps a loader of HR batches [B,3,H,W] into the (lr, hr) batches of `--synth_lr` validation / evaluation: each HR batch goes to
     the device, is cropped to a multiple of the factor and degraded there (ops.degrade_aa) -- the whole-image form of what
-    DeviceHRPool's training patches are windows of."""
+    DeviceHRPool's training patches are windows of.
 
-    def __init__(self, loader, scale: int, quant_bits: int, device):
+    ``degrade`` (a FixedDegrade, or a DegradeSpec standing for its `fixed()` midpoints; None = the clean downscale): every image gets
+    the SAME blur and noise amplitudes and the noise id = its index in the split (the loader must not shuffle), so every epoch and
+    every run scores the same LR images (ops.degrade_blind).  An image whose three channels are equal gets gray noise."""
+
+    def __init__(self, loader, scale: int, quant_bits: int, device, degrade=None):
         self.loader, self.scale, self.quant_bits, self.device = loader, int(scale), int(quant_bits), torch.device(device)
+        self.degrade = degrade.fixed() if isinstance(degrade, DegradeSpec) else degrade
+        if self.degrade is not None:
+            from .ops import pack_degrade_params
+            pack_degrade_params(self.degrade.blur, self.degrade.noise, 0, self.degrade.gray_noise)          # the ranges, before any batch
 
     def __len__(self):
         return len(self.loader)
 
     def __iter__(self):
-        from .ops import degrade_aa
+        from .ops import degrade_aa, degrade_blind
+        first = 0
         for hr in self.loader:
-            yield degrade_aa(hr.to(self.device, dtype=torch.float32), self.scale, self.quant_bits)
+            hr = hr.to(self.device, dtype=torch.float32)
+            if self.degrade is None:
+                yield degrade_aa(hr, self.scale, self.quant_bits)
+                continue
+            B = hr.shape[0]
+            gray = [True] * B
+            if hr.shape[1] == 3 and not self.degrade.gray_noise:
+                gray = ((hr[:, 0] == hr[:, 1]) & (hr[:, 0] == hr[:, 2])).flatten(1).all(dim=1).tolist()
+            yield degrade_blind(hr, self.scale, self.degrade.blur, self.degrade.noise, range(first, first + B), gray, self.quant_bits)
+            first += B
