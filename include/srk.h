@@ -291,6 +291,39 @@ int srk_degrade_blind_f32(const float* x, float* out, const int64_t* par4, int B
  * channels.  Errors as srk_crop_degrade_u8. */
 int srk_crop_degrade_blind_u8(const uint8_t* pool, const int64_t* desc10, float* lr_out, float* hr_out, int B, int lr_patch, int scale,
                               int quant_bits, srk_stream_t stream);
+/* JPEG round trip (csrc/jpeg.hip): what a baseline JPEG file of an 8-bit image at quality q decodes to, as a closed-form fp32 pipeline.
+ * No entropy coding is done: it is lossless and changes nothing.  x, out fp32 [B][C][H][W], C = 1 or 3, H, W >= 1 (no multiple of 8
+ * needed); subsample 0 = 4:4:4, 1 = 4:2:0 (has effect only with C == 3); quality DEVICE int32 [B], each in 1..100, or 0 = sample b is
+ * passed through bit for bit, NaNs included.  The host checks the range; the kernel clamps any other bit pattern into 0..100.
+ * Per sample, every operation in fp32 without contraction:
+ *  1. Level.  p = rintf(fminf(fmaxf(v, 0), 1) * 255); NaN gives 0, k / 255.0f gives k: the stage composes with the 8-bit forms of
+ *     srk_crop_degrade_u8 and srk_crop_degrade_blind_u8.
+ *  2. Colour (C == 3), JFIF full range, each result rintf-ed and clamped to 0..255 as an encoder's 8-bit component planes are:
+ *       Y  = fmaf(0.114f, B, fmaf(0.587f, G, 0.299f * R))
+ *       Cb = fmaf(0.5f, B, fmaf(-0.331264108f, G, fmaf(-0.168735892f, R, 128)))
+ *       Cr = fmaf(-0.081312411f, B, fmaf(-0.418687589f, G, fmaf(0.5f, R, 128)))
+ *     With C == 1 the plane is Y.
+ *  3. Grid.  8 x 8 blocks anchored at (0, 0); the MCU is 8 x 8, or 16 x 16 with subsample.  The plane is extended to a whole number
+ *     of MCUs by replicating its last row and column (libjpeg's edge rule); results outside H x W are dropped.  With subsample a
+ *     chroma sample is the unrounded mean (a + b + c + d) * 0.25f of its 2 x 2 cell (exact in fp32).
+ *  4. Forward DCT.  Subtract 128.  D[u][k] = 1/2 c_u cos((2k + 1) u pi / 16), c_0 = 1/sqrt(2), evaluated in fp64 and rounded once to
+ *     fp32.  Horizontal pass, then vertical pass, each an ascending-k chain acc = fmaf(D[u][k], x[k], acc) from 0.
+ *  5. Quantisation.  ITU-T T.81 Annex K table K.1 for Y, K.2 for Cb and Cr, natural order, scaled the libjpeg way:
+ *     s = q < 50 ? 5000 / q : 200 - 2 q, Q = clamp((base * s + 50) / 100, 1, 255) in integers; k = rintf(c / Q) with IEEE division;
+ *     c' = k * Q (exact).
+ *  6. Inverse.  Vertical pass, then horizontal pass, acc = fmaf(D[k][y], c'[k], acc) from 0; add 128; each component is
+ *     fminf(fmaxf(rintf(.), 0), 255).  Chroma is upsampled by replication (not libjpeg's "fancy" triangle filter).
+ *  7. Back to RGB with cb = Cb - 128, cr = Cr - 128, each rintf-ed and clamped to 0..255, out = level / 255.0f:
+ *       R = fmaf(1.402f, cr, Y)    G = fmaf(-0.714136286f, cr, fmaf(-0.344136286f, cb, Y))    B = fmaf(1.772f, cb, Y)
+ *     With C == 1, out = Y / 255.0f.
+ * coef_out (a test port; production callers pass NULL): the quantised coefficients k as int16 [B][C][Hm][Wm], Hm, Wm = H, W rounded
+ * up to the MCU, natural order in place: coefficient (u, v) of block (by, bx) at row 8 by + u, column 8 bx + v.  With subsample a
+ * chroma plane fills only its top-left [Hm / 2][Wm / 2]; the rest is not written, and neither is anything of a sample with quality 0.
+ * One launch, no device allocation; nothing outside out[0 .. B C H W) and the stated part of coef_out is written.
+ * SRK_E_NULL: null x, out or quality; SRK_E_SHAPE: a non-positive extent, C not 1 or 3, subsample not 0 or 1, x and out overlapping, a
+ * size that does not fit one launch. */
+int srk_jpeg_roundtrip_f32(const float* x, float* out, const int32_t* quality, int B, int C, int H, int W, int subsample, int16_t* coef_out,
+                           srk_stream_t stream);
 /* Tiled inference (csrc/tile.hip): crop a chunk of overlapping tiles out of an fp32 NCHW batch, run a model on them as a batch of
  * n * B, and merge the chunk's outputs into the output image.
  * Tile grid, per axis with extent N, tile t (1 <= t <= N) and stride s (1 <= s <= t; overlap = t - s): k = ceil((N - t) / s) + 1

@@ -528,6 +528,20 @@ int srk_degrade_blind_f32(const float* x, float* out, const int64_t* par4, int B
   return srk_launch_degrade_blind_f32(x, out, reinterpret_cast<const long long*>(par4), B, C, H, W, scale, quant_bits, (hipStream_t)stream);
 }
 
+int srk_jpeg_roundtrip_f32(const float* x, float* out, const int32_t* quality, int B, int C, int H, int W, int subsample, int16_t* coef_out,
+                           srk_stream_t stream) {
+  REQ_PTR(x); REQ_PTR(out); REQ_PTR(quality);
+  SRK_REQUIRE(B >= 1 && H >= 1 && W >= 1, SRK_E_SHAPE, "jpeg_roundtrip: B=%d H=%d W=%d must all be >= 1", B, H, W);
+  SRK_REQUIRE(C == 1 || C == 3, SRK_E_SHAPE, "jpeg_roundtrip: C must be 1 or 3 (got %d)", C);
+  SRK_REQUIRE(subsample == 0 || subsample == 1, SRK_E_SHAPE, "jpeg_roundtrip: subsample must be 0 (4:4:4) or 1 (4:2:0) (got %d)", subsample);
+  const double bytes = 4.0 * B * C * H * W;
+  SRK_REQUIRE(bytes < 9.0e18, SRK_E_SHAPE, "jpeg_roundtrip: B=%d C=%d H=%d W=%d is too large", B, C, H, W);
+  const uintptr_t a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(out);
+  SRK_REQUIRE(a + (uintptr_t)bytes <= b || b + (uintptr_t)bytes <= a, SRK_E_SHAPE, "jpeg_roundtrip: x and out overlap (the blocks are not transformed in place)");
+  return srk_launch_jpeg_roundtrip_f32(x, out, reinterpret_cast<const int*>(quality), B, C, H, W, subsample, reinterpret_cast<short*>(coef_out),
+                                       (hipStream_t)stream);
+}
+
 // the checks srk_tile_gather_f32 and srk_tile_merge_f32 share; img is x or out, whichever the tiles must not overlap
 static int tile_args(const char* fn, const float* tiles, const float* img, int t0, int n, int B, int C, int H, int W, int th, int tw,
                      int sy, int sx, TileAxis* ay, TileAxis* ax) {

@@ -15,7 +15,8 @@ GPU + libsrk); ``--self_ensemble`` averages the eight flipped / rotated predicti
 N x N tiles of the model's input and merges them (tiling.tiled_forward; any --arch; inside the self-ensemble when both are given);
 ``--synth_lr [--synth_lr_bits 0|8]`` (--arch swinir | hat | dat) needs only the HR directory of the test split: LR is its antialiased
 bicubic downscale, formed on the device (ops.resize_aa), with ``--degrade blind --blur_sigma SY SX --noise_sigma N --noise_gain G`` blurred and
-noised there with fixed parameters (ops.degrade_blind); ``main(argv)`` is callable from tests.  SSIM is ``metrics.ssim`` (restated, parity unpinned).
+noised there with fixed parameters (ops.degrade_blind), with ``--jpeg_quality Q [--jpeg_subsample 444|420]`` then sent through a baseline
+JPEG round trip (ops.jpeg_roundtrip); ``main(argv)`` is callable from tests.  SSIM is ``metrics.ssim`` (restated, parity unpinned).
 """
 from __future__ import annotations
 
@@ -110,6 +111,11 @@ def parse_args(argv=None):
                     help="additive, with --degrade blind: sigma of the Gaussian blur in HR pixels along y and x, within [0, 2.5]")
     ap.add_argument("--noise_sigma", type=float, default=5.0, help="additive, with --degrade blind: noise sigma in 8-bit levels")
     ap.add_argument("--noise_gain", type=float, default=0.0, help="additive, with --degrade blind: gain of the signal-dependent noise")
+    ap.add_argument("--jpeg_quality", type=int, default=None, metavar="Q",
+                    help="additive, with --synth_lr --synth_lr_bits 8 (either --degrade): the LR image makes a round trip through baseline "
+                         "JPEG at quality Q in 1..100 on the device (ops.jpeg_roundtrip, csrc/jpeg.hip), before any tiling or self-ensemble")
+    ap.add_argument("--jpeg_subsample", type=str, choices=["444", "420"], default="444",
+                    help="additive, with --jpeg_quality: chroma at 4:4:4, or 4:2:0 (2 x 2 means, upsampled by replication)")
     args = ap.parse_args(argv)
     if args.synth_lr and args.arch == "ms_resunet":
         ap.error("--synth_lr is an option of --arch swinir | hat | dat (MS_ResUNet takes the pre-upscaled LR of the eval transform)")
@@ -121,6 +127,16 @@ def parse_args(argv=None):
             pack_degrade_params(args.blur_sigma, (args.noise_sigma / 255.0, args.noise_gain), 0, False)
         except ValueError as e:
             ap.error(f"--degrade blind: {e}")
+    if args.jpeg_quality is None:
+        if args.jpeg_subsample != "444":
+            ap.error("--jpeg_subsample is an option of the JPEG stage: it needs --jpeg_quality Q")
+    else:
+        if not args.synth_lr:
+            ap.error("--jpeg_quality codes the LR images formed on the device: it needs --synth_lr")
+        if args.synth_lr_bits != 8:
+            ap.error("--jpeg_quality codes 8-bit LR images: it needs --synth_lr_bits 8")
+        if not 1 <= args.jpeg_quality <= 100:
+            ap.error(f"--jpeg_quality must be in 1..100 (got {args.jpeg_quality})")
     if args.tile < 0 or args.tile_batch < 1 or args.tile_overlap < 0 or (args.tile and args.tile_overlap >= args.tile):
         ap.error(f"--tile must be >= 0, --tile_batch >= 1 and 0 <= --tile_overlap < --tile (got --tile {args.tile} "
                  f"--tile_overlap {args.tile_overlap} --tile_batch {args.tile_batch})")
@@ -156,11 +172,14 @@ def main(argv=None):
         if args.degrade == "blind":
             from .sr_datasets import FixedDegrade
             fixed = FixedDegrade(tuple(args.blur_sigma), (args.noise_sigma / 255.0, args.noise_gain))
-        test_loader = SynthLRBatches(test_loader, scale_int, args.synth_lr_bits, device, degrade=fixed)
+        test_loader = SynthLRBatches(test_loader, scale_int, args.synth_lr_bits, device, degrade=fixed, jpeg=args.jpeg_quality,
+                                     jpeg_subsample=args.jpeg_subsample == "420")
         print(f"[synth_lr] LR = antialiased bicubic /{scale_int} of HR on the device, {args.synth_lr_bits or 'no'}-bit rounding")
         if fixed is not None:
             print(f"[degrade] blind: blur sigma=({fixed.blur[0]:.4g}, {fixed.blur[1]:.4g}) HR px, noise sigma={args.noise_sigma:.4g} / 255 "
                   f"gain={args.noise_gain:.4g}, noise id = image index")
+        if args.jpeg_quality is not None:
+            print(f"[degrade] jpeg: quality {args.jpeg_quality}, chroma {args.jpeg_subsample}")
     print(f"[data] test samples: {len(test_ds)} | steps: {len(test_loader)}")
 
     def upscaled(lr, hr):

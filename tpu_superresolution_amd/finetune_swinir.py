@@ -17,6 +17,8 @@ csrc/loss.hip (training.make_loss); with W > 0 validation also reports the mean 
 bicubic downscale of its HR image, made on the device (sr_datasets.DeviceHRPool, csrc/resize.hip); no LR directory is read.
 `--degrade blind [--blur_sigma LO HI --noise_sigma LO HI ...]` blurs and noises every such patch with random parameters in the same
 launch (csrc/degrade.hip); validation uses the midpoints of the ranges and the same noise every epoch.
+`--jpeg_quality LO HI [--jpeg_p P --jpeg_subsample 444|420]` (with either --degrade) sends every 8-bit LR patch through a baseline JPEG
+round trip at a random per-sample quality in a second launch (csrc/jpeg.hip); validation uses the middle of the range.
 
 Also additive: `--arch hat|dat` fine-tunes HAT / DAT (build_sr_model) through the same loop -- the fused, device-gated clip + AdamW step
 over their parameter lists (optim.FusedAdamW, csrc/optim_multi.hip), checkpoints "best_<arch>_finetune_<scale>.pt" /
@@ -265,6 +267,14 @@ def parse_args(argv=None):
                     help="additive, with --degrade blind: probability that a colour image gets one noise draw for its three channels")
     ap.add_argument("--degrade_seed", type=int, default=0,
                     help="additive, with --degrade blind: seed of the degradation parameters' own generator (+ rank)")
+    ap.add_argument("--jpeg_quality", type=int, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="additive, with --synth_lr --synth_lr_bits 8 (either --degrade): every LR training patch makes a round trip through "
+                         "baseline JPEG on the device at a quality uniform in LO..HI (1..100; sr_datasets.JpegSpec, csrc/jpeg.hip; its own "
+                         "generator, seeded by --degrade_seed + rank); validation uses the middle of the range")
+    ap.add_argument("--jpeg_p", type=float, default=1.0,
+                    help="additive, with --jpeg_quality: probability that a training patch takes the JPEG stage (otherwise it passes through)")
+    ap.add_argument("--jpeg_subsample", type=str, choices=["444", "420"], default="444",
+                    help="additive, with --jpeg_quality: chroma at 4:4:4, or 4:2:0 (2 x 2 means, upsampled by replication)")
     args = ap.parse_args(argv)
     if args.synth_lr and not args.gpu_data:
         ap.error("--synth_lr forms the LR patches on the device: it needs --gpu_data")
@@ -275,6 +285,18 @@ def parse_args(argv=None):
             degrade_spec(args)
         except ValueError as e:
             ap.error(f"--degrade blind: {e}")
+    if args.jpeg_quality is None:
+        if args.jpeg_p != 1.0 or args.jpeg_subsample != "444":
+            ap.error("--jpeg_p and --jpeg_subsample are options of the JPEG stage: they need --jpeg_quality LO HI")
+    else:
+        if not (args.gpu_data and args.synth_lr):
+            ap.error("--jpeg_quality codes the LR patches formed on the device: it needs --gpu_data --synth_lr")
+        if args.synth_lr_bits != 8:
+            ap.error("--jpeg_quality codes 8-bit LR images: it needs --synth_lr_bits 8")
+        try:
+            jpeg_spec(args)
+        except ValueError as e:
+            ap.error(f"--jpeg_quality: {e}")
     if args.val_tile < 0 or args.val_tile_overlap < 0 or (args.val_tile and args.val_tile_overlap >= args.val_tile):
         ap.error(f"--val_tile must be >= 0 and 0 <= --val_tile_overlap < --val_tile (got --val_tile {args.val_tile} "
                  f"--val_tile_overlap {args.val_tile_overlap})")
@@ -306,6 +328,28 @@ def degrade_spec(args):
                        noise_gain=tuple(args.noise_gain), gray_noise_p=args.gray_noise_p, seed=args.degrade_seed)
 
 
+def jpeg_spec(args):
+    """The JpegSpec of the command line (None without --jpeg_quality); it reuses --degrade_seed."""
+    if args.jpeg_quality is None:
+        return None
+    from .sr_datasets import JpegSpec
+    return JpegSpec(quality=tuple(args.jpeg_quality), p=args.jpeg_p, subsample=args.jpeg_subsample == "420", seed=args.degrade_seed)
+
+
+def saved_args(args) -> dict:
+    """What a checkpoint keeps of the command line: additive flags leave no trace in the files at their defaults."""
+    at_default = {"ema_decay": not args.ema_decay, "loss": args.loss == "l1", "charbonnier_eps": args.charbonnier_eps == 1e-3,
+                  "ssim_weight": args.ssim_weight == 0, "val_tile": args.val_tile == 0,
+                  "val_tile_overlap": args.val_tile == 0 or args.val_tile_overlap == 32, "synth_lr": not args.synth_lr,
+                  "synth_lr_bits": not args.synth_lr or args.synth_lr_bits == 8, "degrade": args.degrade == "bicubic",
+                  "blur_sigma": args.blur_sigma == [0.2, 2.0], "blur_aniso_p": args.blur_aniso_p == 0.5,
+                  "noise_sigma": args.noise_sigma == [0.0, 10.0], "noise_gain": args.noise_gain == [0.0, 0.0],
+                  "gray_noise_p": args.gray_noise_p == 0.4,
+                  "degrade_seed": args.degrade_seed == 0, "jpeg_quality": args.jpeg_quality is None, "jpeg_p": args.jpeg_p == 1.0,
+                  "jpeg_subsample": args.jpeg_subsample == "444"}
+    return {k: v for k, v in vars(args).items() if not at_default.get(k, False)}
+
+
 def main(argv=None):
     args = parse_args(argv)
     rank, world, local = init_from_env()
@@ -328,7 +372,7 @@ def main(argv=None):
         raw = Shuffled2DHR(args.data_root, split="train")
         pool = DeviceHRPool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, device=device,
                             shard_bytes=(args.gpu_data_shard_mb << 20) or None, augment=args.augment, quant_bits=args.synth_lr_bits,
-                            degrade=degrade_spec(args), rank=rank)
+                            degrade=degrade_spec(args), rank=rank, jpeg=jpeg_spec(args))
         train_loader = sampler = DevicePoolLoader(pool, args.batch_size, rank, world, args.seed)
         valid_ds = Shuffled2DHR(args.data_root, split="valid", transform=hr_to_tensor3)
         if rank == 0:
@@ -340,6 +384,10 @@ def main(argv=None):
                       f"{args.noise_sigma} / 255, gain in {args.noise_gain}, gray p={args.gray_noise_p}, seed {args.degrade_seed}; "
                       f"validation: sigma=({fx.blur[0]:.4g}, {fx.blur[1]:.4g}) noise sigma={fx.noise[0] * 255.0:.4g} / 255 "
                       f"gain={fx.noise[1]:.4g}, noise id = image index")
+            if args.jpeg_quality is not None:
+                js = jpeg_spec(args)
+                print(f"[degrade] jpeg: quality in {list(js.quality)} with p={js.p:g}, chroma {args.jpeg_subsample}, seed {args.degrade_seed}; "
+                      f"validation: quality {js.fixed()}")
     else:
         train_ds = Shuffled2DPaired(args.data_root, split="train", scale=args.scale,
                                     transform_pair=PairTransformTrain(args.lr_patch, scale_int, args.augment))
@@ -358,7 +406,7 @@ def main(argv=None):
     valid_loader = make_loader(valid_ds, max(1, args.batch_size // 2), args.workers, pin=not args.no_pin, shuffle=False,
                                drop_last=False, persistent=not args.no_persistent)
     if args.synth_lr:
-        valid_loader = SynthLRBatches(valid_loader, scale_int, args.synth_lr_bits, device, degrade=degrade_spec(args))
+        valid_loader = SynthLRBatches(valid_loader, scale_int, args.synth_lr_bits, device, degrade=degrade_spec(args), jpeg=jpeg_spec(args))
 
     model = (build_model(scale_int, args.drop_path_rate, args.window_size) if args.arch == "swinir" else
              build_sr_model(args.arch, scale_int, args.drop_path_rate))
@@ -456,22 +504,14 @@ def main(argv=None):
         more = {"params_ema": opt.ema_state_dict()} if args.ema_decay else {}
         if with_ssim:
             more["val_ssim"] = val[2]
-        at_default = {"ema_decay": not args.ema_decay, "loss": args.loss == "l1", "charbonnier_eps": args.charbonnier_eps == 1e-3,
-                      "ssim_weight": args.ssim_weight == 0, "val_tile": args.val_tile == 0,
-                      "val_tile_overlap": args.val_tile == 0 or args.val_tile_overlap == 32, "synth_lr": not args.synth_lr,
-                      "synth_lr_bits": not args.synth_lr or args.synth_lr_bits == 8, "degrade": args.degrade == "bicubic",
-                      "blur_sigma": args.blur_sigma == [0.2, 2.0], "blur_aniso_p": args.blur_aniso_p == 0.5,
-                      "noise_sigma": args.noise_sigma == [0.0, 10.0], "noise_gain": args.noise_gain == [0.0, 0.0],
-                      "gray_noise_p": args.gray_noise_p == 0.4,
-                      "degrade_seed": args.degrade_seed == 0}          # additive flags leave no trace in the files at their defaults
-        saved_args = {k: v for k, v in vars(args).items() if not at_default.get(k, False)}
+        ckpt_args = saved_args(args)
         if val_loss < best_loss:
             best_loss = val_loss
-            torch.save({"model": sd, **more, "epoch": epoch, "best_val_loss": best_loss, "val_psnr": val_psnr, "args": saved_args},
+            torch.save({"model": sd, **more, "epoch": epoch, "best_val_loss": best_loss, "val_psnr": val_psnr, "args": ckpt_args},
                        f"best_{args.arch}_finetune_{args.scale}.pt")
         if val_psnr > best_psnr:
             best_psnr = val_psnr
-            torch.save({"model": sd, **more, "epoch": epoch, "best_val_psnr": best_psnr, "val_loss": val_loss, "args": saved_args},
+            torch.save({"model": sd, **more, "epoch": epoch, "best_val_psnr": best_psnr, "val_loss": val_loss, "args": ckpt_args},
                        f"bestpsnr_{args.arch}_finetune_{args.scale}.pt")
     if rank == 0:
         print(f"[time] total: {fmt(time.time() - t_all)}")

@@ -7,6 +7,7 @@ missing library raises.
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 import struct
 from typing import Optional, Tuple
 
@@ -613,3 +614,37 @@ def degrade_blind(hr: torch.Tensor, scale: int, blur, noise, noise_ids, gray_noi
     lr = torch.empty(B, Cc, H // s, W // s, dtype=torch.float32, device=hr.device)
     check(lib().srk_degrade_blind_f32(_p(hr), _p(lr), _p(par), B, Cc, H - H % s, W - W % s, s, int(quant_bits), _stream()))
     return lr, hr
+
+
+def check_jpeg_quality(q, what: str = "quality") -> int:
+    """A JPEG quality as an int in 1..100 (bools, floats with a fraction and anything else raise ValueError)."""
+    if isinstance(q, bool) or not isinstance(q, numbers.Real) or q != q or int(q) != q or not 1 <= int(q) <= 100:          # q != q: NaN
+        raise ValueError(f"jpeg {what} must be an integer in 1..100 (got {q!r})")
+    return int(q)
+
+
+def jpeg_roundtrip(x: torch.Tensor, quality, subsample: bool = False, return_coef: bool = False):
+    """What a baseline JPEG file of the 8-bit image of x at `quality` decodes to (csrc/jpeg.hip, srk_jpeg_roundtrip_f32): x CUDA fp32
+    [B,C,H,W] with C = 1 or 3 is levelled to 8 bits, converted to JFIF YCbCr, transformed in 8 x 8 blocks anchored at (0, 0),
+    quantised with libjpeg's scaling of the Annex K tables, and decoded again; chroma at 4:2:0 (`subsample`, C == 3 only) is averaged
+    over 2 x 2 cells and upsampled by replication.  quality: an int or one per sample, each in 1..100, or 0 = that sample passes through
+    bit for bit.  return_coef: also the quantised coefficients, int16 [B,C,Hm,Wm] (a test port; the part of a subsampled chroma plane
+    outside its top-left [Hm/2,Wm/2] is zero).  One launch after one small upload."""
+    if x.dim() != 4 or not x.is_cuda or x.dtype != torch.float32:
+        raise ValueError(f"jpeg_roundtrip takes a CUDA fp32 [B,C,H,W] batch (got {x.dtype} {tuple(x.shape)} on {x.device})")
+    B, Cc, H, W = x.shape
+    if Cc not in (1, 3) or min(B, H, W) < 1:
+        raise ValueError(f"jpeg_roundtrip: C must be 1 or 3 and every extent >= 1 (got {tuple(x.shape)})")
+    qs = [quality] * B if isinstance(quality, numbers.Real) else list(quality)
+    if len(qs) != B:
+        raise ValueError(f"jpeg_roundtrip: one quality or one per sample (B={B}; got {len(qs)})")
+    qs = [0 if (not isinstance(q, bool) and q == 0) else check_jpeg_quality(q) for q in qs]
+    x = x.contiguous()
+    qd = torch.tensor(qs, dtype=torch.int32).to(x.device)
+    out = torch.empty_like(x)
+    coef = None
+    if return_coef:
+        m = 16 if (subsample and Cc == 3) else 8
+        coef = torch.zeros(B, Cc, -(-H // m) * m, -(-W // m) * m, dtype=torch.int16, device=x.device)
+    check(lib().srk_jpeg_roundtrip_f32(_p(x), _p(out), _p(qd), B, Cc, H, W, int(bool(subsample)), _p(coef), _stream()))
+    return (out, coef) if return_coef else out

@@ -365,6 +365,45 @@ class DegradeSpec:
         return FixedDegrade((mid(self.blur_sigma),) * 2, (mid(self.noise_sigma), mid(self.noise_gain)), self.gray_noise_p >= 0.5)
 
 
+@dataclass(frozen=True)
+class JpegSpec:
+    """The JPEG stage of `--jpeg_quality`: per training sample, with probability `p`, a round trip through baseline JPEG at
+    a quality uniform in the integers `quality` = (lo, hi), 1 <= lo <= hi <= 100; otherwise the sample passes through (quality 0).
+    `subsample`: chroma at 4:2:0 instead of 4:4:4.  The qualities come from the spec's OWN generator
+    `random.Random(f"jpeg:{seed + rank}")`: neither the global `random` state nor a DegradeSpec's generator sees it."""
+    quality: Tuple[int, int] = (30, 95)
+    p: float = 1.0
+    subsample: bool = False
+    seed: int = 0
+
+    def __post_init__(self):
+        from .ops import check_jpeg_quality
+        try:
+            lo, hi = self.quality
+        except (TypeError, ValueError):
+            raise ValueError(f"jpeg quality must be two integers LO HI (got {self.quality!r})") from None
+        lo, hi = check_jpeg_quality(lo, "quality LO"), check_jpeg_quality(hi, "quality HI")
+        if lo > hi:
+            raise ValueError(f"jpeg quality must satisfy 1 <= LO <= HI <= 100 (got {lo} {hi})")
+        if not 0.0 <= float(self.p) <= 1.0:          # also refuses NaN
+            raise ValueError(f"jpeg p must be a probability (got {self.p!r})")
+        object.__setattr__(self, "quality", (lo, hi))
+        object.__setattr__(self, "subsample", bool(self.subsample))
+
+    def rng(self, rank: int = 0) -> random.Random:
+        return random.Random(f"jpeg:{int(self.seed) + int(rank)}")
+
+    def draw(self, rng: random.Random) -> int:
+        """-> the quality of one sample, 0 = pass-through; always the same two variates, whatever they decide."""
+        lo, hi = self.quality
+        take, q = rng.random() < self.p, min(lo + int(rng.random() * (hi - lo + 1)), hi)
+        return q if take else 0
+
+    def fixed(self) -> int:
+        """The middle of the range: what validation scores, every epoch and every run."""
+        return round((self.quality[0] + self.quality[1]) / 2)
+
+
 class DeviceHRPool(_DeviceImagePool):
     """Training pairs from HR images only (`--synth_lr`): the pool holds the decoded HR images -- half the device memory of a
     DevicePairPool at x2, no LR files to keep in sync -- and `sample` makes the HR patch AND its antialiased bicubic degradation
@@ -378,10 +417,14 @@ class DeviceHRPool(_DeviceImagePool):
 
     ``degrade`` (a DegradeSpec; None = the clean downscale, today's launch): every sample is blurred and noised with parameters drawn
     from the spec's own generator (seed + ``rank``), in one `srk_crop_degrade_blind_u8` launch on ten-slot descriptors.  `draw`, and
-    with it the global `random` state, the HR patches and the D4 codes, is the same with and without a spec."""
+    with it the global `random` state, the HR patches and the D4 codes, is the same with and without a spec.
+
+    ``jpeg`` (a JpegSpec; None = no such stage, no further launch): the LR batch goes through `ops.jpeg_roundtrip` at one quality per
+    sample from the spec's own generator, after the degrade launch and BEFORE the D4 transform, so the block grid is anchored to the
+    patch as cut.  Needs ``quant_bits`` 8: JPEG codes 8-bit images.  `draw` and `draw_degrade` do not see it."""
 
     def __init__(self, images, lr_patch: int, scale: int, device="cuda", shard_bytes: Optional[int] = None, augment: str = "none",
-                 quant_bits: int = 8, degrade: Optional[DegradeSpec] = None, rank: int = 0):
+                 quant_bits: int = 8, degrade: Optional[DegradeSpec] = None, rank: int = 0, jpeg: Optional[JpegSpec] = None):
         """images: iterable of HR PIL images or uint8 / uint16 arrays [H,W] / [H,W,1|3]."""
         if augment not in AUGMENT_MODES:
             raise ValueError(f"augment must be one of {AUGMENT_MODES} (got {augment!r})")
@@ -392,7 +435,12 @@ class DeviceHRPool(_DeviceImagePool):
         if degrade is not None and not isinstance(degrade, DegradeSpec):
             raise ValueError(f"degrade must be a DegradeSpec or None (got {type(degrade).__name__})")
         self.augment, self.quant_bits = augment, int(quant_bits)
+        if jpeg is not None and not isinstance(jpeg, JpegSpec):
+            raise ValueError(f"jpeg must be a JpegSpec or None (got {type(jpeg).__name__})")
+        if jpeg is not None and quant_bits != 8:
+            raise ValueError(f"jpeg= codes 8-bit LR images: it needs quant_bits 8 (got {quant_bits!r})")
         self.degrade, self._degrade_rng = degrade, (degrade.rng(rank) if degrade is not None else None)
+        self.jpeg, self._jpeg_rng = jpeg, (jpeg.rng(rank) if jpeg is not None else None)
         self.lr_patch, self.scale, self.device = int(lr_patch), int(scale), torch.device(device)
         self._pack(((img,) for img in images), shard_bytes)
 
@@ -431,6 +479,9 @@ class DeviceHRPool(_DeviceImagePool):
         st = torch.cuda.current_stream(self.device).cuda_stream
         entry = lib().srk_crop_degrade_u8 if self.degrade is None else lib().srk_crop_degrade_blind_u8
         check(entry(pool.data_ptr(), desc.data_ptr(), lr.data_ptr(), hr.data_ptr(), B, P, s, self.quant_bits, st))
+        if self.jpeg is not None:
+            from .ops import jpeg_roundtrip
+            lr = jpeg_roundtrip(lr, [self.jpeg.draw(self._jpeg_rng) for _ in range(B)], self.jpeg.subsample)
         if any(codes):
             from .augment import dihedral
             ops = torch.tensor(codes, dtype=torch.int32).to(self.device)
@@ -445,10 +496,21 @@ class SynthLRBatches:
 
     ``degrade`` (a FixedDegrade, or a DegradeSpec standing for its `fixed()` midpoints; None = the clean downscale): every image gets
     the SAME blur and noise amplitudes and the noise id = its index in the split (the loader must not shuffle), so every epoch and
-    every run scores the same LR images (ops.degrade_blind).  An image whose three channels are equal gets gray noise."""
+    every run scores the same LR images (ops.degrade_blind).  An image whose three channels are equal gets gray noise.
 
-    def __init__(self, loader, scale: int, quant_bits: int, device, degrade=None):
+    ``jpeg`` (a quality 1..100 with ``jpeg_subsample``, or a JpegSpec standing for its `fixed()` quality and its subsampling; None =
+    no such stage): the whole degraded LR image goes through `ops.jpeg_roundtrip`, the same every epoch.  Needs ``quant_bits`` 8."""
+
+    def __init__(self, loader, scale: int, quant_bits: int, device, degrade=None, jpeg=None, jpeg_subsample: bool = False):
         self.loader, self.scale, self.quant_bits, self.device = loader, int(scale), int(quant_bits), torch.device(device)
+        if isinstance(jpeg, JpegSpec):
+            jpeg, jpeg_subsample = jpeg.fixed(), jpeg.subsample
+        if jpeg is not None:
+            from .ops import check_jpeg_quality
+            jpeg = check_jpeg_quality(jpeg)
+            if self.quant_bits != 8:
+                raise ValueError(f"jpeg= codes 8-bit LR images: it needs quant_bits 8 (got {quant_bits!r})")
+        self.jpeg, self.jpeg_subsample = jpeg, bool(jpeg_subsample)
         self.degrade = degrade.fixed() if isinstance(degrade, DegradeSpec) else degrade
         if self.degrade is not None:
             from .ops import pack_degrade_params
@@ -458,6 +520,11 @@ class SynthLRBatches:
         return len(self.loader)
 
     def __iter__(self):
+        from .ops import jpeg_roundtrip
+        for lr, hr in self._degraded():
+            yield (lr if self.jpeg is None else jpeg_roundtrip(lr, self.jpeg, self.jpeg_subsample)), hr
+
+    def _degraded(self):
         from .ops import degrade_aa, degrade_blind
         first = 0
         for hr in self.loader:
