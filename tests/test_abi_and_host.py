@@ -460,3 +460,84 @@ def test_zero_arena_serves_the_second_pass_from_one_buffer():
     assert third.data_ptr() != second[0].data_ptr() or float(third.abs().sum()) == 0.0     # a fresh buffer per pass: `kept` is untouched
     assert float(kept.abs().sum()) == 0.0 and float(third.abs().sum()) == 0.0
     assert ops.zeros_f32((4,), dev).shape == (4,)
+
+
+def test_grad_sink_hands_every_gradient_over_once_in_creation_order():
+    """host_pass.GradSink: each segment_done() gives the hook the gradients made since the previous one, in the order they were put; every
+    gradient is handed over exactly once, a segment with nothing new is an empty list, and finish() is forwarded once."""
+    import torch
+    import torch.nn as nn
+    from tpu_superresolution_amd.host_pass import GradSink
+
+    class Hook:
+        def __init__(self):
+            self.segments, self.finished = [], 0
+
+        def segment_done(self, tensors):
+            self.segments.append(list(tensors))
+
+        def finish(self):
+            self.finished += 1
+
+    m = nn.Sequential(nn.Linear(4, 4), nn.LayerNorm(4))
+    lin, ln = m[0], m[1]
+    hook = Hook()
+    sink = GradSink(m, hook, 0, torch.device("cpu"), 8, 4, 64, 8, None)
+    g = {n: torch.full(p.shape, float(i)) for i, (n, p) in enumerate(m.named_parameters())}
+    sink.put(lin.weight, g["0.weight"])
+    sink.segment_done()
+    sink.put(ln.bias, g["1.bias"])
+    sink.put(lin.bias, g["0.bias"])
+    sink.segment_done()
+    sink.segment_done()                                  # nothing new
+    sink.put(ln.weight, g["1.weight"])
+    sink.segment_done()
+    sink.finish()
+    order = [["0.weight"], ["1.bias", "0.bias"], [], ["1.weight"]]
+    assert len(hook.segments) == len(order)
+    for seg, names in zip(hook.segments, order):
+        assert len(seg) == len(names) and all(t is g[n] for t, n in zip(seg, names))
+    handed = [id(t) for seg in hook.segments for t in seg]
+    assert sorted(handed) == sorted(id(t) for t in g.values())          # each exactly once
+    assert list(sink.G) == ["0.weight", "1.bias", "0.bias", "1.weight"] and all(sink.G[n] is g[n] for n in g)
+    assert hook.finished == 1
+    quiet = GradSink(m, None, 0, torch.device("cpu"), 8, 4, 64, 8, None)      # without a hook both calls are no-ops
+    quiet.put(lin.weight, g["0.weight"])
+    quiet.segment_done()
+    quiet.finish()
+    assert list(quiet.G) == ["0.weight"]
+
+
+def test_unpack_inverts_pack_for_linear_and_conv_weights():
+    """host_pass._unpack_linear / _unpack_conv give back what hat_arch._pack_linear / _pack_conv packed -- plain, through the head / qkv /
+    PixelShuffle index maps and transposed, at a width that is no multiple of 64 (C = 24, 2 heads, r = 3); integer-valued weights, so the
+    bf16 packed copy is exact and the comparison is torch.equal."""
+    import torch
+    from tpu_superresolution_amd import hat_arch as ha
+    from tpu_superresolution_amd.host_pass import _unpack_conv, _unpack_linear
+    dev = torch.device("cpu")
+    gen = torch.Generator().manual_seed(0)
+
+    def ints(*shape):
+        return torch.randint(-8, 9, shape, generator=gen).float()
+
+    C_, nH, r = 24, 2, 3
+    dh, CA, CP, HP = C_ // nH, nH * 32, 64, 64
+    hm, qkv_rows, pm = ha._head_map(nH, dh, dev), ha._qkv_rows(nH, dh, dev), ha._ps_map(r * r * 64, r, 64, dev)
+    wqkv, wproj, wfc1 = ints(3 * C_, C_), ints(C_, C_), ints(2 * C_, C_)
+    linear_cases = [(wfc1, HP, CP, None, None),                      # plain padding
+                    (wqkv, 3 * CA, CP, qkv_rows, None),              # rows through the qkv map
+                    (wproj, CP, CA, None, hm),                       # columns through the head map
+                    (wqkv.t(), CP, 3 * CA, None, qkv_rows),          # the dgrads' transposed copies
+                    (wproj.t(), CA, CP, hm, None)]
+    for w, NP, KP, row_map, col_map in linear_cases:
+        packed = ha._pack_linear(w, NP, KP, row_map=row_map, col_map=col_map)
+        assert packed.shape == (NP, KP) and packed.dtype == torch.bfloat16
+        back = _unpack_linear(packed.float(), w.shape[0], w.shape[1], row_map, col_map)
+        assert back.is_contiguous() and torch.equal(back, w.contiguous())
+    wbody, wup = ints(C_, C_, 3, 3), ints(r * r * 64, 64, 3, 3)
+    for w, NP, CinP, row_map in [(wbody, CP, CP, None), (wup, r * r * 64, 64, pm)]:
+        packed = ha._pack_conv(w, NP, CinP, row_map=row_map)
+        assert packed.shape == (NP, 9 * CinP) and packed.dtype == torch.bfloat16
+        back = _unpack_conv(packed.float(), w.shape[0], w.shape[1], CinP, row_map)
+        assert back.is_contiguous() and torch.equal(back, w)

@@ -23,17 +23,14 @@ resi_connection '1conv', both upsamplers.  No CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
-import math
 from typing import Dict, Optional
 
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import _lib, host_pass as hp, ops
 from ._lib import SrkUnsupported, check, lib
-from .hat_arch import (Upsample, _cached_map, _gemm, _head_map, _holder_forward, _pack_conv, _pack_linear, _pack_vec, _ps_map, _ptr, _qkv_rows, _rup,
-                       batched_pack)
+from .hat_arch import Upsample, _cached_map, _gemm, _head_map, _holder_forward, _pack_conv, _pack_linear, _pack_vec, _qkv_rows, _rup, batched_pack
 
 
 class UpsampleOneStep(nn.Sequential):
@@ -350,25 +347,7 @@ class DAT(nn.Module):
                     self._pack_sgfn(P, pre, blk, hid, half, HPh, device)
                 P[f"{li}.Wconv"] = _pack_conv(layer.conv.weight, CP, CP)
                 P[f"{li}.bconv"] = _pack_vec(layer.conv.bias, CP)
-            P["Wcab"] = _pack_conv(self.conv_after_body.weight, CP, CP)
-            P["bcab"] = _pack_vec(self.conv_after_body.bias, CP)
-            if self.upsampler == 'pixelshuffle':
-                P["Wbefore"] = _pack_conv(self.conv_before_upsample[0].weight, 64, CP)
-                P["bbefore"] = _pack_vec(self.conv_before_upsample[0].bias, 64)
-                k = 0
-                for m in self.upsample:
-                    if isinstance(m, nn.Conv2d):
-                        r = int(round(math.sqrt(m.weight.shape[0] // 64)))
-                        pm = _ps_map(m.weight.shape[0], r, 64, device)
-                        P[f"Wup{k}"] = _pack_conv(m.weight, m.weight.shape[0], 64, row_map=pm)
-                        P[f"bup{k}"] = _pack_vec(m.bias, m.weight.shape[0], row_map=pm)
-                        P[f"rup{k}"] = torch.tensor(r)
-                        k += 1
-                P["Wlast"] = _pack_conv(self.conv_last.weight, 16, 64)
-                P["blast"] = _pack_vec(self.conv_last.bias, 16)
-            else:
-                P["Wdirect"] = _pack_conv(self.upsample[0].weight, 16, CP)
-                P["bdirect"] = _pack_vec(self.upsample[0].bias, 16)
+            hp.pack_tail(P, self, CP, device)
             pk.resolve(P)
         self._packed, self._packed_version, self._packed_device = P, key, device
         return P
@@ -440,18 +419,13 @@ def _dat_forward(m: DAT, x: torch.Tensor, P: Dict[str, torch.Tensor]) -> torch.T
     s0, s1 = m.split_size
     big = max(s0, s1)
     Hp, Wp = _rup(H, big), _rup(W, big)        # window frame: q / k / v zero-padded to a multiple of the larger split (:376-384)
-    T, HW, s = B * H * W, H * W, m.upscale
+    T, HW = B * H * W, H * W
     C_, CP = m.embed_dim, _rup(m.embed_dim, 64)
     half = int(C_ * m.expansion_factor) // 2
     HPh = _rup(half, 64)
     f32, b16 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.bfloat16, device=dev)
     L = lib()
-    mean3 = (C.c_float * 3)(*(m.mean.flatten().tolist() if m.in_chans == 3 else [0.0, 0.0, 0.0]))
-    img4 = torch.empty(T, 4, **f32)
-    check(L.srk_img_prep(x.data_ptr(), img4.data_ptr(), B, Cin, H, W, H, W, float(m.img_range), C.byref(mean3), st))     # no padding in DAT.forward
-    f0 = torch.empty(T, CP, **f32)
-    check(L.srk_stem_conv(img4.data_ptr(), m.conv_first.weight.data_ptr(), m.conv_first.bias.data_ptr(), f0.data_ptr(), B, H, W, Cin, C_, CP, st))
-    _, cur, _, _ = ops.layernorm_fwd(f0, m.before_RG[1].weight, m.before_RG[1].bias, C_, out_bf16=False, out_f32=True)
+    img4, f0, cur = hp.head_forward(m, x, m.before_RG[1], st, H, W)          # no padding in DAT.forward
 
     CAmax = max(h * 32 for h in m.heads)
     qkv, att, conv, comb = (torch.empty(T, 3 * CAmax, **b16), torch.empty(T, CAmax, **b16), torch.empty(T, CAmax, **b16),
@@ -529,23 +503,4 @@ def _dat_forward(m: DAT, x: torch.Tensor, P: Dict[str, torch.Tensor]) -> torch.T
         xn1 = xn_a if nn_ is not None else None
 
     xnf = xn1 if xn1 is not None else ops.layernorm_fwd(cur, m.norm.weight, m.norm.bias, C_)[0]
-    fb = torch.empty(T, CP, **b16)
-    _gemm(st, _lib.LD_CONV3, _lib.EP_RES_BF16, xnf, P["Wcab"], T, CP, 9 * CP, conv=(B, H, W, CP), bias=P["bcab"], res=f0, outb=fb)
-    y = torch.empty(B, Cin, H * s, W * s, **f32)
-    mean4 = (m.mean.flatten().tolist() if m.in_chans == 3 else [0.0, 0.0, 0.0]) + [0.0]
-    img = dict(inv_range=1.0 / float(m.img_range), Cimg=Cin, Hc=H * s, Wc=W * s, mean=mean4)
-    if m.upsampler == 'pixelshuffle':
-        t1 = torch.empty(T, 64, **b16)
-        _gemm(st, _lib.LD_CONV3, _lib.EP_LRELU, fb, P["Wbefore"], T, 64, 9 * CP, conv=(B, H, W, CP), bias=P["bbefore"], outb=t1, scale=0.01)
-        src, h, w, k = t1, H, W, 0
-        while f"Wup{k}" in P:
-            r = int(P[f"rup{k}"])
-            N = P[f"Wup{k}"].shape[0]
-            up = torch.empty(B * h * r * w * r, 64, **b16)
-            _gemm(st, _lib.LD_CONV3, _lib.EP_PS, src, P[f"Wup{k}"], B * h * w, N, 9 * 64, conv=(B, h, w, 64), bias=P[f"bup{k}"], outb=up, r=r, Cs=64, ldo=N)
-            src, h, w, k = up, h * r, w * r, k + 1
-        _gemm(st, _lib.LD_CONV3, _lib.EP_IMG, src, P["Wlast"], B * h * w, 16, 9 * 64, conv=(B, h, w, 64), bias=P["blast"], outf=y, img=img)
-    else:
-        a = dict(img)
-        _gemm(st, _lib.LD_CONV3, _lib.EP_PS_IMG, fb, P["Wdirect"], T, 16, 9 * CP, conv=(B, H, W, CP), bias=P["bdirect"], outf=y, img=a, r=s)
-    return y
+    return hp.tail_forward(m, P, st, xnf, f0, img4, B, Cin, H, W, H, W)

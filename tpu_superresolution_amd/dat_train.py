@@ -1,6 +1,7 @@
 """DAT training on MI355X: the forward that keeps what the backward needs (every BatchNorm as its own ``training`` flag says: batch
 statistics and running statistics updated, or -- the module in eval mode, "frozen" -- its running statistics and no buffer written) and the backward pass, as host-side sequences of C-ABI calls (include/srk.h) -- the training-mode counterpart
-of ``dat_arch._dat_forward``, in the manner of ``hat_train``.
+of ``dat_arch._dat_forward``.  Head, reconstruction tail, the gradient sink and the autograd node are the shared ones of ``host_pass.py``;
+this file holds the DATB / ResidualGroup bodies.
 
 Reference: dat_arch.py:366-446 (Adaptive_Spatial_Attention.forward), :481-528 (Adaptive_Channel_Attention.forward), :74-90 (SGFN),
 :555-565 (DATB.forward: x + drop_path(attn(norm1 x)), x + drop_path(ffn(norm2 x))), :640-657 (ResidualGroup), :805-860 (DAT.forward).
@@ -25,35 +26,19 @@ statistics pass runs in front of it (srk_bn_frozen_coeffs reads the buffers), th
 """
 from __future__ import annotations
 
-import ctypes as C
-import math
 from typing import Dict, Optional
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-import os
-
-from . import _lib, ops
+from . import _lib, hat_arch as ha, host_pass as hp, ops
 from ._lib import check, lib
-from .hat_arch import _pack_conv_T
-from .hat_train import _arange, _unpack_conv, _unpack_linear
+from .dat_arch import _fc1_rows
+from .hat_arch import _cached_map, _gemm, _head_map, _pack_conv_T, _pack_linear, _pack_vec, _qkv_rows, _rup
+from .host_pass import GradSink, _arange, _full
 
 EPS = 1e-5
-
-
-def _da():
-    from . import dat_arch
-    return dat_arch
-
-
-_POISON = os.environ.get("SRK_DBG_POISON") == "1"
-
-
-def _ha():
-    from . import hat_arch
-    return hat_arch
 
 
 # ---- small functions between token passes ------------------------------------------------------------------------------------------
@@ -164,8 +149,7 @@ def _ci_frozen_ok(B: int, C: int, S: int, ci: nn.Sequential) -> bool:
 
 def _hm32(hm: torch.Tensor) -> torch.Tensor:
     """int32 copy of a head map (padded position of every real channel), cached per map"""
-    from . import hat_arch
-    return hat_arch._cached_map(("hm32", hm.data_ptr(), hm.numel()), lambda: hm.to(torch.int32))
+    return _cached_map(("hm32", hm.data_ptr(), hm.numel()), lambda: hm.to(torch.int32))
 
 
 def _channel_attention_matrix(G: torch.Tensor, sq: torch.Tensor, sk: torch.Tensor, temp: torch.Tensor, dh: int) -> torch.Tensor:
@@ -247,36 +231,35 @@ def _dense_bias(sa) -> torch.Tensor:
 
 # ---- packed operands of the backward pass -----------------------------------------------------------------------------------------------
 def pack_train(m, device) -> Dict[str, torch.Tensor]:
-    ha = _ha()
     ver = sum(p._version for p in m.parameters())
     if getattr(m, "_packedT", None) is not None and m._packedT_version == ver and m._packedT_device == device:
         return m._packedT
-    C_, CP = m.embed_dim, ha._rup(m.embed_dim, 64)
+    C_, CP = m.embed_dim, _rup(m.embed_dim, 64)
     hid = int(C_ * m.expansion_factor)
     half = hid // 2
-    HPh = ha._rup(half, 64)
+    HPh = _rup(half, 64)
     P: Dict[str, torch.Tensor] = {}
-    with torch.no_grad(), ha.batched_pack() as pk:
-        rows = _da()._fc1_rows(hid, half, HPh, device)
+    with torch.no_grad(), ha.batched_pack() as pk:      # the one name looked up on the module at every call (the packing test swaps it)
+        rows = _fc1_rows(hid, half, HPh, device)
         P["fc1_rows"] = rows
         for li, layer in enumerate(m.layers):
             nH = m.heads[li]
             dh, CA = C_ // nH, nH * 32
-            hm = ha._head_map(nH, dh, device)
-            qkv_rows = ha._qkv_rows(nH, dh, device)
+            hm = _head_map(nH, dh, device)
+            qkv_rows = _qkv_rows(nH, dh, device)
             for bi, blk in enumerate(layer.blocks):
                 pre = f"{li}.{bi}."
                 at = blk.attn
-                P[pre + "WqkvT"] = ha._pack_linear(at.qkv.weight.t(), CP, 3 * CA, col_map=qkv_rows)
-                P[pre + "WprojT"] = ha._pack_linear(at.proj.weight.t(), CA, CP, row_map=hm)
-                P[pre + "W1T"] = ha._pack_linear(blk.ffn.fc1.weight.t(), CP, 2 * HPh, col_map=rows)
-                P[pre + "W2T"] = ha._pack_linear(blk.ffn.fc2.weight.t(), HPh, CP)
+                P[pre + "WqkvT"] = _pack_linear(at.qkv.weight.t(), CP, 3 * CA, col_map=qkv_rows)
+                P[pre + "WprojT"] = _pack_linear(at.proj.weight.t(), CA, CP, row_map=hm)
+                P[pre + "W1T"] = _pack_linear(blk.ffn.fc1.weight.t(), CP, 2 * HPh, col_map=rows)
+                P[pre + "W2T"] = _pack_linear(blk.ffn.fc2.weight.t(), HPh, CP)
                 w9 = torch.zeros(CA, 9, device=device)
                 w9[hm] = at.dwconv[0].weight.float().reshape(C_, 9)
                 P[pre + "dw_wf"] = w9.flip(1).contiguous()                         # the depth-wise dgrad: the same conv with flipped taps
-                P[pre + "dw_b"] = ha._pack_vec(at.dwconv[0].bias, CA, row_map=hm)
-                P[pre + "dw_gam"] = ha._pack_vec(at.dwconv[1].weight, CA, row_map=hm)          # BatchNorm affine in the head-padded layout
-                P[pre + "dw_bet"] = ha._pack_vec(at.dwconv[1].bias, CA, row_map=hm)
+                P[pre + "dw_b"] = _pack_vec(at.dwconv[0].bias, CA, row_map=hm)
+                P[pre + "dw_gam"] = _pack_vec(at.dwconv[1].weight, CA, row_map=hm)          # BatchNorm affine in the head-padded layout
+                P[pre + "dw_bet"] = _pack_vec(at.dwconv[1].bias, CA, row_map=hm)
                 sg9 = torch.zeros(HPh, 9, device=device)
                 sg9[:half] = blk.ffn.sg.conv.weight.float().reshape(half, 9)
                 P[pre + "sg_wf"] = sg9.flip(1).contiguous()
@@ -285,16 +268,7 @@ def pack_train(m, device) -> Dict[str, torch.Tensor]:
                 w0[:, hm] = at.spatial_interaction[0].weight.float().reshape(S2, C_)
                 P[pre + "si_w0raw"] = w0.contiguous()
             P[f"{li}.WconvT"] = _pack_conv_T(layer.conv.weight, CP, CP)
-        P["WcabT"] = _pack_conv_T(m.conv_after_body.weight, CP, CP)
-        if m.upsampler == 'pixelshuffle':
-            P["WbeforeT"] = _pack_conv_T(m.conv_before_upsample[0].weight, CP, 64)
-            k = 0
-            for mod in m.upsample:
-                if isinstance(mod, nn.Conv2d):
-                    r = int(round(math.sqrt(mod.weight.shape[0] // 64)))
-                    pm = ha._ps_map(mod.weight.shape[0], r, 64, device)
-                    P[f"WupT{k}"] = _pack_conv_T(mod.weight, 64, mod.weight.shape[0], col_map=pm)
-                    k += 1
+        hp.pack_tail_T(P, m, CP, device)
         P["ones"] = torch.ones(max(2 * HPh, 256), device=device)
         P["zeros"] = torch.zeros(max(2 * HPh, 256), device=device)
         pk.resolve(P)
@@ -305,15 +279,13 @@ def pack_train(m, device) -> Dict[str, torch.Tensor]:
 # ---- forward, keeping activations ---------------------------------------------------------------------------------------------------------
 def dat_forward_train(m, x: torch.Tensor, P: Dict[str, torch.Tensor], PT: Dict[str, torch.Tensor], drop: Optional[torch.Tensor]):
     """drop: None or fp32 [n_blocks][2][B] DropPath factors (0 or 1 / keep_prob) of each block's attention and FFN branch."""
-    ha = _ha()
-    _gemm, _rup = ha._gemm, ha._rup
     dev = x.device
     st = torch.cuda.current_stream(dev).cuda_stream
     B, Cin, H, W = x.shape
     s0, s1 = m.split_size
     big = max(s0, s1)
     Hp, Wp = _rup(H, big), _rup(W, big)
-    T, HW, s = B * H * W, H * W, m.upscale
+    T, HW = B * H * W, H * W
     C_, CP = m.embed_dim, _rup(m.embed_dim, 64)
     half = int(C_ * m.expansion_factor) // 2
     HPh = _rup(half, 64)
@@ -322,13 +294,7 @@ def dat_forward_train(m, x: torch.Tensor, P: Dict[str, torch.Tensor], PT: Dict[s
     S: dict = dict(B=B, Cin=Cin, H=H, W=W, Hp=Hp, Wp=Wp, T=T, blocks=[], layers=[], drop=drop)
     ones, zeros = PT["ones"], PT["zeros"]
 
-    mean3 = (C.c_float * 3)(*(m.mean.flatten().tolist() if m.in_chans == 3 else [0.0, 0.0, 0.0]))
-    img4 = torch.empty(T, 4, **f32)
-    check(L.srk_img_prep(x.data_ptr(), img4.data_ptr(), B, Cin, H, W, H, W, float(m.img_range), C.byref(mean3), st))
-    f0 = torch.empty(T, CP, **f32)
-    check(L.srk_stem_conv(img4.data_ptr(), m.conv_first.weight.data_ptr(), m.conv_first.bias.data_ptr(), f0.data_ptr(), B, H, W, Cin, C_, CP, st))
-    _, cur, mean_pe, rstd_pe = ops.layernorm_fwd(f0, m.before_RG[1].weight, m.before_RG[1].bias, C_, out_bf16=False, out_f32=True)
-    S.update(img4=img4, f0=f0, mean_pe=mean_pe, rstd_pe=rstd_pe)
+    _, _, cur = hp.head_forward(m, x, m.before_RG[1], st, H, W, keep=S)
 
     # the dense position biases of every spatial block, from one batched evaluation of the position-bias MLPs
     pos_groups = _pos_groups(m)
@@ -353,7 +319,7 @@ def dat_forward_train(m, x: torch.Tensor, P: Dict[str, torch.Tensor], PT: Dict[s
     for li, layer in enumerate(m.layers):
         nH = m.heads[li]
         dh, CA, hb = C_ // nH, nH * 32, nH // 2
-        hm = ha._head_map(nH, dh, dev)
+        hm = _head_map(nH, dh, dev)
         scale = float(m.qk_scale or dh ** -0.5)
         layer_in = cur
         for bi, blk in enumerate(layer.blocks):
@@ -366,7 +332,7 @@ def dat_forward_train(m, x: torch.Tensor, P: Dict[str, torch.Tensor], PT: Dict[s
             v_ptr = qkv.data_ptr() + 2 * CA * 2
             # DW-conv branch on v (:418 / :508): conv (+ bias), BatchNorm with the batch's statistics, GELU
             c_pre, conv = torch.empty(T, CA, **b16), torch.empty(T, CA, **b16)
-            real_of = ha._cached_map(("real_of", nH, dh, str(dev)), lambda: torch.full((CA,), -1, dtype=torch.int32, device=dev).scatter_(
+            real_of = _cached_map(("real_of", nH, dh, str(dev)), lambda: torch.full((CA,), -1, dtype=torch.int32, device=dev).scatter_(
                 0, hm, torch.arange(C_, dtype=torch.int32, device=dev)))
             dw_live = _bn_live(at.dwconv[1])
             if dw_live:
@@ -493,44 +459,20 @@ def dat_forward_train(m, x: torch.Tensor, P: Dict[str, torch.Tensor], PT: Dict[s
         cur = nxt
 
     xnf, _, meanf, rstdf = ops.layernorm_fwd(cur, m.norm.weight, m.norm.bias, C_)
-    fb = torch.empty(T, CP, **b16)
-    _gemm(st, _lib.LD_CONV3, _lib.EP_RES_BF16, xnf, P["Wcab"], T, CP, 9 * CP, conv=(B, H, W, CP), bias=P["bcab"], res=f0, outb=fb)
-    S.update(x_last=cur, xnf=xnf, meanf=meanf, rstdf=rstdf, fb=fb, ups=[])
-    y = torch.empty(B, Cin, H * s, W * s, **f32)
-    mean4 = (m.mean.flatten().tolist() if m.in_chans == 3 else [0.0, 0.0, 0.0]) + [0.0]
-    img = dict(inv_range=1.0 / float(m.img_range), Cimg=Cin, Hc=H * s, Wc=W * s, mean=mean4)
-    if m.upsampler == 'pixelshuffle':
-        t1 = torch.empty(T, 64, **b16)
-        _gemm(st, _lib.LD_CONV3, _lib.EP_LRELU, fb, P["Wbefore"], T, 64, 9 * CP, conv=(B, H, W, CP), bias=P["bbefore"], outb=t1, scale=0.01)
-        S["t1"] = t1
-        src, h_, w_, k = t1, H, W, 0
-        while f"Wup{k}" in P:
-            r = int(P[f"rup{k}"])
-            N = P[f"Wup{k}"].shape[0]
-            up = torch.empty(B * h_ * r * w_ * r, 64, **b16)
-            _gemm(st, _lib.LD_CONV3, _lib.EP_PS, src, P[f"Wup{k}"], B * h_ * w_, N, 9 * 64, conv=(B, h_, w_, 64), bias=P[f"bup{k}"], outb=up, r=r, Cs=64,
-                  ldo=N)
-            S["ups"].append(dict(src=src, out=up, h=h_, w=w_, r=r, N=N))
-            src, h_, w_, k = up, h_ * r, w_ * r, k + 1
-        _gemm(st, _lib.LD_CONV3, _lib.EP_IMG, src, P["Wlast"], B * h_ * w_, 16, 9 * 64, conv=(B, h_, w_, 64), bias=P["blast"], outf=y, img=img)
-        S.update(hr_h=h_, hr_w=w_)
-    else:
-        _gemm(st, _lib.LD_CONV3, _lib.EP_PS_IMG, fb, P["Wdirect"], T, 16, 9 * CP, conv=(B, H, W, CP), bias=P["bdirect"], outf=y, img=dict(img), r=s)
-    return y, S
+    S.update(x_last=cur, xnf=xnf, meanf=meanf, rstdf=rstdf)
+    return hp.tail_forward(m, P, st, xnf, S["f0"], S["img4"], B, Cin, H, W, H, W, keep=S), S
 
 
 # ---- backward ---------------------------------------------------------------------------------------------------------------------------------
 def dat_backward(m, S: dict, dy: torch.Tensor, hook=None) -> Dict[str, torch.Tensor]:
     """-> {parameter name: gradient}.  hook (distributed.ListGradSynchronizer or None) gets each finished segment's gradients
     (tail, every ResidualGroup, head) so that their all-reduce overlaps the next segment."""
-    ha = _ha()
-    _gemm, _rup, _ptr = ha._gemm, ha._rup, ha._ptr
     dev = dy.device
     P = m._pack(dev, True)
     PT = pack_train(m, dev)
     st = torch.cuda.current_stream(dev).cuda_stream
     B, Cin, H, W, Hp, Wp, T = S["B"], S["Cin"], S["H"], S["W"], S["Hp"], S["Wp"], S["T"]
-    HW, s = H * W, m.upscale
+    HW = H * W
     s0, s1 = m.split_size
     C_, CP = m.embed_dim, _rup(m.embed_dim, 64)
     hid = int(C_ * m.expansion_factor)
@@ -540,60 +482,11 @@ def dat_backward(m, S: dict, dy: torch.Tensor, hook=None) -> Dict[str, torch.Ten
     L = lib()
     drop = S["drop"]
     ones, zeros = PT["ones"], PT["zeros"]
-    G: Dict[str, torch.Tensor] = {}
-    names = {id(p): n for n, p in m.named_parameters()}
-    handed = set()
-
-    def segment_done():
-        if hook is not None:
-            fresh = [k for k in G if k not in handed]
-            handed.update(fresh)
-            hook.segment_done([G[k] for k in fresh])
-
-    def pname(p):
-        return names[id(p)]
+    sink = GradSink(m, hook, st, dev, T, C_, CP, HW, drop)
+    conv_wgrad, ln_bwd, lin_wgrad, scaled = sink.conv_wgrad, sink.ln_bwd, sink.lin_wgrad, sink.scaled
 
     def put(p, g):
-        G[pname(p)] = g.reshape(p.shape).contiguous()
-
-    pending = []          # the block's linear weight gradients: queued, then ONE launch for all four (flush_wgrads)
-
-    def lin_wgrad(y, x, lin, row_map=None, col_map=None):
-        pending.append((y, x, lin, row_map, col_map))        # y and x must stay untouched until flush_wgrads
-
-    def flush_wgrads():
-        if not pending:
-            return
-        for (y, x, lin, row_map, col_map), (dw, db) in zip(pending, ops.linear_wgrad_multi_bf16([(q[0], q[1]) for q in pending])):
-            N, K = lin.weight.shape
-            G[pname(lin.weight)] = _unpack_linear(dw, N, K, row_map, col_map)
-            if lin.bias is not None:
-                G[pname(lin.bias)] = (db[:N] if row_map is None else db[row_map]).contiguous()
-        pending.clear()
-
-    def conv_wgrad(dyb, xb, conv, Bc, Hc, Wc, CinP, NP, r=1, row_map=None):
-        dw, db = ops.zeros_f32((NP, 9 * CinP), dev), ops.zeros_f32((NP,), dev)
-        ops._bind_wgrad_workspace(dev)
-        if r == 1:
-            check(L.srk_conv3x3_wgrad_bf16(dyb.data_ptr(), xb.data_ptr(), dw.data_ptr(), db.data_ptr(), Bc, Hc, Wc, CinP, NP, st))
-        else:
-            check(L.srk_conv3x3_wgrad_ps_bf16(dyb.data_ptr(), xb.data_ptr(), dw.data_ptr(), db.data_ptr(), Bc, Hc, Wc, CinP, NP, r, 64, st))
-        Cout, Cin_ = conv.weight.shape[:2]
-        G[pname(conv.weight)] = _unpack_conv(dw, Cout, Cin_, CinP, row_map)
-        G[pname(conv.bias)] = (db[:Cout] if row_map is None else db[row_map]).contiguous()
-
-    def ln_bwd(dyb, x, mean, rstd, norm, gx, gxb, accumulate):
-        dg, dbt = ops.zeros_f32((C_,), dev), ops.zeros_f32((C_,), dev)
-        check(L.srk_layernorm_bwd(dyb.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), norm.weight.data_ptr(), gx.data_ptr(), _ptr(gxb),
-                                  dg.data_ptr(), dbt.data_ptr(), T, C_, CP, 1 if accumulate else 0, st))
-        G[pname(norm.weight)], G[pname(norm.bias)] = dg, dbt
-
-    def scaled(gb, bidx, which):
-        if drop is None:
-            return gb
-        out = torch.empty_like(gb)
-        check(L.srk_rowscale_bf16(gb.data_ptr(), out.data_ptr(), drop[bidx, which].data_ptr(), T, HW, CP, st))
-        return out
+        sink.put(p, g.reshape(p.shape).contiguous())
 
     n_chunks = int(L.srk_chan_stats_chunks(HW))
 
@@ -612,48 +505,7 @@ def dat_backward(m, S: dict, dy: torch.Tensor, hook=None) -> Dict[str, torch.Ten
         put(conv.weight, g[:9, real_rows].t())
         put(conv.bias, g[9, real_rows])
 
-    # ---------------- reconstruction tail ----------------
-    if m.upsampler == 'pixelshuffle':
-        hs_, ws_ = S["hr_h"], S["hr_w"]
-        gyimg = torch.empty(B * hs_ * ws_, 4, **f32)
-        check(L.srk_img_grad_prep(dy.data_ptr(), gyimg.data_ptr(), B, Cin, H * s, W * s, hs_, ws_, 1, 4, 1.0 / float(m.img_range), st))
-        last_in = S["ups"][-1]["out"] if S["ups"] else S["t1"]
-        dwl, dbl = torch.zeros_like(m.conv_last.weight, dtype=torch.float32), torch.zeros_like(m.conv_last.bias, dtype=torch.float32)
-        check(L.srk_smallconv_wgrad(last_in.data_ptr(), gyimg.data_ptr(), dwl.data_ptr(), dbl.data_ptr(), B, hs_, ws_, 64, 64, Cin, 4, st))
-        G[pname(m.conv_last.weight)], G[pname(m.conv_last.bias)] = dwl, dbl
-        gcur = torch.empty(B * hs_ * ws_, 64, **b16)
-        check(L.srk_smallconv_dgrad(gyimg.data_ptr(), m.conv_last.weight.data_ptr(), gcur.data_ptr(), B, hs_, ws_, 64, 64, Cin, 4, st))
-        up_convs = [mod for mod in m.upsample if isinstance(mod, nn.Conv2d)]
-        for k in range(len(S["ups"]) - 1, -1, -1):
-            u = S["ups"][k]
-            r, N, h_, w_ = u["r"], u["N"], u["h"], u["w"]
-            conv_wgrad(gcur, u["src"], up_convs[k], B, h_, w_, 64, N, r=r, row_map=ha._ps_map(N, r, 64, dev))
-            gprev = torch.empty(B * h_ * w_, 64, **b16)
-            if k == 0:
-                _gemm(st, _lib.LD_CONV3_PS, _lib.EP_DLRELU, gcur, PT[f"WupT{k}"], B * h_ * w_, 64, 9 * N, conv=(B, h_, w_, N), r=r, Cs=64, outb=gprev,
-                      aux=S["t1"], scale=0.01, ldo=64)
-            else:
-                _gemm(st, _lib.LD_CONV3_PS, _lib.EP_BF16, gcur, PT[f"WupT{k}"], B * h_ * w_, 64, 9 * N, conv=(B, h_, w_, N), r=r, Cs=64, outb=gprev, ldo=64)
-            gcur = gprev
-        conv_wgrad(gcur, S["fb"], m.conv_before_upsample[0], B, H, W, CP, 64)
-        gfb = torch.empty(T, CP, **b16)
-        _gemm(st, _lib.LD_CONV3, _lib.EP_BF16, gcur, PT["WbeforeT"], T, CP, 9 * 64, conv=(B, H, W, 64), outb=gfb)
-    else:
-        Co = s * s * Cin
-        gyimg = torch.empty(T, 16, **f32)
-        check(L.srk_img_grad_prep(dy.data_ptr(), gyimg.data_ptr(), B, Cin, H * s, W * s, H, W, s, 16, 1.0 / float(m.img_range), st))
-        cv = m.upsample[0]
-        dwl, dbl = torch.zeros_like(cv.weight, dtype=torch.float32), torch.zeros_like(cv.bias, dtype=torch.float32)
-        check(L.srk_smallconv_wgrad(S["fb"].data_ptr(), gyimg.data_ptr(), dwl.data_ptr(), dbl.data_ptr(), B, H, W, C_, CP, Co, 16, st))
-        G[pname(cv.weight)], G[pname(cv.bias)] = dwl, dbl
-        gfb = torch.empty(T, CP, **b16)
-        check(L.srk_smallconv_dgrad(gyimg.data_ptr(), cv.weight.data_ptr(), gfb.data_ptr(), B, H, W, C_, CP, Co, 16, st))
-    conv_wgrad(gfb, S["xnf"], m.conv_after_body, B, H, W, CP, CP)
-    dxn = torch.empty(T, CP, **b16)
-    _gemm(st, _lib.LD_CONV3, _lib.EP_BF16, gfb, PT["WcabT"], T, CP, 9 * CP, conv=(B, H, W, CP), outb=dxn)
-    gx, gxb = torch.empty(T, CP, **f32), torch.empty(T, CP, **b16)      # gradient of the current layer's output (later: input)
-    ln_bwd(dxn, S["x_last"], S["meanf"], S["rstdf"], m.norm, gx, gxb, accumulate=False)
-    segment_done()
+    gfb, gx, gxb = hp.tail_backward(sink, m, S, PT, dy, B, Cin, H, W, H, W, direct_CoP=16)
 
     # ---------------- layers, last to first ----------------
     blocks = S["blocks"]
@@ -671,8 +523,8 @@ def dat_backward(m, S: dict, dy: torch.Tensor, hook=None) -> Dict[str, torch.Ten
             pre, blk, nH, CA, bidx = bk["pre"], bk["blk"], bk["nH"], bk["CA"], bk["bidx"]
             at = blk.attn
             dh, hb = C_ // nH, nH // 2
-            hm = ha._head_map(nH, dh, dev)
-            qkv_rows = ha._qkv_rows(nH, dh, dev)
+            hm = _head_map(nH, dh, dev)
+            qkv_rows = _qkv_rows(nH, dh, dev)
             qkv = bk["qkv"]
             v_ptr = qkv.data_ptr() + 2 * CA * 2
             # ---- SGFN: x2 = x1 + f * fc2(x1h * dwconv(LN(x2h))) with (x1h | x2h) = gelu(fc1(norm2 x1)) ----
@@ -732,7 +584,7 @@ def dat_backward(m, S: dict, dy: torch.Tensor, hook=None) -> Dict[str, torch.Ten
                                                            ci[2].running_var.data_ptr(), gci[0].data_ptr(), gci[1].data_ptr(), gci[2].data_ptr(),
                                                            gci[3].data_ptr(), gci[4].data_ptr(), gci[5].data_ptr(), dpool.data_ptr(), B, C_, S1, CA, st))
                 for p_, g_ in zip(ci_params, gci):
-                    G[pname(p_)] = g_
+                    sink.put(p_, g_)
             elif _ci_fused_ok(B, C_, S1, ci) and bk["ci_live"]:
                 dcg = _sum_rows(dcg_part, B, nck)                                       # [B][CA], head-padded
                 gci = [torch.empty(p_.shape, **f32) for p_ in ci_params]
@@ -743,7 +595,7 @@ def dat_backward(m, S: dict, dy: torch.Tensor, hook=None) -> Dict[str, torch.Ten
                                                     gci[2].data_ptr(), gci[3].data_ptr(), gci[4].data_ptr(), gci[5].data_ptr(), dpool.data_ptr(), B, C_,
                                                     S1, CA, st))
                 for p_, g_ in zip(ci_params, gci):
-                    G[pname(p_)] = g_
+                    sink.put(p_, g_)
             else:
                 with torch.enable_grad():
                     pm = bk["pm"].detach().requires_grad_(True)
@@ -810,7 +662,7 @@ def dat_backward(m, S: dict, dy: torch.Tensor, hook=None) -> Dict[str, torch.Ten
             check(L.srk_dwconv3x3(dcpre.data_ptr(), CA, PT[pre + "dw_wf"].data_ptr(), ones.data_ptr(), zeros.data_ptr(), None, 0, dv_conv.data_ptr(), CA,
                                   B, H, W, CA // 8, 0, st))
             # ---- attention core ----
-            dqkv = torch.empty(T, 3 * CA, **b16) if not _POISON else torch.full((T, 3 * CA), float("nan"), **b16)      # every element is written by the attention backward
+            dqkv = _full((T, 3 * CA), b16)      # every element is written by the attention backward
             if bk["spatial"]:
                 for br, (hs, wsz) in enumerate(((s0, s1), (s1, s0))):
                     sa = at.attns[br]
@@ -844,55 +696,28 @@ def dat_backward(m, S: dict, dy: torch.Tensor, hook=None) -> Dict[str, torch.Ten
                 check(L.srk_chan_apply_mat(dGt.data_ptr(), q_ptr, 3 * CA, dsk2.data_ptr(), k_ptr, 3 * CA, dqkv.data_ptr() + CA * 2, 3 * CA, B, HW, nH, 0, st))
             check(L.srk_lincomb2_bf16(dv_conv.data_ptr(), CA, None, 0, None, None, None, dqkv.data_ptr() + 2 * CA * 2, 3 * CA, T, CA // 8, 0, 1, st))
             lin_wgrad(dqkv, bk["xn1"], at.qkv, row_map=qkv_rows)
-            flush_wgrads()            # before the kernel below overwrites gxb2 (the fc2 gradient's operand when no DropPath copy was made)
+            sink.flush_wgrads()            # before the kernel below overwrites gxb2 (the fc2 gradient's operand when no DropPath copy was made)
             if CP in (64, 128, 192):      # qkv dgrad with the norm1 backward in its epilogue (gx2 += d x, gxb2 = its bf16 copy)
                 dg, dbt = ops.zeros_f32((C_,), dev), ops.zeros_f32((C_,), dev)
                 _gemm(st, _lib.LD_ROWS, _lib.EP_LNBWD, dqkv, PT[pre + "WqkvT"], T, CP, 3 * CA, lda=3 * CA, outf=gx2, outb=gxb2, ldo=CP,
                       ln=dict(x=bk["x_in"], mean=bk["mean1"], rstd=bk["rstd1"], gamma=blk.norm1.weight, dgamma=dg, dbeta=dbt, C=C_))
-                G[pname(blk.norm1.weight)], G[pname(blk.norm1.bias)] = dg, dbt
+                sink.put(blk.norm1.weight, dg), sink.put(blk.norm1.bias, dbt)
             else:
                 dxn1 = torch.empty(T, CP, **b16)
                 _gemm(st, _lib.LD_ROWS, _lib.EP_BF16, dqkv, PT[pre + "WqkvT"], T, CP, 3 * CA, lda=3 * CA, outb=dxn1)
                 ln_bwd(dxn1, bk["x_in"], bk["mean1"], bk["rstd1"], blk.norm1, gx2, gxb2, accumulate=True)
         check(L.srk_add_f32_bf16(gx.data_ptr(), gx2.data_ptr(), gxb.data_ptr(), T * CP, st))      # d(layer input) = d(body input) + d(layer output)
-        segment_done()
+        sink.segment_done()
 
     for gq in S["pos_groups"]:            # every position-bias MLP's parameter gradients from one batched backward
         if gq.d_bias is not None:
             gq.backward(put)
     # ---------------- head: before_RG's LayerNorm, long skip, conv_first ----------------
-    gf = torch.empty(T, CP, **f32)
-    ln_bwd(gxb, S["f0"], S["mean_pe"], S["rstd_pe"], m.before_RG[1], gf, None, accumulate=False)
-    check(L.srk_add_bf16_into_f32(gf.data_ptr(), gfb.data_ptr(), T * CP, st))
-    dwf, dbf = torch.zeros_like(m.conv_first.weight, dtype=torch.float32), torch.zeros_like(m.conv_first.bias, dtype=torch.float32)
-    check(L.srk_stem_wgrad(S["img4"].data_ptr(), gf.data_ptr(), dwf.data_ptr(), dbf.data_ptr(), B, H, W, Cin, C_, CP, st))
-    G[pname(m.conv_first.weight)], G[pname(m.conv_first.bias)] = dwf, dbf
-    segment_done()
-    if hook is not None:
-        hook.finish()
-    return G
+    hp.head_backward(sink, m, S, m.before_RG[1], gxb, gfb)
+    return sink.G
 
 
-class DATFunction(torch.autograd.Function):
-    """One autograd node for the whole model (as HATFunction): forward keeps the activations and updates the running statistics of
-    the BatchNorms that are in training mode, backward returns every parameter's gradient.  The input image gets no gradient."""
-
-    @staticmethod
-    def forward(ctx, model, x, drop, *params):
-        with torch.cuda.device(x.device), torch.no_grad():
-            y, saved = dat_forward_train(model, x.contiguous().float(), model._pack(x.device, True), pack_train(model, x.device), drop)
-        ctx.model, ctx.saved = model, saved
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        model = ctx.model
-        arena = model.__dict__.setdefault("_zero_arena", ops.ZeroArena())      # the pass's zeroed accumulators: one buffer, one fill
-        with torch.cuda.device(dy.device), ops.arena_scope(arena, dy.device):
-            G = dat_backward(model, ctx.saved, dy.contiguous().float(), hook=getattr(model, "grad_sync", None))
-        ctx.saved = None
-        grads = []
-        for n, p in model.named_parameters():
-            g = G.get(n)
-            grads.append(None if g is None else g.reshape(p.shape).to(p.dtype))
-        return (None, None, None, *grads)
+class DATFunction(hp.WholeModelFunction):
+    """DAT as one autograd node (as HATFunction); its forward also updates the running statistics of the BatchNorms in training mode"""
+    forward_train = staticmethod(lambda m, x, drop: dat_forward_train(m, x, m._pack(x.device, True), pack_train(m, x.device), drop))
+    backward_pass = staticmethod(dat_backward)

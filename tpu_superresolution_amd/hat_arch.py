@@ -477,6 +477,7 @@ class HAT(nn.Module):
         hid = int(C * self.mlp_ratio)
         HP = _rup(hid, 64)
         P: Dict[str, torch.Tensor] = {}
+        from .host_pass import pack_tail          # (host_pass builds on this module's packing helpers and _gemm)
         with torch.no_grad(), batched_pack() as pk:
             for li, layer in enumerate(self.layers):
                 nH = self.heads[li]
@@ -516,21 +517,7 @@ class HAT(nn.Module):
                 mlp_pack(pre, oc.mlp)
                 P[f"{li}.Wconv"] = _pack_conv(layer.conv.weight, CP, CP)
                 P[f"{li}.bconv"] = _pack_vec(layer.conv.bias, CP)
-            P["Wcab"] = _pack_conv(self.conv_after_body.weight, CP, CP)
-            P["bcab"] = _pack_vec(self.conv_after_body.bias, CP)
-            P["Wbefore"] = _pack_conv(self.conv_before_upsample[0].weight, 64, CP)
-            P["bbefore"] = _pack_vec(self.conv_before_upsample[0].bias, 64)
-            k = 0
-            for m in self.upsample:
-                if isinstance(m, nn.Conv2d):
-                    r = int(round(math.sqrt(m.weight.shape[0] // 64)))
-                    pm = _ps_map(m.weight.shape[0], r, 64, device)
-                    P[f"Wup{k}"] = _pack_conv(m.weight, m.weight.shape[0], 64, row_map=pm)
-                    P[f"bup{k}"] = _pack_vec(m.bias, m.weight.shape[0], row_map=pm)
-                    P[f"rup{k}"] = torch.tensor(r)
-                    k += 1
-            P["Wlast"] = _pack_conv(self.conv_last.weight, 16, 64)
-            P["blast"] = _pack_vec(self.conv_last.bias, 16)
+            pack_tail(P, self, CP, device)
             pk.resolve(P)
         self._packed, self._packed_version, self._packed_device = P, ver, device
         return P
@@ -603,10 +590,11 @@ def _gemm(st, loader, ep, A, W, M, N, K, *, lda=0, conv=None, bias=None, outf=No
 
 
 def _hat_forward(m: HAT, x: torch.Tensor, P: Dict[str, torch.Tensor]) -> torch.Tensor:
+    from . import host_pass          # (host_pass builds on this module's packing helpers and _gemm)
     dev = x.device
     st = torch.cuda.current_stream(dev).cuda_stream
     B, Cin, H0, W0 = x.shape
-    ws, s = m.window_size, m.upscale
+    ws = m.window_size
     H, W = _rup(H0, ws), _rup(W0, ws)
     if (H - H0 >= H0) or (W - W0 >= W0):
         raise RuntimeError(f"reflect padding {H0}x{W0} -> {H}x{W} needs pad < size (as torch 'reflect')")
@@ -618,12 +606,7 @@ def _hat_forward(m: HAT, x: torch.Tensor, P: Dict[str, torch.Tensor]) -> torch.T
     b16 = dict(dtype=torch.bfloat16, device=dev)
     L = lib()
 
-    mean3 = (C.c_float * 3)(*(m.mean.flatten().tolist() if m.in_chans == 3 else [0.0, 0.0, 0.0]))
-    img4 = torch.empty(T, 4, **f32)
-    check(L.srk_img_prep(x.data_ptr(), img4.data_ptr(), B, Cin, H0, W0, H, W, float(m.img_range), C.byref(mean3), st))
-    f0 = torch.empty(T, CP, **f32)
-    check(L.srk_stem_conv(img4.data_ptr(), m.conv_first.weight.data_ptr(), m.conv_first.bias.data_ptr(), f0.data_ptr(), B, H, W, Cin, C_, CP, st))
-    _, cur, _, _ = ops.layernorm_fwd(f0, m.patch_embed.norm.weight, m.patch_embed.norm.bias, C_, out_bf16=False, out_f32=True)
+    img4, f0, cur = host_pass.head_forward(m, x, m.patch_embed.norm, st, H, W)
 
     # scratch shared by all blocks
     qkv = torch.empty(T, 3 * max(h * 32 for h in m.heads), **b16)
@@ -636,24 +619,14 @@ def _hat_forward(m: HAT, x: torch.Tensor, P: Dict[str, torch.Tensor]) -> torch.T
     hh = torch.empty(T, HP, **b16)
     xb = torch.empty(T, CP, **b16)
     stat_a, stat_b = torch.empty(T, **f32), torch.empty(T, **f32)
-    fused_mlp_ok = (CP == 192 and HP == 384 and T % 64 == 0 and T >= 64 * torch.cuda.get_device_properties(dev).multi_processor_count)
+    # out = x_res + fc2(gelu(fc1(xn_in)))   (Mlp.forward :86-92 + the residual add) [+ the next LayerNorm of the new rows]
+    mlp = host_pass.mlp_inference(st, P, T, CP, HP, hh, fused=host_pass.fused_mlp_ok(dev, CP, HP, T) and T % 64 == 0)
 
     ln_fusable = CP in (64, 128, 192)          # the LayerNorm that consumes a freshly written row rides in the producer's epilogue
     xn_a, xn_b = torch.empty(T, CP, **b16), torch.empty(T, CP, **b16)
 
     def next_norm(norm, dst):
         return dict(out=dst, mean=stat_a, rstd=stat_b, gamma=norm.weight, beta=norm.bias, C=C_) if (ln_fusable and norm is not None) else None
-
-    def mlp(pre, xn_in, x_res, out, out_b=None, nn_=None):
-        """out = x_res + fc2(gelu(fc1(xn_in)))   (Mlp.forward :86-92 + the residual add) [+ the next LayerNorm of the new rows]"""
-        if fused_mlp_ok:
-            args = (None, None, None, None, None, 0) if nn_ is None else (nn_["out"].data_ptr(), nn_["mean"].data_ptr(), nn_["rstd"].data_ptr(),
-                                                                       nn_["gamma"].data_ptr(), nn_["beta"].data_ptr(), nn_["C"])
-            check(L.srk_mlp_fused_fwd(xn_in.data_ptr(), P[pre + "W1"].data_ptr(), P[pre + "b1"].data_ptr(), P[pre + "W2"].data_ptr(),
-                                      P[pre + "b2"].data_ptr(), x_res.data_ptr(), out.data_ptr(), _ptr(out_b), *args, T, st))
-        else:
-            _gemm(st, _lib.LD_ROWS, _lib.EP_GELU, xn_in, P[pre + "W1"], T, HP, CP, lda=CP, bias=P[pre + "b1"], outb2=hh)
-            _gemm(st, _lib.LD_ROWS, _lib.EP_RES, hh, P[pre + "W2"], T, CP, HP, lda=HP, bias=P[pre + "b2"], res=x_res, outf=out, outb=out_b, xn=nn_)
 
     xn1 = None            # norm1 of the upcoming block when the previous kernel already produced it in its epilogue
     for li, layer in enumerate(m.layers):
@@ -711,20 +684,4 @@ def _hat_forward(m: HAT, x: torch.Tensor, P: Dict[str, torch.Tensor]) -> torch.T
         xn1 = xn_a if nn_ is not None else None
 
     xnf = xn1 if xn1 is not None else ops.layernorm_fwd(cur, m.norm.weight, m.norm.bias, C_)[0]                  # norm :958
-    fb = torch.empty(T, CP, **b16)
-    _gemm(st, _lib.LD_CONV3, _lib.EP_RES_BF16, xnf, P["Wcab"], T, CP, 9 * CP, conv=(B, H, W, CP), bias=P["bcab"], res=f0, outb=fb)
-    t1 = torch.empty(T, 64, **b16)
-    _gemm(st, _lib.LD_CONV3, _lib.EP_LRELU, fb, P["Wbefore"], T, 64, 9 * CP, conv=(B, H, W, CP), bias=P["bbefore"], outb=t1, scale=0.01)
-    src, h, w = t1, H, W
-    k = 0
-    while f"Wup{k}" in P:
-        r = int(P[f"rup{k}"])
-        N = P[f"Wup{k}"].shape[0]
-        up = torch.empty(B * h * r * w * r, 64, **b16)
-        _gemm(st, _lib.LD_CONV3, _lib.EP_PS, src, P[f"Wup{k}"], B * h * w, N, 9 * 64, conv=(B, h, w, 64), bias=P[f"bup{k}"], outb=up, r=r, Cs=64, ldo=N)
-        src, h, w, k = up, h * r, w * r, k + 1
-    y = torch.empty(B, Cin, H0 * s, W0 * s, **f32)
-    mean4 = (m.mean.flatten().tolist() if m.in_chans == 3 else [0.0, 0.0, 0.0]) + [0.0]
-    _gemm(st, _lib.LD_CONV3, _lib.EP_IMG, src, P["Wlast"], B * h * w, 16, 9 * 64, conv=(B, h, w, 64), bias=P["blast"], outf=y,
-          img=dict(inv_range=1.0 / float(m.img_range), Cimg=Cin, Hc=H0 * s, Wc=W0 * s, mean=mean4))
-    return y
+    return host_pass.tail_forward(m, P, st, xnf, f0, img4, B, Cin, H0, W0, H, W)

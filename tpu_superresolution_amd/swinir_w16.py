@@ -22,16 +22,13 @@ are padded to a multiple of 64 rows, so that the persistent GEMMs and the fused 
 """
 from __future__ import annotations
 
-import ctypes as C
-import math
 from typing import Dict
 
 import torch
-import torch.nn as nn
 
-from . import _lib, ops
+from . import _lib, host_pass as hp, ops
 from ._lib import SrkUnsupported, check, lib
-from .hat_arch import _gemm, _head_map, _pack_conv, _pack_linear, _pack_vec, _ps_map, _ptr, _qkv_rows, _rup, batched_pack
+from .hat_arch import _gemm, _head_map, _pack_conv, _pack_linear, _pack_vec, _qkv_rows, _rup, batched_pack
 
 
 def unsupported_reason(m) -> str:
@@ -78,26 +75,7 @@ def pack(m, device) -> Dict[str, torch.Tensor]:
                 P[pre + "b2"] = _pack_vec(blk.mlp.fc2.bias, CP)
             P[f"{li}.Wconv"] = _pack_conv(layer.conv.weight, CP, CP)
             P[f"{li}.bconv"] = _pack_vec(layer.conv.bias, CP)
-        P["Wcab"] = _pack_conv(m.conv_after_body.weight, CP, CP)
-        P["bcab"] = _pack_vec(m.conv_after_body.bias, CP)
-        if m.upsampler == "pixelshuffle":
-            P["Wbefore"] = _pack_conv(m.conv_before_upsample[0].weight, 64, CP)
-            P["bbefore"] = _pack_vec(m.conv_before_upsample[0].bias, 64)
-            k = 0
-            for mod in m.upsample:
-                if isinstance(mod, nn.Conv2d):
-                    r = int(round(math.sqrt(mod.weight.shape[0] // 64)))
-                    pm = _ps_map(mod.weight.shape[0], r, 64, device)
-                    P[f"Wup{k}"] = _pack_conv(mod.weight, mod.weight.shape[0], 64, row_map=pm)
-                    P[f"bup{k}"] = _pack_vec(mod.bias, mod.weight.shape[0], row_map=pm)
-                    P[f"rup{k}"] = torch.tensor(r)
-                    k += 1
-            P["Wlast"] = _pack_conv(m.conv_last.weight, 16, 64)
-            P["blast"] = _pack_vec(m.conv_last.bias, 16)
-        else:       # 'pixelshuffledirect': UpsampleOneStep's conv; '': conv_last (embed_dim -> in_chans, :832-836)
-            direct = m.upsample[0] if m.upsampler == "pixelshuffledirect" else m.conv_last
-            P["Wdirect"] = _pack_conv(direct.weight, 16, CP)
-            P["bdirect"] = _pack_vec(direct.bias, 16)
+        hp.pack_tail(P, m, CP, device)
         pk.resolve(P)
     m._w16_packed, m._w16_version, m._w16_device = P, ver, device
     return P
@@ -119,7 +97,7 @@ def _forward(m, x: torch.Tensor, P: Dict[str, torch.Tensor]) -> torch.Tensor:
     dev = x.device
     st = torch.cuda.current_stream(dev).cuda_stream
     B, Cin, H0, W0 = x.shape
-    ws, s = m.window_size, m.upscale
+    ws = m.window_size
     H, W = _rup(H0, ws), _rup(W0, ws)
     if (H - H0 >= H0) or (W - W0 >= W0):
         raise RuntimeError(f"reflect padding {H0}x{W0} -> {H}x{W} needs pad < size (as torch 'reflect')")
@@ -128,18 +106,11 @@ def _forward(m, x: torch.Tensor, P: Dict[str, torch.Tensor]) -> torch.Tensor:
     HP = _rup(int(C_ * m.mlp_ratio), 64)
     f32, b16 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.bfloat16, device=dev)
     L = lib()
-    mean3 = (C.c_float * 3)(*(m.mean.flatten().tolist() if m.in_chans == 3 else [0.0, 0.0, 0.0]))
-    img4 = torch.empty(T, 4, **f32)
-    check(L.srk_img_prep(x.data_ptr(), img4.data_ptr(), B, Cin, H0, W0, H, W, float(m.img_range), C.byref(mean3), st))
     # token rows: the persistent GEMMs and the fused MLP cover multiples of 64 rows.  Windows of 8 x 8 / 16 x 16 tokens make T one; with
     # smaller windows (8 x 63 x 63 = 31752 tokens) the row buffers get TR = T rounded up to 64 rows and every row-wise kernel runs on all
     # TR: the padding rows are never read by the attention or the 3x3 convs (their geometry is B x H x W) and never reach the output
     TR = _rup(T, 64)
-    f0 = torch.empty(TR, CP, **f32)
-    if TR > T:
-        f0[T:].zero_()
-    check(L.srk_stem_conv(img4.data_ptr(), m.conv_first.weight.data_ptr(), m.conv_first.bias.data_ptr(), f0.data_ptr(), B, H, W, Cin, C_, CP, st))
-    _, cur, _, _ = ops.layernorm_fwd(f0, m.patch_embed.norm.weight, m.patch_embed.norm.bias, C_, out_bf16=False, out_f32=True)
+    img4, f0, cur = hp.head_forward(m, x, m.patch_embed.norm, st, H, W, TR=TR)
 
     CAmax = max(h * 32 for h in m.heads)
     qkv, ao = torch.empty(TR, 3 * CAmax, **b16), torch.empty(TR, CAmax, **b16)
@@ -148,21 +119,11 @@ def _forward(m, x: torch.Tensor, P: Dict[str, torch.Tensor]) -> torch.Tensor:
     xn2, hh, xb = torch.empty(TR, CP, **b16), torch.empty(TR, HP, **b16), torch.empty(TR, CP, **b16)
     stat_a, stat_b = torch.empty(TR, **f32), torch.empty(TR, **f32)
     xn_a, xn_b = torch.empty(TR, CP, **b16), torch.empty(TR, CP, **b16)
-    fused_mlp_ok = (CP == 192 and HP == 384 and TR % 64 == 0 and TR >= 64 * torch.cuda.get_device_properties(dev).multi_processor_count)
+    mlp = hp.mlp_inference(st, P, TR, CP, HP, hh, fused=hp.fused_mlp_ok(dev, CP, HP, TR))
     ln_fusable = CP in (64, 128, 192)
 
     def next_norm(norm, dst):
         return dict(out=dst, mean=stat_a, rstd=stat_b, gamma=norm.weight, beta=norm.bias, C=C_) if ln_fusable else None
-
-    def mlp(pre, xn_in, x_res, out, out_b=None, nn_=None):
-        if fused_mlp_ok:
-            args = (None, None, None, None, None, 0) if nn_ is None else (nn_["out"].data_ptr(), nn_["mean"].data_ptr(), nn_["rstd"].data_ptr(),
-                                                                       nn_["gamma"].data_ptr(), nn_["beta"].data_ptr(), nn_["C"])
-            check(L.srk_mlp_fused_fwd(xn_in.data_ptr(), P[pre + "W1"].data_ptr(), P[pre + "b1"].data_ptr(), P[pre + "W2"].data_ptr(),
-                                      P[pre + "b2"].data_ptr(), x_res.data_ptr(), out.data_ptr(), _ptr(out_b), *args, TR, st))
-        else:
-            _gemm(st, _lib.LD_ROWS, _lib.EP_GELU, xn_in, P[pre + "W1"], TR, HP, CP, lda=CP, bias=P[pre + "b1"], outb2=hh)
-            _gemm(st, _lib.LD_ROWS, _lib.EP_RES, hh, P[pre + "W2"], TR, CP, HP, lda=HP, bias=P[pre + "b2"], res=x_res, outf=out, outb=out_b, xn=nn_)
 
     xn1 = None
     for li, layer in enumerate(m.layers):
@@ -204,23 +165,4 @@ def _forward(m, x: torch.Tensor, P: Dict[str, torch.Tensor]) -> torch.Tensor:
         xn1 = xn_a if nn_ is not None else None
 
     xnf = xn1 if xn1 is not None else ops.layernorm_fwd(cur, m.norm.weight, m.norm.bias, C_)[0]
-    fb = torch.empty(T, CP, **b16)
-    _gemm(st, _lib.LD_CONV3, _lib.EP_RES_BF16, xnf, P["Wcab"], T, CP, 9 * CP, conv=(B, H, W, CP), bias=P["bcab"], res=f0, outb=fb)
-    y = torch.empty(B, Cin, H0 * s, W0 * s, **f32)
-    mean4 = (m.mean.flatten().tolist() if m.in_chans == 3 else [0.0, 0.0, 0.0]) + [0.0]
-    img = dict(inv_range=1.0 / float(m.img_range), Cimg=Cin, Hc=H0 * s, Wc=W0 * s, mean=mean4)
-    if m.upsampler == "pixelshuffle":
-        t1 = torch.empty(T, 64, **b16)
-        _gemm(st, _lib.LD_CONV3, _lib.EP_LRELU, fb, P["Wbefore"], T, 64, 9 * CP, conv=(B, H, W, CP), bias=P["bbefore"], outb=t1, scale=0.01)
-        src, h, w, k = t1, H, W, 0
-        while f"Wup{k}" in P:
-            r = int(P[f"rup{k}"])
-            N = P[f"Wup{k}"].shape[0]
-            up = torch.empty(B * h * r * w * r, 64, **b16)
-            _gemm(st, _lib.LD_CONV3, _lib.EP_PS, src, P[f"Wup{k}"], B * h * w, N, 9 * 64, conv=(B, h, w, 64), bias=P[f"bup{k}"], outb=up, r=r, Cs=64, ldo=N)
-            src, h, w, k = up, h * r, w * r, k + 1
-        _gemm(st, _lib.LD_CONV3, _lib.EP_IMG, src, P["Wlast"], B * h * w, 16, 9 * 64, conv=(B, h, w, 64), bias=P["blast"], outf=y, img=img)
-    else:       # UpsampleOneStep (:594-615), or '' with upscale 1: x + conv_last(res), x = the normalised, padded input (:832-836)
-        _gemm(st, _lib.LD_CONV3, _lib.EP_PS_IMG, fb, P["Wdirect"], T, 16, 9 * CP, conv=(B, H, W, CP), bias=P["bdirect"], outf=y, img=dict(img), r=s,
-              res=img4 if m.upsampler == "" else None)
-    return y
+    return hp.tail_forward(m, P, st, xnf, f0, img4, B, Cin, H0, W0, H, W)
