@@ -2,6 +2,7 @@
 plan bookkeeping (pure host code) matches the reference's parameter schema, and the product path
 fails loudly without a GPU."""
 import ctypes as C
+import os
 
 import pytest
 import torch
@@ -26,6 +27,21 @@ def test_library_exports_every_declared_symbol(lib):
     undeclared = [n for n in lib._SIGNATURES if n not in names]
     assert not undeclared, undeclared
     assert b"gfx950" in handle.srk_version()
+
+
+def test_lds_limits_are_raised_in_one_place():
+    """Launchers reserve dynamic LDS through srk_reserve_lds (csrc/api.hip): the two HIP runtime calls behind it are written
+    in exactly one .hip file, so a hand-written copy of the reserve-once-per-device block fails here."""
+    from tpu_superresolution_amd import build
+    users = {call: [] for call in ("hipFuncSetAttribute", "hipFuncGetAttributes")}
+    for name in sorted(os.listdir(build.CSRC)):
+        if name.endswith(".hip"):
+            with open(os.path.join(build.CSRC, name)) as f:
+                text = f.read()
+            for call in users:
+                if call in text:
+                    users[call].append(name)
+    assert users == {"hipFuncSetAttribute": ["api.hip"], "hipFuncGetAttributes": ["api.hip"]}, users
 
 
 @pytest.mark.parametrize("cfg", [O.SwinIRConfig.classical_x4(), O.SwinIRConfig.light_x2()])

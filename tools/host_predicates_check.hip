@@ -1,0 +1,42 @@
+// Edge values for the host argument predicates of csrc/common.h (srk_aligned, srk_ranges_overlap, srk_qkv_layout_ok), as a
+// stand-alone program for a sanitizer build; needs no GPU:
+//   hipcc --offload-arch=gfx950 --cuda-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
+//         -Xarch_host -fno-sanitize-recover=undefined tools/host_predicates_check.hip -o /tmp/host_predicates_check && /tmp/host_predicates_check
+#include <stdio.h>
+
+#include "../tpu_superresolution_amd/csrc/common.h"
+
+static int failures = 0;
+#define EXPECT(cond)                                      \
+  do {                                                    \
+    const bool ok_ = (cond);                              \
+    printf("%s  %s\n", ok_ ? "ok  " : "FAIL", #cond);     \
+    failures += !ok_;                                     \
+  } while (0)
+
+int main() {
+  const auto ptr = [](uintptr_t v) { return reinterpret_cast<const void*>(v); };
+  const uintptr_t top = ~(uintptr_t)0;
+  // alignment: null is aligned to everything; the last addresses of the range
+  EXPECT(srk_aligned(nullptr, 16) && srk_aligned(nullptr, 4));
+  EXPECT(srk_aligned(ptr(64), 16) && !srk_aligned(ptr(72), 16) && srk_aligned(ptr(72), 8) && !srk_aligned(ptr(68), 8) && srk_aligned(ptr(68), 4));
+  EXPECT(srk_aligned(ptr(top - 15), 16) && !srk_aligned(ptr(top), 4) && !srk_aligned(ptr(top - 7), 16) && srk_aligned(ptr(top - 7), 8));
+  // overlap: empty ranges overlap nothing, not even themselves
+  EXPECT(!srk_ranges_overlap(ptr(100), 0, ptr(100), 0) && !srk_ranges_overlap(ptr(100), 0, ptr(100), 8) && !srk_ranges_overlap(ptr(100), 8, ptr(104), 0));
+  EXPECT(!srk_ranges_overlap(nullptr, 0, nullptr, 0) && srk_ranges_overlap(nullptr, 1, nullptr, 1));
+  // ranges that touch do not overlap; one shared byte does; either order
+  EXPECT(!srk_ranges_overlap(ptr(100), 8, ptr(108), 8) && !srk_ranges_overlap(ptr(108), 8, ptr(100), 8));
+  EXPECT(srk_ranges_overlap(ptr(100), 9, ptr(108), 8) && srk_ranges_overlap(ptr(108), 8, ptr(100), 9));
+  EXPECT(srk_ranges_overlap(ptr(100), 100, ptr(150), 1) && srk_ranges_overlap(ptr(150), 1, ptr(100), 100) && srk_ranges_overlap(ptr(100), 4, ptr(100), 4));
+  // the top of the address range: a + n would wrap to 0 here
+  EXPECT(!srk_ranges_overlap(ptr(top - 15), 8, ptr(top - 7), 8) && srk_ranges_overlap(ptr(top - 15), 9, ptr(top - 7), 8));
+  EXPECT(!srk_ranges_overlap(ptr(16), 16, ptr(top - 15), 16) && !srk_ranges_overlap(ptr(top - 15), 16, ptr(16), 16));
+  EXPECT(srk_ranges_overlap(ptr(0), (size_t)top, ptr(top - 1), 1) && !srk_ranges_overlap(ptr(0), (size_t)top, ptr(top), 1));
+  // q/k/v layout: the smallest valid one, then each clause broken in turn
+  EXPECT(srk_qkv_layout_ok(1, 32, 96, 32, 8) && srk_qkv_layout_ok(6, 192, 576, 192, 8) && srk_qkv_layout_ok(6, 192, 584, 196, 4));
+  EXPECT(!srk_qkv_layout_ok(0, 32, 96, 32, 8) && !srk_qkv_layout_ok(-1, 32, 96, 32, 8) && !srk_qkv_layout_ok(2, 32, 96, 64, 8));
+  EXPECT(!srk_qkv_layout_ok(1, 48, 144, 32, 8) && !srk_qkv_layout_ok(1, 32, 95, 32, 8) && !srk_qkv_layout_ok(1, 32, 100, 32, 8));
+  EXPECT(!srk_qkv_layout_ok(1, 32, 96, 31, 8) && !srk_qkv_layout_ok(1, 32, 96, 36, 8) && srk_qkv_layout_ok(1, 32, 96, 36, 4));
+  printf("%d failure(s)\n", failures);
+  return failures != 0;
+}

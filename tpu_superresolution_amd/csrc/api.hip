@@ -59,6 +59,35 @@ void srk_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+int srk_reserve_lds_fn(const void* fn, int bytes, SrkLdsState& st, bool refuse_spills, const char* err_fmt, ...) {
+  signed char& s = st.here();
+  if (s) return s > 0 ? SRK_OK : SRK_NOT_COVERED;
+  hipFuncAttributes attr;
+  const bool queried = !refuse_spills || hipFuncGetAttributes(&attr, fn) == hipSuccess;
+  if (queried && refuse_spills && attr.localSizeBytes > 0) {
+    s = -1;
+    return SRK_NOT_COVERED;
+  }
+  if (queried && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess) {
+    s = 1;
+    return SRK_OK;
+  }
+  if (!err_fmt) {
+    s = -1;
+    return SRK_NOT_COVERED;
+  }
+  if (queried) {
+    va_list ap;
+    va_start(ap, err_fmt);
+    vsnprintf(g_err, sizeof(g_err), err_fmt, ap);
+    va_end(ap);
+  } else {   // "<site>: cannot query the kernel", the site's name being what err_fmt has in front of its colon
+    const char* colon = strchr(err_fmt, ':');
+    srk_set_error("%.*s: cannot query the kernel", colon ? (int)(colon - err_fmt) : (int)strlen(err_fmt), err_fmt);
+  }
+  return SRK_E_LAUNCH;
+}
+
 int srk_check_launch(const char* what) {
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -101,10 +130,8 @@ void srk_probe_post(int family, hipStream_t stream) {
   ++g_probe.count;
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 #define REQ_PTR(p) SRK_REQUIRE((p) != nullptr, SRK_E_NULL, "%s: null pointer '%s'", __func__, #p)
-#define REQ_ALIGN(p) SRK_REQUIRE(aligned16(p), SRK_E_ALIGN, "%s: '%s' is not 16-byte aligned", __func__, #p)
+#define REQ_ALIGN(p) SRK_REQUIRE(srk_aligned(p, 16), SRK_E_ALIGN, "%s: '%s' is not 16-byte aligned", __func__, #p)
 
 static int make_geom(const srk_win_geom* g, WinGeom* out, const char* fn) {
   SRK_REQUIRE(g->H > 0 && g->W > 0 && g->H % 8 == 0 && g->W % 8 == 0, SRK_E_SHAPE, "%s: H,W must be multiples of 8 (got %d,%d)",
@@ -291,7 +318,7 @@ int srk_cast_f32_bf16(const float* x, uint16_t* y, int64_t n, srk_stream_t strea
   REQ_PTR(x); REQ_PTR(y);
   SRK_REQUIRE(n > 0 && n % 4 == 0, SRK_E_SHAPE, "cast_f32_bf16: n=%lld must be a positive multiple of 4", (long long)n);
   REQ_ALIGN(x);
-  SRK_REQUIRE((reinterpret_cast<uintptr_t>(y) & 7) == 0, SRK_E_ALIGN, "cast_f32_bf16: 'y' is not 8-byte aligned");
+  SRK_REQUIRE(srk_aligned(y, 8), SRK_E_ALIGN, "cast_f32_bf16: 'y' is not 8-byte aligned");
   return srk_launch_cast_f32_bf16(x, y, n, (hipStream_t)stream);
 }
 
@@ -474,8 +501,7 @@ int srk_dihedral_f32(const float* in, float* out, const int32_t* ops, int op_all
   else SRK_REQUIRE(op_all >= 0 && op_all <= 7, SRK_E_SHAPE, "dihedral: op must be in 0..7 (got %d)", op_all);
   const double bytes = 4.0 * B * C * H * W;
   SRK_REQUIRE(bytes < 9.0e18, SRK_E_SHAPE, "dihedral: B=%d C=%d H=%d W=%d is too large", B, C, H, W);
-  const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out), n = (uintptr_t)bytes;
-  SRK_REQUIRE(a + n <= b || b + n <= a, SRK_E_SHAPE, "dihedral: in and out overlap (the transform is not done in place)");
+  SRK_REQUIRE(!srk_ranges_overlap(in, (size_t)bytes, out, (size_t)bytes), SRK_E_SHAPE, "dihedral: in and out overlap (the transform is not done in place)");
   return srk_launch_dihedral_f32(in, out, reinterpret_cast<const int*>(ops), op_all, B, C, H, W, alpha, accumulate, (hipStream_t)stream);
 }
 
@@ -487,8 +513,7 @@ int srk_resize_aa_f32(const float* x, float* out, int B, int C, int H, int W, in
   const double planes = (double)B * C, ib = 4.0 * planes * H * W, ob = 4.0 * planes * Ho * Wo;
   SRK_REQUIRE(planes <= 2147483647.0 && ib < 9.0e18 && ob < 9.0e18, SRK_E_SHAPE, "resize_aa: B=%d C=%d H=%d W=%d Ho=%d Wo=%d is too large", B, C, H,
               W, Ho, Wo);
-  const uintptr_t a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(out);
-  SRK_REQUIRE(a + (uintptr_t)ib <= b || b + (uintptr_t)ob <= a, SRK_E_SHAPE, "resize_aa: x and out overlap (the resize is not done in place)");
+  SRK_REQUIRE(!srk_ranges_overlap(x, (size_t)ib, out, (size_t)ob), SRK_E_SHAPE, "resize_aa: x and out overlap (the resize is not done in place)");
   SRK_REQUIRE((long long)H <= 8LL * Ho && (long long)W <= 8LL * Wo, SRK_E_UNSUPPORTED,
               "resize_aa: %d x %d -> %d x %d shrinks an axis by more than 8x (more than 33 taps)", H, W, Ho, Wo);
   return srk_launch_resize_aa_f32(x, out, B * C, H, W, Ho, Wo, quant_bits, (hipStream_t)stream);
@@ -523,8 +548,7 @@ int srk_degrade_blind_f32(const float* x, float* out, const int64_t* par4, int B
   SRK_REQUIRE(quant_bits == 0 || quant_bits == 8, SRK_E_SHAPE, "degrade_blind: quant_bits must be 0 or 8 (got %d)", quant_bits);
   const double planes = (double)B * C, ib = 4.0 * planes * H * W, ob = ib / ((double)scale * scale);
   SRK_REQUIRE(planes <= 2147483647.0 && ib < 9.0e18, SRK_E_SHAPE, "degrade_blind: B=%d C=%d H=%d W=%d is too large", B, C, H, W);
-  const uintptr_t a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(out);
-  SRK_REQUIRE(a + (uintptr_t)ib <= b || b + (uintptr_t)ob <= a, SRK_E_SHAPE, "degrade_blind: x and out overlap (the filter is not run in place)");
+  SRK_REQUIRE(!srk_ranges_overlap(x, (size_t)ib, out, (size_t)ob), SRK_E_SHAPE, "degrade_blind: x and out overlap (the filter is not run in place)");
   return srk_launch_degrade_blind_f32(x, out, reinterpret_cast<const long long*>(par4), B, C, H, W, scale, quant_bits, (hipStream_t)stream);
 }
 
@@ -536,8 +560,7 @@ int srk_jpeg_roundtrip_f32(const float* x, float* out, const int32_t* quality, i
   SRK_REQUIRE(subsample == 0 || subsample == 1, SRK_E_SHAPE, "jpeg_roundtrip: subsample must be 0 (4:4:4) or 1 (4:2:0) (got %d)", subsample);
   const double bytes = 4.0 * B * C * H * W;
   SRK_REQUIRE(bytes < 9.0e18, SRK_E_SHAPE, "jpeg_roundtrip: B=%d C=%d H=%d W=%d is too large", B, C, H, W);
-  const uintptr_t a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(out);
-  SRK_REQUIRE(a + (uintptr_t)bytes <= b || b + (uintptr_t)bytes <= a, SRK_E_SHAPE, "jpeg_roundtrip: x and out overlap (the blocks are not transformed in place)");
+  SRK_REQUIRE(!srk_ranges_overlap(x, (size_t)bytes, out, (size_t)bytes), SRK_E_SHAPE, "jpeg_roundtrip: x and out overlap (the blocks are not transformed in place)");
   return srk_launch_jpeg_roundtrip_f32(x, out, reinterpret_cast<const int*>(quality), B, C, H, W, subsample, reinterpret_cast<short*>(coef_out),
                                        (hipStream_t)stream);
 }
@@ -558,8 +581,7 @@ static int tile_args(const char* fn, const float* tiles, const float* img, int t
   const double planes = (double)B * C, tb = 4.0 * n * planes * th * tw, ib = 4.0 * planes * H * W;
   SRK_REQUIRE(planes <= 2147483647.0 && tb < 9.0e18 && ib < 9.0e18, SRK_E_SHAPE, "%s: n=%d B=%d C=%d H=%d W=%d th=%d tw=%d is too large", fn, n,
               B, C, H, W, th, tw);
-  const uintptr_t a = reinterpret_cast<uintptr_t>(tiles), b = reinterpret_cast<uintptr_t>(img);
-  SRK_REQUIRE(a + (uintptr_t)tb <= b || b + (uintptr_t)ib <= a, SRK_E_SHAPE, "%s: the tiles and the image overlap", fn);
+  SRK_REQUIRE(!srk_ranges_overlap(tiles, (size_t)tb, img, (size_t)ib), SRK_E_SHAPE, "%s: the tiles and the image overlap", fn);
   return SRK_OK;
 }
 

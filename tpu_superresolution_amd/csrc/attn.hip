@@ -11,7 +11,7 @@
 // probabilities are already in MFMA B-operand form (k = key index) for the P.V product.
 // Operands that are needed "transposed" (V^T, Q^T, K^T, dO^T, P, dS) are read from small
 // wave-private LDS tiles with ds_read_b64_tr_b16.
-#include "common.h"
+#include "attn_common.h"
 #include "wgrad.h"
 
 namespace {
@@ -28,10 +28,6 @@ __device__ __forceinline__ void stage_tile_64x32(bf16_t* dst, const bf16_t* src,
     const uint4 v = *reinterpret_cast<const uint4*>(src + row * row_stride + ch * 8);
     *reinterpret_cast<uint4*>(dst + row * TS + ch * 8) = v;
   }
-}
-
-__device__ __forceinline__ bf16x8_t cat4(bf16x4_t lo, bf16x4_t hi) {
-  return bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
 
 // transposed fragment: lane (r16, g) gets T[k = k0 + 8g + jj][col c0 + r16], jj = 0..7 (natural k order)
@@ -309,12 +305,11 @@ __global__ __launch_bounds__(256, SRK_ATTN_BWD_WGS) void attn_bwd_kernel(const b
 #pragma unroll
         for (int e = 0; e < 4; ++e) mx = fmaxf(mx, s[jt][e]);
       mx = xmax4(mx);
-      constexpr float L2E = 1.4426950408889634f;      // exp(x - m) = exp2(x log2e - m log2e), as softmax_numerators
-      const float mxl = mx * L2E;
+      const float mxl = mx * SRK_L2E;
       f32x4_t a4 = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int jt = 0; jt < 4; ++jt) {
-        const f32x4_t t = s[jt] * L2E - mxl;
+        const f32x4_t t = s[jt] * SRK_L2E - mxl;
 #pragma unroll
         for (int e = 0; e < 4; ++e) s[jt][e] = __builtin_amdgcn_exp2f(t[e]);
         a4 += s[jt];

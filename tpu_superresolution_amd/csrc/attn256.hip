@@ -19,7 +19,7 @@
 //                 MFMA's K slots), V^T comes from LDS with the transposing read (ds_read_b64_tr_b16), same key order.
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "attn_common.h"
 #include "kernels.h"
 
 namespace {
@@ -43,7 +43,6 @@ struct Win256Params {
   float scale;
 };
 
-__device__ __forceinline__ int region_label(int v, int n, int w, int s) { return v < n - w ? 0 : (v < n - s ? 1 : 2); }
 
 // TABLE: the bias of a (query, key) pair is looked up in the head's column of the bias table, staged once in LDS (3.8 KB / 6 KB),
 // through the closed-form index -- rpi_sa[p][k] = (yp - yk + ws - 1)(2 ws - 1) + (xp - xk + ws - 1) (hat_arch.py:881-894),
@@ -137,7 +136,7 @@ __global__ __launch_bounds__(256, (NT > 16 ? 1 : 3)) void win256_attn_fwd_kernel
     if (x >= p.Wp) x -= p.Wp;
     const bool qreal = y < p.H && x < p.W;                 // a query in the zero padding has no token: its row is not stored
     const long long qtok = tok0 + (long long)y * p.W + x;
-    const int qlab = need_mask ? region_label(wy * p.wh + qy, p.Hp, p.wh, p.sy) * 3 + region_label(wx * p.ww + qx, p.Wp, p.ww, p.sx) : 0;
+    const int qlab = need_mask ? region3(wy * p.wh + qy, p.Hp, p.wh, p.sy) * 3 + region3(wx * p.ww + qx, p.Wp, p.ww, p.sx) : 0;
     const bf16x8_t qf = qf_next;
     if (qt < QT - 1) qf_next = load_q(qt + 1);
 
@@ -181,18 +180,18 @@ __global__ __launch_bounds__(256, (NT > 16 ? 1 : 3)) void win256_attn_fwd_kernel
       if (need_mask) {                                                  // border windows only; any window shape with ww % 4 == 0
         const int cm = 16 * j + 4 * g;
         const int kym = cm / p.ww, kxm = cm - kym * p.ww;
-        const int lh = region_label(wy * p.wh + kym, p.Hp, p.wh, p.sy) * 3;
+        const int lh = region3(wy * p.wh + kym, p.Hp, p.wh, p.sy) * 3;
         const int xb = wx * p.ww + kxm;
-        if (lh + region_label(xb, p.Wp, p.ww, p.sx) != qlab) v0 += -100.0f;          // hat_arch.py:939 (-100, not -inf)
-        if (lh + region_label(xb + 1, p.Wp, p.ww, p.sx) != qlab) v1 += -100.0f;
-        if (lh + region_label(xb + 2, p.Wp, p.ww, p.sx) != qlab) v2 += -100.0f;
-        if (lh + region_label(xb + 3, p.Wp, p.ww, p.sx) != qlab) v3 += -100.0f;
+        if (lh + region3(xb, p.Wp, p.ww, p.sx) != qlab) v0 += -100.0f;          // hat_arch.py:939 (-100, not -inf)
+        if (lh + region3(xb + 1, p.Wp, p.ww, p.sx) != qlab) v1 += -100.0f;
+        if (lh + region3(xb + 2, p.Wp, p.ww, p.sx) != qlab) v2 += -100.0f;
+        if (lh + region3(xb + 3, p.Wp, p.ww, p.sx) != qlab) v3 += -100.0f;
       }
       s[j] = f32x4_t{v0, v1, v2, v3};
       mx = fmaxf(mx, fmaxf(fmaxf(v0, v1), fmaxf(v2, v3)));
     }
     mx = xrow_max4(mx);
-    constexpr float L2E = 1.4426950408889634f;      // exp(x - m) = exp2(x log2e - m log2e): one fma + v_exp_f32 per score (as softmax_numerators)
+    constexpr float L2E = SRK_L2E;                  // a local copy of SRK_L2E: as a namespace-scope constant the compiler schedules this kernel differently ("What the C++ side shares")
     const float mxl = mx * L2E;
     f32x4_t a4 = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -234,15 +233,10 @@ __global__ __launch_bounds__(256, (NT > 16 ? 1 : 3)) void win256_attn_fwd_kernel
 template <int NT, bool OCA, bool TABLE, int QT = 4>
 int launch(const Win256Params& p, hipStream_t stream) {
   constexpr size_t lds = (size_t)2 * NT * 16 * KP * sizeof(bf16_t) + (TABLE ? 1536 * sizeof(float) : 0);
-  static SrkPerDevice<bool> configured_pd; bool& configured = configured_pd.here();
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&win256_attn_fwd_kernel<NT, OCA, TABLE, QT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess) {
-      srk_set_error("win256 attention: cannot reserve %zu bytes of LDS", lds);
-      return SRK_E_LAUNCH;
-    }
-    configured = true;
-  }
+  static SrkLdsState reserved;
+  if (const int rc = srk_reserve_lds(&win256_attn_fwd_kernel<NT, OCA, TABLE, QT>, lds, reserved, false,
+                                     "win256 attention: cannot reserve %zu bytes of LDS", lds))
+    return rc;
   const long long grid = (long long)p.B * p.nWh * p.nWw * p.nH;
   SRK_REQUIRE(grid > 0 && grid < (1LL << 31), SRK_E_SHAPE, "win256 attention: bad grid %lld", grid);
   hipLaunchKernelGGL((win256_attn_fwd_kernel<NT, OCA, TABLE, QT>), dim3((unsigned)grid), dim3(256), lds, stream, p);
@@ -270,7 +264,7 @@ int srk_launch_win_attn_fwd_padded(const bf16_t* qkv, int ldq, int CA, const flo
               "overlapping cross-attention takes unpadded maps and 16x16 windows");
   // CA is the column distance between the q, k and v blocks of a row; a caller may run a SUBSET of the heads (DAT's two branches take
   // heads 0..nH/2-1 and nH/2..nH-1 with different window shapes) by offsetting qkv / out by 32 * first_head
-  SRK_REQUIRE(nH > 0 && CA >= nH * 32 && CA % 32 == 0 && ldq >= 3 * CA && ldq % 8 == 0 && ldo >= nH * 32 && ldo % 4 == 0, SRK_E_SHAPE,
+  SRK_REQUIRE(srk_qkv_layout_ok(nH, CA, ldq, ldo, 4), SRK_E_SHAPE,
               "win256 attention: bad layout nH=%d CA=%d ldq=%d ldo=%d", nH, CA, ldq, ldo);
   SRK_REQUIRE(sy >= 0 && sy < wh && sx >= 0 && sx < ww, SRK_E_SHAPE, "shift_size must in 0-window_size");
   Win256Params p;

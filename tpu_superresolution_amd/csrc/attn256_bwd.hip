@@ -25,22 +25,21 @@
 // summed by win256_table_reduce_kernel (32-window slices, one float atomic per element and slice).
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "attn_common.h"
 #include "kernels.h"
 
 namespace {
 
 // LDS layout of the [rows][32] bf16 tiles.  Overlapping form: row pitch 40 elements (as attn256.hip: 16-byte fragment reads of 16
-// consecutive rows hit 64 distinct banks).  Self-attention: unpadded 64-byte rows with the 16-byte chunk XOR-swizzled by tfs(row) --
-// the swizzle of attn_bwd_fused.hip, conflict-free for the row-fragment and both transposing read patterns -- so that the four
+// consecutive rows hit 64 distinct banks).  Self-attention: unpadded 64-byte rows with the 16-byte chunk XOR-swizzled by tfs(row)
+// (chunk_off of attn_common.h, which says what the swizzle is conflict-free for), so that the four
 // tiles take 64 KB (76 KB with the statistics and table columns: room for a second workgroup per CU once the pass-1 register
 // footprint -- ~380 with the 76 row-offset sums -- fits 256; until then the kernel runs one workgroup per CU).
 template <bool PAD>
 struct TileAddr {
   static constexpr int PITCH = PAD ? 40 : 32;
-  static __device__ __forceinline__ int tfs(int r) { return ((((r >> 2) ^ (r >> 3)) & 1) << 1) | (((r >> 3) ^ (r >> 1)) & 1); }
   // element offset of 16-byte chunk c (0..3) of row r
-  static __device__ __forceinline__ int chunk(int r, int c) { return PAD ? r * 40 + c * 8 : r * 32 + ((c ^ tfs(r)) << 3); }
+  static __device__ __forceinline__ int chunk(int r, int c) { return PAD ? r * 40 + c * 8 : chunk_off(r, c); }
 };
 
 struct Win256BwdParams {
@@ -58,11 +57,6 @@ struct Win256BwdParams {
   float scale;
 };
 
-__device__ __forceinline__ int region3(int v, int n, int w, int s) { return v < n - w ? 0 : (v < n - s ? 1 : 2); }
-
-__device__ __forceinline__ bf16x8_t b_cat4(bf16x4_t lo, bf16x4_t hi) {
-  return bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
 // transposed fragment in accumulator k order (slots (g, jj): rows k0 + 4 g + jj, jj < 4, and k0 + 16 + 4 g + jj - 4), columns
 // c0 .. c0 + 15 (c0 = 0 or 16): the lane supplies the address of row rb + (ll >> 2), columns c0 + 4 (ll & 3) ..
 template <bool PAD>
@@ -70,7 +64,7 @@ __device__ __forceinline__ bf16x8_t tr_acc(const bf16_t* tile, int k0, int c0, i
   const int g = lane >> 4, ll = lane & 15;
   const int ra = k0 + 4 * g + (ll >> 2), rb = ra + 16;
   const int c = (c0 >> 3) + ((ll & 3) >> 1), in = (ll & 1) << 2;
-  return b_cat4(lds_tr_read(tile + TileAddr<PAD>::chunk(ra, c) + in), lds_tr_read(tile + TileAddr<PAD>::chunk(rb, c) + in));
+  return cat4(lds_tr_read(tile + TileAddr<PAD>::chunk(ra, c) + in), lds_tr_read(tile + TileAddr<PAD>::chunk(rb, c) + in));
 }
 
 template <int NT, bool OCA>        // NT = key tiles of 16 (16: 256 keys, 36: 576 keys)
@@ -81,7 +75,7 @@ __global__ __launch_bounds__(256, 1) void win256_attn_bwd_kernel(const Win256Bwd
   constexpr int NK = NT * 16;
   constexpr int KW = OCA ? 24 : 16;
   constexpr int PAD = OCA ? 4 : 0;
-  constexpr float L2E = 1.4426950408889634f;
+  constexpr float L2E = SRK_L2E;                         // a local copy of SRK_L2E: as a namespace-scope constant the compiler schedules this kernel differently ("What the C++ side shares")
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   bf16_t* Ks = reinterpret_cast<bf16_t*>(smem);          // [NK][BP]
   bf16_t* Vs = Ks + NK * BP;                             // [NK][BP]
@@ -391,15 +385,10 @@ template <int NT, bool OCA>
 int launch_bwd(const Win256BwdParams& p, hipStream_t stream) {
   constexpr size_t lds = (size_t)(2 * NT * 16 + 512) * TileAddr<OCA>::PITCH * sizeof(bf16_t) + 256 * 4 * sizeof(float) +
                          2 * (OCA ? 1536 : 964) * sizeof(float);
-  static SrkPerDevice<bool> configured_pd; bool& configured = configured_pd.here();
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&win256_attn_bwd_kernel<NT, OCA>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess) {
-      srk_set_error("win256 attention backward: cannot reserve %zu bytes of LDS", lds);
-      return SRK_E_LAUNCH;
-    }
-    configured = true;
-  }
+  static SrkLdsState reserved;
+  if (const int rc = srk_reserve_lds(&win256_attn_bwd_kernel<NT, OCA>, lds, reserved, false,
+                                     "win256 attention backward: cannot reserve %zu bytes of LDS", lds))
+    return rc;
   const long long grid = (long long)p.B * p.nWh * p.nWw * p.nH;
   SRK_REQUIRE(grid > 0 && grid < (1LL << 31), SRK_E_SHAPE, "win256 attention backward: bad grid %lld", grid);
   hipLaunchKernelGGL((win256_attn_bwd_kernel<NT, OCA>), dim3((unsigned)grid), dim3(256), lds, stream, p);
@@ -421,7 +410,7 @@ int srk_launch_win256_attn_bwd(const bf16_t* qkv, int ldq, int CA, const float* 
                                int overlap, hipStream_t stream) {
   SRK_REQUIRE(qkv && table && dout && dqkv && dtable && scratch, SRK_E_NULL, "win256 attention backward: null pointer");
   SRK_REQUIRE(B > 0 && H % 16 == 0 && W % 16 == 0, SRK_E_SHAPE, "win256 attention backward: %dx%d is not a multiple of the 16x16 window", H, W);
-  SRK_REQUIRE(nH > 0 && CA >= nH * 32 && CA % 32 == 0 && ldq >= 3 * CA && ldq % 8 == 0 && ldo >= nH * 32 && ldo % 8 == 0, SRK_E_SHAPE,
+  SRK_REQUIRE(srk_qkv_layout_ok(nH, CA, ldq, ldo, 8), SRK_E_SHAPE,
               "win256 attention backward: bad layout nH=%d CA=%d ldq=%d ldo=%d", nH, CA, ldq, ldo);
   SRK_REQUIRE(sy >= 0 && sy < 16 && sx >= 0 && sx < 16, SRK_E_SHAPE, "shift_size must in 0-window_size");
   SRK_REQUIRE(table_rows == (overlap > 0 ? 39 * 39 : 31 * 31), SRK_E_UNSUPPORTED,

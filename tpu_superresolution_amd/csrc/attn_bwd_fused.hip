@@ -29,10 +29,11 @@
 // there waits for the DMAs and not for the stores.
 //
 // LDS images (148 KB): rows [64][192] bf16 with the 16-byte chunk XOR-swizzled by (row & 7) on the DMA's source address
-// (conflict-free ds_read_b128 B fragments, as gemm_stream.hip); head tiles [64][32] bf16 with chunk ^ tf(row) and P / dS tiles
+// (conflict-free ds_read_b128 B fragments, as gemm_stream.hip); head tiles [64][32] bf16 with chunk ^ tfs(row) (attn_common.h) and P / dS tiles
 // [64][64] bf16 with chunk ^ ps(row), chosen so that the row-fragment ds_read_b128 (lane groups {0-3, 12-15, 20-27} ...),
 // both k orders of ds_read_b64_tr_b16 (32-lane groups) and the MFMA-layout ds_write_b64 hit every bank once (the 8-byte
 // writes twice: 16 rows x 8 bytes of one column group cannot do better on 64-byte rows).
+#include "attn_common.h"
 #include "kernels.h"
 
 namespace {
@@ -81,26 +82,21 @@ struct BwdFusedParams {
   WinGeom geom;
 };
 
-// chunk swizzle of a [64][32] head tile / a [64][64] P tile: functions of row bits 1..3 only
-__device__ __forceinline__ int tf(int r) { return ((((r >> 2) ^ (r >> 3)) & 1) << 1) | (((r >> 3) ^ (r >> 1)) & 1); }
+// chunk swizzle of a [64][64] P tile: like tfs (attn_common.h) of the [64][32] head tiles, a function of row bits 1..3 only
 __device__ __forceinline__ int ps(int r) { return (((r >> 3) & 1) << 2) | (((r >> 1) & 1) << 1) | ((r >> 2) & 1); }
-
-__device__ __forceinline__ bf16x8_t h_cat4(bf16x4_t lo, bf16x4_t hi) {
-  return bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
 
 // transposed fragment of a swizzled [64][32] head tile: this lane's column 16 dt + r16 of the eight rows rb0 .. rb0 + 3 and
 // rb1 .. rb1 + 3 (the lane supplies the address of row rb + (r16 >> 2), columns 16 dt + 4 (r16 & 3) ..)
 __device__ __forceinline__ bf16x8_t tile_tr(const bf16_t* tile, int rb0, int rb1, int dt, int r16) {
   const int q = r16 >> 2, c = 2 * dt + ((r16 & 3) >> 1), in = (r16 & 1) << 2;
   const int ra = rb0 + q, rb = rb1 + q;
-  return h_cat4(lds_tr_read(tile + ra * 32 + ((c ^ tf(ra)) << 3) + in), lds_tr_read(tile + rb * 32 + ((c ^ tf(rb)) << 3) + in));
+  return cat4(lds_tr_read(tile + ra * 32 + ((c ^ tfs(ra)) << 3) + in), lds_tr_read(tile + rb * 32 + ((c ^ tfs(rb)) << 3) + in));
 }
 // the same for a [64][64] P / dS tile, column 16 jt + r16
 __device__ __forceinline__ bf16x8_t ptile_tr(const bf16_t* tile, int rb0, int rb1, int jt, int r16) {
   const int q = r16 >> 2, c = 2 * jt + ((r16 & 3) >> 1), in = (r16 & 1) << 2;
   const int ra = rb0 + q, rb = rb1 + q;
-  return h_cat4(lds_tr_read(tile + ra * 64 + ((c ^ ps(ra)) << 3) + in), lds_tr_read(tile + rb * 64 + ((c ^ ps(rb)) << 3) + in));
+  return cat4(lds_tr_read(tile + ra * 64 + ((c ^ ps(ra)) << 3) + in), lds_tr_read(tile + rb * 64 + ((c ^ ps(rb)) << 3) + in));
 }
 
 __global__ __launch_bounds__(768) void qkv_attn_bwd_kernel(const BwdFusedParams p, int ngrp) {
@@ -177,7 +173,7 @@ __global__ __launch_bounds__(768) void qkv_attn_bwd_kernel(const BwdFusedParams 
     }
     issue(first, 0);
 
-    const int tfr = tf(r16), psr = ps(r16);
+    const int tfr = tfs(r16), psr = ps(r16);
     bf16_t* mytile = tiles + (hl * 4 + it) * H_TILE;
     const bf16_t* Qs = tiles + (hl * 4 + 0) * H_TILE;
     const bf16_t* Ks = tiles + (hl * 4 + 1) * H_TILE;
@@ -289,7 +285,7 @@ __global__ __launch_bounds__(768) void qkv_attn_bwd_kernel(const BwdFusedParams 
 #pragma unroll
         for (int jt = 1; jt < 4; ++jt) mx = fmaxf(fmaxf(mx, s[jt][0]), fmaxf(fmaxf(s[jt][1], s[jt][2]), s[jt][3]));
         mx = xrow_max4(mx);
-        constexpr float L2E = 1.4426950408889634f;        // exp(x - m) = exp2(x log2e - m log2e), as softmax_numerators
+        constexpr float L2E = SRK_L2E;                    // a local copy of SRK_L2E: as a namespace-scope constant the compiler schedules this kernel differently ("What the C++ side shares")
         const float mxl = mx * L2E;
         f32x4_t a4 = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -408,21 +404,14 @@ int srk_launch_qkv_attn_bwd(const bf16_t* xn, int lda, const bf16_t* Wqkv, const
                             WinGeom geom, hipStream_t stream) {
   const int nslab = srk_qkv_attn_bwd_slabs(B_, nH, CA, K);
   if (nslab == 0 || lda % 8 != 0 || ldg % 8 != 0 || B_ * 64 * (long long)(lda > ldg ? lda : ldg) >= (1LL << 31)) return SRK_NOT_COVERED;
-  static SrkPerDevice<int> configured_pd; int& configured = configured_pd.here();
-  if (!configured) {
-    const void* fn = reinterpret_cast<const void*>(&qkv_attn_bwd_kernel);
-    hipFuncAttributes attr;
-    configured = -1;
-    // a build that spills would put scratch traffic on the counted vmcnt waits: never run it
+  // a build that spills would put scratch traffic on the counted vmcnt waits: never run it (the instrumented build tolerates spills)
 #ifdef SRK_PROBE_ABF
-    attr.localSizeBytes = 0;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, H_LDS) == hipSuccess) configured = 1;   // instrumented build: spills tolerated
+  constexpr bool refuse_spills = false;
+#else
+  constexpr bool refuse_spills = true;
 #endif
-    if (configured < 0 && hipFuncGetAttributes(&attr, fn) == hipSuccess && attr.localSizeBytes == 0 &&
-        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, H_LDS) == hipSuccess)
-      configured = 1;
-  }
-  if (configured < 0) return SRK_NOT_COVERED;
+  static SrkLdsState reserved;
+  if (srk_reserve_lds(&qkv_attn_bwd_kernel, H_LDS, reserved, refuse_spills) != SRK_OK) return SRK_NOT_COVERED;
   BwdFusedParams bp;
   bp.xn = xn; bp.lda = lda; bp.g = g; bp.ldg = ldg; bp.Wqkv = Wqkv; bp.bqkv = bqkv; bp.scale = scale; bp.WprojT = WprojT;
   bp.biasd = biasd; bp.dqkv = dqkv; bp.slab = slab; bp.B_ = B_; bp.geom = geom;

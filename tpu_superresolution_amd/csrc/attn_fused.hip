@@ -27,6 +27,7 @@
 #include <atomic>
 #include <type_traits>
 
+#include "attn_common.h"
 #include "kernels.h"
 
 #ifndef SRK_NT_ATTN
@@ -73,10 +74,6 @@ struct FusedParams {
   long long B_;
   WinGeom geom;
 };
-
-__device__ __forceinline__ bf16x8_t f_cat4(bf16x4_t lo, bf16x4_t hi) {
-  return bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
 
 // NF: 16-column fragments of the projection owned by this wave (5 or 4); LOADER: this wave issues the DMA and never stores
 template <int NF, bool LOADER>
@@ -222,7 +219,7 @@ __device__ __forceinline__ void fused_wave(const FusedParams& p, unsigned char* 
         for (int ss = 0; ss < 2; ++ss) {
 #pragma unroll
           for (int dt = 0; dt < 2; ++dt) {
-            const bf16x8_t vf = f_cat4(lds_tr_read(tr_addr(Vs, FT, 32 * ss + 4 * g, 16 * dt, lane)),
+            const bf16x8_t vf = cat4(lds_tr_read(tr_addr(Vs, FT, 32 * ss + 4 * g, 16 * dt, lane)),
                                        lds_tr_read(tr_addr(Vs, FT, 32 * ss + 16 + 4 * g, 16 * dt, lane)));
             o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[ss], o[dt], 0, 0, 0);
           }
@@ -459,7 +456,7 @@ __global__ __launch_bounds__(256, 3) void qkv_attn_fwd3_kernel(const FusedParams
 #pragma unroll
           for (int dt = 0; dt < 2; ++dt) {
             const int ch = ((2 * dt + ((ll & 3) >> 1)) ^ g) << 3, in = (ll & 1) << 2;
-            const bf16x8_t vf = f_cat4(lds_tr_read(Vs + (32 * ss + 4 * g + (ll >> 2)) * 32 + ch + in),
+            const bf16x8_t vf = cat4(lds_tr_read(Vs + (32 * ss + 4 * g + (ll >> 2)) * 32 + ch + in),
                                        lds_tr_read(Vs + (32 * ss + 16 + 4 * g + (ll >> 2)) * 32 + ch + in));
             o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[ss], o[dt], 0, 0, 0);
           }
@@ -498,38 +495,17 @@ int srk_launch_qkv_attn_fwd(const bf16_t* xn, int lda, const bf16_t* Wt, const f
   if (!g_attn_fused || nH != F_NH || CA != F_CA || K != F_K || lda % 8 != 0) return SRK_NOT_COVERED;
   const int g_fused_cus = srk_device_cus();
   if (g_fused_cus < 1 || B_ < g_fused_cus) return SRK_NOT_COVERED;      // fewer windows than CUs: the W preload does not amortise
-  static SrkPerDevice<int> configured_pd; int& configured = configured_pd.here();
-  if (!configured) {
-    const void* fn = reinterpret_cast<const void*>(&qkv_attn_fwd_kernel);
-    hipFuncAttributes attr;
-    if (hipFuncGetAttributes(&attr, fn) != hipSuccess) {
-      srk_set_error("qkv+attention: cannot query the kernel");
-      return SRK_E_LAUNCH;
-    }
-    if (attr.localSizeBytes > 0) {
-      configured = -1;              // spills would put scratch traffic on the loader's vmcnt counter
-    } else {
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS) != hipSuccess) {
-        srk_set_error("qkv+attention: cannot reserve %d bytes of LDS", F_LDS);
-        return SRK_E_LAUNCH;
-      }
-      configured = 1;
-    }
-  }
-  static SrkPerDevice<int> configured3_pd; int& configured3 = configured3_pd.here();
-  if (!configured3) {
-    const void* fn = reinterpret_cast<const void*>(&qkv_attn_fwd3_kernel);
-    hipFuncAttributes attr;
-    configured3 = -1;
-    if (hipFuncGetAttributes(&attr, fn) == hipSuccess && attr.localSizeBytes == 0 &&
-        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, G_LDS) == hipSuccess)
-      configured3 = 1;
-  }
-  if (configured < 0) return SRK_NOT_COVERED;
+  // neither kernel runs from a build that spills: the scratch traffic would sit on the vmcnt counter of the loaders' counted waits.
+  // Without the 8-wave kernel nothing is fused; without the 3-per-CU kernel mode 2 falls back to it.
+  static SrkLdsState reserved8, reserved3;
+  const int rc8 = srk_reserve_lds(&qkv_attn_fwd_kernel, F_LDS, reserved8, true, "qkv+attention: cannot reserve %d bytes of LDS", F_LDS);
+  if (rc8 == SRK_E_LAUNCH) return rc8;
+  const bool have3 = srk_reserve_lds(&qkv_attn_fwd3_kernel, G_LDS, reserved3, true) == SRK_OK;
+  if (rc8) return rc8;
   FusedParams fp;
   fp.xn = xn; fp.lda = lda; fp.Wt = Wt; fp.bias = bias; fp.scale = scale; fp.qkv = qkv; fp.biasd = biasd; fp.ao = ao; fp.B_ = B_;
   fp.geom = geom;
-  if (g_attn_fused == 2 && configured3 > 0) {
+  if (g_attn_fused == 2 && have3) {
     long long ngrp = g_fused_cus / 8;                       // 24 workgroups per group of 8 windows in flight: 3 per CU
     if (ngrp * 8 > B_) ngrp = (B_ + 7) / 8;
     hipLaunchKernelGGL(qkv_attn_fwd3_kernel, dim3((unsigned)(24 * ngrp)), dim3(256), G_LDS, stream, fp, (int)ngrp);

@@ -16,17 +16,15 @@
 // no destination), as queries their dO is zero, so they contribute nothing and their dq is not stored.
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "attn_common.h"
 #include "kernels.h"
 
 namespace {
 
-// [rows][32] bf16 tiles without padding, the four 16-byte chunks of a row XOR-swizzled (the scheme of attn256_bwd.hip's self-attention
-// form): conflict-free for the row-per-lane fragment reads and for the transposing reads, and 4 x 256 x 64 B + statistics = 68 KB per
+// [rows][32] bf16 tiles without padding, the four 16-byte chunks of a row XOR-swizzled (tfs / chunk_off of attn_common.h):
+// conflict-free for the row-per-lane fragment reads and for the transposing reads, and 4 x 256 x 64 B + statistics = 68 KB per
 // workgroup, so that TWO workgroups share a CU (the 40-element pitch needed 86 KB: one workgroup, one wave per SIMD).
 constexpr int RP = 32;
-__device__ __forceinline__ int tfs(int r) { return ((((r >> 2) ^ (r >> 3)) & 1) << 1) | (((r >> 3) ^ (r >> 1)) & 1); }
-__device__ __forceinline__ int chunk_off(int r, int c) { return r * 32 + ((c ^ tfs(r)) << 3); }      // element offset of 16-byte chunk c of row r
 
 struct RectBwdParams {
   const bf16_t* qkv;    // [T][ldq]
@@ -43,11 +41,6 @@ struct RectBwdParams {
   float scale;
 };
 
-__device__ __forceinline__ int region3r(int v, int n, int w, int s) { return v < n - w ? 0 : (v < n - s ? 1 : 2); }
-
-__device__ __forceinline__ bf16x8_t r_cat4(bf16x4_t lo, bf16x4_t hi) {
-  return bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
 // transposed fragment in accumulator k order (slots (g, jj): rows k0 + 4 g + jj, jj < 4, and k0 + 16 + 4 g + jj - 4)
 // k0 is a multiple of 32: the swizzle of rows k0 + 4 g + (ll >> 2) (+ 16) depends on the lane only -> `tro` = the lane's element offset
 // inside a 32-row block for c0 = 0 (tr_lane_off), c0 = 16 flips chunk bit 1
@@ -57,13 +50,12 @@ __device__ __forceinline__ int tr_lane_off(int lane, int c0) {
   return chunk_off(ra, (c0 >> 3) + ((ll & 3) >> 1)) + ((ll & 1) << 2);
 }
 __device__ __forceinline__ bf16x8_t r_tr_acc(const bf16_t* tile, int k0, int tro) {
-  return r_cat4(lds_tr_read(tile + k0 * 32 + tro), lds_tr_read(tile + (k0 + 16) * 32 + tro));
+  return cat4(lds_tr_read(tile + k0 * 32 + tro), lds_tr_read(tile + (k0 + 16) * 32 + tro));
 }
 
 template <int QT>        // 16-query tiles per wave: 4 (256-token windows) or 2 (128-token windows)
 __global__ __launch_bounds__(256, 2) void win_rect_attn_bwd_kernel(const RectBwdParams p) {
   constexpr int NQ = 64 * QT, NT = NQ / 16;
-  constexpr float L2E = 1.4426950408889634f;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   bf16_t* Ks = reinterpret_cast<bf16_t*>(smem);          // [NQ][RP]
   bf16_t* Vs = Ks + NQ * RP;
@@ -72,7 +64,7 @@ __global__ __launch_bounds__(256, 2) void win_rect_attn_bwd_kernel(const RectBwd
   float* stats = reinterpret_cast<float*>(Os + NQ * RP);   // [NQ][4]: max * log2e, 1 / sum, rowsum(P dP)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r16 = lane & 15, g = lane >> 4;
-  const int fro = r16 * 32 + ((g ^ tfs(r16)) << 3);           // fragment read of row 16 x + r16, chunk g: + 16 x * 32
+  const int fro = chunk_off(r16, g);                          // fragment read of row 16 x + r16, chunk g: + 16 x * 32
   const int tro[2] = {tr_lane_off(lane, 0), tr_lane_off(lane, 16)};
   const int h = blockIdx.x % p.nH;
   const int wflat = blockIdx.x / p.nH;
@@ -122,7 +114,7 @@ __global__ __launch_bounds__(256, 2) void win_rect_attn_bwd_kernel(const RectBwd
   const bool need_mask = masked && (wy == p.nWh - 1 || wx == p.nWw - 1);
   auto label = [&](int l) {      // region label of window-local position l in the shifted frame (dat_arch.py:318-364)
     const int ly = l / p.ww, lx = l - ly * p.ww;
-    return region3r(wy * p.wh + ly, p.Hp, p.wh, p.sy) * 3 + region3r(wx * p.ww + lx, p.Wp, p.ww, p.sx);
+    return region3(wy * p.wh + ly, p.Hp, p.wh, p.sy) * 3 + region3(wx * p.ww + lx, p.Wp, p.ww, p.sx);
   };
   const float* bias_h = p.bias + (long long)h * NQ * NQ;
   const float* biasT_h = p.biasT ? p.biasT + (long long)h * NQ * NQ : nullptr;
@@ -159,13 +151,13 @@ __global__ __launch_bounds__(256, 2) void win_rect_attn_bwd_kernel(const RectBwd
       }
     }
     mx = xrow_max4(mx);
-    const float mxl = mx * L2E;
+    const float mxl = mx * SRK_L2E;
     float sum = 0.f;
 #pragma unroll
     for (int j = 0; j < NT; ++j)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        s[j][e] = __builtin_amdgcn_exp2f(s[j][e] * L2E - mxl);
+        s[j][e] = __builtin_amdgcn_exp2f(s[j][e] * SRK_L2E - mxl);
         sum += s[j][e];
       }
     const float inv = __builtin_amdgcn_rcpf(xrow_sum4(sum));
@@ -250,7 +242,7 @@ __global__ __launch_bounds__(256, 2) void win_rect_attn_bwd_kernel(const RectBwd
           const float4 st = *reinterpret_cast<const float4*>(stats + q * 4);
           float v = sa[e] * p.scale + bq[e];
           if (need_mask && label(q) != klab) v += -100.0f;
-          pv[e] = __builtin_amdgcn_exp2f(v * L2E - st.x) * st.y;              // P
+          pv[e] = __builtin_amdgcn_exp2f(v * SRK_L2E - st.x) * st.y;              // P
           dv[e] = pv[e] * (da[e] - st.z);                                      // dS
         }
         pl[u] = pack_bf4(pv[0], pv[1], pv[2], pv[3]);
@@ -309,15 +301,10 @@ __global__ __launch_bounds__(256) void rect_bias_transpose_kernel(const float* _
 template <int QT>
 int launch_rect(const RectBwdParams& p, hipStream_t stream) {
   constexpr size_t lds = (size_t)4 * 64 * QT * RP * sizeof(bf16_t) + (size_t)64 * QT * 4 * sizeof(float);
-  static SrkPerDevice<bool> configured_pd; bool& configured = configured_pd.here();
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&win_rect_attn_bwd_kernel<QT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-        hipSuccess) {
-      srk_set_error("window attention backward: cannot reserve %zu bytes of LDS", lds);
-      return SRK_E_LAUNCH;
-    }
-    configured = true;
-  }
+  static SrkLdsState reserved;
+  if (const int rc = srk_reserve_lds(&win_rect_attn_bwd_kernel<QT>, lds, reserved, false,
+                                     "window attention backward: cannot reserve %zu bytes of LDS", lds))
+    return rc;
   const long long grid = (long long)p.B * p.nWh * p.nWw * p.nH;
   SRK_REQUIRE(grid > 0 && grid < (1LL << 31), SRK_E_SHAPE, "window attention backward: bad grid %lld", grid);
   RectBwdParams pp = p;
@@ -348,7 +335,7 @@ int srk_launch_win_attn_bwd_padded(const bf16_t* qkv, int ldq, int CA, const flo
   SRK_REQUIRE(B > 0 && H > 0 && W > 0 && Hp >= H && Wp >= W && Hp % wh == 0 && Wp % ww == 0, SRK_E_SHAPE,
               "window attention backward: window frame %dx%d must cover the %dx%d map and be a multiple of the %dx%d window", Hp, Wp, H, W, wh,
               ww);
-  SRK_REQUIRE(nH > 0 && CA >= nH * 32 && CA % 32 == 0 && ldq >= 3 * CA && ldq % 8 == 0 && ldo >= nH * 32 && ldo % 8 == 0, SRK_E_SHAPE,
+  SRK_REQUIRE(srk_qkv_layout_ok(nH, CA, ldq, ldo, 8), SRK_E_SHAPE,
               "window attention backward: bad layout nH=%d CA=%d ldq=%d ldo=%d", nH, CA, ldq, ldo);
   SRK_REQUIRE(sy >= 0 && sy < wh && sx >= 0 && sx < ww, SRK_E_SHAPE, "shift_size must in 0-window_size");
   RectBwdParams p;

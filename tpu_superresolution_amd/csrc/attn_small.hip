@@ -1,7 +1,7 @@
 // (Shifted-)window attention, forward, for SMALL windows: ws x ws with ws = 2 .. 7 (N = ws * ws <= 49 tokens), for gfx950
 // (v_mfma_f32_16x16x32_bf16, fp32 softmax).  Reference: WindowAttention.forward network_swinir.py:114-145 plus the roll /
 // window_partition / window_reverse of SwinTransformerBlock.forward :240-279; the shift mask is calculate_mask :216-237 with
-// shift = ws // 2, evaluated arithmetically from region labels (as attn256.hip).
+// shift = ws // 2, evaluated arithmetically from region labels (region3 of attn_common.h).
 //
 // q, k, v are read straight from the qkv projection's output in raster token order ([T][ldq] bf16, head h at columns
 // which * CA + 32 h .. +31, head_dim zero-padded to 32, q NOT pre-scaled): roll + partition are folded into the row addresses of
@@ -23,7 +23,7 @@
 //   operand and V^T from LDS through the transposing read (ds_read_b64_tr_b16) -- the same operand maps as attn256.hip.
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "attn_common.h"
 #include "kernels.h"
 
 namespace {
@@ -39,8 +39,6 @@ struct SmallParams {
   int B, H, W, shift, nH, nWh, nWw;
   float scale;
 };
-
-__device__ __forceinline__ int region_label(int v, int n, int w, int s) { return v < n - w ? 0 : (v < n - s ? 1 : 2); }
 
 template <int WS>
 __global__ __launch_bounds__(64 * MAX_WAVES) void win_small_attn_fwd_kernel(const SmallParams p) {
@@ -76,7 +74,7 @@ __global__ __launch_bounds__(64 * MAX_WAVES) void win_small_attn_fwd_kernel(cons
   };
   auto label = [&](int l) {
     const int ly = l / WS, lx = l - ly * WS;
-    return region_label(wy * WS + ly, p.H, WS, sh) * 3 + region_label(wx * WS + lx, p.W, WS, sh);
+    return region3(wy * WS + ly, p.H, WS, sh) * 3 + region3(wx * WS + lx, p.W, WS, sh);
   };
   const bf16x8_t zero8 = bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
 
@@ -133,15 +131,14 @@ __global__ __launch_bounds__(64 * MAX_WAVES) void win_small_attn_fwd_kernel(cons
           if (kreal) mx = fmaxf(mx, v);
         }
       mx = xrow_max4(mx);
-      constexpr float L2E = 1.4426950408889634f;
-      const float mxl = mx * L2E;
+      const float mxl = mx * SRK_L2E;
       float sum = 0.f;
 #pragma unroll
       for (int j = 0; j < NT; ++j)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const bool kreal = 16 * j + 4 * g + e < N;
-          const float pv = kreal ? __builtin_amdgcn_exp2f(s[j][e] * L2E - mxl) : 0.f;   // padded keys: probability exactly 0
+          const float pv = kreal ? __builtin_amdgcn_exp2f(s[j][e] * SRK_L2E - mxl) : 0.f;   // padded keys: probability exactly 0
           s[j][e] = pv;
           sum += pv;
         }
@@ -196,10 +193,8 @@ int srk_win_small_attention_fwd(const uint16_t* qkv, int ldq, int CA, const floa
   SRK_REQUIRE(B > 0 && H > 0 && W > 0 && H % ws == 0 && W % ws == 0, SRK_E_SHAPE,
               "win_small attention: the %dx%d map must be a multiple of the window %d", H, W, ws);
   SRK_REQUIRE(shift >= 0 && shift < ws, SRK_E_SHAPE, "shift_size must in 0-window_size");
-  SRK_REQUIRE(num_heads > 0 && CA >= num_heads * 32 && CA % 32 == 0 && ldq >= 3 * CA && ldq % 8 == 0 && ldo >= num_heads * 32 &&
-                  ldo % 4 == 0,
-              SRK_E_SHAPE, "win_small attention: bad layout nH=%d CA=%d ldq=%d ldo=%d", num_heads, CA, ldq, ldo);
-  SRK_REQUIRE((reinterpret_cast<uintptr_t>(qkv) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0, SRK_E_ALIGN,
+  SRK_REQUIRE(srk_qkv_layout_ok(num_heads, CA, ldq, ldo, 4), SRK_E_SHAPE, "win_small attention: bad layout nH=%d CA=%d ldq=%d ldo=%d", num_heads, CA, ldq, ldo);
+  SRK_REQUIRE(srk_aligned(qkv, 16) && srk_aligned(out, 8), SRK_E_ALIGN,
               "win_small attention: qkv must be 16-byte and out 8-byte aligned");
   SmallParams p;
   p.qkv = reinterpret_cast<const bf16_t*>(qkv); p.out = reinterpret_cast<bf16_t*>(out); p.table = table;

@@ -26,7 +26,7 @@
 // win_small_table_reduce_kernel with one float atomic per element and 32-window slice.
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "attn_common.h"
 #include "kernels.h"
 
 namespace {
@@ -43,10 +43,6 @@ struct SmallBwdParams {
   int B, H, W, shift, nH, nHc, nWh, nWw;      // nHc = CA / 32 column blocks (>= nH)
   float scale;
 };
-
-__device__ __forceinline__ int region_label_b(int v, int n, int w, int s) { return v < n - w ? 0 : (v < n - s ? 1 : 2); }
-
-__device__ __forceinline__ bf16x8_t cat4(bf16x4_t lo, bf16x4_t hi) { return bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}; }
 
 // transposed fragment in accumulator k order: slots (g, i) = rows k0 + 4 g + i (i < 4) and k0 + 16 + 4 g + i - 4, columns c0 .. c0 + 15
 __device__ __forceinline__ bf16x8_t tr_acc(const bf16_t* tile, int k0, int c0, int lane) {
@@ -66,7 +62,6 @@ __global__ __launch_bounds__(64) void win_small_attn_bwd_kernel(const SmallBwdPa
   constexpr int TRP = (TR + 3) & ~3;
   constexpr int NU = (TR + 63) / 64;                   // table entries per lane
   constexpr int DP = NK + 4;                           // pitch of the fp32 dS tile
-  constexpr float L2E = 1.4426950408889634f;
   __shared__ __attribute__((aligned(16))) bf16_t Ks[NK * KP];
   __shared__ __attribute__((aligned(16))) bf16_t Qs[NK * KP];
   __shared__ __attribute__((aligned(16))) bf16_t Os[NK * KP];
@@ -95,7 +90,7 @@ __global__ __launch_bounds__(64) void win_small_attn_bwd_kernel(const SmallBwdPa
   };
   auto label = [&](int l) {
     const int ly = l / WS, lx = l - ly * WS;
-    return region_label_b(wy * WS + ly, p.H, WS, sh) * 3 + region_label_b(wx * WS + lx, p.W, WS, sh);
+    return region3(wy * WS + ly, p.H, WS, sh) * 3 + region3(wx * WS + lx, p.W, WS, sh);
   };
 
   if (h >= p.nH) {        // a column block of CA that holds no head: its gradient is zero (uniform over the workgroup)
@@ -174,14 +169,14 @@ __global__ __launch_bounds__(64) void win_small_attn_bwd_kernel(const SmallBwdPa
         if (kreal) mx = fmaxf(mx, v);
       }
     mx = xrow_max4(mx);
-    const float mxl = mx * L2E;
+    const float mxl = mx * SRK_L2E;
     float sum = 0.f;
 #pragma unroll
     for (int j = 0; j < NT; ++j)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const bool kreal = 16 * j + 4 * g + e < N;
-        const float pv = kreal ? __builtin_amdgcn_exp2f(s[j][e] * L2E - mxl) : 0.f;   // padded keys: probability exactly 0
+        const float pv = kreal ? __builtin_amdgcn_exp2f(s[j][e] * SRK_L2E - mxl) : 0.f;   // padded keys: probability exactly 0
         s[j][e] = pv;
         sum += pv;
       }
@@ -277,7 +272,7 @@ __global__ __launch_bounds__(64) void win_small_attn_bwd_kernel(const SmallBwdPa
           const float4 st = *reinterpret_cast<const float4*>(stats + ql * 4);
           float v = sa[e] * p.scale + tab[(qy - ky + WS - 1) * TW + (qx - kx + WS - 1)];
           if (need_mask && label(qc) != klab) v += -100.0f;
-          const float pe = __builtin_amdgcn_exp2f(v * L2E - st.x) * st.y;
+          const float pe = __builtin_amdgcn_exp2f(v * SRK_L2E - st.x) * st.y;
           pv[e] = real ? pe : 0.f;                                             // P
           dv[e] = real ? pe * (da[e] - st.z) : 0.f;                            // dS
         }
@@ -353,14 +348,11 @@ int srk_win_small_attention_bwd(const uint16_t* qkv, int ldq, int CA, const floa
   SRK_REQUIRE(B > 0 && H > 0 && W > 0 && H % ws == 0 && W % ws == 0, SRK_E_SHAPE,
               "win_small attention backward: the %dx%d map must be a multiple of the window %d", H, W, ws);
   SRK_REQUIRE(shift >= 0 && shift < ws, SRK_E_SHAPE, "shift_size must in 0-window_size");
-  SRK_REQUIRE(num_heads > 0 && CA >= num_heads * 32 && CA % 32 == 0 && ldq >= 3 * CA && ldq % 8 == 0 && ldo >= num_heads * 32 &&
-                  ldo % 8 == 0,
-              SRK_E_SHAPE, "win_small attention backward: bad layout nH=%d CA=%d ldq=%d ldo=%d", num_heads, CA, ldq, ldo);
+  SRK_REQUIRE(srk_qkv_layout_ok(num_heads, CA, ldq, ldo, 8), SRK_E_SHAPE, "win_small attention backward: bad layout nH=%d CA=%d ldq=%d ldo=%d", num_heads, CA, ldq, ldo);
   SRK_REQUIRE(scratch || srk_win_small_attention_bwd_scratch(B, H, W, ws, num_heads) == 0, SRK_E_NULL,
               "win_small attention backward: null scratch (srk_win_small_attention_bwd_scratch bytes)");
-  SRK_REQUIRE((reinterpret_cast<uintptr_t>(qkv) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(d_qkv) & 15) == 0 && (reinterpret_cast<uintptr_t>(scratch) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(table) & 3) == 0 && (reinterpret_cast<uintptr_t>(d_table) & 3) == 0,
+  SRK_REQUIRE(srk_aligned(qkv, 16) && srk_aligned(d_out, 16) && srk_aligned(d_qkv, 16) && srk_aligned(scratch, 16) && srk_aligned(table, 4) &&
+                  srk_aligned(d_table, 4),
               SRK_E_ALIGN, "win_small attention backward: qkv, d_out, d_qkv and scratch must be 16-byte, table and d_table 4-byte aligned");
   SmallBwdParams p;
   p.qkv = reinterpret_cast<const bf16_t*>(qkv); p.dout = reinterpret_cast<const bf16_t*>(d_out); p.table = table;

@@ -28,6 +28,7 @@
 // stream fp32).
 #include <type_traits>
 
+#include "attn_common.h"
 #include "kernels.h"
 
 #ifdef SRK_PROBE_LIGHT
@@ -329,16 +330,8 @@ int srk_launch_swin_block_light(const float* x, float* y, bf16_t* yb, const floa
                                 const float* bproj, const float* b1, const float* b2, const float* biasd, float scale, int C, int CP, int HP,
                                 int nH, int dh, int HID, long long B_, WinGeom geom, hipStream_t stream) {
   if (!g_block_light || CP != 64 || HP != 128 || nH != 6 || dh > 16 || C > 64 || B_ < 1 || B_ >= (1LL << 24)) return SRK_NOT_COVERED;
-  static SrkPerDevice<int> configured_pd; int& configured = configured_pd.here();
-  if (!configured) {
-    const void* fn = reinterpret_cast<const void*>(&swin_block_light_kernel);
-    hipFuncAttributes attr;
-    configured = -1;
-    if (hipFuncGetAttributes(&attr, fn) == hipSuccess && attr.localSizeBytes == 0 &&
-        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, L_LDS) == hipSuccess)
-      configured = 1;
-  }
-  if (configured < 0) return SRK_NOT_COVERED;
+  static SrkLdsState reserved;
+  if (srk_reserve_lds(&swin_block_light_kernel, L_LDS, reserved, true) != SRK_OK) return SRK_NOT_COVERED;
   LightParams p;
   p.x = x; p.y = y; p.yb = yb; p.n1w = n1w; p.n1b = n1b; p.n2w = n2w; p.n2b = n2b; p.Wqkv = Wqkv; p.Wproj = Wproj; p.W1 = W1; p.W2 = W2;
   p.bqkv = bqkv; p.bproj = bproj; p.b1 = b1; p.b2 = b2; p.biasd = biasd; p.scale = scale; p.C = C; p.B_ = B_; p.geom = geom;

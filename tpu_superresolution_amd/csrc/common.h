@@ -65,6 +65,19 @@ struct SrkPerDevice {
   T& here() { return v[srk_current_device()]; }
 };
 
+// A kernel's dynamic-LDS reservation on each device: 0 not tried yet, 1 reserved, -1 this build must not run there.
+typedef SrkPerDevice<signed char> SrkLdsState;
+// Raises `kernel`'s dynamic-LDS limit to `bytes` on the first call per device; later calls read `st` and nothing else.
+// refuse_spills: a build of the kernel that uses scratch never runs (its scratch traffic would sit on the vmcnt counter that the
+// kernel's counted waits read).  Three outcomes: SRK_OK; SRK_NOT_COVERED -- this build must not run, remembered in `st`, the
+// caller takes its other path; SRK_E_LAUNCH after srk_set_error(err_fmt, ...), tried again on the next call.  A call site that
+// has another path for every failure passes no err_fmt: whatever goes wrong is SRK_NOT_COVERED.
+int srk_reserve_lds_fn(const void* fn, int bytes, SrkLdsState& st, bool refuse_spills, const char* err_fmt, ...);
+template <class K, class... A>
+inline int srk_reserve_lds(K* kernel, size_t bytes, SrkLdsState& st, bool refuse_spills = false, const char* err_fmt = nullptr, A... a) {
+  return srk_reserve_lds_fn(reinterpret_cast<const void*>(kernel), (int)bytes, st, refuse_spills, err_fmt, a...);
+}
+
 // optional per-launch timing probe (bench.py roofline leg): HIP events around launches of one kernel family
 enum { FAM_GEMM_LINEAR = 1, FAM_GEMM_CONV = 2, FAM_WGRAD_LINEAR = 3, FAM_WGRAD_CONV = 4, FAM_ATTN_FWD = 5, FAM_ATTN_BWD = 6,
        FAM_LN = 7 };
@@ -78,6 +91,18 @@ void srk_probe_post(int family, hipStream_t stream);
       return (code);                      \
     }                                     \
   } while (0)
+
+// argument checks shared by the launchers (host)
+static inline bool srk_aligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }   // bytes: power of 2
+// [a, a + na) and [b, b + nb) share a byte: neither is empty and the lower one reaches the start of the upper one (no sum that could wrap)
+static inline bool srk_ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t ua = reinterpret_cast<uintptr_t>(a), ub = reinterpret_cast<uintptr_t>(b);
+  return na != 0 && nb != 0 && (ua <= ub ? ub - ua < na : ua - ub < nb);
+}
+// q/k/v rows of 32-element head slices: q | k | v at column offsets 0, CA, 2 CA of rows of ldq; outputs in rows of ldo
+static inline bool srk_qkv_layout_ok(int nH, int CA, int ldq, int ldo, int ldo_mult) {
+  return nH > 0 && CA >= nH * 32 && CA % 32 == 0 && ldq >= 3 * CA && ldq % 8 == 0 && ldo >= nH * 32 && ldo % ldo_mult == 0;
+}
 
 // ---------------------------------------------------------------------------------------------
 // bf16 helpers (device)
@@ -261,36 +286,6 @@ __device__ __forceinline__ float xrow_sum4(float v) {
   v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
   const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
   return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-
-// Softmax numerators of one 16-query x 64-key score tile held as four MFMA accumulators (s[jt][e] = S[query r16][key
-// 16 jt + 4 g + e], bias and mask already added).  Returns exp(s - rowmax) -- in [0, 1], UNNORMALISED -- as the two bf16
-// B-operand fragments of P (k = key) and 1 / row sum: the caller scales its 8 outputs instead of the 64 probabilities.
-// exp(x - m) = exp2(x log2e - m log2e): one packed fma per two scores + v_exp_f32, v_rcp_f32 for the sum (the phase is
-// VALU-issue-bound: 4 cycles per wave-instruction, 8 for a transcendental).
-__device__ __forceinline__ float softmax_numerators(const f32x4_t (&s)[4], bf16x8_t (&pf)[2]) {
-  constexpr float L2E = 1.4426950408889634f;
-  float mx = fmaxf(fmaxf(s[0][0], s[0][1]), fmaxf(s[0][2], s[0][3]));
-#pragma unroll
-  for (int jt = 1; jt < 4; ++jt) mx = fmaxf(fmaxf(mx, s[jt][0]), fmaxf(fmaxf(s[jt][1], s[jt][2]), s[jt][3]));
-  mx = xrow_max4(mx);
-  const float mxl = mx * L2E;
-  f32x4_t e[4];
-#pragma unroll
-  for (int jt = 0; jt < 4; ++jt) {
-    const f32x4_t t = s[jt] * L2E - mxl;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) e[jt][k] = __builtin_amdgcn_exp2f(t[k]);
-  }
-  const f32x4_t a = (e[0] + e[1]) + (e[2] + e[3]);
-  const float sum = xrow_sum4((a[0] + a[1]) + (a[2] + a[3]));
-#pragma unroll
-  for (int ss = 0; ss < 2; ++ss) {
-    const uint2 lo = pack_bf4(e[2 * ss][0], e[2 * ss][1], e[2 * ss][2], e[2 * ss][3]);
-    const uint2 hi = pack_bf4(e[2 * ss + 1][0], e[2 * ss + 1][1], e[2 * ss + 1][2], e[2 * ss + 1][3]);
-    pf[ss] = __builtin_bit_cast(bf16x8_t, make_uint4(lo.x, lo.y, hi.x, hi.y));
-  }
-  return __builtin_amdgcn_rcpf(sum);
 }
 
 __device__ __forceinline__ float wave_sum64(float v) {

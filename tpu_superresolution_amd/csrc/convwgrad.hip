@@ -175,15 +175,8 @@ SrkOpt g_taps_enabled{OPT_TAPS_ENABLED, 1};
 template <bool SHUF>
 int launch_taps(const WgradParams& p, hipStream_t stream) {
   constexpr size_t lds = (size_t)2 * (CT + XROWS) * SP * sizeof(bf16_t);
-  static SrkPerDevice<bool> configured_pd; bool& configured = configured_pd.here();
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_taps_kernel<SHUF>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess) {
-      srk_set_error("conv wgrad: cannot reserve %zu bytes of LDS", lds);
-      return SRK_E_LAUNCH;
-    }
-    configured = true;
-  }
+  static SrkLdsState reserved;
+  if (const int rc = srk_reserve_lds(&conv_wgrad_taps_kernel<SHUF>, lds, reserved, false, "conv wgrad: cannot reserve %zu bytes of LDS", lds)) return rc;
   const int tiles = (p.N / 64) * (p.K / 64);
   const int nchunks = p.M / CT;
   // one workgroup per CU (LDS-limited): ~256 workgroups; every m-split costs one pass of fp32 atomics over the tile
@@ -653,19 +646,14 @@ int launch_taps_dma(const WgradParams& p, hipStream_t stream) {
   constexpr int lds_staged = TD_RING * TD_STAGE_BYTES;
   constexpr int lds_roll = RL<2>::LDS > RL<1>::LDS ? RL<2>::LDS : RL<1>::LDS;
   static_assert(lds_roll <= 160 * 1024 && lds_staged <= 160 * 1024, "LDS budget");
-  static SrkPerDevice<bool> configured_pd; bool& configured = configured_pd.here();
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_taps_dma_kernel<SHUF>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            lds_roll) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_taps_dma_staged_kernel<SHUF>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds_staged) != hipSuccess) {
-      srk_set_error("conv wgrad (dma): cannot reserve %d bytes of LDS", lds_roll > lds_staged ? lds_roll : lds_staged);
-      return SRK_E_LAUNCH;
-    }
-    configured = true;
-  }
   // rolling X-row window: one or two runs per image row; the M-splits are whole image rows (at W = 64 a run IS a row: same splits)
   const int rpr = g_taps_roll && (p.W == CT || p.W == 2 * CT) && p.M % p.W == 0 ? p.W / CT : 0;
+  static SrkLdsState reserved[2];                       // [staged, rolling]: the kernel this launch runs
+  constexpr const char* err = "conv wgrad (dma): cannot reserve %d bytes of LDS";
+  constexpr int lds_max = lds_roll > lds_staged ? lds_roll : lds_staged;
+  if (const int rc = rpr ? srk_reserve_lds(&conv_wgrad_taps_dma_kernel<SHUF>, lds_roll, reserved[1], false, err, lds_max)
+                         : srk_reserve_lds(&conv_wgrad_taps_dma_staged_kernel<SHUF>, lds_staged, reserved[0], false, err, lds_max))
+    return rc;
   const int lds = rpr == 1 ? RL<1>::LDS : (rpr == 2 ? RL<2>::LDS : lds_staged);
   const int unit = rpr ? rpr : 1;
   const int tiles = (p.N / 64) * (p.K / 64);
@@ -1040,24 +1028,20 @@ int launch_smallconv_mfma(const bf16_t* x, const float* gy, float* dW, float* db
                           hipStream_t stream) {
   constexpr int lds_staged = (int)((2 * 2 * CT * 16 + 2 * XROWS * SP) * sizeof(bf16_t));
   static_assert(2 * SR<COP>::LDS <= 160 * 1024, "two workgroups per CU");
-  static SrkPerDevice<bool> configured_pd; bool& configured = configured_pd.here();
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&smallconv_wgrad_mfma_kernel<COP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            SR<COP>::LDS) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&smallconv_wgrad_mfma_staged_kernel<COP>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds_staged) != hipSuccess) {
-      srk_set_error("smallconv wgrad: cannot reserve %d bytes of LDS", SR<COP>::LDS > lds_staged ? SR<COP>::LDS : lds_staged);
-      return SRK_E_LAUNCH;
-    }
-    configured = true;
-  }
+  static SrkLdsState reserved[2];                       // [staged, rolling]: the kernel this launch runs
+  constexpr const char* err = "smallconv wgrad: cannot reserve %d bytes of LDS";
+  constexpr int lds_max = SR<COP>::LDS > lds_staged ? SR<COP>::LDS : lds_staged;
+  const bool roll = g_taps_roll;
+  if (const int rc = roll ? srk_reserve_lds(&smallconv_wgrad_mfma_kernel<COP>, SR<COP>::LDS, reserved[1], false, err, lds_max)
+                          : srk_reserve_lds(&smallconv_wgrad_mfma_staged_kernel<COP>, lds_staged, reserved[0], false, err, lds_max))
+    return rc;
   const int tiles = CinP / 64;
   const int nchunks = (int)(((long long)B * H * W) / CT);
   int splits = 512 / tiles;                       // two workgroups per CU
   if (splits > nchunks) splits = nchunks;
   const int chunks_per = cdiv(nchunks, splits);
   splits = cdiv(nchunks, chunks_per);
-  if (g_taps_roll)
+  if (roll)
     hipLaunchKernelGGL((smallconv_wgrad_mfma_kernel<COP>), dim3(tiles * splits), dim3(256), SR<COP>::LDS, stream, x, gy, dW, db, B, H, W,
                        Cin, CinP, Co, tiles, chunks_per);
   else

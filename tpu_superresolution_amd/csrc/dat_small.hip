@@ -439,17 +439,13 @@ __global__ __launch_bounds__(256) void chan_attn_matrix_bwd_kernel(const float* 
 
 #define REQS(cond, ...) SRK_REQUIRE(cond, SRK_E_SHAPE, __VA_ARGS__)
 
-extern "C" {
-
-static int ci_configure(const void* fn, size_t bytes, int* state) {
-  if (*state >= (int)bytes) return SRK_OK;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, CI_MAX_LDS) != hipSuccess) {
-    srk_set_error("channel_interaction: cannot reserve %d bytes of LDS", CI_MAX_LDS);
-    return SRK_E_LAUNCH;
-  }
-  *state = CI_MAX_LDS;
-  return SRK_OK;
+// every channel-interaction kernel may use the whole budget; its launch asks for what the shape needs
+template <class K>
+static int ci_reserve(K* kernel, SrkLdsState& st) {
+  return srk_reserve_lds(kernel, CI_MAX_LDS, st, false, "channel_interaction: cannot reserve %d bytes of LDS", CI_MAX_LDS);
 }
+
+extern "C" {
 
 /* 1 when srk_channel_interaction_fwd / _bwd cover the shape (everything of the one workgroup fits its LDS) */
 int srk_channel_interaction_covered(int B, int C, int S) {
@@ -464,9 +460,9 @@ int srk_channel_interaction_fwd(const float* pooled, int ldp, float inv_hw, cons
   REQS(srk_channel_interaction_covered(B, C, S) && CA >= C && ldp >= CA && (running_mean == nullptr) == (running_var == nullptr),
        "channel_interaction_fwd: B=%d C=%d S=%d (B > 1 as nn.BatchNorm2d in training; S <= 64; the arrays must fit %d bytes of LDS)", B, C, S,
        CI_MAX_LDS);
-  static SrkPerDevice<int> st_pd;
+  static SrkLdsState reserved;
   const size_t lds = ci_lds_floats(B, C, S, false) * 4;
-  const int rc = ci_configure(reinterpret_cast<const void*>(&channel_interaction_fwd_kernel), lds, &st_pd.here());
+  const int rc = ci_reserve(&channel_interaction_fwd_kernel, reserved);
   if (rc) return rc;
   CiParams p{pooled, ldp, inv_hw, pad_of, W1, b1, gamma, beta, W2, b2, eps, B, C, S, CA};
   hipLaunchKernelGGL(channel_interaction_fwd_kernel, dim3(1), dim3(CI_THREADS), lds, (hipStream_t)stream, p, pm_out, cgate, running_mean,
@@ -481,9 +477,9 @@ int srk_channel_interaction_bwd(const float* pm, const float* dcgate, int ldg, f
   SRK_REQUIRE(pm && dcgate && pad_of && W1 && b1 && gamma && beta && W2 && b2 && dW1 && db1 && dgamma && dbeta && dW2 && db2 && dpool, SRK_E_NULL,
               "channel_interaction_bwd: null pointer");
   REQS(srk_channel_interaction_covered(B, C, S) && CA >= C && ldg >= CA, "channel_interaction_bwd: B=%d C=%d S=%d", B, C, S);
-  static SrkPerDevice<int> st_pd;
+  static SrkLdsState reserved;
   const size_t lds = ci_lds_floats(B, C, S, true) * 4;
-  const int rc = ci_configure(reinterpret_cast<const void*>(&channel_interaction_bwd_kernel), lds, &st_pd.here());
+  const int rc = ci_reserve(&channel_interaction_bwd_kernel, reserved);
   if (rc) return rc;
   CiParams p{nullptr, 0, inv_hw, pad_of, W1, b1, gamma, beta, W2, b2, eps, B, C, S, CA};
   hipLaunchKernelGGL(channel_interaction_bwd_kernel, dim3(1), dim3(CI_THREADS), lds, (hipStream_t)stream, p, pm, dcgate, ldg, dW1, db1, dgamma,
@@ -505,9 +501,9 @@ int srk_channel_interaction_frozen_fwd(const float* pooled, int ldp, float inv_h
   REQS(srk_channel_interaction_frozen_covered(B, C, S) && CA >= C && ldp >= CA,
        "channel_interaction_frozen_fwd: B=%d C=%d S=%d CA=%d ldp=%d (S <= 64; CA >= C; ldp >= CA; the arrays must fit %d bytes of LDS)", B, C, S, CA,
        ldp, CI_MAX_LDS);
-  static SrkPerDevice<int> st_pd;
+  static SrkLdsState reserved;
   const size_t lds = ci_lds_floats(B, C, S, false) * 4;
-  const int rc = ci_configure(reinterpret_cast<const void*>(&channel_interaction_frozen_fwd_kernel), lds, &st_pd.here());
+  const int rc = ci_reserve(&channel_interaction_frozen_fwd_kernel, reserved);
   if (rc) return rc;
   CiParams p{pooled, ldp, inv_hw, pad_of, W1, b1, gamma, beta, W2, b2, eps, B, C, S, CA};
   hipLaunchKernelGGL(channel_interaction_frozen_fwd_kernel, dim3(1), dim3(CI_THREADS), lds, (hipStream_t)stream, p, running_mean, running_var,
@@ -524,9 +520,9 @@ int srk_channel_interaction_frozen_bwd(const float* pm, const float* dcgate, int
               SRK_E_NULL, "channel_interaction_frozen_bwd: null pointer");
   REQS(srk_channel_interaction_frozen_covered(B, C, S) && CA >= C && ldg >= CA, "channel_interaction_frozen_bwd: B=%d C=%d S=%d CA=%d ldg=%d", B, C,
        S, CA, ldg);
-  static SrkPerDevice<int> st_pd;
+  static SrkLdsState reserved;
   const size_t lds = ci_lds_floats(B, C, S, true) * 4;
-  const int rc = ci_configure(reinterpret_cast<const void*>(&channel_interaction_frozen_bwd_kernel), lds, &st_pd.here());
+  const int rc = ci_reserve(&channel_interaction_frozen_bwd_kernel, reserved);
   if (rc) return rc;
   CiParams p{nullptr, 0, inv_hw, pad_of, W1, b1, gamma, beta, W2, b2, eps, B, C, S, CA};
   hipLaunchKernelGGL(channel_interaction_frozen_bwd_kernel, dim3(1), dim3(CI_THREADS), lds, (hipStream_t)stream, p, running_mean, running_var, pm,

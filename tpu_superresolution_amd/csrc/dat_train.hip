@@ -1009,16 +1009,9 @@ int srk_spatial_gate_train(int what, const uint16_t* x, int ldx, const float* W0
 #define SGT_LAUNCH(WHAT_, NV_)                                                                                                              \
   {                                                                                                                                         \
     constexpr size_t lds = (size_t)(16 * NV_ * 64 + 7 * 16 + (WHAT_ == 2 ? 256 + 16 * NV_ * 64 : 16 * 64)) * sizeof(float);                 \
-    static SrkPerDevice<bool> configured_pd;                                                                                                \
-    bool& configured = configured_pd.here();                                                                                                \
-    if (!configured) {                                                                                                                      \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&spatial_gate_train_kernel<WHAT_, NV_>),                                        \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {                                        \
-        srk_set_error("spatial_gate_train: cannot reserve LDS");                                                                            \
-        return SRK_E_LAUNCH;                                                                                                                \
-      }                                                                                                                                     \
-      configured = true;                                                                                                                    \
-    }                                                                                                                                       \
+    static SrkLdsState reserved;                                                                                                            \
+    if (const int rc = srk_reserve_lds(&spatial_gate_train_kernel<WHAT_, NV_>, lds, reserved, false, "spatial_gate_train: cannot reserve LDS")) \
+      return rc;                                                                                                                            \
     hipLaunchKernelGGL((spatial_gate_train_kernel<WHAT_, NV_>), dim3(grid), dim3(256), lds, st, x, ldx, W0, b0, bn_scale, bn_shift, w3,     \
                        dsmap, cA, cB, cC, dx, lddx, accumulate, partial, (long long)rows, S);                                               \
   }
@@ -1048,24 +1041,21 @@ int srk_rowln_bwd_bf16(const uint16_t* dy, int lddy, const uint16_t* x, int ldx,
        "rowln_bwd: bad shape (CP_out and the row strides multiples of 8, C <= CP_out <= 512 <= strides)");
   const dim3 grid((unsigned)srk_rowln_bwd_blocks(rows));
   hipStream_t st = (hipStream_t)stream;
-  static SrkPerDevice<bool> configured_pd; bool& configured = configured_pd.here();
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&rowln_bwd_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 2 * 384 * 4) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&rowln_bwd_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 2 * 512 * 4) != hipSuccess) {
-      srk_set_error("rowln_bwd: cannot reserve LDS");
-      return SRK_E_LAUNCH;
-    }
-    configured = true;
-  }
-  if (CP_out <= 128)
-    hipLaunchKernelGGL(rowln_bwd_kernel<1>, grid, dim3(256), 16 * 2 * 128 * sizeof(float), st, dy, lddy, x, ldx, gamma, dx, lddx, partial,
-                       (long long)rows, C, CP_out);
-  else if (CP_out <= 384)
+  // the two variants that need their LDS limit raised come first (the instantiation order is the kernels' order in the code object)
+  static SrkLdsState reserved[2];
+  constexpr const char* err = "rowln_bwd: cannot reserve LDS";
+  if (CP_out > 128 && CP_out <= 384) {
+    if (const int rc = srk_reserve_lds(&rowln_bwd_kernel<3>, 16 * 2 * 384 * sizeof(float), reserved[0], false, err)) return rc;
     hipLaunchKernelGGL(rowln_bwd_kernel<3>, grid, dim3(256), 16 * 2 * 384 * sizeof(float), st, dy, lddy, x, ldx, gamma, dx, lddx, partial,
                        (long long)rows, C, CP_out);
-  else
+  } else if (CP_out > 384) {
+    if (const int rc = srk_reserve_lds(&rowln_bwd_kernel<4>, 16 * 2 * 512 * sizeof(float), reserved[1], false, err)) return rc;
     hipLaunchKernelGGL(rowln_bwd_kernel<4>, grid, dim3(256), 16 * 2 * 512 * sizeof(float), st, dy, lddy, x, ldx, gamma, dx, lddx, partial,
                        (long long)rows, C, CP_out);
+  } else {
+    hipLaunchKernelGGL(rowln_bwd_kernel<1>, grid, dim3(256), 16 * 2 * 128 * sizeof(float), st, dy, lddy, x, ldx, gamma, dx, lddx, partial,
+                       (long long)rows, C, CP_out);
+  }
   return srk_check_launch("rowln_bwd");
 }
 

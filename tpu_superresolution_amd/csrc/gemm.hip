@@ -357,15 +357,8 @@ int launch(const GemmParams& p, hipStream_t stream) {
   constexpr int BN = NARROW ? 16 : NT * 32;
   constexpr int WS_ROWS = NARROW ? 32 : BN;
   constexpr size_t lds = (size_t)(2 * BM * BK + 2 * WS_ROWS * BK) * sizeof(bf16_t);
-  static SrkPerDevice<bool> configured_pd; bool& configured = configured_pd.here();
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<LD, EP, NT, NARROW>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      srk_set_error("gemm: cannot reserve %zu bytes of LDS", lds);
-      return SRK_E_LAUNCH;
-    }
-    configured = true;
-  }
+  static SrkLdsState reserved;
+  if (const int rc = srk_reserve_lds(&gemm_kernel<LD, EP, NT, NARROW>, lds, reserved, false, "gemm: cannot reserve %zu bytes of LDS", lds)) return rc;
   dim3 grid(cdiv(p.M, BM) * cdiv(p.N, BN));
   const int fam = LD == LD_ROWS ? FAM_GEMM_LINEAR : FAM_GEMM_CONV;
   srk_probe_pre(fam, stream, p.flops, p.bytes);

@@ -1225,46 +1225,36 @@ SrkOpt g_mlp_bwd_fused_enabled{OPT_MLP_BWD_FUSED, 1};
 SrkOpt g_mlp_dgelu_store{OPT_MLP_DGELU_STORE, 1};   // fused MLP pair of the training plan: keep gelu'(u) instead of u between the passes
 
 SrkOpt g_stream_enabled{OPT_GEMM_STREAM, -1};     // -1: read SRK_GEMM_STREAM once
-thread_local int g_num_cus = 0;      // CU count of the device the current launch goes to (refreshed by every launcher)
 SrkOpt g_tune_bm{OPT_TUNE_BM, 0};             // tuning overrides (srk_set_option): rows per tile 16/32/64, 0 = per-epilogue default
 SrkOpt g_tune_ks2{OPT_TUNE_KS2, -1};           // split K over the two wave groups: 0/1, -1 = default
 SrkOpt g_tune_split{OPT_TUNE_SPLIT, -1};         // role-split kernel (MFMA on the loader waves): 0/1, -1 = default
 SrkOpt g_tune_nb{OPT_TUNE_NB, 0};             // role-split kernel: epilogue waves 4/8, 0 = default
 
+// a variant that spills would put scratch traffic on the loaders' vmcnt counter: never run it (SRK_NOT_COVERED)
 template <typename KernelT>
-int stream_configure(KernelT kernel, int lds, int* state) {
-  if (*state) return SRK_OK;
-  const void* fn = reinterpret_cast<const void*>(kernel);
-  hipFuncAttributes attr;
-  if (hipFuncGetAttributes(&attr, fn) != hipSuccess) {
-    srk_set_error("gemm(stream): cannot query the kernel");
-    return SRK_E_LAUNCH;
+int stream_reserve(KernelT kernel, int lds, SrkLdsState& st) {
+  return srk_reserve_lds(kernel, lds, st, true, "gemm(stream): cannot reserve %d bytes of LDS", lds);
+}
+
+int stream_enabled() {
+  if (g_stream_enabled < 0) {
+    const char* e = getenv("SRK_GEMM_STREAM");
+    g_stream_enabled = (e && e[0] == '0') ? 0 : 1;
   }
-  // a variant that spills would put scratch traffic on the loaders' vmcnt counter: never run it
-  if (attr.localSizeBytes > 0) {
-    *state = -1;
-    return SRK_OK;
-  }
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-    srk_set_error("gemm(stream): cannot reserve %d bytes of LDS", lds);
-    return SRK_E_LAUNCH;
-  }
-  *state = 1;
-  return SRK_OK;
+  return g_stream_enabled;
 }
 
 template <int EP, int KC, int BM, int NB>
-int launch_split(const GemmParams& p, hipStream_t stream) {
+int launch_split(const GemmParams& p, int cus, hipStream_t stream) {
   using S = SplitCfg<EP, KC, BM>;
   if constexpr (!S::VALID || BM % (4 * NB) != 0 || (NB == 8 && (KC > 3 || EP == EP_LNBWD))) {   // 12 waves: <= 168 VGPRs
     return SRK_NOT_COVERED;
   } else {
-    static SrkPerDevice<int> configured_pd; int& configured = configured_pd.here();     // 1 usable, -1 not usable
-    const int rc = stream_configure(&gemm_stream_split_kernel<EP, KC, BM, NB>, S::LDS, &configured);
+    static SrkLdsState reserved;
+    const int rc = stream_reserve(&gemm_stream_split_kernel<EP, KC, BM, NB>, S::LDS, reserved);
     if (rc) return rc;
-    if (configured < 0) return SRK_NOT_COVERED;
     const int nchunk = p.N / SBN;
-    const int per_xcd = g_num_cus / 8;
+    const int per_xcd = cus / 8;
     srk_probe_pre(FAM_GEMM_LINEAR, stream, p.flops, p.bytes);
     hipLaunchKernelGGL((gemm_stream_split_kernel<EP, KC, BM, NB>), dim3(per_xcd * 8), dim3(64 * (NB + 4)), S::LDS, stream, p, nchunk, per_xcd / nchunk);
     srk_probe_post(FAM_GEMM_LINEAR, stream);
@@ -1273,17 +1263,16 @@ int launch_split(const GemmParams& p, hipStream_t stream) {
 }
 
 template <int EP, int KC, int BM, bool KS2>
-int launch_stream(const GemmParams& p, hipStream_t stream) {
+int launch_stream(const GemmParams& p, int cus, hipStream_t stream) {
   using C = StreamCfg<EP, KC, BM>;
   if constexpr (!C::VALID || (KC == 9 && !KS2)) {
     return SRK_NOT_COVERED;
   } else {
-    static SrkPerDevice<int> configured_pd; int& configured = configured_pd.here();     // 1 usable, -1 not usable
-    const int rcc = stream_configure(&gemm_stream_kernel<EP, KC, BM, KS2>, C::LDS, &configured);
+    static SrkLdsState reserved;
+    const int rcc = stream_reserve(&gemm_stream_kernel<EP, KC, BM, KS2>, C::LDS, reserved);
     if (rcc) return rcc;
-    if (configured < 0) return SRK_NOT_COVERED;
     const int nchunk = p.N / SBN;
-    const int per_xcd = g_num_cus / 8;
+    const int per_xcd = cus / 8;
     const int groups_per_xcd = per_xcd / nchunk;
     srk_probe_pre(FAM_GEMM_LINEAR, stream, p.flops, p.bytes);
     hipLaunchKernelGGL((gemm_stream_kernel<EP, KC, BM, KS2>), dim3(per_xcd * 8), dim3(512), C::LDS, stream, p, nchunk, groups_per_xcd);
@@ -1293,23 +1282,23 @@ int launch_stream(const GemmParams& p, hipStream_t stream) {
 }
 
 template <int EP, int KC>
-int launch_cfg(const GemmParams& p, hipStream_t stream, int bm, bool ks2) {
-  if (bm == 16) return ks2 ? launch_stream<EP, KC, 16, true>(p, stream) : launch_stream<EP, KC, 16, false>(p, stream);
-  if (bm == 32) return ks2 ? launch_stream<EP, KC, 32, true>(p, stream) : launch_stream<EP, KC, 32, false>(p, stream);
-  if (bm == 64) return ks2 ? launch_stream<EP, KC, 64, true>(p, stream) : launch_stream<EP, KC, 64, false>(p, stream);
+int launch_cfg(const GemmParams& p, int cus, hipStream_t stream, int bm, bool ks2) {
+  if (bm == 16) return ks2 ? launch_stream<EP, KC, 16, true>(p, cus, stream) : launch_stream<EP, KC, 16, false>(p, cus, stream);
+  if (bm == 32) return ks2 ? launch_stream<EP, KC, 32, true>(p, cus, stream) : launch_stream<EP, KC, 32, false>(p, cus, stream);
+  if (bm == 64) return ks2 ? launch_stream<EP, KC, 64, true>(p, cus, stream) : launch_stream<EP, KC, 64, false>(p, cus, stream);
   return SRK_NOT_COVERED;
 }
 
 template <int EP, int KC>
-int launch_split_bm(const GemmParams& p, hipStream_t stream, int bm, int nb) {
+int launch_split_bm(const GemmParams& p, int cus, hipStream_t stream, int bm, int nb) {
   if (nb == 8) {
-    if (bm == 32) return launch_split<EP, KC, 32, 8>(p, stream);
-    if (bm == 64) return launch_split<EP, KC, 64, 8>(p, stream);
+    if (bm == 32) return launch_split<EP, KC, 32, 8>(p, cus, stream);
+    if (bm == 64) return launch_split<EP, KC, 64, 8>(p, cus, stream);
     return SRK_NOT_COVERED;
   }
-  if (bm == 16) return launch_split<EP, KC, 16, 4>(p, stream);
-  if (bm == 32) return launch_split<EP, KC, 32, 4>(p, stream);
-  if (bm == 64) return launch_split<EP, KC, 64, 4>(p, stream);
+  if (bm == 16) return launch_split<EP, KC, 16, 4>(p, cus, stream);
+  if (bm == 32) return launch_split<EP, KC, 32, 4>(p, cus, stream);
+  if (bm == 64) return launch_split<EP, KC, 64, 4>(p, cus, stream);
   return SRK_NOT_COVERED;
 }
 
@@ -1322,21 +1311,21 @@ struct StreamChoice {
 };
 
 template <int EP, int KC>
-int pick(const GemmParams& p, hipStream_t stream, StreamChoice def) {
+int pick(const GemmParams& p, int cus, hipStream_t stream, StreamChoice def) {
   StreamChoice c = def;
   if (g_tune_bm) c.bm = g_tune_bm;
   if (g_tune_ks2 >= 0) c.ks2 = g_tune_ks2 != 0;
   if (g_tune_split >= 0) c.split = g_tune_split != 0;
   if (g_tune_nb > 0) c.nb = g_tune_nb;
-  int rc = c.split ? launch_split_bm<EP, KC>(p, stream, c.bm, c.nb) : launch_cfg<EP, KC>(p, stream, c.bm, c.ks2);
-  if (rc == SRK_NOT_COVERED) rc = def.split ? launch_split_bm<EP, KC>(p, stream, def.bm, def.nb) : launch_cfg<EP, KC>(p, stream, def.bm, def.ks2);
+  int rc = c.split ? launch_split_bm<EP, KC>(p, cus, stream, c.bm, c.nb) : launch_cfg<EP, KC>(p, cus, stream, c.bm, c.ks2);
+  if (rc == SRK_NOT_COVERED) rc = def.split ? launch_split_bm<EP, KC>(p, cus, stream, def.bm, def.nb) : launch_cfg<EP, KC>(p, cus, stream, def.bm, def.ks2);
   return rc;
 }
 
 template <int EP>
-int dispatch_k(const GemmParams& p, hipStream_t stream, StreamChoice k192, StreamChoice k384) {
-  if (p.K == 192) return pick<EP, 3>(p, stream, k192);
-  if (p.K == 384) return pick<EP, 6>(p, stream, k384);
+int dispatch_k(const GemmParams& p, int cus, hipStream_t stream, StreamChoice k192, StreamChoice k384) {
+  if (p.K == 192) return pick<EP, 3>(p, cus, stream, k192);
+  if (p.K == 384) return pick<EP, 6>(p, cus, stream, k384);
   return SRK_NOT_COVERED;
 }
 
@@ -1350,13 +1339,7 @@ void srk_gemm_stream_tune(int bm, int ks2, int split, int nb) {
   g_tune_split = split;
   g_tune_nb = nb;
 }
-int srk_gemm_stream_enabled() {
-  if (g_stream_enabled < 0) {
-    const char* e = getenv("SRK_GEMM_STREAM");
-    g_stream_enabled = (e && e[0] == '0') ? 0 : 1;
-  }
-  return g_stream_enabled;
-}
+int srk_gemm_stream_enabled() { return stream_enabled(); }
 void srk_gemm_stream_tune_get(int* bm, int* ks2, int* split, int* nb) {
   *bm = g_tune_bm; *ks2 = g_tune_ks2; *split = g_tune_split; *nb = g_tune_nb;
 }
@@ -1364,42 +1347,38 @@ void srk_gemm_stream_tune_get(int* bm, int* ks2, int* split, int* nb) {
 // launches of the streaming kernels through srk_launch_gemm_stream in this process so far (tests assert which GEMM path ran)
 static std::atomic<long long> g_gemm_stream_launches{0};
 extern "C" long long srk_gemm_stream_launches(void) { return g_gemm_stream_launches.load(); }
-static int stream_dispatch(int epilogue, const GemmParams& p, hipStream_t stream);
+static int stream_dispatch(int epilogue, const GemmParams& p, int cus, hipStream_t stream);
 
 // Returns SRK_NOT_COVERED when the streaming kernel does not cover this problem (the caller then uses the tile kernel).
 int srk_launch_gemm_stream(int epilogue, const GemmParams& p, hipStream_t stream) {
-  if (g_stream_enabled < 0) {
-    const char* e = getenv("SRK_GEMM_STREAM");
-    g_stream_enabled = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (!g_stream_enabled) return SRK_NOT_COVERED;
-  g_num_cus = srk_device_cus() & ~7;          // of the CURRENT device (cached per device id)
-  if (g_num_cus < 8) return SRK_NOT_COVERED;
-  if (p.N % SBN != 0 || p.M % 64 != 0 || p.lda % 8 != 0 || p.N / SBN > g_num_cus / 8) return SRK_NOT_COVERED;
-  if (p.M < 64 * g_num_cus) return SRK_NOT_COVERED;            // too few tiles to fill the persistent grid
+  if (!stream_enabled()) return SRK_NOT_COVERED;
+  const int cus = srk_device_cus() & ~7;      // of the CURRENT device (cached per device id)
+  if (cus < 8) return SRK_NOT_COVERED;
+  if (p.N % SBN != 0 || p.M % 64 != 0 || p.lda % 8 != 0 || p.N / SBN > cus / 8) return SRK_NOT_COVERED;
+  if (p.M < 64 * cus) return SRK_NOT_COVERED;            // too few tiles to fill the persistent grid
   if (p.rowscale && (p.rows_per_sample <= 0 || p.rows_per_sample % 64 != 0)) return SRK_NOT_COVERED;   // a tile lies inside one sample
   if (p.M >= (1 << 24)) return SRK_NOT_COVERED;                // row / token indices go through fdiv24
   // window-ordered rows: stream_issue_tile takes a tile's sample from its image (tokbase / rows_per_sample), which is the sample of
   // its tokens only where a sample IS an image; anything else goes to the tile kernel (token / rows_per_sample per row)
   if (p.rowscale && (epilogue == EP_PROJ_RES || (epilogue == EP_LNBWD && p.ln_rows_window)) && p.rows_per_sample != p.geom.H * p.geom.W)
     return SRK_NOT_COVERED;
-  const int rc_stream = stream_dispatch(epilogue, p, stream);
+  const int rc_stream = stream_dispatch(epilogue, p, cus, stream);
   if (rc_stream == SRK_OK) g_gemm_stream_launches.fetch_add(1);
   return rc_stream;
 }
 
-static int stream_dispatch(int epilogue, const GemmParams& p, hipStream_t stream) {
+static int stream_dispatch(int epilogue, const GemmParams& p, int cus, hipStream_t stream) {
   switch (epilogue) {
-    case EP_BF16: return dispatch_k<EP_BF16>(p, stream, {32, false, true}, {32, false, true});
-    case EP_QKV: return dispatch_k<EP_QKV>(p, stream, {64, false, false}, {32, false, true});   // front-bound when split: 3 slices share A
-    case EP_GELU: return dispatch_k<EP_GELU>(p, stream, {32, false, true}, {32, false, true});
-    case EP_DGELU: return dispatch_k<EP_DGELU>(p, stream, {32, false, true}, {32, false, true});
-    case EP_PROJ_RES: if (p.N != SBN) return SRK_NOT_COVERED; return dispatch_k<EP_PROJ_RES>(p, stream, {16, false, true}, {16, false, true});
-    case EP_RES: if (p.N != SBN) return SRK_NOT_COVERED; return dispatch_k<EP_RES>(p, stream, {16, false, true}, {16, false, true});
+    case EP_BF16: return dispatch_k<EP_BF16>(p, cus, stream, {32, false, true}, {32, false, true});
+    case EP_QKV: return dispatch_k<EP_QKV>(p, cus, stream, {64, false, false}, {32, false, true});   // front-bound when split: 3 slices share A
+    case EP_GELU: return dispatch_k<EP_GELU>(p, cus, stream, {32, false, true}, {32, false, true});
+    case EP_DGELU: return dispatch_k<EP_DGELU>(p, cus, stream, {32, false, true}, {32, false, true});
+    case EP_PROJ_RES: if (p.N != SBN) return SRK_NOT_COVERED; return dispatch_k<EP_PROJ_RES>(p, cus, stream, {16, false, true}, {16, false, true});
+    case EP_RES: if (p.N != SBN) return SRK_NOT_COVERED; return dispatch_k<EP_RES>(p, cus, stream, {16, false, true}, {16, false, true});
     case EP_LNBWD:
       if (p.N != SBN) return SRK_NOT_COVERED;
-      if (p.K == 576) return pick<EP_LNBWD, 9>(p, stream, {16, true, false});
-      return dispatch_k<EP_LNBWD>(p, stream, {16, true, false}, {16, true, false});
+      if (p.K == 576) return pick<EP_LNBWD, 9>(p, cus, stream, {16, true, false});
+      return dispatch_k<EP_LNBWD>(p, cus, stream, {16, true, false}, {16, true, false});
     default: return SRK_NOT_COVERED;
   }
 }
@@ -1413,26 +1392,21 @@ int srk_mlp_fused_enabled() { return g_mlp_fused_enabled; }
 
 int srk_launch_mlp_fused(const GemmParams& p, hipStream_t stream) {
   if (!g_mlp_fused_enabled) return SRK_NOT_COVERED;
-  if (g_stream_enabled < 0) {
-    const char* e = getenv("SRK_GEMM_STREAM");
-    g_stream_enabled = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (!g_stream_enabled) return SRK_NOT_COVERED;
-  g_num_cus = srk_device_cus() & ~7;          // of the CURRENT device (cached per device id)
-  if (g_num_cus < 8) return SRK_NOT_COVERED;
+  if (!stream_enabled()) return SRK_NOT_COVERED;
+  const int cus = srk_device_cus() & ~7;      // of the CURRENT device (cached per device id)
+  if (cus < 8) return SRK_NOT_COVERED;
   if (p.K != MlpCfg::K1 || p.HP != MlpCfg::HP || p.N != SBN || p.lda % 8 != 0 || p.ldo != SBN) return SRK_NOT_COVERED;
-  if (p.M % 64 != 0 || p.M < 64 * g_num_cus || p.M >= (1 << 24)) return SRK_NOT_COVERED;
+  if (p.M % 64 != 0 || p.M < 64 * cus || p.M >= (1 << 24)) return SRK_NOT_COVERED;
   if (p.rowscale && (p.rows_per_sample <= 0 || p.rows_per_sample % 64 != 0)) return SRK_NOT_COVERED;
   if (!p.A || !p.Wt || !p.W2 || !p.res || !p.outf || (p.u_out != nullptr) != (p.h_out != nullptr)) return SRK_NOT_COVERED;
   if (p.u_dgelu && !p.u_out) return SRK_NOT_COVERED;
-  static SrkPerDevice<int> configured_pd[2]; int& configured = configured_pd[p.u_dgelu ? 1 : 0].here();
-  const int rc = p.u_dgelu ? stream_configure(&mlp_fused_fwd_kernel<true>, MlpCfg::LDS, &configured)
-                           : stream_configure(&mlp_fused_fwd_kernel<false>, MlpCfg::LDS, &configured);
-  if (rc) return rc;
-  if (configured < 0) return SRK_NOT_COVERED;       // the build spilled: never run it (scratch traffic would break the counted waits)
+  static SrkLdsState reserved[2];
+  const int rc = p.u_dgelu ? stream_reserve(&mlp_fused_fwd_kernel<true>, MlpCfg::LDS, reserved[1])
+                           : stream_reserve(&mlp_fused_fwd_kernel<false>, MlpCfg::LDS, reserved[0]);
+  if (rc) return rc;                                // SRK_NOT_COVERED: the build spilled (scratch traffic would break the counted waits)
   srk_probe_pre(FAM_GEMM_LINEAR, stream, p.flops, p.bytes);
-  if (p.u_dgelu) hipLaunchKernelGGL(mlp_fused_fwd_kernel<true>, dim3(g_num_cus), dim3(512), MlpCfg::LDS, stream, p, g_num_cus / 8);
-  else hipLaunchKernelGGL(mlp_fused_fwd_kernel<false>, dim3(g_num_cus), dim3(512), MlpCfg::LDS, stream, p, g_num_cus / 8);
+  if (p.u_dgelu) hipLaunchKernelGGL(mlp_fused_fwd_kernel<true>, dim3(cus), dim3(512), MlpCfg::LDS, stream, p, cus / 8);
+  else hipLaunchKernelGGL(mlp_fused_fwd_kernel<false>, dim3(cus), dim3(512), MlpCfg::LDS, stream, p, cus / 8);
   srk_probe_post(FAM_GEMM_LINEAR, stream);
   g_mlp_fused_launches[0][p.u_dgelu ? 1 : 0].fetch_add(1);
   return srk_check_launch("mlp_fused");
@@ -1447,27 +1421,22 @@ int srk_mlp_bwd_fused_enabled() { return g_mlp_bwd_fused_enabled; }
 // LayerNorm-backward fields, outf / outb / geom / rowscale as for EP_LNBWD.  SRK_NOT_COVERED -> run the two GEMMs.
 int srk_launch_mlp_fused_bwd(const GemmParams& p, hipStream_t stream) {
   if (!g_mlp_bwd_fused_enabled) return SRK_NOT_COVERED;
-  if (g_stream_enabled < 0) {
-    const char* e = getenv("SRK_GEMM_STREAM");
-    g_stream_enabled = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (!g_stream_enabled) return SRK_NOT_COVERED;
-  g_num_cus = srk_device_cus() & ~7;          // of the CURRENT device (cached per device id)
-  if (g_num_cus < 8) return SRK_NOT_COVERED;
+  if (!stream_enabled()) return SRK_NOT_COVERED;
+  const int cus = srk_device_cus() & ~7;      // of the CURRENT device (cached per device id)
+  if (cus < 8) return SRK_NOT_COVERED;
   if (p.K != MlpBwdCfg::K1 || p.HP != MlpBwdCfg::HP || p.N != SBN || p.lda % 8 != 0 || p.ldo != SBN) return SRK_NOT_COVERED;
-  if (p.M % 64 != 0 || p.M < 64 * g_num_cus || p.M >= (1 << 24)) return SRK_NOT_COVERED;
+  if (p.M % 64 != 0 || p.M < 64 * cus || p.M >= (1 << 24)) return SRK_NOT_COVERED;
   if (p.rowscale && (p.rows_per_sample <= 0 || p.rows_per_sample % 64 != 0)) return SRK_NOT_COVERED;
   if (!p.A || !p.Wt || !p.W2 || !p.aux || !p.u_out || !p.outf || !p.ln_x || !p.ln_mean || !p.ln_rstd || !p.ln_gamma || !p.ln_dgamma ||
       !p.ln_dbeta || p.ln_rows_window != 0)
     return SRK_NOT_COVERED;
-  static SrkPerDevice<int> configured_pd[2]; int& configured = configured_pd[p.u_dgelu ? 1 : 0].here();
-  const int rc = p.u_dgelu ? stream_configure(&mlp_fused_bwd_kernel<true>, MlpBwdCfg::LDS, &configured)
-                           : stream_configure(&mlp_fused_bwd_kernel<false>, MlpBwdCfg::LDS, &configured);
-  if (rc) return rc;
-  if (configured < 0) return SRK_NOT_COVERED;       // the build spilled: never run it (scratch traffic would break the counted waits)
+  static SrkLdsState reserved[2];
+  const int rc = p.u_dgelu ? stream_reserve(&mlp_fused_bwd_kernel<true>, MlpBwdCfg::LDS, reserved[1])
+                           : stream_reserve(&mlp_fused_bwd_kernel<false>, MlpBwdCfg::LDS, reserved[0]);
+  if (rc) return rc;                                // SRK_NOT_COVERED: the build spilled (scratch traffic would break the counted waits)
   srk_probe_pre(FAM_GEMM_LINEAR, stream, p.flops, p.bytes);
-  if (p.u_dgelu) hipLaunchKernelGGL(mlp_fused_bwd_kernel<true>, dim3(g_num_cus), dim3(512), MlpBwdCfg::LDS, stream, p, g_num_cus / 8);
-  else hipLaunchKernelGGL(mlp_fused_bwd_kernel<false>, dim3(g_num_cus), dim3(512), MlpBwdCfg::LDS, stream, p, g_num_cus / 8);
+  if (p.u_dgelu) hipLaunchKernelGGL(mlp_fused_bwd_kernel<true>, dim3(cus), dim3(512), MlpBwdCfg::LDS, stream, p, cus / 8);
+  else hipLaunchKernelGGL(mlp_fused_bwd_kernel<false>, dim3(cus), dim3(512), MlpBwdCfg::LDS, stream, p, cus / 8);
   srk_probe_post(FAM_GEMM_LINEAR, stream);
   g_mlp_fused_launches[1][p.u_dgelu ? 1 : 0].fetch_add(1);
   return srk_check_launch("mlp_fused_bwd");

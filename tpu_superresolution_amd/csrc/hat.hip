@@ -305,12 +305,10 @@ int srk_mlp_fused_fwd(const uint16_t* xn, const uint16_t* w1, const float* b1, c
   return rc;
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 int srk_img_prep(const float* x, float* out, int B, int Cimg, int H0, int W0, int H, int W, float range, const float* mean3, srk_stream_t stream) {
   SRK_REQUIRE(x && out && mean3, SRK_E_NULL, "img_prep: null pointer");
   SRK_REQUIRE(B > 0 && H >= H0 && W >= W0 && H - H0 < H0 && W - W0 < W0 && Cimg >= 1 && Cimg <= 3, SRK_E_SHAPE, "img_prep: bad geometry");
-  SRK_REQUIRE(aligned16(out), SRK_E_ALIGN, "img_prep: out is not 16-byte aligned");
+  SRK_REQUIRE(srk_aligned(out, 16), SRK_E_ALIGN, "img_prep: out is not 16-byte aligned");
   return srk_launch_img_prep(x, out, B, Cimg, H0, W0, H, W, range, mean3, (hipStream_t)stream);
 }
 
@@ -321,7 +319,7 @@ int srk_stem_conv(const float* img4, const float* weight, const float* bias, flo
   // the kernel stages [36][CP] weights + 16 pixels x 36 taps in dynamic LDS: (36 CP + 576) * 4 bytes, 39 KB at CP = 256
   SRK_REQUIRE(Cin >= 1 && Cin <= 4 && C >= 1 && C <= CP && CP % 4 == 0 && CP <= 256, SRK_E_SHAPE,
               "stem_conv: Cin=%d C=%d CP=%d (1 <= Cin <= 4, 1 <= C <= CP, CP a multiple of 4, <= 256)", Cin, C, CP);
-  SRK_REQUIRE(aligned16(img4) && aligned16(out), SRK_E_ALIGN, "stem_conv: img4 / out not 16-byte aligned");
+  SRK_REQUIRE(srk_aligned(img4, 16) && srk_aligned(out, 16), SRK_E_ALIGN, "stem_conv: img4 / out not 16-byte aligned");
   return srk_launch_stem_conv(img4, weight, bias, out, B, H, W, Cin, C, CP, (hipStream_t)stream);
 }
 

@@ -202,15 +202,12 @@ int srk_win256_attention_bwd(const uint16_t* qkv, int ldq, int CA, const float* 
                                     scale, overlap, (hipStream_t)stream);
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
-
 int srk_layernorm_bwd(const uint16_t* dy, const float* x, const float* mean, const float* rstd, const float* gamma, float* gx,
                       uint16_t* gx_bf16, float* dgamma, float* dbeta, int rows, int C, int CP, int accumulate, srk_stream_t stream) {
   SRK_REQUIRE(dy && x && mean && rstd && gamma && gx && dgamma && dbeta, SRK_E_NULL, "layernorm_bwd: null pointer");
   SRK_REQUIRE(rows > 0 && C > 0 && C <= CP && CP % 64 == 0 && CP <= 256, SRK_E_SHAPE, "layernorm_bwd: rows=%d C=%d CP=%d", rows, C, CP);
   // float4 accesses of x / gx, uint2 (four bf16) accesses of dy / gx_bf16
-  SRK_REQUIRE(aligned16(x) && aligned16(gx) && aligned8(dy) && aligned8(gx_bf16), SRK_E_ALIGN,
+  SRK_REQUIRE(srk_aligned(x, 16) && srk_aligned(gx, 16) && srk_aligned(dy, 8) && srk_aligned(gx_bf16, 8), SRK_E_ALIGN,
               "layernorm_bwd: x / gx not 16-byte or dy / gx_bf16 not 8-byte aligned");
   return srk_launch_ln_bwd(dy, x, mean, rstd, gamma, gx, gx_bf16, dgamma, dbeta, rows, C, CP, nullptr, 0, 0, 0, accumulate, nullptr, rows,
                            (hipStream_t)stream);
@@ -219,21 +216,22 @@ int srk_layernorm_bwd(const uint16_t* dy, const float* x, const float* mean, con
 int srk_add_f32_bf16(float* a, const float* b, uint16_t* ab_bf16, int64_t n, srk_stream_t stream) {
   SRK_REQUIRE(a && b && ab_bf16, SRK_E_NULL, "add_f32_bf16: null pointer");
   SRK_REQUIRE(n > 0 && n % 4 == 0, SRK_E_SHAPE, "add_f32_bf16: n=%lld must be a positive multiple of 4", (long long)n);
-  SRK_REQUIRE(aligned16(a) && aligned16(b) && aligned8(ab_bf16), SRK_E_ALIGN, "add_f32_bf16: a / b not 16-byte or ab_bf16 not 8-byte aligned");
+  SRK_REQUIRE(srk_aligned(a, 16) && srk_aligned(b, 16) && srk_aligned(ab_bf16, 8), SRK_E_ALIGN,
+              "add_f32_bf16: a / b not 16-byte or ab_bf16 not 8-byte aligned");
   return srk_launch_add_f32_bf16(a, b, ab_bf16, n, (hipStream_t)stream);
 }
 
 int srk_add_bf16_into_f32(float* a, const uint16_t* b, int64_t n, srk_stream_t stream) {
   SRK_REQUIRE(a && b, SRK_E_NULL, "add_bf16_into_f32: null pointer");
   SRK_REQUIRE(n > 0 && n % 4 == 0, SRK_E_SHAPE, "add_bf16_into_f32: n=%lld must be a positive multiple of 4", (long long)n);
-  SRK_REQUIRE(aligned16(a) && aligned8(b), SRK_E_ALIGN, "add_bf16_into_f32: a not 16-byte or b not 8-byte aligned");
+  SRK_REQUIRE(srk_aligned(a, 16) && srk_aligned(b, 8), SRK_E_ALIGN, "add_bf16_into_f32: a not 16-byte or b not 8-byte aligned");
   return srk_launch_add_bf16_into_f32(a, b, n, (hipStream_t)stream);
 }
 
 int srk_add_f32(float* out, const float* a, const float* b, int64_t n, srk_stream_t stream) {
   SRK_REQUIRE(out && a && b, SRK_E_NULL, "add_f32: null pointer");
   SRK_REQUIRE(n > 0 && n % 4 == 0, SRK_E_SHAPE, "add_f32: n=%lld must be a positive multiple of 4", (long long)n);
-  SRK_REQUIRE(aligned16(out) && aligned16(a) && aligned16(b), SRK_E_ALIGN, "add_f32: out / a / b not 16-byte aligned");
+  SRK_REQUIRE(srk_aligned(out, 16) && srk_aligned(a, 16) && srk_aligned(b, 16), SRK_E_ALIGN, "add_f32: out / a / b not 16-byte aligned");
   const long long n4 = n / 4;
   const int grid = (int)((n4 + 255) / 256 < 16384 ? (n4 + 255) / 256 : 16384);
   hipLaunchKernelGGL(add3_f32_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, a, b, n4);
@@ -244,7 +242,7 @@ int srk_rowscale_bf16(const uint16_t* src, uint16_t* dst, const float* f, int64_
   SRK_REQUIRE(src && dst && f, SRK_E_NULL, "rowscale_bf16: null pointer");
   SRK_REQUIRE(rows > 0 && rows_per_sample > 0 && CP > 0 && CP % 4 == 0, SRK_E_SHAPE, "rowscale_bf16: rows=%lld rows_per_sample=%d CP=%d",
               (long long)rows, rows_per_sample, CP);
-  SRK_REQUIRE(aligned8(src) && aligned8(dst), SRK_E_ALIGN, "rowscale_bf16: src / dst not 8-byte aligned");
+  SRK_REQUIRE(srk_aligned(src, 8) && srk_aligned(dst, 8), SRK_E_ALIGN, "rowscale_bf16: src / dst not 8-byte aligned");
   const long long n4 = rows * (CP / 4);
   const int grid = (int)((n4 + 255) / 256 < 16384 ? (n4 + 255) / 256 : 16384);
   hipLaunchKernelGGL(rowscale_bf16_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, dst, f, (long long)rows, rows_per_sample, CP);
@@ -274,7 +272,7 @@ int srk_smallconv_wgrad(const uint16_t* x, const float* gy, float* dw, float* db
                         srk_stream_t stream) {
   SRK_REQUIRE(x && gy && dw && db, SRK_E_NULL, "smallconv_wgrad: null pointer");
   if (int rc = smallconv_check("smallconv_wgrad", B, H, W, Cin, CinP, Co, CoP)) return rc;
-  SRK_REQUIRE(aligned16(x) && aligned16(gy), SRK_E_ALIGN, "smallconv_wgrad: x and gy must be 16-byte aligned");
+  SRK_REQUIRE(srk_aligned(x, 16) && srk_aligned(gy, 16), SRK_E_ALIGN, "smallconv_wgrad: x and gy must be 16-byte aligned");
   return srk_launch_smallconv_wgrad(x, gy, dw, db, B, H, W, Cin, CinP, Co, CoP, (hipStream_t)stream);
 }
 
@@ -282,7 +280,7 @@ int srk_smallconv_dgrad(const float* gy, const float* weight, uint16_t* dx, int 
                         srk_stream_t stream) {
   SRK_REQUIRE(gy && weight && dx, SRK_E_NULL, "smallconv_dgrad: null pointer");
   if (int rc = smallconv_check("smallconv_dgrad", B, H, W, Cin, CinP, Co, CoP)) return rc;
-  SRK_REQUIRE(aligned16(gy) && aligned16(dx), SRK_E_ALIGN, "smallconv_dgrad: gy and dx must be 16-byte aligned");
+  SRK_REQUIRE(srk_aligned(gy, 16) && srk_aligned(dx, 16), SRK_E_ALIGN, "smallconv_dgrad: gy and dx must be 16-byte aligned");
   return srk_launch_smallconv_dgrad(gy, weight, dx, B, H, W, Cin, CinP, Co, CoP, (hipStream_t)stream);
 }
 
@@ -291,14 +289,14 @@ int srk_stem_wgrad(const float* img4, const float* gy, float* dw, float* db, int
   SRK_REQUIRE(B > 0 && H > 0 && W > 0, SRK_E_SHAPE, "stem_wgrad: B=%d H=%d W=%d", B, H, W);
   SRK_REQUIRE(Cin >= 1 && Cin <= 4 && C >= 1 && C <= CP && C <= 256 && CP % 4 == 0, SRK_E_SHAPE,
               "stem_wgrad: Cin=%d C=%d CP=%d (Cin <= 4, C <= CP, C <= 256, CP a multiple of 4)", Cin, C, CP);
-  SRK_REQUIRE(aligned16(img4) && aligned16(gy), SRK_E_ALIGN, "stem_wgrad: img4 and gy must be 16-byte aligned");
+  SRK_REQUIRE(srk_aligned(img4, 16) && srk_aligned(gy, 16), SRK_E_ALIGN, "stem_wgrad: img4 and gy must be 16-byte aligned");
   return srk_launch_stem_wgrad(img4, gy, dw, db, B, H, W, Cin, C, CP, (hipStream_t)stream);
 }
 
 int srk_conv3x3_wgrad_ps_bf16(const uint16_t* y, const uint16_t* x, float* dw, float* db, int B, int H, int W, int CinP, int N, int r, int Cs,
                               srk_stream_t stream) {
   SRK_REQUIRE(y && x && dw, SRK_E_NULL, "conv3x3_wgrad_ps: null pointer");
-  SRK_REQUIRE(aligned16(y) && aligned16(x), SRK_E_ALIGN, "conv3x3_wgrad_ps: y and x must be 16-byte aligned");
+  SRK_REQUIRE(srk_aligned(y, 16) && srk_aligned(x, 16), SRK_E_ALIGN, "conv3x3_wgrad_ps: y and x must be 16-byte aligned");
   SRK_REQUIRE(B > 0 && H > 0 && W > 0 && (long long)B * H * W < (1ll << 31), SRK_E_SHAPE, "conv3x3_wgrad_ps: B=%d H=%d W=%d", B, H, W);
   SRK_REQUIRE(r >= 1 && Cs > 0 && Cs % 8 == 0 && N == r * r * Cs, SRK_E_SHAPE, "conv3x3_wgrad_ps: N=%d r=%d Cs=%d (N == r*r*Cs, Cs a multiple of 8)", N, r,
               Cs);
@@ -375,7 +373,7 @@ static int block_rowscale(const float* rowscale, int rows_per_sample, long long 
 #define BLOCK_ALIGNED(fn, ...)                                                                                      \
   do {                                                                                                              \
     const void* ptrs_[] = {__VA_ARGS__};                                                                            \
-    for (const void* q_ : ptrs_) SRK_REQUIRE(aligned16(q_), SRK_E_ALIGN, fn ": every buffer must be 16-byte aligned"); \
+    for (const void* q_ : ptrs_) SRK_REQUIRE(srk_aligned(q_, 16), SRK_E_ALIGN, fn ": every buffer must be 16-byte aligned"); \
   } while (0)
 
 int srk_mlp_fused_fwd_ex(const uint16_t* xn, const uint16_t* w1, const float* b1, const uint16_t* w2, const float* b2, const float* res,

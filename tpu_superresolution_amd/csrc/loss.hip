@@ -261,12 +261,6 @@ __global__ void ssim_loss_finish_kernel(const float* __restrict__ partial, int t
   }
 }
 
-bool overlaps(const void* p, const void* q, double bytes) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  const uintptr_t n = (uintptr_t)bytes;
-  return !(a + n <= b || b + n <= a);
-}
-
 }  // namespace
 
 int srk_launch_pixel_loss(const float* pred, const float* target, float* dpred, float* loss, unsigned* nonfinite, long long n, int kind,
@@ -290,16 +284,9 @@ int srk_launch_pixel_loss(const float* pred, const float* target, float* dpred, 
 
 int srk_launch_ssim_loss(const float* x, const float* y, float* partial, int B, int C, int H, int W, float data_range, float alpha, float* d_x,
                          int accumulate, float* ssim_mean, float* loss, hipStream_t stream) {
-  static SrkPerDevice<int> raised_pd;
-  int& raised = raised_pd.here();
-  if (!raised) {          // 66768 bytes of dynamic LDS: above the default 64 KB limit, well inside the CU's 160 KB
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ssim_loss_tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)SSIM_LOSS_LDS) != hipSuccess) {
-      srk_set_error("ssim_loss: cannot reserve %zu bytes of LDS", SSIM_LOSS_LDS);
-      return SRK_E_LAUNCH;
-    }
-    raised = 1;
-  }
+  static SrkLdsState reserved;      // 66768 bytes of dynamic LDS: above the default 64 KB limit, well inside the CU's 160 KB
+  if (const int rc = srk_reserve_lds(&ssim_loss_tile_kernel, SSIM_LOSS_LDS, reserved, false, "ssim_loss: cannot reserve %zu bytes of LDS", SSIM_LOSS_LDS))
+    return rc;
   // The 11-tap Gaussian (sigma 1.5) of srk_ssim, but normalised in fp64 and rounded once per tap: its taps sum to 1 within 2e-9.
   // sigma^2 = E[x^2] - mu^2 picks up (s - s^2) mean^2 when the taps sum to s != 1; with the fp32-normalised taps (s - 1 = 4.5e-8)
   // that alone moved S by 4.5e-6 on smooth images against the same formula under torch's fp32 window (s - 1 = -3.1e-8).
@@ -360,7 +347,8 @@ int srk_ssim_loss_fwd_bwd(const float* x, const float* y, void* workspace, int B
   SRK_REQUIRE(accumulate == 0 || accumulate == 1, SRK_E_SHAPE, "ssim_loss: accumulate must be 0 or 1 (got %d)", accumulate);
   const double bytes = 4.0 * B * C * H * W;
   SRK_REQUIRE(bytes < 9.0e18, SRK_E_SHAPE, "ssim_loss: B=%d C=%d H=%d W=%d is too large", B, C, H, W);
-  SRK_REQUIRE(!d_x || (!overlaps(d_x, x, bytes) && !overlaps(d_x, y, bytes)), SRK_E_SHAPE, "ssim_loss: d_x overlaps x or y");
+  const size_t n = (size_t)bytes;
+  SRK_REQUIRE(!d_x || (!srk_ranges_overlap(d_x, n, x, n) && !srk_ranges_overlap(d_x, n, y, n)), SRK_E_SHAPE, "ssim_loss: d_x overlaps x or y");
   return srk_launch_ssim_loss(x, y, static_cast<float*>(workspace), B, C, H, W, data_range, alpha, d_x, accumulate, ssim_mean, loss,
                               (hipStream_t)stream);
 }

@@ -392,15 +392,8 @@ SrkOpt g_wgrad_partials{OPT_WGRAD_PARTIALS, 1};   // split partials to scratch s
 template <int TA, int TB, bool CONV>
 int launch(const WgradParams* ps, int nprob, hipStream_t stream) {
   constexpr size_t lds = (size_t)2 * 64 * ((64 * TA + 16) + (64 * TB + 16)) * sizeof(bf16_t);
-  static SrkPerDevice<bool> configured_pd; bool& configured = configured_pd.here();
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<TA, TB, CONV>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      srk_set_error("wgrad: cannot reserve %zu bytes of LDS", lds);
-      return SRK_E_LAUNCH;
-    }
-    configured = true;
-  }
+  static SrkLdsState reserved;
+  if (const int rc = srk_reserve_lds(&wgrad_kernel<TA, TB, CONV>, lds, reserved, false, "wgrad: cannot reserve %zu bytes of LDS", lds)) return rc;
   WgradMulti mp;
   mp.nprob = nprob;
   mp.partial = nullptr;
@@ -436,16 +429,10 @@ int launch(const WgradParams* ps, int nprob, hipStream_t stream) {
                                       &wgrad_stream_kernel<32, false, false>, &wgrad_stream_kernel<32, true, false>,
                                       &wgrad_stream_kernel<64, false, true>,  &wgrad_stream_kernel<64, true, true>,
                                       &wgrad_stream_kernel<32, false, true>,  &wgrad_stream_kernel<32, true, true>};
-      static SrkPerDevice<bool> sconf_pd; bool& sconf = sconf_pd.here();
-      if (!sconf) {
-        for (KernelFn f : fns)
-          if (hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, slds) != hipSuccess) {
-            srk_set_error("wgrad(stream): cannot reserve %d bytes of LDS", slds);
-            return SRK_E_LAUNCH;
-          }
-        sconf = true;
-      }
-      const KernelFn fn = fns[(g_wgrad_w8 ? 4 : 0) + (g_wgrad_rows == 32 ? 2 : 0) + (g_wgrad_nt ? 1 : 0)];
+      static SrkLdsState reserved[8];
+      const int variant = (g_wgrad_w8 ? 4 : 0) + (g_wgrad_rows == 32 ? 2 : 0) + (g_wgrad_nt ? 1 : 0);
+      const KernelFn fn = fns[variant];
+      if (const int rc = srk_reserve_lds(fn, slds, reserved[variant], false, "wgrad(stream): cannot reserve %d bytes of LDS", slds)) return rc;
       mp.nsplit = splits;
       mp.w8 = g_wgrad_w8;
       mp.partial = g_wgrad_partials && splits > 1 ? srk_wgrad_scratch(stream, (size_t)tiles * splits * WS_SLAB_VEC * 16) : nullptr;
