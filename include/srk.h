@@ -370,6 +370,35 @@ int srk_eval_psnr(const float* x, const float* y, void* workspace, int B, int64_
 int64_t srk_ssim_workspace(int B, int C, int H, int W);
 int srk_ssim(const float* x, const float* y, void* workspace, int B, int C, int H, int W, float data_range, float* per_image, float* mean,
              srk_stream_t stream);
+/* Benchmark-protocol PSNR / SSIM: the scores the SwinIR / HAT / DAT papers report -- 8-bit, border-cropped, on the
+ * BT.601 luma or on the colour planes, on a 0..255 scale, per image.  One definition, all in fp32:
+ *   quantise  q(x) = rintf(c(x) * 255.0f); c clamps to [0, 1] by comparisons (x < 0 -> 0, x > 1 -> 1, else x), so a NaN stays a
+ *             NaN and reaches the result; one multiply, then round-half-to-even (numpy's .round() in the published test
+ *             scripts; NOT the truncation of a PNG dump)
+ *   crop      rows [border, H - border), columns [border, W - border): Hc x Wc = (H - 2 border) x (W - 2 border)
+ *   mode Y    C == 3: one plane, t = 65.481f * qR; t = fmaf(128.553f, qG, t); t = fmaf(24.966f, qB, t); Y = 16.0f + t / 255.0f
+ *             (one IEEE division, one add); C == 1: the plane is q itself (a single-channel image is its own luma)
+ *   mode RGB  the C planes of q, any C >= 1
+ *   PSNR      10 log10(255^2 / mse), mse = sqsum / (Cm Hc Wc) over the cropped planes of ONE image; mse == 0 gives +inf; sums in
+ *             fp32 in a fixed order, no atomics
+ *   SSIM      srk_ssim on the planes with data_range 255 (needs Hc, Wc >= 11).  Restated from the published algorithm: PARITY
+ *             with the third-party test scripts (BasicSR, OpenCV) is UNPINNED, neither is available to compare with.
+ * srk_bench_planes_f32: pred / target fp32 [B][C][H][W] -> planes_pred / planes_target fp32 [B][Cm][Hc][Wc] (Cm = 1 in mode Y,
+ * C in mode RGB; either may be null: nothing is written for it) and, in the same pass, the per-workgroup sums of the squared
+ * plane differences into workspace (srk_bench_workspace(B, Cm, Hc, Wc) bytes, caller-owned).  Every input element inside the crop
+ * is read once, none outside it; nothing outside the planes and the workspace is written.
+ * srk_bench_psnr: finishes that workspace: sqsum[b], psnr[b] (fp32 [B], either may be null) and psnr_sum[0] += sum_b psnr[b]
+ * (may be null; zero it before the first batch, read it once after the last, like srk_batch_psnr's).
+ * SRK_E_NULL: null pred / target / workspace; all three outputs of srk_bench_psnr null.  SRK_E_SHAPE: B outside 1..1024, a
+ * non-positive extent, border < 0, 2 border >= H or W, an unknown mode, mode Y with C other than 1 or 3, C * H beyond 2^31 - 1,
+ * planes overlapping an input.  srk_bench_workspace returns 0 for such arguments. */
+#define SRK_BENCH_Y 0
+#define SRK_BENCH_RGB 1
+int64_t srk_bench_workspace(int B, int Cm, int Hc, int Wc);
+int srk_bench_planes_f32(const float* pred, const float* target, float* planes_pred, float* planes_target, void* workspace, int B, int C,
+                         int H, int W, int border, int mode, srk_stream_t stream);
+int srk_bench_psnr(const void* workspace, int B, int Cm, int Hc, int Wc, float* sqsum, float* psnr, float* psnr_sum,
+                   srk_stream_t stream);
 /* sum of squares of a flat fp32 gradient, ACCUMULATED into sumsq[0] (for clip_grad_norm_ :170) */
 int srk_grad_sumsq(const float* grads, int64_t n, float* sumsq, srk_stream_t stream);
 /* clip_grad_norm_(max_norm) + AdamW step (:168-171, :303) on flat fp32 buffers.  The clip coefficient is

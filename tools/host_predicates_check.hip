@@ -37,6 +37,20 @@ int main() {
   EXPECT(!srk_qkv_layout_ok(0, 32, 96, 32, 8) && !srk_qkv_layout_ok(-1, 32, 96, 32, 8) && !srk_qkv_layout_ok(2, 32, 96, 64, 8));
   EXPECT(!srk_qkv_layout_ok(1, 48, 144, 32, 8) && !srk_qkv_layout_ok(1, 32, 95, 32, 8) && !srk_qkv_layout_ok(1, 32, 100, 32, 8));
   EXPECT(!srk_qkv_layout_ok(1, 32, 96, 31, 8) && !srk_qkv_layout_ok(1, 32, 96, 36, 8) && srk_qkv_layout_ok(1, 32, 96, 36, 4));
+  // benchmark-protocol planes: the smallest valid shapes, then each clause broken in turn, then the ends of the int range
+  EXPECT(srk_bench_planes_shape_ok(1, 3, 9, 10, 4, SRK_BENCH_Y) && srk_bench_planes_shape_ok(1024, 1, 1, 1, 0, SRK_BENCH_Y));
+  EXPECT(srk_bench_planes_shape_ok(2, 5, 12, 12, 5, SRK_BENCH_RGB) && !srk_bench_planes_shape_ok(2, 5, 12, 12, 5, SRK_BENCH_Y));
+  EXPECT(!srk_bench_planes_shape_ok(0, 3, 9, 10, 4, 0) && !srk_bench_planes_shape_ok(1025, 3, 9, 10, 4, 0) && !srk_bench_planes_shape_ok(-1, 3, 9, 10, 4, 0));
+  EXPECT(!srk_bench_planes_shape_ok(1, 0, 9, 10, 4, 1) && !srk_bench_planes_shape_ok(1, 2, 9, 10, 4, 0) && !srk_bench_planes_shape_ok(1, 4, 9, 10, 4, 0));
+  EXPECT(!srk_bench_planes_shape_ok(1, 3, 9, 10, 5, 0) && !srk_bench_planes_shape_ok(1, 3, 10, 9, 5, 0) && !srk_bench_planes_shape_ok(1, 3, 8, 10, 4, 0));
+  EXPECT(!srk_bench_planes_shape_ok(1, 3, 9, 10, -1, 0) && !srk_bench_planes_shape_ok(1, 3, 9, 10, 0, 2) && !srk_bench_planes_shape_ok(1, 3, 9, 10, 0, -1));
+  EXPECT(!srk_bench_planes_shape_ok(1, 3, 0, 10, 0, 1) && !srk_bench_planes_shape_ok(1, 3, 9, 0, 0, 1) && !srk_bench_planes_shape_ok(1, 3, -9, -10, 0, 1));
+  EXPECT(srk_bench_planes_shape_ok(1, 1, 0x7fffffff, 0x7fffffff, 0x3fffffff, 0) && !srk_bench_planes_shape_ok(1, 1, 0x7fffffff, 0x7fffffff, 0x40000000, 0));
+  EXPECT(!srk_bench_planes_shape_ok(1, 3, 0x7fffffff, 3, 0x7fffffff, 0) && !srk_bench_planes_shape_ok(1, 2, 0x40000000, 1, 0, 1));
+  EXPECT(srk_bench_planes_shape_ok(1, 1, 0x7fffffff, 1, 0, 1) && !srk_bench_planes_shape_ok(1, 0x7fffffff, 0x7fffffff, 1, 0, 1));
+  EXPECT(srk_bench_plane_dims_ok(1, 1, 1, 1) && srk_bench_plane_dims_ok(1024, 3, 11, 11) && !srk_bench_plane_dims_ok(1025, 3, 11, 11));
+  EXPECT(!srk_bench_plane_dims_ok(0, 1, 1, 1) && !srk_bench_plane_dims_ok(1, 0, 1, 1) && !srk_bench_plane_dims_ok(1, 1, 0, 1) && !srk_bench_plane_dims_ok(1, 1, 1, 0));
+  EXPECT(srk_bench_plane_dims_ok(1, 1, 0x7fffffff, 0x7fffffff) && !srk_bench_plane_dims_ok(1, 2, 0x40000000, 1) && !srk_bench_plane_dims_ok(1, 0x7fffffff, 0x7fffffff, 1));
   printf("%d failure(s)\n", failures);
   return failures != 0;
 }

@@ -103,6 +103,15 @@ static inline bool srk_ranges_overlap(const void* a, size_t na, const void* b, s
 static inline bool srk_qkv_layout_ok(int nH, int CA, int ldq, int ldo, int ldo_mult) {
   return nH > 0 && CA >= nH * 32 && CA % 32 == 0 && ldq >= 3 * CA && ldq % 8 == 0 && ldo >= nH * 32 && ldo % ldo_mult == 0;
 }
+// benchmark-protocol metrics (metrics.hip, srk.h "Benchmark-protocol PSNR / SSIM"): the shapes srk_bench_planes_f32 takes, and
+// the plane shapes srk_bench_psnr / srk_bench_workspace take (Cm * Hc plane rows per image index an int)
+static inline bool srk_bench_planes_shape_ok(int B, int C, int H, int W, int border, int mode) {
+  return B > 0 && B <= 1024 && C > 0 && H > 0 && W > 0 && border >= 0 && border <= (H - 1) / 2 && border <= (W - 1) / 2 &&      // 2 border < H, W without a product that could wrap
+         (mode == SRK_BENCH_RGB || (mode == SRK_BENCH_Y && (C == 1 || C == 3))) && (long long)C * H <= 0x7fffffffLL;
+}
+static inline bool srk_bench_plane_dims_ok(int B, int Cm, int Hc, int Wc) {
+  return B > 0 && B <= 1024 && Cm > 0 && Hc > 0 && Wc > 0 && (long long)Cm * Hc <= 0x7fffffffLL;
+}
 
 // ---------------------------------------------------------------------------------------------
 // bf16 helpers (device)

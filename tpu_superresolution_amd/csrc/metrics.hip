@@ -134,9 +134,178 @@ __global__ void ssim_finish_kernel(const float* __restrict__ partial, int tiles,
   }
 }
 
+// ---- benchmark-protocol planes and PSNR (srk.h "Benchmark-protocol PSNR / SSIM") ----------------------------------
+// A streaming pass: workgroup (chunk, image) takes `rpb` consecutive plane rows of one image -- about BENCH_ELEMS plane elements
+// -- and walks them in groups of four input elements that are 16-byte aligned in the input row; a whole group is one dwordx4
+// load per tensor and channel, the groups cut by the crop at a row's head and tail are scalar loads of the elements inside the
+// crop only (nothing of the cropped-away frame is read).  The plane rows are dense (Wc), so a group's place in the output is
+// 16-byte aligned only where crop offset and widths happen to agree: a dwordx4 store there, four dword stores elsewhere.
+constexpr int BENCH_ELEMS = 8192;
+inline int bench_rows_per_block(int Wc) { return Wc >= BENCH_ELEMS ? 1 : BENCH_ELEMS / Wc; }
+inline int bench_chunks(int Cm, int Hc, int Wc) {
+  const int rpb = bench_rows_per_block(Wc);
+  return (int)(((long long)Cm * Hc + rpb - 1) / rpb);
+}
+
+__device__ __forceinline__ float bench_q(float x) {
+  const float c = x < 0.f ? 0.f : (x > 1.f ? 1.f : x);          // comparisons: a NaN fails both and stays
+  return rintf(__fmul_rn(c, 255.0f));
+}
+__device__ __forceinline__ float bench_luma(float r, float g, float b) {
+  const float t = fmaf(24.966f, b, fmaf(128.553f, g, __fmul_rn(65.481f, r)));
+  return __fadd_rn(16.0f, __fdiv_rn(t, 255.0f));
+}
+// elements j of p[0..4) with bit j of mask set; the others are never addressed
+__device__ __forceinline__ void bench_load4(const float* __restrict__ p, unsigned mask, float v[4]) {
+  if (mask == 0xFu && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+    const float4 t = *reinterpret_cast<const float4*>(p);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = ((mask >> j) & 1u) ? p[j] : 0.f;
+  }
+}
+__device__ __forceinline__ void bench_store4(float* __restrict__ p, unsigned mask, const float v[4]) {
+  if (mask == 0xFu && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if ((mask >> j) & 1u) p[j] = v[j];
+  }
+}
+
+// Y3: C == 3 in, one luma plane out (rows = Hc); otherwise plane row R = c * Hc + r of the image is input channel c (rows = C * Hc)
+template <bool Y3>
+__global__ __launch_bounds__(256) void bench_planes_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                           float* __restrict__ pp, float* __restrict__ pt, float* __restrict__ partial,
+                                                           int C, int H, int W, int border, int Hc, int Wc, int rows, int rpb) {
+  __shared__ float red[4];
+  const int b = blockIdx.y;
+  const int R0 = blockIdx.x * rpb;
+  const int nr = min(rpb, rows - R0);
+  const int S = Wc / 4 + 2;                                     // aligned groups a row can touch, whatever its phase
+  const long long plane = (long long)H * W;
+  float sq = 0.f;
+  for (int i = threadIdx.x; i < nr * S; i += 256) {
+    const int rr = i / S, s = i - rr * S;
+    const int R = R0 + rr;
+    const int c = Y3 ? 0 : R / Hc, r = Y3 ? R : R - c * Hc;
+    const long long in0 = (((long long)b * C + c) * H + border + r) * W + border;      // first element of the row inside the crop
+    const long long x0 = 4LL * s - (in0 & 3);                   // crop column of the group's first element (-3..Wc+7)
+    unsigned mask = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) mask |= (x0 + j >= 0 && x0 + j < Wc) ? (1u << j) : 0u;
+    if (!mask) continue;
+    float P[4], T[4];
+    if (Y3) {
+      float pr[4], pg[4], pb[4], tr[4], tg[4], tb[4];
+      bench_load4(pred + in0 + x0, mask, pr);
+      bench_load4(pred + in0 + x0 + plane, mask, pg);
+      bench_load4(pred + in0 + x0 + 2 * plane, mask, pb);
+      bench_load4(target + in0 + x0, mask, tr);
+      bench_load4(target + in0 + x0 + plane, mask, tg);
+      bench_load4(target + in0 + x0 + 2 * plane, mask, tb);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        P[j] = bench_luma(bench_q(pr[j]), bench_q(pg[j]), bench_q(pb[j]));
+        T[j] = bench_luma(bench_q(tr[j]), bench_q(tg[j]), bench_q(tb[j]));
+      }
+    } else {
+      bench_load4(pred + in0 + x0, mask, P);
+      bench_load4(target + in0 + x0, mask, T);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        P[j] = bench_q(P[j]);
+        T[j] = bench_q(T[j]);
+      }
+    }
+    const long long o0 = ((long long)b * rows + R) * Wc + x0;
+    if (pp) bench_store4(pp + o0, mask, P);
+    if (pt) bench_store4(pt + o0, mask, T);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float d = P[j] - T[j];
+      if ((mask >> j) & 1u) sq = fmaf(d, d, sq);
+    }
+  }
+  sq = wave_sum64(sq);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[(long long)blockIdx.y * gridDim.x + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
+// One workgroup of 1024 threads.  A group of L lanes (a power of two <= 64, chosen on the host from the number of partials: a
+// full-size image has hundreds, a training patch one) owns an image: lane l adds partials l, l + L, ... in order, then an xor
+// butterfly adds the group's lanes -- a fixed order for a given shape.  The batch total is added by thread 0 in image order.
+__global__ __launch_bounds__(1024) void bench_psnr_finish_kernel(const float* __restrict__ partial, int chunks, int B, int L, float count,
+                                                                 float* __restrict__ sqsum, float* __restrict__ psnr,
+                                                                 float* __restrict__ psnr_sum) {
+  __shared__ float sh[1024];
+  const int groups = 1024 / L, gi = threadIdx.x / L, l = threadIdx.x & (L - 1);
+  for (int b0 = 0; b0 < B; b0 += groups) {                      // the same trip count for every thread: the shuffles see whole waves
+    const int b = b0 + gi;
+    float sq = 0.f;
+    if (b < B)
+      for (int c = l; c < chunks; c += L) sq += partial[(long long)b * chunks + c];
+    for (int o = L >> 1; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
+    if (b < B && l == 0) {
+      const float mse = sq / count;
+      const float v = mse == 0.f ? INFINITY : 10.0f * log10f(65025.0f / mse);      // a NaN mse is not 0: it reaches the result
+      if (sqsum) sqsum[b] = sq;
+      if (psnr) psnr[b] = v;
+      sh[b] = v;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && psnr_sum) {
+    float s = 0.f;
+    for (int b = 0; b < B; ++b) s += sh[b];
+    *psnr_sum += s;
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+int64_t srk_bench_workspace(int B, int Cm, int Hc, int Wc) {
+  if (!srk_bench_plane_dims_ok(B, Cm, Hc, Wc)) return 0;
+  return (int64_t)sizeof(float) * B * bench_chunks(Cm, Hc, Wc);
+}
+
+int srk_bench_planes_f32(const float* pred, const float* target, float* planes_pred, float* planes_target, void* workspace, int B, int C,
+                         int H, int W, int border, int mode, srk_stream_t stream) {
+  SRK_REQUIRE(pred && target && workspace, SRK_E_NULL, "bench_planes: null pointer");
+  SRK_REQUIRE(srk_bench_planes_shape_ok(B, C, H, W, border, mode), SRK_E_SHAPE,
+              "bench_planes: B=%d (1..1024) C=%d H=%d W=%d border=%d (0 <= 2 border < H, W) mode=%d (Y: C 1 or 3; RGB)", B, C, H, W, border, mode);
+  const bool y3 = mode == SRK_BENCH_Y && C == 3;
+  const int Cm = mode == SRK_BENCH_Y ? 1 : C, Hc = H - 2 * border, Wc = W - 2 * border;
+  const size_t in_bytes = sizeof(float) * (size_t)B * C * H * W, out_bytes = sizeof(float) * (size_t)B * Cm * Hc * Wc;
+  for (const float* o : {planes_pred, planes_target})
+    SRK_REQUIRE(!o || (!srk_ranges_overlap(o, out_bytes, pred, in_bytes) && !srk_ranges_overlap(o, out_bytes, target, in_bytes)), SRK_E_SHAPE,
+                "bench_planes: planes overlap an input");
+  const int rows = Cm * Hc, rpb = bench_rows_per_block(Wc);
+  const dim3 grid(bench_chunks(Cm, Hc, Wc), B);
+  if (y3)
+    hipLaunchKernelGGL(bench_planes_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, pred, target, planes_pred, planes_target,
+                       static_cast<float*>(workspace), C, H, W, border, Hc, Wc, rows, rpb);
+  else
+    hipLaunchKernelGGL(bench_planes_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, pred, target, planes_pred, planes_target,
+                       static_cast<float*>(workspace), C, H, W, border, Hc, Wc, rows, rpb);
+  return srk_check_launch("bench_planes");
+}
+
+int srk_bench_psnr(const void* workspace, int B, int Cm, int Hc, int Wc, float* sqsum, float* psnr, float* psnr_sum, srk_stream_t stream) {
+  SRK_REQUIRE(workspace && (sqsum || psnr || psnr_sum), SRK_E_NULL, "bench_psnr: null workspace, or no output");
+  SRK_REQUIRE(srk_bench_plane_dims_ok(B, Cm, Hc, Wc), SRK_E_SHAPE, "bench_psnr: B=%d (1..1024) Cm=%d Hc=%d Wc=%d", B, Cm, Hc, Wc);
+  const int chunks = bench_chunks(Cm, Hc, Wc);
+  int L = 1;                                                    // lanes per image of the finish step
+  while (L < 64 && L < chunks) L <<= 1;
+  hipLaunchKernelGGL(bench_psnr_finish_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, static_cast<const float*>(workspace), chunks, B, L,
+                     (float)((long long)Cm * Hc * Wc), sqsum, psnr, psnr_sum);
+  return srk_check_launch("bench_psnr");
+}
 
 int64_t srk_eval_psnr_workspace(int64_t per_image, int B) {
   if (per_image <= 0 || B <= 0) return 0;

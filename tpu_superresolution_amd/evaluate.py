@@ -17,6 +17,9 @@ N x N tiles of the model's input and merges them (tiling.tiled_forward; any --ar
 bicubic downscale, formed on the device (ops.resize_aa), with ``--degrade blind --blur_sigma SY SX --noise_sigma N --noise_gain G`` blurred and
 noised there with fixed parameters (ops.degrade_blind), with ``--jpeg_quality Q [--jpeg_subsample 444|420]`` then sent through a baseline
 JPEG round trip (ops.jpeg_roundtrip); ``main(argv)`` is callable from tests.  SSIM is ``metrics.ssim`` (restated, parity unpinned).
+``--bench_metric y | rgb [--crop_border N]`` (any --arch, any of the options above: it looks at (pred, hr) only) adds ``[bench]`` lines
+and ``bench_*`` keys with the scores of the papers' protocol -- 8-bit, border-cropped (default: the scale), BT.601 luma or RGB, 0..255
+scale, mean over images (metrics.bench_metrics); the other lines and keys stay as they are.
 """
 from __future__ import annotations
 
@@ -116,7 +119,18 @@ def parse_args(argv=None):
                          "JPEG at quality Q in 1..100 on the device (ops.jpeg_roundtrip, csrc/jpeg.hip), before any tiling or self-ensemble")
     ap.add_argument("--jpeg_subsample", type=str, choices=["444", "420"], default="444",
                     help="additive, with --jpeg_quality: chroma at 4:4:4, or 4:2:0 (2 x 2 means, upsampled by replication)")
+    ap.add_argument("--bench_metric", type=str, choices=["y", "rgb"], default=None,
+                    help="additive: also report PSNR / SSIM by the protocol of the SwinIR / HAT / DAT papers (metrics.bench_metrics): "
+                         "8-bit, border-cropped, y = BT.601 luma of RGB (a single-channel image is its own luma), rgb = every channel, "
+                         "0..255 scale, mean over images")
+    ap.add_argument("--crop_border", type=int, default=None, metavar="N",
+                    help="additive, with --bench_metric: pixels cropped on every side before scoring (default: the scale)")
     args = ap.parse_args(argv)
+    if args.crop_border is not None:
+        if args.bench_metric is None:
+            ap.error("--crop_border is an option of the benchmark-protocol scores: it needs --bench_metric y | rgb")
+        if args.crop_border < 0:
+            ap.error(f"--crop_border must be >= 0 (got {args.crop_border})")
     if args.synth_lr and args.arch == "ms_resunet":
         ap.error("--synth_lr is an option of --arch swinir | hat | dat (MS_ResUNet takes the pre-upscaled LR of the eval transform)")
     if args.degrade == "blind":
@@ -196,6 +210,12 @@ def main(argv=None):
               "| shapes:", tuple(lr.shape), tuple(hr.shape))
         break
 
+    bench = args.bench_metric is not None
+    border = scale_int if args.crop_border is None else args.crop_border
+    if bench:
+        from .metrics import bench_metrics
+    bench_ps, bench_ss, bench_bic_ps, bench_bic_ss = [], [], [], []          # per-image tensors, read once after each loop
+
     with torch.no_grad():                               # bicubic baseline, :115-134
         ps, ss = [], []
         for lr, hr in test_loader:
@@ -203,7 +223,23 @@ def main(argv=None):
             up = upscaled(lr, hr)
             ps.append(psnr(up, hr, max_val=1.0))
             ss.append(float(ssim(up, hr, data_range=1.0, size_average=True)))
+            if bench:
+                bp, bs = bench_metrics(up, hr, border, args.bench_metric)
+                bench_bic_ps.append(bp)
+                bench_bic_ss.append(bs)
     print(f"[baseline] Bicubic PSNR: {sum(ps) / len(ps):.2f} dB | SSIM: {sum(ss) / len(ss):.4f}")
+    more = {}
+    if bench:
+        tag = args.bench_metric.upper()
+
+        def bench_line(what, p_list, s_list):
+            """The mean over IMAGES (not over batches: a short last batch weighs what its images weigh)."""
+            p_all, s_all = torch.cat(p_list), torch.cat(s_list)
+            mp, ms = float(p_all.double().mean()), float(s_all.double().mean())
+            print(f"[bench] {what}PSNR-{tag}: {mp:.2f} dB | SSIM-{tag}: {ms:.4f} (8-bit, border {border}, mean over {p_all.numel()} images)")
+            return mp, ms
+
+        more["bench_bicubic_psnr"], more["bench_bicubic_ssim"] = bench_line("Bicubic ", bench_bic_ps, bench_bic_ss)
 
     if swin:
         from .finetune_swinir import build_sr_model
@@ -257,6 +293,10 @@ def main(argv=None):
             pred_f, hr_f = pred.to(torch.float32), hr.to(torch.float32)
             psnr_vals.append(psnr(pred_f, hr_f, max_val=1.0))
             ssim_vals.append(float(ssim(pred_f, hr_f, data_range=1.0, size_average=True)))
+            if bench:
+                bp, bs = bench_metrics(pred_f, hr_f, border, args.bench_metric)
+                bench_ps.append(bp)
+                bench_ss.append(bs)
             for b in range(pred.size(0)):
                 idx = global_idx + b
                 if save_set is not None:
@@ -278,9 +318,11 @@ def main(argv=None):
     mean_psnr = sum(psnr_vals) / max(1, len(psnr_vals))
     mean_ssim = sum(ssim_vals) / max(1, len(ssim_vals))
     print(f"[done] test PSNR: {mean_psnr:.2f} dB | SSIM: {mean_ssim:.4f} | time: {dt:.1f}s for {len(test_ds)} samples")
+    if bench:
+        more["bench_psnr"], more["bench_ssim"] = bench_line("", bench_ps, bench_ss)
     print(f"[saved] examples in: {out_dir.resolve()}")
     return {"psnr": mean_psnr, "ssim": mean_ssim, "bicubic_psnr": sum(ps) / len(ps), "bicubic_ssim": sum(ss) / len(ss),
-            "saved": saved, "n": len(test_ds)}
+            "saved": saved, "n": len(test_ds), **more}
 
 
 if __name__ == "__main__":

@@ -13,6 +13,8 @@ on flipped / rotated patches (augment.py; on the device with `--gpu_data`).  `--
 `--ssim_weight W` (default 0) choose the objective: the pixel loss plus W * (1 - SSIM), value and gradient from the fused kernels of
 csrc/loss.hip (training.make_loss); with W > 0 validation also reports the mean per-image SSIM and checkpoints gain 'val_ssim'.
 `--val_tile N` (default 0 = whole images) validates on overlapping N x N LR tiles merged on the device (tiling.tiled_forward).
+`--val_bench_metric y|rgb [--val_crop_border N]` adds the papers' scores to the epoch line and the checkpoints ('val_bench_psnr',
+'val_bench_ssim'): 8-bit, border-cropped (default: the scale), BT.601 luma or RGB, 0..255 scale (metrics.bench_metrics).
 `--gpu_data --synth_lr [--synth_lr_bits 0|8]` trains and validates from the HR directories alone: every LR patch is the antialiased
 bicubic downscale of its HR image, made on the device (sr_datasets.DeviceHRPool, csrc/resize.hip); no LR directory is read.
 `--degrade blind [--blur_sigma LO HI --noise_sigma LO HI ...]` blurs and noises every such patch with random parameters in the same
@@ -128,8 +130,23 @@ def validate(model, loader, device, with_ssim=False, predict=None):
     """-> (mean L1 over batches, mean per-image PSNR, seconds); with_ssim (device only): also the mean per-image SSIM (ops.ssim,
     data_range 1), inserted before the seconds.  predict: what maps an LR batch to the prediction instead of the model itself
     (--val_tile: tiling.tiled_forward around the model)."""
+    return _validate(model, loader, device, with_ssim, predict, None, 0)
+
+
+@torch.no_grad()
+def validate_bench(model, loader, device, bench_metric, crop_border, with_ssim=False, predict=None):
+    """``validate`` plus the mean per-image PSNR and SSIM of the papers' protocol (bench_metric 'y' | 'rgb'; metrics.bench_metrics: 8-bit,
+    crop_border cropped, luma or RGB, 0..255 scale), the two of them inserted before the seconds; they are summed on the device and
+    read once, after the loop.  bench_metric None is ``validate`` itself."""
+    return _validate(model, loader, device, with_ssim, predict, bench_metric, crop_border)
+
+
+def _validate(model, loader, device, with_ssim, predict, bench_metric, crop_border):
     model.eval()
     predict = model if predict is None else predict
+    if bench_metric is not None:
+        from .metrics import bench_metrics
+        bench_acc = torch.zeros(2, dtype=torch.float32, device=device)
     total, n, sum_psnr, n_imgs, t0 = 0.0, 0, 0.0, 0, time.time()
     ssim_acc = torch.zeros(1, dtype=torch.float32, device=device) if with_ssim else None
     on_gpu = torch.device(device).type == "cuda"
@@ -151,13 +168,16 @@ def validate(model, loader, device, with_ssim=False, predict=None):
         else:
             total += float(l1_loss(out, hr))
             sum_psnr += float(batch_psnr(out, hr).sum())
+        if bench_metric is not None:
+            bench_acc += torch.stack([v.sum() for v in bench_metrics(out.float(), hr.float(), crop_border, bench_metric)])
         n += 1
         n_imgs += lr.size(0)
     if on_gpu:
         total, sum_psnr = float(l1_acc), float(psnr_acc)
-    if with_ssim:
-        return total / max(1, n), sum_psnr / max(1, n_imgs), float(ssim_acc) / max(1, n_imgs), time.time() - t0
-    return total / max(1, n), sum_psnr / max(1, n_imgs), time.time() - t0
+    more = (float(ssim_acc) / max(1, n_imgs),) if with_ssim else ()
+    if bench_metric is not None:
+        more += tuple(v / max(1, n_imgs) for v in bench_acc.tolist())
+    return (total / max(1, n), sum_psnr / max(1, n_imgs), *more, time.time() - t0)
 
 
 def build_model(scale_int: int, drop_path_rate: float = 0.1, window_size: int = 8) -> SwinIR:
@@ -244,6 +264,12 @@ def parse_args(argv=None):
                     help="additive: validate on overlapping tiles of N x N LR pixels merged by their mean (tiling.tiled_forward; 0 = "
                          "off, the whole image in one call)")
     ap.add_argument("--val_tile_overlap", type=int, default=32, help="additive, with --val_tile: LR pixels two neighbouring tiles share")
+    ap.add_argument("--val_bench_metric", type=str, choices=["y", "rgb"], default=None,
+                    help="additive: validation also reports PSNR / SSIM by the protocol of the SwinIR / HAT / DAT papers "
+                         "(metrics.bench_metrics: 8-bit, border-cropped, y = BT.601 luma, rgb = every channel, 0..255 scale, mean over "
+                         "images); checkpoints gain 'val_bench_psnr' / 'val_bench_ssim'; which checkpoint is best does not change")
+    ap.add_argument("--val_crop_border", type=int, default=None, metavar="N",
+                    help="additive, with --val_bench_metric: pixels cropped on every side before scoring (default: the scale)")
     ap.add_argument("--synth_lr", action="store_true",
                     help="additive, with --gpu_data: train and validate from the HR directories alone -- every LR patch is the "
                          "antialiased bicubic (PIL BICUBIC convention) downscale of its HR image, computed on the device in the launch "
@@ -300,6 +326,8 @@ def parse_args(argv=None):
     if args.val_tile < 0 or args.val_tile_overlap < 0 or (args.val_tile and args.val_tile_overlap >= args.val_tile):
         ap.error(f"--val_tile must be >= 0 and 0 <= --val_tile_overlap < --val_tile (got --val_tile {args.val_tile} "
                  f"--val_tile_overlap {args.val_tile_overlap})")
+    if args.val_crop_border is not None and (args.val_bench_metric is None or args.val_crop_border < 0):
+        ap.error(f"--val_crop_border must be >= 0 and is an option of --val_bench_metric y | rgb (got {args.val_crop_border})")
     if not 0.0 <= args.ssim_weight < float("inf"):          # also refuses NaN
         ap.error(f"--ssim_weight must be a finite number >= 0 (got {args.ssim_weight})")
     if not args.charbonnier_eps > 0.0:
@@ -346,7 +374,8 @@ def saved_args(args) -> dict:
                   "noise_sigma": args.noise_sigma == [0.0, 10.0], "noise_gain": args.noise_gain == [0.0, 0.0],
                   "gray_noise_p": args.gray_noise_p == 0.4,
                   "degrade_seed": args.degrade_seed == 0, "jpeg_quality": args.jpeg_quality is None, "jpeg_p": args.jpeg_p == 1.0,
-                  "jpeg_subsample": args.jpeg_subsample == "444"}
+                  "jpeg_subsample": args.jpeg_subsample == "444", "val_bench_metric": args.val_bench_metric is None,
+                  "val_crop_border": args.val_crop_border is None}
     return {k: v for k, v in vars(args).items() if not at_default.get(k, False)}
 
 
@@ -479,6 +508,12 @@ def main(argv=None):
         if rank == 0:
             print(f"[val_tile] {args.val_tile} overlap {args.val_tile_overlap}")
 
+    validate_fn, val_border = validate, None          # without --val_bench_metric: the validation call of ever
+    if args.val_bench_metric is not None:
+        from functools import partial
+        val_border = (2 if args.scale.upper() == "X2" else 4) if args.val_crop_border is None else args.val_crop_border
+        validate_fn = partial(validate_bench, bench_metric=args.val_bench_metric, crop_border=val_border)
+
     best_loss, best_psnr, t_all = float("inf"), -float("inf"), time.time()
     for epoch in range(1, args.epochs + 1):
         if sampler is not None:
@@ -487,9 +522,9 @@ def main(argv=None):
                                         freeze_bn=args.freeze_bn, loss_fn=loss_fn)
         if args.ema_decay:          # validate what gets shipped: the averaged weights (ranks hold identical averages)
             with opt.swap_ema():
-                val = validate(model, valid_loader, device, with_ssim, predict)
+                val = validate_fn(model, valid_loader, device, with_ssim=with_ssim, predict=predict)
         else:
-            val = validate(model, valid_loader, device, with_ssim, predict)
+            val = validate_fn(model, valid_loader, device, with_ssim=with_ssim, predict=predict)
         val_loss, val_psnr, val_t = val[0], val[1], val[-1]
         if sched is not None:
             sched.step()
@@ -497,6 +532,9 @@ def main(argv=None):
             continue
         train_name = f"loss[{loss_name(args.loss, args.ssim_weight)}]" if custom else "L1"
         val_more = f", SSIM={val[2]:.4f}" if with_ssim else ""
+        if val_border is not None:
+            tag = args.val_bench_metric.upper()
+            val_more += f", bench PSNR-{tag}={val[-3]:.2f}dB SSIM-{tag}={val[-2]:.4f} (8-bit, border {val_border})"
         print(f"[{args.scale}] epoch {epoch:03d}/{args.epochs} | lr={opt.param_groups[0]['lr']:.2e} | "
               f"train {train_name}={tr_loss:.6f} ({tr_t:.1f}s) | val L1={val_loss:.6f}, PSNR={val_psnr:.2f}dB{val_more} ({val_t:.1f}s)")
         sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}     # un-prefixed keys, like the reference
@@ -504,6 +542,8 @@ def main(argv=None):
         more = {"params_ema": opt.ema_state_dict()} if args.ema_decay else {}
         if with_ssim:
             more["val_ssim"] = val[2]
+        if val_border is not None:
+            more["val_bench_psnr"], more["val_bench_ssim"] = val[-3], val[-2]
         ckpt_args = saved_args(args)
         if val_loss < best_loss:
             best_loss = val_loss

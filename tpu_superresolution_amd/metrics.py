@@ -9,6 +9,9 @@
                  then mean over channels (and over the batch when size_average) -- **parity unpinned**: no
                  reference-produced fixture exists; tests check it against the closed form on cases with a known answer
                  (identical images -> 1, constant shift, scipy's gaussian_filter1d windows).
+``bench_metrics`` nothing in the reference: PSNR / SSIM by the protocol of the SwinIR / HAT / DAT papers (8-bit, border-cropped, BT.601
+                 luma or RGB, 0..255 scale, per image; include/srk.h) -> ``srk_bench_planes_f32`` / ``srk_bench_psnr`` and
+                 ``srk_ssim`` on the planes; its SSIM shares the restatement above, parity with the third-party test scripts unpinned.
 
 CPU tensors use the torch-operator forms below (evaluate.py / train.py run BASELINE cfg1 on the CPU).  fp32 GPU tensors go to
 the libsrk kernels: ``psnr`` -> ``srk_eval_psnr``, ``batch_psnr`` -> ``srk_batch_psnr``, ``ssim`` (4-D,
@@ -112,3 +115,48 @@ def ssim(X: torch.Tensor, Y: torch.Tensor, data_range: float = 255.0, size_avera
         per, mean = ops.ssim(X.detach(), Y.detach(), data_range)
         return mean.reshape(()) if size_average else per
     return ssim_torch(X, Y, data_range=data_range, size_average=size_average, **kw)
+
+
+# ---- benchmark-protocol PSNR / SSIM (include/srk.h) -------------------------------------------------------------------
+def bench_planes_torch(x: torch.Tensor, crop_border: int, mode: str = "y") -> torch.Tensor:
+    """The torch-operator form of srk_bench_planes_f32 for one tensor: fp32 [B, C, H, W] -> fp32 [B, Cm, Hc, Wc].  The clamp is by
+    comparisons (torch.where), so a NaN stays; each fmaf of the luma chain is an fp64 multiply-add of fp32 operands -- exact there --
+    rounded once to fp32, which is what a fused multiply-add returns."""
+    from .ops import bench_plane_shape
+    bench_plane_shape(x.shape, crop_border, mode)
+    x = x.to(torch.float32)
+    b = int(crop_border)
+    x = x[:, :, b:x.shape[2] - b, b:x.shape[3] - b]
+    c = torch.where(x < 0, torch.zeros_like(x), torch.where(x > 1, torch.ones_like(x), x))
+    q = (c * 255.0).round()                                  # one fp32 multiply, round-half-to-even
+    if mode == "rgb" or q.shape[1] == 1:
+        return q.contiguous()
+    k = [torch.tensor(v, dtype=torch.float32).double() for v in (65.481, 128.553, 24.966)]
+    t = q[:, 0] * torch.tensor(65.481, dtype=torch.float32)
+    t = (k[1] * q[:, 1].double() + t.double()).float()
+    t = (k[2] * q[:, 2].double() + t.double()).float()
+    return (16.0 + t / 255.0).unsqueeze(1).contiguous()
+
+
+def bench_metrics(pred: torch.Tensor, target: torch.Tensor, crop_border: int, mode: str = "y", with_ssim: bool = True):
+    """PSNR and SSIM as the SwinIR / HAT / DAT papers report them -> (psnr [B], ssim [B] or None), fp32, per image: both images
+    clamped and rounded to 8 bits, `crop_border` pixels cropped on every side, the BT.601 luma of RGB images (mode 'y'; a
+    single-channel image is its own luma) or every channel (mode 'rgb'), on the 0..255 scale; equal planes give +inf.  fp32 GPU
+    tensors take the kernels (ops.bench_planes / ops.bench_psnr, then ops.ssim on the planes), anything else the torch operators.
+    The SSIM is ``ssim`` above on the planes with data_range 255: restated, **parity with the third-party test scripts unpinned**."""
+    from .ops import bench_plane_shape
+    if pred.shape != target.shape:
+        raise ValueError(f"bench metric: pred / target must have one shape (got {tuple(pred.shape)}, {tuple(target.shape)})")
+    shape = bench_plane_shape(pred.shape, crop_border, mode)
+    if with_ssim and min(shape[2:]) < 11:
+        raise ValueError(f"bench metric: the SSIM window needs cropped planes of at least 11 x 11 (border {crop_border} leaves "
+                         f"{shape[2]} x {shape[3]} of {pred.shape[2]} x {pred.shape[3]})")
+    if _on_device(pred, target):
+        from . import ops
+        pp, pt, ws = ops.bench_planes(pred.detach(), target.detach(), crop_border, mode, planes=with_ssim)
+        ps = ops.bench_psnr(ws, shape)[1]
+        return ps, (ops.ssim(pp, pt, 255.0)[0] if with_ssim else None)
+    pp, pt = bench_planes_torch(pred.detach(), crop_border, mode), bench_planes_torch(target.detach(), crop_border, mode)
+    mse = ((pp - pt) ** 2).flatten(1).mean(1)
+    ps = torch.where(mse == 0, torch.full_like(mse, float("inf")), 10.0 * torch.log10(65025.0 / mse))
+    return ps, (ssim_torch(pp, pt, data_range=255.0, size_average=False) if with_ssim else None)

@@ -371,6 +371,59 @@ def ssim(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0):
     return per, mean
 
 
+BENCH_MODES = {"y": 0, "rgb": 1}          # SRK_BENCH_Y, SRK_BENCH_RGB
+
+
+def bench_plane_shape(shape, border: int, mode: str) -> Tuple[int, int, int, int]:
+    """[B, C, H, W] -> the [B, Cm, Hc, Wc] of the benchmark-protocol planes; ValueError for what srk_bench_planes_f32 refuses."""
+    if mode not in BENCH_MODES:
+        raise ValueError(f"bench metric: mode must be 'y' or 'rgb' (got {mode!r})")
+    if len(shape) != 4:
+        raise ValueError(f"bench metric: images must be [B, C, H, W] (got {tuple(shape)})")
+    B, Cc, H, W = (int(v) for v in shape)
+    if isinstance(border, bool) or not isinstance(border, numbers.Integral) or border < 0:
+        raise ValueError(f"bench metric: crop border must be an integer >= 0 (got {border!r})")
+    if min(B, Cc, H, W) < 1 or B > 1024:
+        raise ValueError(f"bench metric: needs 1 <= B <= 1024 and non-empty images (got {tuple(shape)})")
+    if 2 * border >= H or 2 * border >= W:
+        raise ValueError(f"bench metric: a border of {border} leaves nothing of {H} x {W} images")
+    if mode == "y" and Cc not in (1, 3):
+        raise ValueError(f"bench metric: mode 'y' takes RGB (C = 3) or single-channel (C = 1) images (got C = {Cc})")
+    return B, (1 if mode == "y" else Cc), H - 2 * int(border), W - 2 * int(border)
+
+
+def bench_planes(pred: torch.Tensor, target: torch.Tensor, border: int, mode: str = "y", planes: bool = True):
+    """The benchmark-protocol planes of fp32 [B, C, H, W] images (include/srk.h, DESIGN 7m: clamp, round to 8 bits, crop `border`,
+    BT.601 luma for mode 'y') -> (planes of pred, planes of target: fp32 [B, Cm, Hc, Wc], or None each with planes=False,
+    workspace fp32 [B, chunks] with the partial sums of their squared differences for bench_psnr).  One pass, no host read."""
+    if pred.shape != target.shape or pred.dtype != torch.float32 or target.dtype != torch.float32:
+        raise ValueError(f"bench metric: pred / target must be fp32 of one shape (got {pred.dtype} {tuple(pred.shape)}, "
+                         f"{target.dtype} {tuple(target.shape)})")
+    B, Cm, Hc, Wc = bench_plane_shape(pred.shape, border, mode)
+    pred, target = pred.contiguous(), target.contiguous()
+    ws = torch.empty((B, int(lib().srk_bench_workspace(B, Cm, Hc, Wc)) // (4 * B)), dtype=torch.float32, device=pred.device)
+    pp = torch.empty((B, Cm, Hc, Wc), dtype=torch.float32, device=pred.device) if planes else None
+    pt = torch.empty((B, Cm, Hc, Wc), dtype=torch.float32, device=pred.device) if planes else None
+    check(lib().srk_bench_planes_f32(_p(pred), _p(target), _p(pp), _p(pt), _p(ws), B, pred.shape[1], pred.shape[2], pred.shape[3],
+                                     int(border), BENCH_MODES[mode], _stream()))
+    return pp, pt, ws
+
+
+def bench_psnr(ws: torch.Tensor, plane_shape, psnr_sum: Optional[torch.Tensor] = None):
+    """Finishes bench_planes' workspace for planes of plane_shape = (B, Cm, Hc, Wc) -> (sum of squared plane differences [B],
+    PSNR on the 0..255 scale [B]; +inf for equal planes); ACCUMULATES the batch's PSNR sum into the fp32 scalar psnr_sum when given."""
+    B, Cm, Hc, Wc = (int(v) for v in plane_shape)
+    if min(B, Cm, Hc, Wc) < 1 or B > 1024:
+        raise ValueError(f"bench metric: needs 1 <= B <= 1024 and non-empty planes (got {tuple(plane_shape)})")
+    if ws.dtype != torch.float32 or ws.numel() * 4 != int(lib().srk_bench_workspace(B, Cm, Hc, Wc)):
+        raise ValueError(f"bench metric: the workspace does not belong to planes of {(B, Cm, Hc, Wc)}")
+    if psnr_sum is not None and (psnr_sum.dtype != torch.float32 or psnr_sum.numel() != 1):
+        raise ValueError("bench metric: psnr_sum must be one fp32 scalar")
+    sq, ps = torch.empty(B, dtype=torch.float32, device=ws.device), torch.empty(B, dtype=torch.float32, device=ws.device)
+    check(lib().srk_bench_psnr(_p(ws), B, Cm, Hc, Wc, _p(sq), _p(ps), _p(psnr_sum), _stream()))
+    return sq, ps
+
+
 class TensorTable:
     """Host table of a list of fp32 device tensors for the multi-tensor kernels (srk_multi_*): one ctypes array of data pointers per
     role plus the element counts.  Only pointers are kept; the caller keeps the tensors alive until the launches have run."""
