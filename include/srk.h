@@ -291,6 +291,36 @@ int srk_degrade_blind_f32(const float* x, float* out, const int64_t* par4, int B
  * channels.  Errors as srk_crop_degrade_u8. */
 int srk_crop_degrade_blind_u8(const uint8_t* pool, const int64_t* desc10, float* lr_out, float* hr_out, int B, int lr_patch, int scale,
                               int quant_bits, srk_stream_t stream);
+/* General 2-D blur (csrc/blur2d.hip): a rotated, generalized or plateau Gaussian, or a measured point-spread function, as a table.
+ * A PSF table is ks x ks fp32, ks odd in 1..21, R = (ks - 1) / 2; one table per sample, psf = DEVICE fp32 [B][ks][ks].
+ * The blur is a CORRELATION (cv2.filter2D's convention: no flip of the table) with the border rule of the resize applied per blurred
+ * pixel -- mass outside the image is dropped and the rest renormalised:
+ *   num(p, q)  = sum over a, b ascending (a outer, b inner) of K[a][b] * x(p + a - R, q + b - R)      -- only taps inside the image
+ *   mass(p, q) = the same chain with x == 1
+ *   blurred    = num / mass
+ * Each chain is acc = fmaf(K[a][b], x, acc) from 0 in fp32, no other contraction; the division is IEEE and is performed at every pixel,
+ * in the interior too: one code path, one set of bits.  (An interior pixel may take a mass computed once by the same chain.)
+ * fmaf(0, x, acc) == acc for finite x, so a table zero-padded, centred, to a larger ks gives IDENTICAL bits on finite images: one ks
+ * per launch is enough for a batch of mixed sizes.  A pixel is NaN exactly when an in-image tap of its ks x ks window is.
+ * The host (ops) checks a table: taps finite and >= 0, K[R][R] > 0 (so mass > 0 everywhere), fp64 sum within 1e-3 of 1.  The kernels
+ * check nothing of it: for ANY table bits they stay inside their buffers, and the values are then unspecified.
+ *
+ * srk_blur2d_f32: x fp32 [B][C][H][W] -> out of the same shape, sample b blurred with table b.  out must overlap neither x nor psf.
+ * One launch, no device allocation; nothing outside out[0 .. B*C*H*W) is written and nothing outside x and psf is read.
+ * SRK_E_NULL: a null pointer; SRK_E_SHAPE: a non-positive extent, ks even or outside 1..21, an overlap, a size that does not fit one launch. */
+int srk_blur2d_f32(const float* x, const float* psf, float* out, int B, int C, int H, int W, int ks, srk_stream_t stream);
+/* srk_crop_degrade_blind_u8 with the 2-D blur in place of the composed Gaussian: LR = noise(resize_aa(blur2d(HR))).  desc10 as there;
+ * slot 6 (the sigma pair) is reserved and ignored.  The blur and the resize are both bounded by the image's top-left
+ * (H - H % scale, W - W % scale) region; the resize runs the plain cubic tables of srk_resize_aa_f32 on the blurred values; noise and the
+ * 8-bit rounding are those of srk_degrade_blind_f32, counter on whole-image LR coordinates.  hr_out is never blurred: bit-identical to
+ * srk_crop_degrade_u8's.  lr_out is BIT-IDENTICAL to the window of srk_blur2d_f32 on the whole converted region followed by
+ * srk_degrade_blind_f32 with sigma (0, 0) and the same slots 7..9 (the entries share their device routines).  Within R + 2 scale HR
+ * pixels of the region's border this differs from srk_crop_degrade_blind_u8 at the same Gaussian: that entry renormalises once per LR
+ * output (one composed table), this one per blurred pixel and then per cubic table; in the interior the two agree to rounding.
+ * A gray source is blurred and filtered once, gets one draw and is written to three channels.  One launch for the batch.
+ * Errors as srk_crop_degrade_blind_u8, plus SRK_E_SHAPE for ks even or outside 1..21. */
+int srk_crop_degrade_psf_u8(const uint8_t* pool, const int64_t* desc10, const float* psf, int ks, float* lr_out, float* hr_out, int B,
+                            int lr_patch, int scale, int quant_bits, srk_stream_t stream);
 /* JPEG round trip (csrc/jpeg.hip): what a baseline JPEG file of an 8-bit image at quality q decodes to, as a closed-form fp32 pipeline.
  * No entropy coding is done: it is lossless and changes nothing.  x, out fp32 [B][C][H][W], C = 1 or 3, H, W >= 1 (no multiple of 8
  * needed); subsample 0 = 4:4:4, 1 = 4:2:0 (has effect only with C == 3); quality DEVICE int32 [B], each in 1..100, or 0 = sample b is

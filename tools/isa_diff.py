@@ -5,7 +5,7 @@
 
 For every entry of build.SOURCES, in both trees, hipcc compiles the device side to assembly (build.FLAGS plus
 --cuda-device-only -S; no GPU needed).  Lines with __hip_cuid_ (a hash of the source path) are dropped.  The report has, per
-file, the number of differing lines and, per kernel, .vgpr_count, .sgpr_count, LDS bytes, ScratchSize and Occupancy as the
+file (one that only the branch has is listed as new), the number of differing lines and, per kernel, .vgpr_count, .sgpr_count, LDS bytes, ScratchSize and Occupancy as the
 assembly's own metadata states them.  Exit status 1 when anything differs.
 """
 from __future__ import annotations
@@ -32,6 +32,8 @@ def load_build(root: str):
 
 
 def assemble(build, root: str, src: str, out: str) -> list[str]:
+    if not os.path.exists(os.path.join(root, PKG, "csrc", src)):          # a source the other tree does not have: reported as new
+        return []
     cmd = [build._hipcc(), *build.FLAGS, "--cuda-device-only", "-S", os.path.join(root, PKG, "csrc", src), "-o", out]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
@@ -104,8 +106,13 @@ def main() -> int:
     bad = 0
     for s in sources:
         a, b = asm[(s, 0)], asm[(s, 1)]
-        ndiff = 0 if a == b else sum(1 for d in difflib.ndiff(a, b) if d[:2] in ("- ", "+ "))
         ka, kb = kernel_stats(a), kernel_stats(b)
+        if not a:          # new in the branch: nothing to compare with, and no difference to report
+            report["files"][s] = {"lines": len(b), "new": True, "kernels": len(kb)}
+            report["kernels"][s] = {k: kb[k] for k in sorted(kb)}
+            print(f"{s:24s}    new in the branch, {len(kb):3d} kernels")
+            continue
+        ndiff = 0 if a == b else sum(1 for d in difflib.ndiff(a, b) if d[:2] in ("- ", "+ "))
         report["files"][s] = {"lines": len(b), "differing_lines": ndiff, "kernels": len(kb), "kernel_stats_equal": ka == kb}
         report["kernels"][s] = {k: ({"parent": ka.get(k), "branch": kb.get(k)} if ka.get(k) != kb.get(k) else kb[k])
                                 for k in sorted(set(ka) | set(kb))}

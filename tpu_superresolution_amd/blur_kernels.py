@@ -1,0 +1,110 @@
+"""2-D blur tables for the PSF degradation (include/srk.h "General 2-D blur"; ops.blur2d, ops.degrade_psf, sr_datasets.PsfSpec): the
+kernel pool of BSRGAN / Real-ESRGAN -- rotated anisotropic Gaussians, generalized Gaussians, plateau kernels -- evaluated in fp64 numpy,
+normalised in fp64 and rounded once to fp32.
+
+A table is ks x ks, ks odd in 1..21, R = (ks - 1) / 2, row a <-> y = a - R, column b <-> x = b - R.  With q = (x, y) and
+Sigma = Rot(theta) diag(s1^2, s2^2) Rot(theta)^T, theta counter-clockwise in the (x, y) frame of the array (y grows downwards):
+    gaussian     exp(-0.5 q^T Sigma^-1 q)
+    generalized  exp(-0.5 (q^T Sigma^-1 q)^beta)
+    plateau      1 / ((q^T Sigma^-1 q)^beta + 1)
+At theta = 0, s1 is the sigma along x (columns) and s2 the one along y (rows); theta = pi / 2 swaps them.  The device applies a table as a
+correlation, so what matters for an asymmetric table is this orientation and nothing is flipped anywhere."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+KS_MAX = 21
+
+
+def check_ks(ks) -> int:
+    if isinstance(ks, bool) or int(ks) != ks or not 1 <= int(ks) <= KS_MAX or int(ks) % 2 == 0:
+        raise ValueError(f"a blur table is ks x ks with ks odd in 1..{KS_MAX} (got {ks!r})")
+    return int(ks)
+
+
+_GRIDS: dict = {}
+
+
+def _grid(ks: int):
+    """(x^2, x y, y^2) of the integer grid of a ks x ks table, made once per size."""
+    if ks not in _GRIDS:
+        r = (ks - 1) // 2
+        y, x = np.meshgrid(np.arange(-r, r + 1, dtype=np.float64), np.arange(-r, r + 1, dtype=np.float64), indexing="ij")
+        _GRIDS[ks] = (x * x, x * y, y * y)
+    return _GRIDS[ks]
+
+
+def _quad(ks: int, s1: float, s2: float, theta: float) -> np.ndarray:
+    """q^T Sigma^-1 q with Sigma^-1 = Rot diag(1 / s1^2, 1 / s2^2) Rot^T written out: A x^2 + 2 B x y + C y^2."""
+    ks = check_ks(ks)
+    s1, s2, theta = float(s1), float(s2), float(theta)
+    if not (s1 > 0.0 and s2 > 0.0 and math.isfinite(s1) and math.isfinite(s2) and math.isfinite(theta)):
+        raise ValueError(f"blur sigmas must be finite and > 0, theta finite (got {(s1, s2, theta)})")
+    c, s = math.cos(theta), math.sin(theta)
+    i1, i2 = 1.0 / (s1 * s1), 1.0 / (s2 * s2)
+    xx, xy, yy = _grid(ks)
+    return (c * c * i1 + s * s * i2) * xx + (2.0 * c * s * (i1 - i2)) * xy + (s * s * i1 + c * c * i2) * yy
+
+
+def _finish(k: np.ndarray) -> np.ndarray:
+    return (k / k.sum()).astype(np.float32)
+
+
+def gaussian(ks: int, s1: float, s2: float, theta: float = 0.0) -> np.ndarray:
+    return _finish(np.exp(-0.5 * _quad(ks, s1, s2, theta)))
+
+
+def _beta(beta) -> float:
+    beta = float(beta)
+    if not (beta > 0.0 and np.isfinite(beta)):
+        raise ValueError(f"beta must be finite and > 0 (got {beta!r})")
+    return beta
+
+
+def generalized(ks: int, s1: float, s2: float, theta: float, beta: float) -> np.ndarray:
+    return _finish(np.exp(-0.5 * _quad(ks, s1, s2, theta) ** _beta(beta)))
+
+
+def plateau(ks: int, s1: float, s2: float, theta: float, beta: float) -> np.ndarray:
+    return _finish(1.0 / (_quad(ks, s1, s2, theta) ** _beta(beta) + 1.0))
+
+
+def pad_to(table, ks: int) -> np.ndarray:
+    """`table` zero-padded, centred, to ks x ks: the device gives identical bits for both on finite images."""
+    t = np.asarray(table, dtype=np.float32)
+    ks = check_ks(ks)
+    if t.ndim != 2 or t.shape[0] != t.shape[1] or t.shape[0] % 2 == 0 or t.shape[0] > ks:
+        raise ValueError(f"pad_to: an odd square table of at most {ks} x {ks} (got {t.shape})")
+    return np.pad(t, (ks - t.shape[0]) // 2)
+
+
+def check_table(table, what: str = "psf") -> np.ndarray:
+    """The host rule of a table -> fp32 [ks][ks]: odd square with ks <= 21, taps finite and >= 0, a centre > 0 (so that the mass is > 0 at
+    every pixel), an fp64 sum within 1e-3 of 1."""
+    t = np.asarray(table)
+    if t.ndim != 2 or t.shape[0] != t.shape[1] or t.shape[0] % 2 == 0 or not 1 <= t.shape[0] <= KS_MAX:
+        raise ValueError(f"{what}: a table is ks x ks with ks odd in 1..{KS_MAX} (got shape {t.shape})")
+    t = t.astype(np.float32)
+    if not np.isfinite(t).all():
+        raise ValueError(f"{what}: taps must be finite")
+    if (t < 0).any():
+        raise ValueError(f"{what}: taps must be >= 0 (kernels with negative lobes need another mass rule)")
+    r = t.shape[0] // 2
+    if not t[r, r] > 0:
+        raise ValueError(f"{what}: the centre tap must be > 0")
+    total = float(t.astype(np.float64).sum())
+    if abs(total - 1.0) > 1e-3:
+        raise ValueError(f"{what}: the taps must sum to 1 within 1e-3 (got {total:.6f})")
+    return t
+
+
+def load_psf_file(path: str) -> np.ndarray:
+    """A measured PSF: .npy of shape [k][k] or [n][k][k] -> checked fp32 [n][k][k]."""
+    a = np.load(path, allow_pickle=False)
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3 or a.shape[0] < 1:
+        raise ValueError(f"{path}: a PSF file holds [k][k] or [n][k][k] (got shape {a.shape})")
+    return np.stack([check_table(t, f"{path}[{i}]") for i, t in enumerate(a)])

@@ -552,6 +552,27 @@ int srk_degrade_blind_f32(const float* x, float* out, const int64_t* par4, int B
   return srk_launch_degrade_blind_f32(x, out, reinterpret_cast<const long long*>(par4), B, C, H, W, scale, quant_bits, (hipStream_t)stream);
 }
 
+int srk_blur2d_f32(const float* x, const float* psf, float* out, int B, int C, int H, int W, int ks, srk_stream_t stream) {
+  REQ_PTR(x); REQ_PTR(psf); REQ_PTR(out);
+  SRK_REQUIRE(srk_psf_ks_ok(ks), SRK_E_SHAPE, "blur2d: ks must be odd and in 1..21 (got %d)", ks);
+  SRK_REQUIRE(srk_blur2d_shape_ok(B, C, H, W), SRK_E_SHAPE, "blur2d: B=%d C=%d H=%d W=%d must all be >= 1 and fit one launch", B, C, H, W);
+  const size_t bytes = (size_t)(4.0 * B * C * H * W), kb = sizeof(float) * (size_t)B * ks * ks;
+  SRK_REQUIRE(!srk_ranges_overlap(x, bytes, out, bytes) && !srk_ranges_overlap(psf, kb, out, bytes), SRK_E_SHAPE,
+              "blur2d: out overlaps x or psf (the blur is not run in place)");
+  return srk_launch_blur2d_f32(x, psf, out, B, C, H, W, ks, (hipStream_t)stream);
+}
+
+int srk_crop_degrade_psf_u8(const uint8_t* pool, const int64_t* desc10, const float* psf, int ks, float* lr_out, float* hr_out, int B,
+                            int lr_patch, int scale, int quant_bits, srk_stream_t stream) {
+  REQ_PTR(pool); REQ_PTR(desc10); REQ_PTR(psf); REQ_PTR(lr_out); REQ_PTR(hr_out);
+  SRK_REQUIRE(srk_crop_degrade_shape_ok(B, lr_patch, scale), SRK_E_SHAPE, "crop_degrade_psf: B=%d (1..65535) patch=%d (1..2048) scale=%d (2..4)",
+              B, lr_patch, scale);
+  SRK_REQUIRE(quant_bits == 0 || quant_bits == 8, SRK_E_SHAPE, "crop_degrade_psf: quant_bits must be 0 or 8 (got %d)", quant_bits);
+  SRK_REQUIRE(srk_psf_ks_ok(ks), SRK_E_SHAPE, "crop_degrade_psf: ks must be odd and in 1..21 (got %d)", ks);
+  return srk_launch_crop_degrade_psf_u8(pool, reinterpret_cast<const long long*>(desc10), psf, ks, lr_out, hr_out, B, lr_patch, scale,
+                                        quant_bits, (hipStream_t)stream);
+}
+
 int srk_jpeg_roundtrip_f32(const float* x, float* out, const int32_t* quality, int B, int C, int H, int W, int subsample, int16_t* coef_out,
                            srk_stream_t stream) {
   REQ_PTR(x); REQ_PTR(out); REQ_PTR(quality);

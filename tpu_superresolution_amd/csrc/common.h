@@ -113,6 +113,17 @@ static inline bool srk_bench_plane_dims_ok(int B, int Cm, int Hc, int Wc) {
   return B > 0 && B <= 1024 && Cm > 0 && Hc > 0 && Wc > 0 && (long long)Cm * Hc <= 0x7fffffffLL;
 }
 
+// 2-D blur tables (blur2d.hip, srk.h "General 2-D blur"): the side of a table, and the shapes srk_blur2d_f32 takes (the byte counts of
+// x / out and of psf stay below 2^63, the planes index an int)
+static inline bool srk_psf_ks_ok(int ks) { return ks >= 1 && ks <= 21 && (ks & 1) == 1; }
+static inline bool srk_blur2d_shape_ok(int B, int C, int H, int W) {
+  return B > 0 && C > 0 && H > 0 && W > 0 && (double)B * C <= 2147483647.0 && 4.0 * B * C * H * W < 9.0e18;
+}
+// the batch shapes of the crop + degrade entries (srk_crop_degrade_u8, _blind_u8, _psf_u8)
+static inline bool srk_crop_degrade_shape_ok(int B, int lr_patch, int scale) {
+  return B > 0 && B <= 65535 && lr_patch > 0 && lr_patch <= 2048 && scale >= 2 && scale <= 4;
+}
+
 // ---------------------------------------------------------------------------------------------
 // bf16 helpers (device)
 // ---------------------------------------------------------------------------------------------

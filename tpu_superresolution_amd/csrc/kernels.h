@@ -69,6 +69,11 @@ int srk_launch_degrade_blind_f32(const float* x, float* out, const long long* pa
                                  hipStream_t stream);
 int srk_launch_crop_degrade_blind_u8(const unsigned char* pool, const long long* desc, float* lr_out, float* hr_out, int B, int P, int scale,
                                      int quant_bits, hipStream_t stream);
+// blur2d.hip: a per-sample ks x ks blur table as a correlation, and the training degradation behind it (arguments checked by
+// srk_blur2d_f32 / srk_crop_degrade_psf_u8)
+int srk_launch_blur2d_f32(const float* x, const float* psf, float* out, int B, int C, int H, int W, int ks, hipStream_t stream);
+int srk_launch_crop_degrade_psf_u8(const unsigned char* pool, const long long* desc, const float* psf, int ks, float* lr_out, float* hr_out,
+                                   int B, int P, int scale, int quant_bits, hipStream_t stream);
 // jpeg.hip: the closed-form JPEG round trip at a per-sample quality (arguments checked by srk_jpeg_roundtrip_f32)
 int srk_launch_jpeg_roundtrip_f32(const float* x, float* out, const int* quality, int B, int C, int H, int W, int subsample, short* coef_out,
                                   hipStream_t stream);

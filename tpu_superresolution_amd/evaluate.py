@@ -16,7 +16,8 @@ N x N tiles of the model's input and merges them (tiling.tiled_forward; any --ar
 ``--synth_lr [--synth_lr_bits 0|8]`` (--arch swinir | hat | dat) needs only the HR directory of the test split: LR is its antialiased
 bicubic downscale, formed on the device (ops.resize_aa), with ``--degrade blind --blur_sigma SY SX --noise_sigma N --noise_gain G`` blurred and
 noised there with fixed parameters (ops.degrade_blind), with ``--jpeg_quality Q [--jpeg_subsample 444|420]`` then sent through a baseline
-JPEG round trip (ops.jpeg_roundtrip); ``main(argv)`` is callable from tests.  SSIM is ``metrics.ssim`` (restated, parity unpinned).
+JPEG round trip (ops.jpeg_roundtrip), with ``--blur_theta DEG`` or ``--blur_psf FILE`` blurred with a 2-D table instead (ops.degrade_psf,
+DESIGN 7n); ``main(argv)`` is callable from tests.  SSIM is ``metrics.ssim`` (restated, parity unpinned).
 ``--bench_metric y | rgb [--crop_border N]`` (any --arch, any of the options above: it looks at (pred, hr) only) adds ``[bench]`` lines
 and ``bench_*`` keys with the scores of the papers' protocol -- 8-bit, border-cropped (default: the scale), BT.601 luma or RGB, 0..255
 scale, mean over images (metrics.bench_metrics); the other lines and keys stay as they are.
@@ -114,6 +115,12 @@ def parse_args(argv=None):
                     help="additive, with --degrade blind: sigma of the Gaussian blur in HR pixels along y and x, within [0, 2.5]")
     ap.add_argument("--noise_sigma", type=float, default=5.0, help="additive, with --degrade blind: noise sigma in 8-bit levels")
     ap.add_argument("--noise_gain", type=float, default=0.0, help="additive, with --degrade blind: gain of the signal-dependent noise")
+    ap.add_argument("--blur_theta", type=float, default=None, metavar="DEG",
+                    help="additive, with --degrade blind: the Gaussian of --blur_sigma turned by DEG degrees, applied as a 2-D table "
+                         "(blur_kernels.gaussian, ops.degrade_psf, csrc/blur2d.hip); 0 is the axis-aligned Gaussian on the 2-D path")
+    ap.add_argument("--blur_psf", type=str, default=None, metavar="FILE",
+                    help="additive, with --degrade blind: blur with table 0 of a measured point-spread function, .npy [k][k] or [n][k][k] "
+                         "(k odd <= 21, taps >= 0 summing to 1), instead of the Gaussian")
     ap.add_argument("--jpeg_quality", type=int, default=None, metavar="Q",
                     help="additive, with --synth_lr --synth_lr_bits 8 (either --degrade): the LR image makes a round trip through baseline "
                          "JPEG at quality Q in 1..100 on the device (ops.jpeg_roundtrip, csrc/jpeg.hip), before any tiling or self-ensemble")
@@ -141,6 +148,14 @@ def parse_args(argv=None):
             pack_degrade_params(args.blur_sigma, (args.noise_sigma / 255.0, args.noise_gain), 0, False)
         except ValueError as e:
             ap.error(f"--degrade blind: {e}")
+    if (args.blur_theta is not None or args.blur_psf is not None) and args.degrade != "blind":
+        ap.error("--blur_theta and --blur_psf shape the blur of --degrade blind: they need it")
+    if args.blur_theta is not None and args.blur_psf is not None:
+        ap.error("--blur_psf FILE replaces the Gaussian: it does not go with --blur_theta")
+    try:
+        eval_psf(args)
+    except (ValueError, OSError) as e:
+        ap.error(f"--blur_theta / --blur_psf: {e}")
     if args.jpeg_quality is None:
         if args.jpeg_subsample != "444":
             ap.error("--jpeg_subsample is an option of the JPEG stage: it needs --jpeg_quality Q")
@@ -157,6 +172,24 @@ def parse_args(argv=None):
     if not 2 <= args.window_size <= 8 or (args.window_size != 8 and args.arch != "swinir"):
         ap.error(f"--window_size must be in 2..8 and is an option of --arch swinir (got {args.window_size} with --arch {args.arch})")
     return args
+
+
+def eval_psf(args):
+    """The 2-D blur table of the command line: table 0 of --blur_psf, the rotated Gaussian of --blur_theta (sigma_x along the columns at
+    0 degrees, as on the separable path; a sigma of 0 is floored as in sr_datasets.PsfSpec), or None."""
+    if args.blur_psf is not None:
+        from .blur_kernels import load_psf_file
+        return load_psf_file(args.blur_psf)[0]
+    if args.blur_theta is None:
+        return None
+    import math
+
+    from .blur_kernels import gaussian
+    from .sr_datasets import PSF_SIGMA_FLOOR
+    if not math.isfinite(args.blur_theta):
+        raise ValueError(f"--blur_theta must be finite (got {args.blur_theta})")
+    sy, sx = (max(float(v), PSF_SIGMA_FLOOR) for v in args.blur_sigma)
+    return gaussian(2 * min(math.ceil(3.0 * max(float(v) for v in args.blur_sigma)), 10) + 1, sx, sy, math.radians(args.blur_theta))
 
 
 def main(argv=None):
@@ -187,11 +220,15 @@ def main(argv=None):
             from .sr_datasets import FixedDegrade
             fixed = FixedDegrade(tuple(args.blur_sigma), (args.noise_sigma / 255.0, args.noise_gain))
         test_loader = SynthLRBatches(test_loader, scale_int, args.synth_lr_bits, device, degrade=fixed, jpeg=args.jpeg_quality,
-                                     jpeg_subsample=args.jpeg_subsample == "420")
+                                     jpeg_subsample=args.jpeg_subsample == "420", psf=eval_psf(args))
         print(f"[synth_lr] LR = antialiased bicubic /{scale_int} of HR on the device, {args.synth_lr_bits or 'no'}-bit rounding")
         if fixed is not None:
             print(f"[degrade] blind: blur sigma=({fixed.blur[0]:.4g}, {fixed.blur[1]:.4g}) HR px, noise sigma={args.noise_sigma:.4g} / 255 "
                   f"gain={args.noise_gain:.4g}, noise id = image index")
+        if eval_psf(args) is not None:
+            k = eval_psf(args)
+            print(f"[degrade] blur kernel: {k.shape[0]} x {k.shape[0]} table, " + (f"table 0 of {args.blur_psf}" if args.blur_psf is not None else
+                                                                                    f"the Gaussian turned by {args.blur_theta:g} degrees"))
         if args.jpeg_quality is not None:
             print(f"[degrade] jpeg: quality {args.jpeg_quality}, chroma {args.jpeg_subsample}")
     print(f"[data] test samples: {len(test_ds)} | steps: {len(test_loader)}")

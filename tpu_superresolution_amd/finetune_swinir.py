@@ -21,6 +21,8 @@ bicubic downscale of its HR image, made on the device (sr_datasets.DeviceHRPool,
 launch (csrc/degrade.hip); validation uses the midpoints of the ranges and the same noise every epoch.
 `--jpeg_quality LO HI [--jpeg_p P --jpeg_subsample 444|420]` (with either --degrade) sends every 8-bit LR patch through a baseline JPEG
 round trip at a random per-sample quality in a second launch (csrc/jpeg.hip); validation uses the middle of the range.
+`--blur_kernel rotated|mixed` or `--blur_psf FILE` (with --degrade blind) blurs every patch with a 2-D table -- a rotated, generalized or
+plateau Gaussian, or a measured point-spread function -- in the same single launch (csrc/blur2d.hip).
 
 Also additive: `--arch hat|dat` fine-tunes HAT / DAT (build_sr_model) through the same loop -- the fused, device-gated clip + AdamW step
 over their parameter lists (optim.FusedAdamW, csrc/optim_multi.hip), checkpoints "best_<arch>_finetune_<scale>.pt" /
@@ -301,6 +303,23 @@ def parse_args(argv=None):
                     help="additive, with --jpeg_quality: probability that a training patch takes the JPEG stage (otherwise it passes through)")
     ap.add_argument("--jpeg_subsample", type=str, choices=["444", "420"], default="444",
                     help="additive, with --jpeg_quality: chroma at 4:4:4, or 4:2:0 (2 x 2 means, upsampled by replication)")
+    ap.add_argument("--blur_kernel", type=str, choices=["axis", "rotated", "mixed"], default="axis",
+                    help="additive, with --degrade blind: the blur of a training patch -- 'axis': the axis-aligned Gaussian composed into the "
+                         "bicubic taps; 'rotated': the same Gaussian turned by a random angle; 'mixed': Real-ESRGAN's pool of (an)isotropic, "
+                         "generalized and plateau kernels -- as a 2-D table on the device (sr_datasets.PsfSpec, csrc/blur2d.hip; its own "
+                         "generator, seeded by --degrade_seed + rank); validation keeps the isotropic midpoints")
+    ap.add_argument("--blur_kernel_prob", type=float, nargs=6, default=None, metavar="P",
+                    help="additive, with --blur_kernel mixed: probabilities of iso, aniso, generalized iso, generalized aniso, plateau iso, "
+                         "plateau aniso (default 0.45 0.25 0.12 0.03 0.12 0.03)")
+    ap.add_argument("--blur_beta_g", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="additive, with --blur_kernel mixed: range of the generalized Gaussian's shape beta (default 0.5 4)")
+    ap.add_argument("--blur_beta_p", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="additive, with --blur_kernel mixed: range of the plateau kernel's shape beta (default 1 2)")
+    ap.add_argument("--blur_ksize", type=int, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="additive, with --blur_kernel mixed: range of the odd table size (default 7 21)")
+    ap.add_argument("--blur_psf", type=str, default=None, metavar="FILE",
+                    help="additive, with --degrade blind: a measured point-spread function, .npy [k][k] or [n][k][k] (k odd <= 21, taps >= 0 "
+                         "summing to 1); every training patch is blurred with one of its tables, validation with table 0")
     args = ap.parse_args(argv)
     if args.synth_lr and not args.gpu_data:
         ap.error("--synth_lr forms the LR patches on the device: it needs --gpu_data")
@@ -311,6 +330,17 @@ def parse_args(argv=None):
             degrade_spec(args)
         except ValueError as e:
             ap.error(f"--degrade blind: {e}")
+    mixed_opts = [n for n in ("blur_kernel_prob", "blur_beta_g", "blur_beta_p", "blur_ksize") if getattr(args, n) is not None]
+    if (args.blur_kernel != "axis" or args.blur_psf is not None) and args.degrade != "blind":
+        ap.error("--blur_kernel and --blur_psf shape the blur of --degrade blind: they need it")
+    if args.blur_psf is not None and args.blur_kernel != "axis":
+        ap.error("--blur_psf FILE replaces the generated kernels: it does not go with --blur_kernel rotated | mixed")
+    if mixed_opts and args.blur_kernel != "mixed":
+        ap.error(f"--{mixed_opts[0]} is an option of --blur_kernel mixed")
+    try:
+        psf_spec(args)
+    except (ValueError, OSError) as e:
+        ap.error(f"--blur_kernel / --blur_psf: {e}")
     if args.jpeg_quality is None:
         if args.jpeg_p != 1.0 or args.jpeg_subsample != "444":
             ap.error("--jpeg_p and --jpeg_subsample are options of the JPEG stage: they need --jpeg_quality LO HI")
@@ -356,6 +386,18 @@ def degrade_spec(args):
                        noise_gain=tuple(args.noise_gain), gray_noise_p=args.gray_noise_p, seed=args.degrade_seed)
 
 
+def psf_spec(args):
+    """The PsfSpec of the command line (None for --blur_kernel axis without --blur_psf); it reuses --degrade_seed."""
+    if args.blur_kernel == "axis" and args.blur_psf is None:
+        return None
+    from .sr_datasets import PsfSpec
+    opts = {k: tuple(v) for k, v in (("kernel_prob", args.blur_kernel_prob), ("beta_g", args.blur_beta_g), ("beta_p", args.blur_beta_p),
+                                     ("ksize", args.blur_ksize)) if v is not None}
+    if args.blur_psf is not None:
+        return PsfSpec(mode="file", file=args.blur_psf, seed=args.degrade_seed)
+    return PsfSpec(mode=args.blur_kernel, seed=args.degrade_seed, **opts)
+
+
 def jpeg_spec(args):
     """The JpegSpec of the command line (None without --jpeg_quality); it reuses --degrade_seed."""
     if args.jpeg_quality is None:
@@ -374,7 +416,10 @@ def saved_args(args) -> dict:
                   "noise_sigma": args.noise_sigma == [0.0, 10.0], "noise_gain": args.noise_gain == [0.0, 0.0],
                   "gray_noise_p": args.gray_noise_p == 0.4,
                   "degrade_seed": args.degrade_seed == 0, "jpeg_quality": args.jpeg_quality is None, "jpeg_p": args.jpeg_p == 1.0,
-                  "jpeg_subsample": args.jpeg_subsample == "444", "val_bench_metric": args.val_bench_metric is None,
+                  "jpeg_subsample": args.jpeg_subsample == "444", "blur_kernel": args.blur_kernel == "axis",
+                  "blur_kernel_prob": args.blur_kernel_prob is None, "blur_beta_g": args.blur_beta_g is None,
+                  "blur_beta_p": args.blur_beta_p is None, "blur_ksize": args.blur_ksize is None, "blur_psf": args.blur_psf is None,
+                  "val_bench_metric": args.val_bench_metric is None,
                   "val_crop_border": args.val_crop_border is None}
     return {k: v for k, v in vars(args).items() if not at_default.get(k, False)}
 
@@ -401,7 +446,7 @@ def main(argv=None):
         raw = Shuffled2DHR(args.data_root, split="train")
         pool = DeviceHRPool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, device=device,
                             shard_bytes=(args.gpu_data_shard_mb << 20) or None, augment=args.augment, quant_bits=args.synth_lr_bits,
-                            degrade=degrade_spec(args), rank=rank, jpeg=jpeg_spec(args))
+                            degrade=degrade_spec(args), rank=rank, jpeg=jpeg_spec(args), psf=psf_spec(args))
         train_loader = sampler = DevicePoolLoader(pool, args.batch_size, rank, world, args.seed)
         valid_ds = Shuffled2DHR(args.data_root, split="valid", transform=hr_to_tensor3)
         if rank == 0:
@@ -413,6 +458,11 @@ def main(argv=None):
                       f"{args.noise_sigma} / 255, gain in {args.noise_gain}, gray p={args.gray_noise_p}, seed {args.degrade_seed}; "
                       f"validation: sigma=({fx.blur[0]:.4g}, {fx.blur[1]:.4g}) noise sigma={fx.noise[0] * 255.0:.4g} / 255 "
                       f"gain={fx.noise[1]:.4g}, noise id = image index")
+            if psf_spec(args) is not None:
+                ps = psf_spec(args)
+                what = (f"{len(ps.tables)} measured table(s) of {args.blur_psf}, {ps.tables.shape[-1]} x {ps.tables.shape[-1]}; validation: table 0"
+                        if ps.mode == "file" else f"{ps.mode} 2-D kernels; validation: the isotropic midpoints")
+                print(f"[degrade] blur kernel: {what}, seed {args.degrade_seed}")
             if args.jpeg_quality is not None:
                 js = jpeg_spec(args)
                 print(f"[degrade] jpeg: quality in {list(js.quality)} with p={js.p:g}, chroma {args.jpeg_subsample}, seed {args.degrade_seed}; "
@@ -435,7 +485,8 @@ def main(argv=None):
     valid_loader = make_loader(valid_ds, max(1, args.batch_size // 2), args.workers, pin=not args.no_pin, shuffle=False,
                                drop_last=False, persistent=not args.no_persistent)
     if args.synth_lr:
-        valid_loader = SynthLRBatches(valid_loader, scale_int, args.synth_lr_bits, device, degrade=degrade_spec(args), jpeg=jpeg_spec(args))
+        valid_loader = SynthLRBatches(valid_loader, scale_int, args.synth_lr_bits, device, degrade=degrade_spec(args), jpeg=jpeg_spec(args),
+                                      psf=psf_spec(args))
 
     model = (build_model(scale_int, args.drop_path_rate, args.window_size) if args.arch == "swinir" else
              build_sr_model(args.arch, scale_int, args.drop_path_rate))

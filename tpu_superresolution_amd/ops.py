@@ -669,6 +669,74 @@ def degrade_blind(hr: torch.Tensor, scale: int, blur, noise, noise_ids, gray_noi
     return lr, hr
 
 
+def pack_psf(psf, B: int, checked: bool = False):
+    """psf: one [ks][ks] table or B of them (a list of tables of different odd sizes, or an array [B][ks][ks]) -> (fp32 numpy
+    [B][ks][ks], ks): every table checked by the host rule (blur_kernels.check_table) and zero-padded, centred, to the largest ks --
+    which changes no bit of the result (include/srk.h "General 2-D blur").  checked: a list of fp32 tables that blur_kernels made or
+    checked already (sr_datasets.PsfSpec's draws) is only padded."""
+    from . import blur_kernels as bk
+    import numpy as np
+    if checked:
+        ks = max(t.shape[0] for t in psf)
+        out = np.zeros((len(psf), ks, ks), dtype=np.float32)
+        for i, t in enumerate(psf):
+            p = (ks - t.shape[0]) // 2
+            out[i, p:p + t.shape[0], p:p + t.shape[0]] = t
+        if len(psf) != B:
+            raise ValueError(f"psf: one table per sample (B={B}; got {len(psf)})")
+        return out, ks
+    if isinstance(psf, torch.Tensor):
+        psf = psf.detach().cpu().numpy()
+    try:
+        arr = np.asarray(psf, dtype=np.float32)
+    except (ValueError, TypeError):          # tables of different sizes
+        arr = None
+    if arr is not None and arr.ndim == 2:
+        tabs = [bk.check_table(arr)] * B
+    else:
+        tabs = [bk.check_table(t, f"psf[{i}]") for i, t in enumerate(psf if arr is None else arr)]
+    if len(tabs) != B:
+        raise ValueError(f"psf: one table or one per sample (B={B}; got {len(tabs)})")
+    ks = max(t.shape[0] for t in tabs)
+    return np.stack([bk.pad_to(t, ks) for t in tabs]), ks
+
+
+def blur2d(x: torch.Tensor, psf, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x CUDA fp32 [B,C,H,W] blurred with one ks x ks table or one per sample (csrc/blur2d.hip, srk_blur2d_f32): a correlation (no flip,
+    cv2.filter2D's convention) in which taps outside the image are dropped and the rest renormalised per pixel.  Tables: odd ks <= 21,
+    taps finite and >= 0, centre > 0, sum within 1e-3 of 1 (ValueError otherwise); mixed sizes are zero-padded to the largest.  One
+    launch after one small upload."""
+    if x.dim() != 4 or not x.is_cuda or x.dtype != torch.float32 or min(x.shape) < 1:
+        raise ValueError(f"blur2d takes a non-empty CUDA fp32 [B,C,H,W] batch (got {x.dtype} {tuple(x.shape)} on {x.device})")
+    x = x.contiguous()
+    B, Cc, H, W = x.shape
+    tabs, ks = pack_psf(psf, B)
+    if out is None:
+        out = torch.empty_like(x)
+    elif tuple(out.shape) != tuple(x.shape) or out.dtype != torch.float32 or out.device != x.device or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous fp32 {tuple(x.shape)} on {x.device} (got {out.dtype} {tuple(out.shape)} on {out.device})")
+    k = torch.from_numpy(tabs).to(x.device)
+    check(lib().srk_blur2d_f32(_p(x), _p(k), _p(out), B, Cc, H, W, ks, _stream()))
+    return out
+
+
+def degrade_psf(hr: torch.Tensor, scale: int, psf, noise=(0.0, 0.0), noise_ids=None, gray_noise=False, quant_bits: int = 8) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(lr, hr_cropped) like `degrade_blind` with a general 2-D blur: LR = noise(resize_aa(blur2d(HR))), i.e. `blur2d` on the region
+    cropped to a multiple of the factor, then `degrade_blind` with sigma (0, 0) -- the plain bicubic tables on the blurred values, the
+    same noise and rounding.  What DeviceHRPool(psf=)'s training patches are windows of, bit for bit.  The HR target is not blurred."""
+    if hr.dim() != 4 or not hr.is_cuda:
+        raise ValueError(f"degrade_psf takes a CUDA [B,C,H,W] batch (got {tuple(hr.shape)} on {hr.device})")
+    s = int(scale)
+    if not 2 <= s <= 4:
+        raise ValueError(f"degrade_psf: the factor must be in 2..4 (got {scale!r})")
+    B, Cc, H, W = hr.shape
+    if H < s or W < s or B < 1 or Cc < 1:
+        raise ValueError(f"degrade_psf: {tuple(hr.shape)} is smaller than one output pixel at factor {s}")
+    hr = hr[..., :H - H % s, :W - W % s].float().contiguous()
+    lr, _ = degrade_blind(blur2d(hr, psf), s, (0.0, 0.0), noise, list(range(B)) if noise_ids is None else noise_ids, gray_noise, quant_bits)
+    return lr, hr
+
+
 def check_jpeg_quality(q, what: str = "quality") -> int:
     """A JPEG quality as an int in 1..100 (bools, floats with a fraction and anything else raise ValueError)."""
     if isinstance(q, bool) or not isinstance(q, numbers.Real) or q != q or int(q) != q or not 1 <= int(q) <= 100:          # q != q: NaN

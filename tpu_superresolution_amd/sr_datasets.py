@@ -7,6 +7,7 @@ Pairs are matched by stem; ``transform_pair(lr_pil, hr_pil) -> (lr_tensor, hr_te
 """
 from __future__ import annotations
 
+import math
 import random
 import re
 from dataclasses import dataclass
@@ -404,6 +405,100 @@ class JpegSpec:
         return round((self.quality[0] + self.quality[1]) / 2)
 
 
+PSF_MODES = ("rotated", "mixed", "file")
+PSF_SIGMA_FLOOR = 1e-3          # a sigma of 0 (no blur on that axis) as a Gaussian: every tap off the axis underflows to 0
+
+
+@dataclass(frozen=True)
+class PsfSpec:
+    """The 2-D blur of `--blur_kernel rotated|mixed` / `--blur_psf FILE`: per training sample one ks x ks table
+    (blur_kernels) in place of the axis-aligned Gaussian.  It takes the (sigma_y, sigma_x) that `DegradeSpec.draw` produced -- as
+    (s2, s1): at theta = 0 the table is the separable path's Gaussian -- and draws the rest from its OWN generator
+    `random.Random(f"psf:{seed + rank}")`, six variates per sample whatever they decide.
+    `rotated`: a Gaussian, theta uniform in [-pi/2, pi/2), ks = 2 min(ceil(3 max(s1, s2)), 10) + 1.
+    `mixed`: Real-ESRGAN's six kinds {iso, aniso, generalized iso / aniso, plateau iso / aniso} with probabilities `kernel_prob`
+    (iso: s2 = s1), beta uniform in `beta_g` / `beta_p`, an odd ks uniform in `ksize`.
+    `file`: one table, uniformly, of the .npy `file` ([k][k] or [n][k][k]), a measured point-spread function."""
+    mode: str = "rotated"
+    kernel_prob: Tuple[float, ...] = (0.45, 0.25, 0.12, 0.03, 0.12, 0.03)
+    beta_g: Tuple[float, float] = (0.5, 4.0)
+    beta_p: Tuple[float, float] = (1.0, 2.0)
+    ksize: Tuple[int, int] = (7, 21)
+    file: Optional[str] = None
+    seed: int = 0
+
+    def __post_init__(self):
+        from . import blur_kernels as bk
+        if self.mode not in PSF_MODES:
+            raise ValueError(f"psf mode must be one of {PSF_MODES} (got {self.mode!r})")
+        try:
+            prob = tuple(float(v) for v in self.kernel_prob)
+        except (TypeError, ValueError):
+            raise ValueError(f"kernel_prob must be six numbers (got {self.kernel_prob!r})") from None
+        if len(prob) != 6 or not all(0.0 <= v <= 1.0 for v in prob) or abs(sum(prob) - 1.0) > 1e-6:
+            raise ValueError(f"kernel_prob must be six probabilities that sum to 1 (got {self.kernel_prob!r})")
+        object.__setattr__(self, "kernel_prob", prob)
+        for name in ("beta_g", "beta_p"):
+            try:
+                lo, hi = (float(v) for v in getattr(self, name))
+            except (TypeError, ValueError):
+                raise ValueError(f"{name} must be two numbers LO HI (got {getattr(self, name)!r})") from None
+            if not 0.0 < lo <= hi <= 16.0:          # also refuses NaN
+                raise ValueError(f"{name} must satisfy 0 < LO <= HI <= 16 (got {lo} {hi})")
+            object.__setattr__(self, name, (lo, hi))
+        try:
+            lo, hi = self.ksize
+            lo, hi = bk.check_ks(lo), bk.check_ks(hi)
+        except (TypeError, ValueError):
+            raise ValueError(f"ksize must be two odd integers LO HI in 1..{bk.KS_MAX} (got {self.ksize!r})") from None
+        if lo > hi:
+            raise ValueError(f"ksize must satisfy LO <= HI (got {lo} {hi})")
+        object.__setattr__(self, "ksize", (lo, hi))
+        if (self.mode == "file") != (self.file is not None):
+            raise ValueError("psf mode 'file' needs file=, and the other modes take none")
+        object.__setattr__(self, "_tables", bk.load_psf_file(self.file) if self.file is not None else None)
+
+    def rng(self, rank: int = 0) -> random.Random:
+        return random.Random(f"psf:{int(self.seed) + int(rank)}")
+
+    @property
+    def tables(self):
+        """The checked tables of `file`, fp32 [n][k][k] (None in the other modes)."""
+        return self._tables
+
+    def draw(self, rng: random.Random, blur):
+        """-> the fp32 table of one sample with blur = (sigma_y, sigma_x); always the same six variates, whatever they decide."""
+        from . import blur_kernels as bk
+        u_kind, u_theta, u_bg, u_bp, u_ks, u_idx = (rng.random() for _ in range(6))
+        if self.mode == "file":
+            return self._tables[min(int(u_idx * len(self._tables)), len(self._tables) - 1)]
+        s2, s1 = (max(float(v), PSF_SIGMA_FLOOR) for v in blur)
+        theta = math.pi * (u_theta - 0.5)
+        if self.mode == "rotated":
+            return bk.gaussian(2 * min(math.ceil(3.0 * max(0.0, *(float(v) for v in blur))), 10) + 1, s1, s2, theta)          # sigma 0: R = 0
+        kind, acc = 5, 0.0
+        for i, pr in enumerate(self.kernel_prob):
+            acc += pr
+            if u_kind < acc:
+                kind = i
+                break
+        lo, hi = self.ksize
+        n = (hi - lo) // 2 + 1
+        ks = lo + 2 * min(int(u_ks * n), n - 1)
+        if kind % 2 == 0:          # the isotropic kinds
+            s2 = s1
+        if kind < 2:
+            return bk.gaussian(ks, s1, s2, theta)
+        if kind < 4:
+            return bk.generalized(ks, s1, s2, theta, self.beta_g[0] + u_bg * (self.beta_g[1] - self.beta_g[0]))
+        return bk.plateau(ks, s1, s2, theta, self.beta_p[0] + u_bp * (self.beta_p[1] - self.beta_p[0]))
+
+    def fixed(self):
+        """Table 0 of `file` (what validation scores); None in the other modes: validation keeps the isotropic midpoints, for which a
+        rotation is moot."""
+        return self._tables[0] if self._tables is not None else None
+
+
 class DeviceHRPool(_DeviceImagePool):
     """Training pairs from HR images only (`--synth_lr`): the pool holds the decoded HR images -- half the device memory of a
     DevicePairPool at x2, no LR files to keep in sync -- and `sample` makes the HR patch AND its antialiased bicubic degradation
@@ -421,10 +516,16 @@ class DeviceHRPool(_DeviceImagePool):
 
     ``jpeg`` (a JpegSpec; None = no such stage, no further launch): the LR batch goes through `ops.jpeg_roundtrip` at one quality per
     sample from the spec's own generator, after the degrade launch and BEFORE the D4 transform, so the block grid is anchored to the
-    patch as cut.  Needs ``quant_bits`` 8: JPEG codes 8-bit images.  `draw` and `draw_degrade` do not see it."""
+    patch as cut.  Needs ``quant_bits`` 8: JPEG codes 8-bit images.  `draw` and `draw_degrade` do not see it.
+
+    ``psf`` (a PsfSpec; None = the axis-aligned Gaussian composed into the cubic tables, today's launch; needs ``degrade``): every
+    sample is blurred with a 2-D table made from the sigmas of its `DegradeSpec.draw` and the PsfSpec's own generator, uploaded as one
+    [B][ks][ks] block, in one `srk_crop_degrade_psf_u8` launch.  The DegradeSpec's draws, `draw` and the global `random` state are the
+    same with and without it."""
 
     def __init__(self, images, lr_patch: int, scale: int, device="cuda", shard_bytes: Optional[int] = None, augment: str = "none",
-                 quant_bits: int = 8, degrade: Optional[DegradeSpec] = None, rank: int = 0, jpeg: Optional[JpegSpec] = None):
+                 quant_bits: int = 8, degrade: Optional[DegradeSpec] = None, rank: int = 0, jpeg: Optional[JpegSpec] = None,
+                 psf: Optional[PsfSpec] = None):
         """images: iterable of HR PIL images or uint8 / uint16 arrays [H,W] / [H,W,1|3]."""
         if augment not in AUGMENT_MODES:
             raise ValueError(f"augment must be one of {AUGMENT_MODES} (got {augment!r})")
@@ -441,6 +542,11 @@ class DeviceHRPool(_DeviceImagePool):
             raise ValueError(f"jpeg= codes 8-bit LR images: it needs quant_bits 8 (got {quant_bits!r})")
         self.degrade, self._degrade_rng = degrade, (degrade.rng(rank) if degrade is not None else None)
         self.jpeg, self._jpeg_rng = jpeg, (jpeg.rng(rank) if jpeg is not None else None)
+        if psf is not None and not isinstance(psf, PsfSpec):
+            raise ValueError(f"psf must be a PsfSpec or None (got {type(psf).__name__})")
+        if psf is not None and degrade is None:
+            raise ValueError("psf= shapes the blur of degrade=: it needs a DegradeSpec")
+        self.psf, self._psf_rng, self._psf_buf = psf, (psf.rng(rank) if psf is not None else None), None
         self.lr_patch, self.scale, self.device = int(lr_patch), int(scale), torch.device(device)
         self._pack(((img,) for img in images), shard_bytes)
 
@@ -466,6 +572,25 @@ class DeviceHRPool(_DeviceImagePool):
         from .ops import pack_degrade_params
         return [tuple(d) + tuple(pack_degrade_params(*self.degrade.draw(self._degrade_rng, colour=(d[3] & 0xff) == 3))) for d in hd]
 
+    def draw_psf(self, hd):
+        """(ten-slot descriptors, fp32 numpy [B][ks][ks], ks) of a batch: `draw_degrade`'s draws, in its order, plus one `PsfSpec.draw`
+        per sample on the sigmas of that sample; slot 6 keeps the sigmas, which the PSF entry ignores."""
+        from .ops import pack_degrade_params, pack_psf
+        rows, tabs = [], []
+        for d in hd:
+            drawn = self.degrade.draw(self._degrade_rng, colour=(d[3] & 0xff) == 3)
+            rows.append(tuple(d) + tuple(pack_degrade_params(*drawn)))
+            tabs.append(self.psf.draw(self._psf_rng, drawn[0]))
+        return (rows,) + pack_psf(tabs, len(tabs), checked=True)
+
+    def _psf_upload(self, tabs) -> torch.Tensor:
+        """The batch's tables in the pool's device buffer (grown when a batch is larger than any before): one copy."""
+        n = tabs.size
+        if self._psf_buf is None or self._psf_buf.numel() < n:
+            self._psf_buf = torch.empty(max(n, 32 * 21 * 21), dtype=torch.float32, device=self.device)
+        self._psf_buf[:n].copy_(torch.from_numpy(tabs).reshape(-1))
+        return self._psf_buf
+
     def sample(self, indices):
         """-> (lr [B,3,P,P], hr [B,3,P*s,P*s]) fp32 on the device."""
         from ._lib import check, lib
@@ -473,12 +598,21 @@ class DeviceHRPool(_DeviceImagePool):
         pool = self._batch_pool(indices)
         hd, codes = self.draw(indices)
         B = len(hd)
-        desc = torch.tensor(hd if self.degrade is None else self.draw_degrade(hd), dtype=torch.int64).to(self.device)
+        tabs = None
+        if self.psf is not None:
+            rows, tabs, ks = self.draw_psf(hd)
+        else:
+            rows = hd if self.degrade is None else self.draw_degrade(hd)
+        desc = torch.tensor(rows, dtype=torch.int64).to(self.device)
         lr = torch.empty(B, 3, P, P, dtype=torch.float32, device=self.device)
         hr = torch.empty(B, 3, P * s, P * s, dtype=torch.float32, device=self.device)
         st = torch.cuda.current_stream(self.device).cuda_stream
-        entry = lib().srk_crop_degrade_u8 if self.degrade is None else lib().srk_crop_degrade_blind_u8
-        check(entry(pool.data_ptr(), desc.data_ptr(), lr.data_ptr(), hr.data_ptr(), B, P, s, self.quant_bits, st))
+        if tabs is not None:
+            check(lib().srk_crop_degrade_psf_u8(pool.data_ptr(), desc.data_ptr(), self._psf_upload(tabs).data_ptr(), ks, lr.data_ptr(),
+                                                hr.data_ptr(), B, P, s, self.quant_bits, st))
+        else:
+            entry = lib().srk_crop_degrade_u8 if self.degrade is None else lib().srk_crop_degrade_blind_u8
+            check(entry(pool.data_ptr(), desc.data_ptr(), lr.data_ptr(), hr.data_ptr(), B, P, s, self.quant_bits, st))
         if self.jpeg is not None:
             from .ops import jpeg_roundtrip
             lr = jpeg_roundtrip(lr, [self.jpeg.draw(self._jpeg_rng) for _ in range(B)], self.jpeg.subsample)
@@ -499,10 +633,21 @@ class SynthLRBatches:
     every run scores the same LR images (ops.degrade_blind).  An image whose three channels are equal gets gray noise.
 
     ``jpeg`` (a quality 1..100 with ``jpeg_subsample``, or a JpegSpec standing for its `fixed()` quality and its subsampling; None =
-    no such stage): the whole degraded LR image goes through `ops.jpeg_roundtrip`, the same every epoch.  Needs ``quant_bits`` 8."""
+    no such stage): the whole degraded LR image goes through `ops.jpeg_roundtrip`, the same every epoch.  Needs ``quant_bits`` 8.
 
-    def __init__(self, loader, scale: int, quant_bits: int, device, degrade=None, jpeg=None, jpeg_subsample: bool = False):
+    ``psf`` (one ks x ks table, or a PsfSpec standing for its `fixed()` table -- table 0 of a PSF file, None otherwise; needs
+    ``degrade``): the table replaces the Gaussian of ``degrade`` (ops.degrade_psf); the noise stays."""
+
+    def __init__(self, loader, scale: int, quant_bits: int, device, degrade=None, jpeg=None, jpeg_subsample: bool = False, psf=None):
         self.loader, self.scale, self.quant_bits, self.device = loader, int(scale), int(quant_bits), torch.device(device)
+        if isinstance(psf, PsfSpec):
+            psf = psf.fixed()
+        if psf is not None:
+            from .blur_kernels import check_table
+            if degrade is None:
+                raise ValueError("psf= shapes the blur of degrade=: it needs a FixedDegrade or a DegradeSpec")
+            psf = check_table(psf)
+        self.psf = psf
         if isinstance(jpeg, JpegSpec):
             jpeg, jpeg_subsample = jpeg.fixed(), jpeg.subsample
         if jpeg is not None:
@@ -525,7 +670,7 @@ class SynthLRBatches:
             yield (lr if self.jpeg is None else jpeg_roundtrip(lr, self.jpeg, self.jpeg_subsample)), hr
 
     def _degraded(self):
-        from .ops import degrade_aa, degrade_blind
+        from .ops import degrade_aa, degrade_blind, degrade_psf
         first = 0
         for hr in self.loader:
             hr = hr.to(self.device, dtype=torch.float32)
@@ -536,5 +681,8 @@ class SynthLRBatches:
             gray = [True] * B
             if hr.shape[1] == 3 and not self.degrade.gray_noise:
                 gray = ((hr[:, 0] == hr[:, 1]) & (hr[:, 0] == hr[:, 2])).flatten(1).all(dim=1).tolist()
-            yield degrade_blind(hr, self.scale, self.degrade.blur, self.degrade.noise, range(first, first + B), gray, self.quant_bits)
+            if self.psf is not None:
+                yield degrade_psf(hr, self.scale, self.psf, self.degrade.noise, range(first, first + B), gray, self.quant_bits)
+            else:
+                yield degrade_blind(hr, self.scale, self.degrade.blur, self.degrade.noise, range(first, first + B), gray, self.quant_bits)
             first += B
