@@ -354,6 +354,37 @@ int srk_crop_degrade_psf_u8(const uint8_t* pool, const int64_t* desc10, const fl
  * size that does not fit one launch. */
 int srk_jpeg_roundtrip_f32(const float* x, float* out, const int32_t* quality, int B, int C, int H, int W, int subsample, int16_t* coef_out,
                            srk_stream_t stream);
+/* Scale-1 restoration (csrc/restore.hip): denoising and JPEG-artifact pairs.  "clean" is the target, "degraded" the network input;
+ * both have the same size.  degraded = jpeg_roundtrip(noise(convert(image))): the noise stage of the blind degradation and the JPEG
+ * round trip above, with no resize in between.  Parameters are slots 6..9 as above, except that slot 6 carries no blur.
+ *
+ * srk_noise_f32: x fp32 [B][C][H][W] -> out of the same shape, C = 1 or 3; par4 DEVICE int64 [B][4] = slots 6..9, slot 6 ignored.
+ * out = the noise formula of srk_degrade_blind_f32 per element (the same device routine), counter (x, y, ch, 0) on IMAGE coordinates,
+ * ch = 0 with gray noise, which a one-channel image always gets; key = noise_id.  sigma_n == 0 && gain == 0: the bits of x pass
+ * through.  quant_bits 0 | 8 as srk_resize_aa_f32.  out must not overlap x.  One launch, no device allocation; nothing outside
+ * out[0 .. B*C*H*W) is written.  SRK_E_NULL: a null pointer; SRK_E_SHAPE: a non-positive extent, C not 1 or 3, quant_bits other than
+ * 0 / 8, x and out overlapping, a size that does not fit one launch. */
+int srk_noise_f32(const float* x, float* out, const int64_t* par4, int B, int C, int H, int W, int quant_bits, srk_stream_t stream);
+/* Training pairs at scale 1, ONE launch for the batch.  pool and slots 0..5 of desc10 as srk_crop_degrade_u8: {byte offset, H, W,
+ * C | (wide << 8), top, left}; top and left are ANY image pixels with top + patch <= H and left + patch <= W (the caller checks; the
+ * kernel does not, it only keeps its loads inside the image).  Slot 6: low word = JPEG quality as int32, 0 = no JPEG stage, any other
+ * bit pattern is clamped into 0..100 as srk_jpeg_roundtrip_f32 does; slots 7..9 = sigma_n / gain, noise_id, flags as above.
+ * clean_out, degraded_out: fp32 [B][out_chans][patch][patch], out_chans = 1 or 3.
+ * Conversion: stored sample / 255 (/ 65535 when wide) in IEEE fp32, as srk_paired_crop_u8.  out_chans 3: a gray source is repeated -- it
+ * gets one noise draw and is coded as a gray JPEG written three times.  out_chans 1: a gray source as is; an RGB source becomes the
+ * integer luma (4899 R + 9617 G + 1868 B + 8192) >> 14 of the stored samples, u8 or u16 alike (the coefficients sum to 16384, the sum
+ * fits 32 bits), which is then divided as above.  clean_out is the converted window and nothing else.
+ * degraded_out is the window at (top, left) of the WHOLE-IMAGE chain: noise keyed on image coordinates; 8 x 8 blocks (16 x 16 MCUs
+ * with subsample) anchored at the IMAGE's (0, 0), the image extended by replicating its last row and column, and the noise of a
+ * replicated pixel is that of the pixel it replicates.  It is BIT-IDENTICAL to the same window of srk_noise_f32 followed, where the
+ * quality is > 0, by srk_jpeg_roundtrip_f32 on the whole converted image (the entries share their device routines).  Quality 0
+ * stores the noised (with quant_bits 8: rounded) values; with a quality > 0 the level step of the round trip does the rounding and
+ * quant_bits has no further effect.  subsample has effect only when three distinct planes are coded (out_chans 3, RGB source).
+ * No device allocation, no intermediate image; nothing outside the two outputs is written.
+ * SRK_E_NULL: a null pointer; SRK_E_SHAPE: B outside 1..65535, patch outside 1..2048, out_chans not 1 or 3, subsample not 0 or 1,
+ * quant_bits other than 0 / 8, the two outputs overlapping. */
+int srk_crop_restore_u8(const uint8_t* pool, const int64_t* desc10, float* clean_out, float* degraded_out, int B, int patch, int out_chans,
+                        int subsample, int quant_bits, srk_stream_t stream);
 /* Tiled inference (csrc/tile.hip): crop a chunk of overlapping tiles out of an fp32 NCHW batch, run a model on them as a batch of
  * n * B, and merge the chunk's outputs into the output image.
  * Tile grid, per axis with extent N, tile t (1 <= t <= N) and stride s (1 <= s <= t; overlap = t - s): k = ceil((N - t) / s) + 1

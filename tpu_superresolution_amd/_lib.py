@@ -113,6 +113,8 @@ _SIGNATURES = {
     "srk_blur2d_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "srk_crop_degrade_psf_u8": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "srk_jpeg_roundtrip_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "srk_noise_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "srk_crop_restore_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "srk_tile_gather_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "srk_tile_merge_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "srk_batch_psnr_workspace": (_i64, [_i64, _i]),

@@ -586,6 +586,29 @@ int srk_jpeg_roundtrip_f32(const float* x, float* out, const int32_t* quality, i
                                        (hipStream_t)stream);
 }
 
+int srk_noise_f32(const float* x, float* out, const int64_t* par4, int B, int C, int H, int W, int quant_bits, srk_stream_t stream) {
+  REQ_PTR(x); REQ_PTR(out); REQ_PTR(par4);
+  SRK_REQUIRE(srk_noise_shape_ok(B, C, H, W), SRK_E_SHAPE, "noise: B=%d H=%d W=%d must all be >= 1, C=%d must be 1 or 3, and the size must fit one launch",
+              B, H, W, C);
+  SRK_REQUIRE(srk_quant_bits_ok(quant_bits), SRK_E_SHAPE, "noise: quant_bits must be 0 or 8 (got %d)", quant_bits);
+  const size_t bytes = (size_t)(4.0 * B * C * H * W);
+  SRK_REQUIRE(!srk_ranges_overlap(x, bytes, out, bytes), SRK_E_SHAPE, "noise: x and out overlap (the stage is not run in place)");
+  return srk_launch_noise_f32(x, out, reinterpret_cast<const long long*>(par4), B, C, H, W, quant_bits, (hipStream_t)stream);
+}
+
+int srk_crop_restore_u8(const uint8_t* pool, const int64_t* desc10, float* clean_out, float* degraded_out, int B, int patch, int out_chans,
+                        int subsample, int quant_bits, srk_stream_t stream) {
+  REQ_PTR(pool); REQ_PTR(desc10); REQ_PTR(clean_out); REQ_PTR(degraded_out);
+  SRK_REQUIRE(srk_crop_restore_shape_ok(B, patch, out_chans), SRK_E_SHAPE, "crop_restore: B=%d (1..65535) patch=%d (1..2048) out_chans=%d (1 or 3)", B,
+              patch, out_chans);
+  SRK_REQUIRE(srk_flag01_ok(subsample), SRK_E_SHAPE, "crop_restore: subsample must be 0 (4:4:4) or 1 (4:2:0) (got %d)", subsample);
+  SRK_REQUIRE(srk_quant_bits_ok(quant_bits), SRK_E_SHAPE, "crop_restore: quant_bits must be 0 or 8 (got %d)", quant_bits);
+  const size_t bytes = sizeof(float) * (size_t)B * out_chans * patch * patch;          // <= 4 * 65535 * 3 * 2048^2 < 2^42
+  SRK_REQUIRE(!srk_ranges_overlap(clean_out, bytes, degraded_out, bytes), SRK_E_SHAPE, "crop_restore: clean_out and degraded_out overlap");
+  return srk_launch_crop_restore_u8(pool, reinterpret_cast<const long long*>(desc10), clean_out, degraded_out, B, patch, out_chans, subsample,
+                                    quant_bits, (hipStream_t)stream);
+}
+
 // the checks srk_tile_gather_f32 and srk_tile_merge_f32 share; img is x or out, whichever the tiles must not overlap
 static int tile_args(const char* fn, const float* tiles, const float* img, int t0, int n, int B, int C, int H, int W, int th, int tw,
                      int sy, int sx, TileAxis* ay, TileAxis* ax) {

@@ -123,6 +123,16 @@ static inline bool srk_blur2d_shape_ok(int B, int C, int H, int W) {
 static inline bool srk_crop_degrade_shape_ok(int B, int lr_patch, int scale) {
   return B > 0 && B <= 65535 && lr_patch > 0 && lr_patch <= 2048 && scale >= 2 && scale <= 4;
 }
+// scale-1 restoration (restore.hip, srk.h "Scale-1 restoration"): the shapes srk_noise_f32 takes (the planes index an int, the bytes stay
+// below 2^63), and the batch shapes and switches of srk_crop_restore_u8
+static inline bool srk_noise_shape_ok(int B, int C, int H, int W) {
+  return B > 0 && (C == 1 || C == 3) && H > 0 && W > 0 && (double)B * C <= 2147483647.0 && 4.0 * B * C * H * W < 9.0e18;
+}
+static inline bool srk_crop_restore_shape_ok(int B, int patch, int out_chans) {
+  return B > 0 && B <= 65535 && patch > 0 && patch <= 2048 && (out_chans == 1 || out_chans == 3);
+}
+static inline bool srk_flag01_ok(int v) { return v == 0 || v == 1; }
+static inline bool srk_quant_bits_ok(int v) { return v == 0 || v == 8; }
 
 // ---------------------------------------------------------------------------------------------
 // bf16 helpers (device)

@@ -77,6 +77,10 @@ int srk_launch_crop_degrade_psf_u8(const unsigned char* pool, const long long* d
 // jpeg.hip: the closed-form JPEG round trip at a per-sample quality (arguments checked by srk_jpeg_roundtrip_f32)
 int srk_launch_jpeg_roundtrip_f32(const float* x, float* out, const int* quality, int B, int C, int H, int W, int subsample, short* coef_out,
                                   hipStream_t stream);
+// restore.hip: the whole-image noise stage and the scale-1 training pairs (arguments checked by srk_noise_f32 / srk_crop_restore_u8)
+int srk_launch_noise_f32(const float* x, float* out, const long long* par, int B, int C, int H, int W, int quant_bits, hipStream_t stream);
+int srk_launch_crop_restore_u8(const unsigned char* pool, const long long* desc, float* clean_out, float* degraded_out, int B, int P,
+                               int out_chans, int subsample, int quant_bits, hipStream_t stream);
 // tile.hip: tiled inference (arguments checked by srk_tile_gather_f32 / srk_tile_merge_f32).  One axis of the tile grid: extent n,
 // tile t (1 <= t <= n), stride s (1 <= s <= t), k = ceil((n - t) / s) + 1 tiles, origin o_i = min(i * s, n - t)
 struct TileAxis { int n, t, s, k; };

@@ -21,6 +21,8 @@ DESIGN 7n); ``main(argv)`` is callable from tests.  SSIM is ``metrics.ssim`` (re
 ``--bench_metric y | rgb [--crop_border N]`` (any --arch, any of the options above: it looks at (pred, hr) only) adds ``[bench]`` lines
 and ``bench_*`` keys with the scores of the papers' protocol -- 8-bit, border-cropped (default: the scale), BT.601 luma or RGB, 0..255
 scale, mean over images (metrics.bench_metrics); the other lines and keys stay as they are.
+``--task dn | car --scale X1 --arch swinir [--channels 1|3 --dn_sigma S --jpeg_quality Q]`` scores the scale-1 restoration models: the clean test
+images are noised / JPEG-coded as whole images on the device (ops.restore_degrade) and the baseline line is the degraded input itself.
 """
 from __future__ import annotations
 
@@ -76,7 +78,8 @@ def _load_state(path: str, param_key: str = "auto"):
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scale", type=str, choices=["X2", "X4"], required=True, help="dataset configuration")
+    ap.add_argument("--scale", type=str, choices=["X1", "X2", "X4"], required=True,
+                    help="dataset configuration; X1 (input and target of one size) with --task dn | car")
     ap.add_argument("--data_root", type=str, default="DeepRockSR-2D")
     ap.add_argument("--batch_size", type=int, default=4)
     ap.add_argument("--workers", type=int, default=0)
@@ -91,7 +94,19 @@ def parse_args(argv=None):
     ap.add_argument("--param_key", type=str, choices=["auto", *PARAM_KEYS], default="auto",
                     help="additive: which envelope of the checkpoint to load (auto: model, then params, then params_ema)")
     ap.add_argument("--device", type=str, default=None, help="additive: force 'cpu' / 'cuda' (default: cuda if available)")
-    ap.add_argument("--window_size", type=int, default=8, help="additive, --arch swinir: SwinIR(window_size=N), N in 2..8")
+    ap.add_argument("--window_size", type=int, default=None,
+                    help="additive, --arch swinir: SwinIR(window_size=N), N in 2..8 (default: 8, or 7 with --task car)")
+    ap.add_argument("--task", type=str, choices=["sr", "dn", "car"], default="sr",
+                    help="additive, --arch swinir: dn = denoising, car = JPEG compression-artifact reduction -- the published scale-1 "
+                         "models (finetune_swinir.build_restoration_model), scored from the HR directory of the test split alone: each "
+                         "image is degraded on the device as a whole (ops.restore_degrade; the noise id of an image is its index in the "
+                         "split) and the baseline is the degraded input itself.  They need --scale X1")
+    ap.add_argument("--channels", type=int, choices=[1, 3], default=3,
+                    help="additive, with --task dn | car: 3 = colour, 1 = gray (an RGB file becomes its integer BT.601 luma, ops.to_gray)")
+    ap.add_argument("--dn_sigma", type=float, default=None, metavar="S",
+                    help="additive, with --task dn (required) | car: the Gaussian noise sigma on the 0..255 scale of the papers (15 / 25 / 50)")
+    ap.add_argument("--dn_bits", type=int, choices=[0, 8], default=0,
+                    help="additive, with --task dn | car: 0 = the noisy input is neither clipped nor rounded, 8 = rounded to k / 255")
     ap.add_argument("--self_ensemble", action="store_true",
                     help="additive: predict with the x8 self-ensemble (the '+' of SwinIR+ / HAT+ / DAT+): the mean of the eight "
                          "inverse-transformed predictions on the flipped / rotated inputs (augment.self_ensemble)")
@@ -133,6 +148,32 @@ def parse_args(argv=None):
     ap.add_argument("--crop_border", type=int, default=None, metavar="N",
                     help="additive, with --bench_metric: pixels cropped on every side before scoring (default: the scale)")
     args = ap.parse_args(argv)
+    if args.window_size is None:
+        args.window_size = 7 if args.task == "car" else 8
+    if args.task == "sr":
+        if args.scale == "X1":
+            ap.error("--scale X1 is the scale of --task dn | car; --task sr takes X2 | X4")
+        if args.channels != 3 or args.dn_sigma is not None or args.dn_bits != 0:
+            ap.error("--channels, --dn_sigma and --dn_bits are options of --task dn | car")
+    else:
+        if args.scale != "X1":
+            ap.error(f"--task {args.task} restores at one size: it needs --scale X1 (got {args.scale})")
+        if args.arch != "swinir":
+            ap.error(f"--task {args.task} is built for --arch swinir only (HAT and DAT end in a pixel-shuffle tail; got --arch {args.arch})")
+        if args.synth_lr or args.degrade != "bicubic":
+            ap.error(f"--synth_lr and --degrade form LR images for --task sr; --task {args.task} degrades at scale 1 on its own")
+        if args.task == "dn" and args.dn_sigma is None:
+            ap.error("--task dn needs --dn_sigma S (0..255 scale, e.g. 25)")
+        if args.task == "dn" and args.jpeg_quality is not None:
+            ap.error("--jpeg_quality with noise is --task car --dn_sigma S; --task dn has no JPEG stage")
+        if args.task == "car" and args.jpeg_quality is None:
+            ap.error("--task car needs --jpeg_quality Q")
+        if args.bench_metric is not None and args.channels == 1:
+            ap.error("--bench_metric is not offered with --channels 1 (the benchmark-protocol scores take RGB predictions)")
+        try:
+            eval_restore(args)
+        except ValueError as e:
+            ap.error(f"--task {args.task}: {e}")
     if args.crop_border is not None:
         if args.bench_metric is None:
             ap.error("--crop_border is an option of the benchmark-protocol scores: it needs --bench_metric y | rgb")
@@ -159,7 +200,7 @@ def parse_args(argv=None):
     if args.jpeg_quality is None:
         if args.jpeg_subsample != "444":
             ap.error("--jpeg_subsample is an option of the JPEG stage: it needs --jpeg_quality Q")
-    else:
+    elif args.task == "sr":
         if not args.synth_lr:
             ap.error("--jpeg_quality codes the LR images formed on the device: it needs --synth_lr")
         if args.synth_lr_bits != 8:
@@ -172,6 +213,17 @@ def parse_args(argv=None):
     if not 2 <= args.window_size <= 8 or (args.window_size != 8 and args.arch != "swinir"):
         ap.error(f"--window_size must be in 2..8 and is an option of --arch swinir (got {args.window_size} with --arch {args.arch})")
     return args
+
+
+def eval_restore(args):
+    """The FixedRestore of the command line (None for --task sr); --dn_sigma is given on the 0..255 scale."""
+    if args.task == "sr":
+        return None
+    from .ops import pack_restore_params
+    from .sr_datasets import FixedRestore
+    fx = FixedRestore((args.dn_sigma or 0.0) / 255.0, args.jpeg_quality or 0, False, args.jpeg_subsample == "420")
+    pack_restore_params(fx.jpeg_quality, (fx.sigma, 0.0), 0, False)          # the ranges
+    return fx
 
 
 def eval_psf(args):
@@ -200,20 +252,31 @@ def main(argv=None):
     swin = args.arch in ("swinir", "hat", "dat")
     if swin and device.type != "cuda":
         raise SystemExit(f"--arch {args.arch} runs on the MI355X HIP path only (no CPU fallback)")
-    scale_int = 2 if args.scale.upper() == "X2" else 4
+    scale_int = {"X1": 1, "X2": 2, "X4": 4}[args.scale.upper()]
+    restore = args.task != "sr"
 
     if swin:
         from .sr_datasets import PairTransformValid
         tf_test = PairTransformValid(scale_int)
     else:
         tf_test = build_pair_transform_eval()
-    if args.synth_lr:
+    if restore:
+        from functools import partial
+
+        from .sr_datasets import RestoreBatches, Shuffled2DHR, clean_to_tensor
+        test_ds = Shuffled2DHR(args.data_root, split="test", transform=partial(clean_to_tensor, out_chans=args.channels))
+    elif args.synth_lr:
         from .sr_datasets import Shuffled2DHR, SynthLRBatches, hr_to_tensor3
         test_ds = Shuffled2DHR(args.data_root, split="test", transform=hr_to_tensor3)
     else:
         test_ds = Shuffled2DPaired(args.data_root, split="test", scale=args.scale, transform_pair=tf_test)
     test_loader = DataLoader(test_ds, batch_size=args.batch_size, shuffle=False, num_workers=args.workers,
                              pin_memory=(device.type == "cuda"), persistent_workers=False)
+    if restore:          # (degraded, clean) batches formed on the device
+        fx = eval_restore(args)
+        test_loader = RestoreBatches(test_loader, args.channels, fx, args.dn_bits, device)
+        print(f"[task {args.task}] {args.channels} channel(s); degraded = whole image on the device: noise sigma={fx.sigma * 255.0:.4g} / 255 "
+              f"({args.dn_bits or 'no'}-bit rounding), jpeg quality {fx.jpeg_quality or 'none'} chroma {args.jpeg_subsample}, noise id = image index")
     if args.synth_lr:          # (lr, hr) batches formed on the device, before the peek, the baseline and the prediction loop
         fixed = None
         if args.degrade == "blind":
@@ -264,7 +327,8 @@ def main(argv=None):
                 bp, bs = bench_metrics(up, hr, border, args.bench_metric)
                 bench_bic_ps.append(bp)
                 bench_bic_ss.append(bs)
-    print(f"[baseline] Bicubic PSNR: {sum(ps) / len(ps):.2f} dB | SSIM: {sum(ss) / len(ss):.4f}")
+    base_name = "Degraded input" if restore else "Bicubic"          # at scale 1 the baseline is the degraded input itself
+    print(f"[baseline] {base_name} PSNR: {sum(ps) / len(ps):.2f} dB | SSIM: {sum(ss) / len(ss):.4f}")
     more = {}
     if bench:
         tag = args.bench_metric.upper()
@@ -276,11 +340,12 @@ def main(argv=None):
             print(f"[bench] {what}PSNR-{tag}: {mp:.2f} dB | SSIM-{tag}: {ms:.4f} (8-bit, border {border}, mean over {p_all.numel()} images)")
             return mp, ms
 
-        more["bench_bicubic_psnr"], more["bench_bicubic_ssim"] = bench_line("Bicubic ", bench_bic_ps, bench_bic_ss)
+        more["bench_bicubic_psnr"], more["bench_bicubic_ssim"] = bench_line(base_name + " ", bench_bic_ps, bench_bic_ss)
 
     if swin:
-        from .finetune_swinir import build_sr_model
-        model = build_sr_model(args.arch, scale_int, drop_path_rate=0.0, window_size=args.window_size)
+        from .finetune_swinir import build_restoration_model, build_sr_model
+        model = (build_restoration_model(args.task, args.channels, 0.0, args.window_size) if restore else
+                 build_sr_model(args.arch, scale_int, drop_path_rate=0.0, window_size=args.window_size))
     else:
         model = MS_ResUNet()
     state, msg = _load_state(args.ckpt, args.param_key)

@@ -19,6 +19,9 @@ csrc/loss.hip (training.make_loss); with W > 0 validation also reports the mean 
 bicubic downscale of its HR image, made on the device (sr_datasets.DeviceHRPool, csrc/resize.hip); no LR directory is read.
 `--degrade blind [--blur_sigma LO HI --noise_sigma LO HI ...]` blurs and noises every such patch with random parameters in the same
 launch (csrc/degrade.hip); validation uses the midpoints of the ranges and the same noise every epoch.
+`--task dn|car --scale X1 [--channels 1|3 --dn_sigma LO HI --dn_bits 0|8]` trains the published scale-1 SwinIR models (denoising; JPEG
+compression-artifact reduction with --jpeg_quality LO HI) from the HR directories alone: every patch is cut at any image pixel and is the
+window of the whole-image degradation, JPEG blocks anchored at the image's (0, 0) (sr_datasets.DeviceRestorePool, csrc/restore.hip).
 `--jpeg_quality LO HI [--jpeg_p P --jpeg_subsample 444|420]` (with either --degrade) sends every 8-bit LR patch through a baseline JPEG
 round trip at a random per-sample quality in a second launch (csrc/jpeg.hip); validation uses the middle of the range.
 `--blur_kernel rotated|mixed` or `--blur_psf FILE` (with --degrade blind) blurs every patch with a 2-D table -- a rotated, generalized or
@@ -192,6 +195,27 @@ def build_model(scale_int: int, drop_path_rate: float = 0.1, window_size: int = 
                   drop_path_rate=drop_path_rate)
 
 
+RESTORATION_TASKS = {"dn": dict(window_size=8, img_size=128, img_range=1.0), "car": dict(window_size=7, img_size=126, img_range=255.0)}
+SCALES = {"X1": 1, "X2": 2, "X4": 4}
+
+
+def build_restoration_model(task: str, channels: int = 3, drop_path_rate: float = 0.1, window_size: int = None) -> SwinIR:
+    """The published scale-1 SwinIR configurations: 'dn' (gray / colour denoising: window 8, img_size 128, img_range 1) and 'car' (JPEG
+    compression-artifact reduction: window 7, img_size 126, img_range 255); upscale 1, upsampler '', in_chans = channels (1 | 3).
+    window_size: None = the task's; another window rounds img_size -- which only sizes the attn_mask buffers -- down to its multiple."""
+    if task not in RESTORATION_TASKS:
+        raise ValueError(f"task must be one of {tuple(RESTORATION_TASKS)} (got {task!r})")
+    if channels not in (1, 3):
+        raise ValueError(f"channels must be 1 or 3 (got {channels!r})")
+    cfg = RESTORATION_TASKS[task]
+    ws = cfg["window_size"] if window_size is None else int(window_size)
+    if not 2 <= ws <= 8:
+        raise ValueError(f"window_size must be in 2..8 (got {window_size!r})")
+    return SwinIR(upscale=1, in_chans=channels, img_size=cfg["img_size"] // ws * ws, window_size=ws, img_range=cfg["img_range"],
+                  depths=[6] * 6, embed_dim=180, num_heads=[6] * 6, mlp_ratio=2, upsampler="", resi_connection="1conv",
+                  drop_path_rate=drop_path_rate)
+
+
 def build_sr_model(arch: str, scale_int: int, drop_path_rate: float = 0.1, window_size: int = 8):
     """The transformer SR models of modules/ at their published x2 / x4 hyper-parameters, on the HIP path: 'swinir'
     (finetune_swinir.py:269-281), 'hat' (HAT-SRx4 configuration of hat_arch.py's constructor defaults: window 16, overlap 0.5, CAB),
@@ -215,7 +239,8 @@ def build_sr_model(arch: str, scale_int: int, drop_path_rate: float = 0.1, windo
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--data_root", type=str, required=True)
-    ap.add_argument("--scale", type=str, choices=["X2", "X4"], required=True)
+    ap.add_argument("--scale", type=str, choices=["X1", "X2", "X4"], required=True,
+                    help="X2 | X4 with --task sr; X1 (input and target of one size) with --task dn | car")
     ap.add_argument("--weights", type=str, default=None, help="Path to SwinIR pretrained checkpoint (.pth/.pt)")
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--batch_size", type=int, default=8, help="per-process batch size")
@@ -246,9 +271,9 @@ def parse_args(argv=None):
     ap.add_argument("--ema_decay", type=float, default=0.0,
                     help="additive: keep an exponential moving average of the weights inside the fused optimizer step (0 = off; "
                          "published recipes use 0.999); validation runs on it and checkpoints gain 'params_ema'")
-    ap.add_argument("--window_size", type=int, default=8,
+    ap.add_argument("--window_size", type=int, default=None,
                     help="additive, --arch swinir: build SwinIR(window_size=N); 2..7 train through enable_small_window_training() "
-                         "(7 is the window of the published JPEG-artifact models) and allow --graph")
+                         "(7 is the window of the published JPEG-artifact models) and allow --graph.  Default: 8, or 7 with --task car")
     ap.add_argument("--augment", type=str, choices=["none", "flip", "d4"], default="none",
                     help="additive: training augmentation by the symmetries of the square, one drawn per sample after its crop corners "
                          "and applied to LR and HR alike (validation is never augmented).  flip: horizontal and vertical flip, each "
@@ -320,7 +345,49 @@ def parse_args(argv=None):
     ap.add_argument("--blur_psf", type=str, default=None, metavar="FILE",
                     help="additive, with --degrade blind: a measured point-spread function, .npy [k][k] or [n][k][k] (k odd <= 21, taps >= 0 "
                          "summing to 1); every training patch is blurred with one of its tables, validation with table 0")
+    ap.add_argument("--task", type=str, choices=["sr", "dn", "car"], default="sr",
+                    help="additive: sr = super-resolution (as ever); dn = denoising, car = JPEG compression-artifact reduction: the published "
+                         "scale-1 SwinIR models (build_restoration_model), trained from the HR directories alone -- every patch is cut at "
+                         "any image pixel and degraded on the device as a window of the whole-image degradation (sr_datasets."
+                         "DeviceRestorePool, csrc/restore.hip).  They need --scale X1 and imply --gpu_data")
+    ap.add_argument("--channels", type=int, choices=[1, 3], default=3,
+                    help="additive, with --task dn | car: 3 = colour, 1 = gray (an RGB file becomes its integer BT.601 luma, ops.to_gray)")
+    ap.add_argument("--dn_sigma", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="additive, with --task dn (required) | car: range of the Gaussian noise sigma on the 0..255 scale of the papers "
+                         "(15 / 25 / 50; divided by 255); validation uses the midpoint")
+    ap.add_argument("--dn_bits", type=int, choices=[0, 8], default=0,
+                    help="additive, with --task dn | car: 0 = the noisy input is neither clipped nor rounded, as the published training has "
+                         "it; 8 = rounded to k / 255")
     args = ap.parse_args(argv)
+    if args.window_size is None:
+        args.window_size = RESTORATION_TASKS[args.task]["window_size"] if args.task != "sr" else 8
+    if args.task == "sr":
+        if args.scale == "X1":
+            ap.error("--scale X1 is the scale of --task dn | car; --task sr takes X2 | X4")
+        if args.channels != 3 or args.dn_sigma is not None or args.dn_bits != 0:
+            ap.error("--channels, --dn_sigma and --dn_bits are options of --task dn | car")
+    else:
+        if args.scale != "X1":
+            ap.error(f"--task {args.task} restores at one size: it needs --scale X1 (got {args.scale})")
+        if args.arch != "swinir":
+            ap.error(f"--task {args.task} is built for --arch swinir only (HAT and DAT end in a pixel-shuffle tail; got --arch {args.arch})")
+        if args.synth_lr or args.degrade != "bicubic":
+            ap.error(f"--synth_lr and --degrade form LR images for --task sr; --task {args.task} degrades at scale 1 on its own")
+        if args.task == "dn" and args.dn_sigma is None:
+            ap.error("--task dn needs --dn_sigma LO HI (0..255 scale, e.g. 25 25)")
+        if args.task == "dn" and args.jpeg_quality is not None:
+            ap.error("--jpeg_quality with noise is --task car --dn_sigma LO HI; --task dn has no JPEG stage")
+        if args.task == "car" and args.jpeg_quality is None:
+            ap.error("--task car needs --jpeg_quality LO HI")
+        if args.jpeg_p != 1.0:
+            ap.error(f"--jpeg_p is an option of the JPEG stage of --synth_lr; with --task {args.task} every patch is coded")
+        if args.val_bench_metric is not None and args.channels == 1:
+            ap.error("--val_bench_metric is not offered with --channels 1 (the benchmark-protocol scores take RGB predictions)")
+        try:
+            restore_spec(args)
+        except ValueError as e:
+            ap.error(f"--task {args.task}: {e}")
+        args.gpu_data = True          # the pairs are made on the device; the HR directories alone are read
     if args.synth_lr and not args.gpu_data:
         ap.error("--synth_lr forms the LR patches on the device: it needs --gpu_data")
     if args.degrade == "blind":
@@ -344,7 +411,7 @@ def parse_args(argv=None):
     if args.jpeg_quality is None:
         if args.jpeg_p != 1.0 or args.jpeg_subsample != "444":
             ap.error("--jpeg_p and --jpeg_subsample are options of the JPEG stage: they need --jpeg_quality LO HI")
-    else:
+    elif args.task == "sr":
         if not (args.gpu_data and args.synth_lr):
             ap.error("--jpeg_quality codes the LR patches formed on the device: it needs --gpu_data --synth_lr")
         if args.synth_lr_bits != 8:
@@ -362,9 +429,9 @@ def parse_args(argv=None):
         ap.error(f"--ssim_weight must be a finite number >= 0 (got {args.ssim_weight})")
     if not args.charbonnier_eps > 0.0:
         ap.error(f"--charbonnier_eps must be > 0 (got {args.charbonnier_eps})")
-    if args.ssim_weight > 0 and args.lr_patch * (2 if args.scale.upper() == "X2" else 4) < 11:
+    if args.ssim_weight > 0 and args.lr_patch * SCALES[args.scale.upper()] < 11:
         ap.error(f"--ssim_weight needs HR patches of at least 11 x 11 (lr_patch * scale = "
-                 f"{args.lr_patch * (2 if args.scale.upper() == 'X2' else 4)})")
+                 f"{args.lr_patch * SCALES[args.scale.upper()]})")
     if not 0.0 <= args.ema_decay < 1.0:          # also refuses NaN
         ap.error(f"--ema_decay must be in [0, 1) (got {args.ema_decay})")
     if not 2 <= args.window_size <= 8:
@@ -406,6 +473,17 @@ def jpeg_spec(args):
     return JpegSpec(quality=tuple(args.jpeg_quality), p=args.jpeg_p, subsample=args.jpeg_subsample == "420", seed=args.degrade_seed)
 
 
+def restore_spec(args):
+    """The RestoreSpec of the command line (None for --task sr); --dn_sigma is given on the 0..255 scale; it reuses --degrade_seed and
+    --gray_noise_p is not consulted: a colour image gets colour noise, as in the published training."""
+    if args.task == "sr":
+        return None
+    from .sr_datasets import RestoreSpec
+    sigma = (0.0, 0.0) if args.dn_sigma is None else tuple(v / 255.0 for v in args.dn_sigma)
+    return RestoreSpec(sigma=sigma, jpeg_quality=None if args.jpeg_quality is None else tuple(args.jpeg_quality),
+                       subsample=args.jpeg_subsample == "420", seed=args.degrade_seed)
+
+
 def saved_args(args) -> dict:
     """What a checkpoint keeps of the command line: additive flags leave no trace in the files at their defaults."""
     at_default = {"ema_decay": not args.ema_decay, "loss": args.loss == "l1", "charbonnier_eps": args.charbonnier_eps == 1e-3,
@@ -420,7 +498,8 @@ def saved_args(args) -> dict:
                   "blur_kernel_prob": args.blur_kernel_prob is None, "blur_beta_g": args.blur_beta_g is None,
                   "blur_beta_p": args.blur_beta_p is None, "blur_ksize": args.blur_ksize is None, "blur_psf": args.blur_psf is None,
                   "val_bench_metric": args.val_bench_metric is None,
-                  "val_crop_border": args.val_crop_border is None}
+                  "val_crop_border": args.val_crop_border is None, "task": args.task == "sr", "channels": args.channels == 3,
+                  "dn_sigma": args.dn_sigma is None, "dn_bits": args.dn_bits == 0}
     return {k: v for k, v in vars(args).items() if not at_default.get(k, False)}
 
 
@@ -439,9 +518,26 @@ def main(argv=None):
     torch.cuda.set_device(device)
     if rank == 0:
         print("[device]", device, torch.cuda.get_device_name(local), f"world={world}")
-    scale_int = 2 if args.scale.upper() == "X2" else 4
+    scale_int = SCALES[args.scale.upper()]
 
-    if args.synth_lr:
+    if args.task != "sr":
+        from functools import partial
+
+        from .sr_datasets import DeviceRestorePool, RestoreBatches, Shuffled2DHR, clean_to_tensor
+        raw = Shuffled2DHR(args.data_root, split="train")
+        spec = restore_spec(args)
+        pool = DeviceRestorePool((raw[i] for i in range(len(raw))), args.lr_patch, args.channels, spec, device=device,
+                                 shard_bytes=(args.gpu_data_shard_mb << 20) or None, augment=args.augment, quant_bits=args.dn_bits, rank=rank)
+        train_loader = sampler = DevicePoolLoader(pool, args.batch_size, rank, world, args.seed)
+        valid_ds = Shuffled2DHR(args.data_root, split="valid", transform=partial(clean_to_tensor, out_chans=args.channels))
+        if rank == 0:
+            fx = spec.fixed()
+            print(f"[task {args.task}] {len(pool)} clean images in {pool.num_shards} shard(s), {sum(t.numel() for t in pool._host) / 2**20:.1f} "
+                  f"MiB decoded; {args.channels} channel(s), patches of {args.lr_patch} cut at any pixel and degraded on the device")
+            print(f"[degrade] noise sigma in {[0.0, 0.0] if args.dn_sigma is None else args.dn_sigma} / 255 ({args.dn_bits or 'no'}-bit "
+                  f"rounding), jpeg quality in {args.jpeg_quality} chroma {args.jpeg_subsample}, blocks on the image's grid, seed "
+                  f"{args.degrade_seed}; validation: sigma={fx.sigma * 255.0:.4g} / 255 quality {fx.jpeg_quality or 'none'}, noise id = image index")
+    elif args.synth_lr:
         from .sr_datasets import DeviceHRPool, Shuffled2DHR, SynthLRBatches, hr_to_tensor3
         raw = Shuffled2DHR(args.data_root, split="train")
         pool = DeviceHRPool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, device=device,
@@ -474,7 +570,7 @@ def main(argv=None):
         sampler = DistributedSampler(train_ds, num_replicas=world, rank=rank, shuffle=True, seed=args.seed) if world > 1 else None
         train_loader = make_loader(train_ds, args.batch_size, args.workers, pin=not args.no_pin, shuffle=True, drop_last=True,
                                    persistent=not args.no_persistent, sampler=sampler)
-    if args.gpu_data and not args.synth_lr:
+    if args.gpu_data and not args.synth_lr and args.task == "sr":
         from .sr_datasets import DevicePairPool
         raw = Shuffled2DPaired(args.data_root, split="train", scale=args.scale, transform_pair=None)
         pool = DevicePairPool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, device=device,
@@ -484,12 +580,17 @@ def main(argv=None):
             print(f"[gpu_data] {len(pool)} pairs in {pool.num_shards} shard(s), {sum(t.numel() for t in pool._host) / 2**20:.1f} MiB decoded")
     valid_loader = make_loader(valid_ds, max(1, args.batch_size // 2), args.workers, pin=not args.no_pin, shuffle=False,
                                drop_last=False, persistent=not args.no_persistent)
+    if args.task != "sr":
+        valid_loader = RestoreBatches(valid_loader, args.channels, restore_spec(args), args.dn_bits, device)
     if args.synth_lr:
         valid_loader = SynthLRBatches(valid_loader, scale_int, args.synth_lr_bits, device, degrade=degrade_spec(args), jpeg=jpeg_spec(args),
                                       psf=psf_spec(args))
 
-    model = (build_model(scale_int, args.drop_path_rate, args.window_size) if args.arch == "swinir" else
-             build_sr_model(args.arch, scale_int, args.drop_path_rate))
+    if args.task != "sr":
+        model = build_restoration_model(args.task, args.channels, args.drop_path_rate, args.window_size)
+    else:
+        model = (build_model(scale_int, args.drop_path_rate, args.window_size) if args.arch == "swinir" else
+                 build_sr_model(args.arch, scale_int, args.drop_path_rate))
     small = args.arch == "swinir" and args.window_size < 8
     if small:
         model.enable_small_window_training()          # before the optimizer is constructed: the model steps on the multi-tensor path
@@ -562,7 +663,7 @@ def main(argv=None):
     validate_fn, val_border = validate, None          # without --val_bench_metric: the validation call of ever
     if args.val_bench_metric is not None:
         from functools import partial
-        val_border = (2 if args.scale.upper() == "X2" else 4) if args.val_crop_border is None else args.val_crop_border
+        val_border = scale_int if args.val_crop_border is None else args.val_crop_border
         validate_fn = partial(validate_bench, bench_metric=args.val_bench_metric, crop_border=val_border)
 
     best_loss, best_psnr, t_all = float("inf"), -float("inf"), time.time()

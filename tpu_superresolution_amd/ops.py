@@ -769,3 +769,70 @@ def jpeg_roundtrip(x: torch.Tensor, quality, subsample: bool = False, return_coe
         coef = torch.zeros(B, Cc, -(-H // m) * m, -(-W // m) * m, dtype=torch.int16, device=x.device)
     check(lib().srk_jpeg_roundtrip_f32(_p(x), _p(out), _p(qd), B, Cc, H, W, int(bool(subsample)), _p(coef), _stream()))
     return (out, coef) if return_coef else out
+
+
+# ---- scale-1 restoration: denoising and JPEG-artifact pairs (csrc/restore.hip) ---------------------------------------
+def pack_restore_params(jpeg_quality, noise, noise_id: int, gray_noise: bool):
+    """Slots 6..9 of a `srk_crop_restore_u8` descriptor / one row of `srk_noise_f32`'s table: `pack_degrade_params` with the JPEG
+    quality (0 = no JPEG stage, else 1..100) as the low word of slot 6 in place of the blur sigmas."""
+    q = 0 if (not isinstance(jpeg_quality, bool) and jpeg_quality == 0) else check_jpeg_quality(jpeg_quality)
+    return [q] + pack_degrade_params((0.0, 0.0), noise, noise_id, gray_noise)[1:]
+
+
+def noise(x: torch.Tensor, noise, noise_ids, gray_noise=False, quant_bits: int = 0) -> torch.Tensor:
+    """The noise stage of `degrade_blind` at scale 1 (csrc/restore.hip, srk_noise_f32): x CUDA fp32 [B,C,H,W], C = 1 or 3, gets
+    `v + sqrt(sigma_n^2 + gain max(v, 0)) z` per element, z from Philox on the counter (x, y, ch | 0 with gray noise) under the key
+    noise_id.  noise = (sigma_n, gain): one pair or one per sample, image units in [0, 1]; noise_ids: B integers; gray_noise: a bool or
+    B of them (always so for C == 1).  Zero amplitudes pass the bits through; quant_bits 8 rounds to k / 255.  One launch after one small
+    upload."""
+    if x.dim() != 4 or not x.is_cuda or x.dtype != torch.float32:
+        raise ValueError(f"noise takes a CUDA fp32 [B,C,H,W] batch (got {x.dtype} {tuple(x.shape)} on {x.device})")
+    B, Cc, H, W = x.shape
+    if Cc not in (1, 3) or min(B, H, W) < 1:
+        raise ValueError(f"noise: C must be 1 or 3 and every extent >= 1 (got {tuple(x.shape)})")
+    if quant_bits not in (0, 8):
+        raise ValueError(f"noise: quant_bits must be 0 or 8 (got {quant_bits!r})")
+    ids = [int(v) for v in noise_ids]
+    grays = [bool(gray_noise)] * B if isinstance(gray_noise, (bool, int)) else [bool(v) for v in gray_noise]
+    if len(ids) != B or len(grays) != B:
+        raise ValueError(f"noise: one noise id and one gray flag per sample (B={B}; got {len(ids)} ids, {len(grays)} flags)")
+    rows = [pack_restore_params(0, n, i, g) for n, i, g in zip(_per_sample(noise, B, 2, "noise"), ids, grays)]
+    x = x.contiguous()
+    par = torch.tensor(rows, dtype=torch.int64).to(x.device)
+    out = torch.empty_like(x)
+    check(lib().srk_noise_f32(_p(x), _p(out), _p(par), B, Cc, H, W, int(quant_bits), _stream()))
+    return out
+
+
+_noise_stage = noise          # `restore_degrade` names its amplitude pair `noise`, as `degrade_blind` does
+
+
+def restore_degrade(x: torch.Tensor, noise, noise_ids, gray_noise=False, jpeg_quality=0, subsample: bool = False,
+                    quant_bits: int = 0) -> torch.Tensor:
+    """The whole-image degradation of the scale-1 tasks: `noise`, then `jpeg_roundtrip` where the quality (an int or one per sample,
+    0 = no JPEG stage) is > 0.  What DeviceRestorePool's training patches are windows of, bit for bit.  It is the composition of the
+    two entries, no kernel of its own."""
+    y = _noise_stage(x, noise, noise_ids, gray_noise, quant_bits)
+    qs = [jpeg_quality] * x.shape[0] if isinstance(jpeg_quality, numbers.Real) else list(jpeg_quality)
+    if any((isinstance(q, bool) or q != 0) for q in qs):
+        y = jpeg_roundtrip(y, qs, subsample)
+    return y
+
+
+LUMA_COEF = (4899, 9617, 1868)          # /16384: full-range BT.601 in 14-bit fixed point, the sum is 16384
+
+
+def to_gray(x):
+    """The integer luma `(4899 R + 9617 G + 1868 B + 8192) >> 14` of stored samples, on the CPU: x uint8 / uint16, a numpy array or a
+    CPU tensor, [..., H, W, 3] -> [..., H, W] of the same type and dtype.  What srk_crop_restore_u8 makes of an RGB source at
+    out_chans 1, so a validation loader can form the same one-channel HR images."""
+    import numpy as np
+    is_t = isinstance(x, torch.Tensor)
+    a = x.detach().cpu().numpy() if is_t else np.asarray(x)
+    if a.dtype not in (np.uint8, np.uint16):
+        raise ValueError(f"to_gray takes uint8 or uint16 samples (got {a.dtype})")
+    if a.ndim < 3 or a.shape[-1] != 3:
+        raise ValueError(f"to_gray takes [..., H, W, 3] samples (got shape {tuple(a.shape)})")
+    v = a.astype(np.uint32)          # 16384 * 65535 + 8192 < 2^32
+    y = ((LUMA_COEF[0] * v[..., 0] + LUMA_COEF[1] * v[..., 1] + LUMA_COEF[2] * v[..., 2] + 8192) >> 14).astype(a.dtype)
+    return torch.from_numpy(y) if is_t else y

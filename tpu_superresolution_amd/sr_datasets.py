@@ -686,3 +686,198 @@ class SynthLRBatches:
             else:
                 yield degrade_blind(hr, self.scale, self.degrade.blur, self.degrade.noise, range(first, first + B), gray, self.quant_bits)
             first += B
+
+
+# ---- scale-1 restoration: denoising and JPEG-artifact pairs ---------------------------------------------------------
+class FixedRestore(NamedTuple):
+    """One fixed scale-1 degradation (validation, evaluation): the noise sigma in image units (0..1), the JPEG quality (0 = no JPEG
+    stage), gray_noise = one draw for the three channels of a colour image, subsample = chroma at 4:2:0."""
+    sigma: float
+    jpeg_quality: int = 0
+    gray_noise: bool = False
+    subsample: bool = False
+
+
+@dataclass(frozen=True)
+class RestoreSpec:
+    """The random degradation of `--task dn | car`: per training sample Gaussian noise with sigma uniform in `sigma`
+    (image units, 0..1) and, with `jpeg_quality` = (lo, hi), a round trip through baseline JPEG at a quality uniform in the integers
+    lo..hi (None = no JPEG stage); for a colour image one noise draw for all channels with probability `gray_noise_p`; `subsample`:
+    chroma at 4:2:0; a 64-bit noise id.  Everything comes from the spec's OWN generator `random.Random(f"restore:{seed + rank}")`:
+    neither the global `random` state, which places the crops, nor a DegradeSpec's or JpegSpec's generator sees it."""
+    sigma: Tuple[float, float] = (0.0, 0.0)
+    jpeg_quality: Optional[Tuple[int, int]] = None
+    gray_noise_p: float = 0.0
+    subsample: bool = False
+    seed: int = 0
+
+    def __post_init__(self):
+        from .ops import check_jpeg_quality
+        object.__setattr__(self, "sigma", _check_range("sigma", self.sigma, 1.0))
+        if self.jpeg_quality is not None:
+            try:
+                lo, hi = self.jpeg_quality
+            except (TypeError, ValueError):
+                raise ValueError(f"jpeg quality must be two integers LO HI or None (got {self.jpeg_quality!r})") from None
+            lo, hi = check_jpeg_quality(lo, "quality LO"), check_jpeg_quality(hi, "quality HI")
+            if lo > hi:
+                raise ValueError(f"jpeg quality must satisfy 1 <= LO <= HI <= 100 (got {lo} {hi})")
+            object.__setattr__(self, "jpeg_quality", (lo, hi))
+        if not 0.0 <= float(self.gray_noise_p) <= 1.0:          # also refuses NaN
+            raise ValueError(f"gray_noise_p must be a probability (got {self.gray_noise_p!r})")
+        object.__setattr__(self, "subsample", bool(self.subsample))
+
+    def rng(self, rank: int = 0) -> random.Random:
+        return random.Random(f"restore:{int(self.seed) + int(rank)}")
+
+    def draw(self, rng: random.Random, colour: bool):
+        """-> (sigma, quality, noise_id, gray_noise) of one sample, quality 0 = no JPEG stage; always the same four variates, whatever
+        they decide."""
+        sigma, u_q = rng.uniform(*self.sigma), rng.random()
+        gray = rng.random() < self.gray_noise_p
+        q = 0
+        if self.jpeg_quality is not None:
+            lo, hi = self.jpeg_quality
+            q = min(lo + int(u_q * (hi - lo + 1)), hi)
+        return sigma, q, rng.getrandbits(64), gray or not colour
+
+    def fixed(self) -> FixedRestore:
+        """The midpoint sigma and the middle quality: what validation scores, every epoch and every run."""
+        q = 0 if self.jpeg_quality is None else round((self.jpeg_quality[0] + self.jpeg_quality[1]) / 2)
+        return FixedRestore(0.5 * (self.sigma[0] + self.sigma[1]), q, self.gray_noise_p >= 0.5, self.subsample)
+
+
+class DeviceRestorePool(_DeviceImagePool):
+    """Training pairs of the scale-1 tasks from clean images only (`--task dn | car`): `sample` cuts a P x P patch at ANY image pixel and
+    makes the clean target and the degraded input in one launch (`srk_crop_restore_u8`, csrc/restore.hip).  The degraded patch is
+    exactly the window of the whole-image degradation (ops.restore_degrade): noise keyed on image coordinates, JPEG blocks anchored
+    at the image's (0, 0) -- so a batch sees 8 x 8 block edges at every phase relative to its patch, as crops of compressed files do.
+
+    ``out_chans`` 3: RGB (a gray source is repeated); 1: gray (an RGB source becomes the integer luma of ops.to_gray).
+    Same surface as DevicePairPool (shards, prefetch, augment): `draw` takes `random.randint(0, H - P)`, `random.randint(0, W - P)` and
+    the D4 code per sample from the global `random`, in DevicePairPool's order, so from one `random` state a DevicePairPool at
+    lr_patch P cuts the same LR windows.  The degradation parameters come from ``spec``'s own generator (seed + ``rank``).
+    ``quant_bits`` 0 (default): the noised values are neither clipped nor rounded, as the published denoising recipe has it; 8: they
+    are rounded to k / 255 (with a JPEG stage its 8-bit level step does that in either case)."""
+
+    def __init__(self, images, patch: int, out_chans: int = 3, spec: Optional[RestoreSpec] = None, device="cuda",
+                 shard_bytes: Optional[int] = None, augment: str = "none", quant_bits: int = 0, rank: int = 0):
+        """images: iterable of clean PIL images or uint8 / uint16 arrays [H,W] / [H,W,1|3]."""
+        if augment not in AUGMENT_MODES:
+            raise ValueError(f"augment must be one of {AUGMENT_MODES} (got {augment!r})")
+        if quant_bits not in (0, 8):
+            raise ValueError(f"quant_bits must be 0 or 8 (got {quant_bits!r})")
+        if out_chans not in (1, 3):
+            raise ValueError(f"out_chans must be 1 or 3 (got {out_chans!r})")
+        if not isinstance(spec, RestoreSpec):
+            raise ValueError(f"spec must be a RestoreSpec (got {type(spec).__name__})")
+        if not 1 <= int(patch) <= 2048:
+            raise ValueError(f"patch must be in 1..2048 (got {patch!r})")
+        self.augment, self.quant_bits, self.out_chans = augment, int(quant_bits), int(out_chans)
+        self.spec, self._spec_rng = spec, spec.rng(rank)
+        self.patch, self.device = int(patch), torch.device(device)
+        self._pack(((img,) for img in images), shard_bytes)
+
+    def _check_group(self, img) -> None:
+        _, h, w, _ = img
+        if h < self.patch or w < self.patch:
+            raise ValueError(f"image ({h},{w}) too small for patch {self.patch}")
+
+    def draw(self, indices):
+        """-> (descriptors, D4 codes) of a batch; advances the global `random` state exactly as DevicePairPool.sample does."""
+        P = self.patch
+        hd, codes = [], []
+        for i in indices:
+            _, (o, h, w, c) = self.meta[int(i)]
+            top, left = random.randint(0, h - P), random.randint(0, w - P)
+            hd.append((o, h, w, c, top, left))
+            codes.append(draw_op(self.augment))
+        return hd, codes
+
+    def draw_restore(self, hd):
+        """The ten-slot descriptors of a batch: `draw`'s six plus the packed parameters of one `RestoreSpec.draw` per sample, from the
+        spec's generator alone (the global `random` state is not touched)."""
+        from .ops import pack_restore_params
+        rows = []
+        for d in hd:
+            sigma, q, nid, gray = self.spec.draw(self._spec_rng, colour=(d[3] & 0xff) == 3 and self.out_chans == 3)
+            rows.append(tuple(d) + tuple(pack_restore_params(q, (sigma, 0.0), nid, gray)))
+        return rows
+
+    def sample(self, indices):
+        """-> (degraded [B,out_chans,P,P], clean [B,out_chans,P,P]) fp32 on the device: one descriptor upload, one launch."""
+        from ._lib import check, lib
+        P, Co = self.patch, self.out_chans
+        pool = self._batch_pool(indices)
+        hd, codes = self.draw(indices)
+        B = len(hd)
+        desc = torch.tensor(self.draw_restore(hd), dtype=torch.int64).to(self.device)
+        clean = torch.empty(B, Co, P, P, dtype=torch.float32, device=self.device)
+        degraded = torch.empty(B, Co, P, P, dtype=torch.float32, device=self.device)
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        check(lib().srk_crop_restore_u8(pool.data_ptr(), desc.data_ptr(), clean.data_ptr(), degraded.data_ptr(), B, P, Co,
+                                        int(self.spec.subsample), self.quant_bits, st))
+        if any(codes):
+            from .augment import dihedral
+            ops = torch.tensor(codes, dtype=torch.int32).to(self.device)
+            degraded, clean = dihedral(degraded, ops), dihedral(clean, ops)
+        return degraded, clean
+
+
+class RestoreBatches:
+    """Wraps a loader of clean batches [B,out_chans,H,W] into the (degraded, clean) batches of `--task dn | car` validation /
+    evaluation: each batch goes to the device and is degraded there as a whole image (ops.restore_degrade) -- what
+    DeviceRestorePool's training patches are windows of.  ``spec_or_fixed``: a FixedRestore, or a RestoreSpec standing for its
+    `fixed()` values.  Every image gets the SAME sigma and quality and the noise id = its index in the split (the loader must not
+    shuffle), so every epoch and every run scores the same degraded images.  A colour image whose three channels are equal gets gray
+    noise, as its gray file would."""
+
+    def __init__(self, loader, out_chans: int, spec_or_fixed, quant_bits: int, device):
+        if out_chans not in (1, 3):
+            raise ValueError(f"out_chans must be 1 or 3 (got {out_chans!r})")
+        if quant_bits not in (0, 8):
+            raise ValueError(f"quant_bits must be 0 or 8 (got {quant_bits!r})")
+        fx = spec_or_fixed.fixed() if isinstance(spec_or_fixed, RestoreSpec) else spec_or_fixed
+        if not isinstance(fx, FixedRestore):
+            raise ValueError(f"spec_or_fixed must be a RestoreSpec or a FixedRestore (got {type(spec_or_fixed).__name__})")
+        from .ops import pack_restore_params
+        pack_restore_params(fx.jpeg_quality, (fx.sigma, 0.0), 0, fx.gray_noise)          # the ranges, before any batch
+        self.loader, self.out_chans, self.fixed, self.quant_bits, self.device = loader, int(out_chans), fx, int(quant_bits), torch.device(device)
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        from .ops import restore_degrade
+        fx, first = self.fixed, 0
+        for clean in self.loader:
+            clean = clean.to(self.device, dtype=torch.float32).contiguous()
+            if clean.dim() != 4 or clean.shape[1] != self.out_chans:
+                raise ValueError(f"RestoreBatches(out_chans={self.out_chans}) got a batch of shape {tuple(clean.shape)}")
+            B = clean.shape[0]
+            gray = [True] * B
+            if self.out_chans == 3 and not fx.gray_noise:
+                gray = ((clean[:, 0] == clean[:, 1]) & (clean[:, 0] == clean[:, 2])).flatten(1).all(dim=1).tolist()
+            yield restore_degrade(clean, (fx.sigma, 0.0), range(first, first + B), gray, fx.jpeg_quality, fx.subsample, self.quant_bits), clean
+            first += B
+
+
+def clean_to_tensor(img, out_chans: int) -> torch.Tensor:
+    """A clean PIL image as the fp32 [out_chans,H,W] tensor in [0, 1] that DeviceRestorePool cuts its targets from: three channels as
+    `hr_to_tensor3`; one channel = the stored gray samples, or the integer luma (ops.to_gray) of an RGB image, over 255 / 65535."""
+    if out_chans == 3:
+        return hr_to_tensor3(img)
+    from .ops import to_gray
+    a = np.asarray(img)
+    if a.dtype.byteorder == ">":
+        a = a.astype(a.dtype.newbyteorder("="))
+    if a.dtype not in (np.uint8, np.uint16):
+        raise ValueError(f"clean images are 8-bit or 16-bit (got {a.dtype})")
+    if a.ndim == 3 and a.shape[2] == 3:
+        a = to_gray(a)
+    elif a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    elif a.ndim != 2:
+        raise ValueError(f"Expected C=1 or C=3, got shape {a.shape}")
+    div = np.float32(255.0 if a.dtype == np.uint8 else 65535.0)
+    return torch.from_numpy(np.ascontiguousarray(a).astype(np.float32) / div).unsqueeze(0)          # IEEE fp32 division, as pil_to_tensor01
