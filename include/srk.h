@@ -225,6 +225,10 @@ int srk_set_wgrad_workspace(void* workspace, int64_t bytes);
  * value = u8 / 255 in IEEE fp32, a gray image is repeated into three channels: bit-identical to the host transform. */
 int srk_paired_crop_u8(const uint8_t* pool, const int64_t* lr_desc, const int64_t* hr_desc, float* lr_out, float* hr_out, int B,
                        int lr_patch, int scale, srk_stream_t stream);
+/* One side of srk_paired_crop_u8 (the same kernel): B windows of patch x patch, descriptors and conversion as there, into
+ * out fp32 [B][3][patch][patch].  What cuts the extended window of the second-order degradation, whose side is no multiple of the
+ * HR patch's.  SRK_E_NULL: a null pointer; SRK_E_SHAPE: B outside 1..65535, patch outside 1..8192. */
+int srk_crop_u8(const uint8_t* pool, const int64_t* desc, float* out, int B, int patch, srk_stream_t stream);
 /* D4 transform of a batch of fp32 NCHW images (flip / rot90 augmentation of a training batch, the forward and inverse transforms of
  * the x8 self-ensemble).  op in 0..7: bit 0 = horizontal flip (x -> W-1-x), bit 1 = vertical flip (y -> H-1-y), bit 2 = transpose,
  * applied in that order: T_op = Tr^b2 . V^b1 . H^b0.
@@ -385,6 +389,51 @@ int srk_noise_f32(const float* x, float* out, const int64_t* par4, int B, int C,
  * quant_bits other than 0 / 8, the two outputs overlapping. */
 int srk_crop_restore_u8(const uint8_t* pool, const int64_t* desc10, float* clean_out, float* degraded_out, int B, int patch, int out_chans,
                         int subsample, int quant_bits, srk_stream_t stream);
+/* Ragged batches (csrc/ragged.h, ragged.hip, filter2d.hip): the stages of the second-order degradation -- blur, resize, noise, JPEG,
+ * twice, then a sinc filter -- give every sample its own intermediate size.  The contract of the three entries below, stated once:
+ *   - the buffer is fp32 [B][C][Hp][Wp]; ext is DEVICE int32 [B][2] = (h_b, w_b) with 1 <= h_b <= Hp and 1 <= w_b <= Wp;
+ *   - sample b occupies the top-left h_b x w_b of each of its planes, at row pitch Wp; the rest of the buffer is padding;
+ *   - a ragged kernel never reads an input element outside a sample's extents and never writes an output element outside them
+ *     (padding may hold anything, NaNs included, and output padding keeps its bits);
+ *   - the grid covers the padded extents times B; a workgroup whose tile misses its sample's extents leaves before any barrier;
+ *   - ext == NULL means dense: every sample is Hp x Wp;
+ *   - the host that wrote ext checks it (the entries cannot: it is device memory and no entry synchronises); for ANY bit pattern in
+ *     ext the kernels clamp into 1..Hp / 1..Wp and stay inside their buffers.
+ * One launch each, no device allocation.
+ *
+ * srk_filter2d_f32: a SIGNED table -- a sinc (ringing) filter, or any table of srk_blur2d_f32 -- as a CORRELATION with a reflect-101
+ * border (cv2.filter2D's default; Real-ESRGAN's filter2D).  tab = DEVICE fp32 [B][ks][ks], ks odd in 1..21, R = (ks - 1) / 2:
+ *   out(p, q) = sum over a, b ascending (a outer, b inner) of K[a][b] * x(rho(p + a - R, h), rho(q + b - R, w))
+ *   rho(i, n) = i < 0 ? -i : (i >= n ? 2 (n - 1) - i : i), then clamped into 0..n-1
+ * as the chain acc = fmaf(K[a][b], x, acc) from 0 in fp32, no other contraction.  No mass and no division (srk_blur2d_f32's rule needs
+ * a mass that a signed table does not have).  The reflection is exact for h, w > R, which the host requires of every sample at the R
+ * of its own table; the clamp keeps any other extent in bounds.  fmaf(0, x, acc) == acc for finite x: a table zero-padded, centred,
+ * to a larger ks gives IDENTICAL bits on finite images -- also on a sample that is smaller than the padded R, where the clamped
+ * positions are read and multiplied by 0 -- so one ks per launch is enough for a batch of mixed table and image sizes.  quant_bits 0 | 8 as srk_resize_aa_f32.  A delta table (centre tap 1, every other tap +-0) is a
+ * pass-through: with quant_bits 0 the words of x are copied, NaN payloads and -0 included.  The host (ops) checks a table: taps
+ * finite, fp64 sum within 1e-3 of 1, no sign rule.  out must overlap none of x, tab, ext.
+ * SRK_E_NULL: null x / tab / out; SRK_E_SHAPE: B or C < 1, ks even or outside 1..21, Hp or Wp <= R, quant_bits other than 0 / 8, an
+ * overlap, a size that does not fit one launch. */
+int srk_filter2d_f32(const float* x, const float* tab, float* out, const int32_t* ext, int B, int C, int Hp, int Wp, int ks, int quant_bits,
+                     srk_stream_t stream);
+/* srk_resize_aa_f32 per sample: x [B][C][Hp][Wp] with ext_in -> out [B][C][Hop][Wop] with ext_out, sample b resized from
+ * (h_b, w_b) to (ho_b, wo_b) by the tables of those two extents on the tile grid from (0, 0) of srk_resize_aa_f32 (the entries share
+ * their device routines): sample b is BIT-IDENTICAL to srk_resize_aa_f32 on that sample alone.  Either table may be NULL (dense).
+ * An axis of a sample shrinking by more than 8x is not supported.  With both tables NULL the entry checks that itself; otherwise the
+ * CALLER checks it from its host copy of the tables (ops.resize_aa_ragged does) -- the kernel then still stays in bounds, it drops the
+ * taps past the 33rd.  SRK_E_NULL: null x / out; SRK_E_SHAPE: a non-positive extent, quant_bits other than 0 / 8, out overlapping x
+ * or a table, a size that does not fit one launch; SRK_E_UNSUPPORTED: a dense call shrinking an axis by more than 8x. */
+int srk_resize_aa_ragged_f32(const float* x, const int32_t* ext_in, float* out, const int32_t* ext_out, int B, int C, int Hp, int Wp, int Hop,
+                             int Wop, int quant_bits, srk_stream_t stream);
+/* srk_jpeg_roundtrip_f32 per sample: the 8 x 8 grid is anchored at (0, 0) of each sample and its last row and column at (h_b, w_b)
+ * are replicated into the last MCU (the entries share their device routines): sample b is BIT-IDENTICAL to srk_jpeg_roundtrip_f32 on
+ * that sample alone.  Quality 0 copies the in-extent words of the sample.  No coefficient port.
+ * SRK_E_NULL: null x / out / quality; SRK_E_SHAPE: a non-positive extent, C not 1 or 3, subsample not 0 or 1, x and out overlapping, a
+ * size that does not fit one launch. */
+int srk_jpeg_roundtrip_ragged_f32(const float* x, float* out, const int32_t* quality, const int32_t* ext, int B, int C, int Hp, int Wp,
+                                  int subsample, srk_stream_t stream);
+/* The noise stage of a ragged chain is srk_noise_f32 on the padded buffer: its counter is (x, y, ch) only, so inside the extents its
+ * bits are those of the dense call on the sample alone; what it writes into the padding is never read. */
 /* Tiled inference (csrc/tile.hip): crop a chunk of overlapping tiles out of an fp32 NCHW batch, run a model on them as a batch of
  * n * B, and merge the chunk's outputs into the output image.
  * Tile grid, per axis with extent N, tile t (1 <= t <= N) and stride s (1 <= s <= t; overlap = t - s): k = ceil((N - t) / s) + 1

@@ -105,6 +105,7 @@ _SIGNATURES = {
     "srk_wgrad_workspace_bytes": (_i64, []),
     "srk_set_wgrad_workspace": (_i, [_vp, _i64]),
     "srk_paired_crop_u8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "srk_crop_u8": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "srk_dihedral_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp]),
     "srk_resize_aa_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "srk_crop_degrade_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -115,6 +116,9 @@ _SIGNATURES = {
     "srk_jpeg_roundtrip_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "srk_noise_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "srk_crop_restore_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "srk_filter2d_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "srk_resize_aa_ragged_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "srk_jpeg_roundtrip_ragged_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "srk_tile_gather_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "srk_tile_merge_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "srk_batch_psnr_workspace": (_i64, [_i64, _i]),

@@ -100,6 +100,61 @@ def check_table(table, what: str = "psf") -> np.ndarray:
     return t
 
 
+# ---- signed tables of the second-order degradation (include/srk.h: srk_filter2d_f32; ops.filter2d) ------------------------------
+_J1_N = 512          # intervals of the trapezoid rule below
+
+
+def j1(z) -> np.ndarray:
+    """The Bessel function J1 in fp64 numpy: the trapezoid rule on Bessel's integral (1 / pi) int_0^pi cos(t - z sin t) dt.  The
+    integrand is an even 2 pi-periodic entire function of t, so the rule converges geometrically once the intervals outnumber |z|:
+    512 of them give fp64 rounding error for |z| < 200 (a 21 x 21 sinc table needs |z| <= 10 sqrt(2) pi < 45)."""
+    z = np.asarray(z, dtype=np.float64)
+    if not np.isfinite(z).all() or (np.abs(z) >= 200.0).any():
+        raise ValueError("j1: arguments must be finite and below 200 in magnitude")
+    t = np.linspace(0.0, math.pi, _J1_N + 1)
+    f = np.cos(t - z[..., None] * np.sin(t))
+    return (f[..., 1:-1].sum(-1) + 0.5 * (f[..., 0] + f[..., -1])) / _J1_N
+
+
+def sinc(cutoff: float, ks: int) -> np.ndarray:
+    """Real-ESRGAN's circular low-pass (sinc) kernel, the source of ringing and overshoot: off-centre taps cutoff J1(cutoff r) / (2 pi r)
+    at r = |(x, y)|, the centre tap cutoff^2 / (4 pi); normalised to sum 1 in fp64 and rounded once to fp32.  cutoff in (0, pi] radians
+    per pixel.  The table has negative lobes: it goes through ops.filter2d (reflect border, no mass), never through ops.blur2d."""
+    ks = check_ks(ks)
+    cutoff = float(cutoff)
+    if not 0.0 < cutoff <= math.pi:          # also refuses NaN
+        raise ValueError(f"sinc: the cutoff must be in (0, pi] (got {cutoff!r})")
+    xx, _, yy = _grid(ks)
+    r = np.sqrt(xx + yy)
+    c = (ks - 1) // 2
+    r[c, c] = 1.0          # any value: the tap is replaced below
+    k = cutoff * j1(cutoff * r) / (2.0 * math.pi * r)
+    k[c, c] = cutoff * cutoff / (4.0 * math.pi)
+    return _finish(k)
+
+
+def delta(ks: int = 1) -> np.ndarray:
+    """The identity table: ops.filter2d passes a sample with it through bit for bit."""
+    t = np.zeros((check_ks(ks),) * 2, dtype=np.float32)
+    t[ks // 2, ks // 2] = 1.0
+    return t
+
+
+def check_filter_table(table, what: str = "table") -> np.ndarray:
+    """The host rule of a table for ops.filter2d -> fp32 [ks][ks]: odd square with ks <= 21, taps finite, an fp64 sum within 1e-3 of 1.
+    No sign rule: the reflect border needs no mass."""
+    t = np.asarray(table)
+    if t.ndim != 2 or t.shape[0] != t.shape[1] or t.shape[0] % 2 == 0 or not 1 <= t.shape[0] <= KS_MAX:
+        raise ValueError(f"{what}: a table is ks x ks with ks odd in 1..{KS_MAX} (got shape {t.shape})")
+    t = t.astype(np.float32)
+    if not np.isfinite(t).all():
+        raise ValueError(f"{what}: taps must be finite")
+    total = float(t.astype(np.float64).sum())
+    if abs(total - 1.0) > 1e-3:
+        raise ValueError(f"{what}: the taps must sum to 1 within 1e-3 (got {total:.6f})")
+    return t
+
+
 def load_psf_file(path: str) -> np.ndarray:
     """A measured PSF: .npy of shape [k][k] or [n][k][k] -> checked fp32 [n][k][k]."""
     a = np.load(path, allow_pickle=False)

@@ -492,6 +492,12 @@ int srk_paired_crop_u8(const uint8_t* pool, const int64_t* lr_desc, const int64_
   return srk_launch_crop_u8(pool, reinterpret_cast<const long long*>(hr_desc), hr_out, B, lr_patch * scale, (hipStream_t)stream);
 }
 
+int srk_crop_u8(const uint8_t* pool, const int64_t* desc, float* out, int B, int patch, srk_stream_t stream) {
+  REQ_PTR(pool); REQ_PTR(desc); REQ_PTR(out);
+  SRK_REQUIRE(B > 0 && B <= 65535 && patch > 0 && patch <= 8192, SRK_E_SHAPE, "crop_u8: B=%d (1..65535) patch=%d (1..8192)", B, patch);
+  return srk_launch_crop_u8(pool, reinterpret_cast<const long long*>(desc), out, B, patch, (hipStream_t)stream);
+}
+
 int srk_dihedral_f32(const float* in, float* out, const int32_t* ops, int op_all, int B, int C, int H, int W, float alpha,
                      int accumulate, srk_stream_t stream) {
   REQ_PTR(in); REQ_PTR(out);
@@ -594,6 +600,50 @@ int srk_noise_f32(const float* x, float* out, const int64_t* par4, int B, int C,
   const size_t bytes = (size_t)(4.0 * B * C * H * W);
   SRK_REQUIRE(!srk_ranges_overlap(x, bytes, out, bytes), SRK_E_SHAPE, "noise: x and out overlap (the stage is not run in place)");
   return srk_launch_noise_f32(x, out, reinterpret_cast<const long long*>(par4), B, C, H, W, quant_bits, (hipStream_t)stream);
+}
+
+int srk_filter2d_f32(const float* x, const float* tab, float* out, const int32_t* ext, int B, int C, int Hp, int Wp, int ks, int quant_bits,
+                     srk_stream_t stream) {
+  REQ_PTR(x); REQ_PTR(tab); REQ_PTR(out);
+  SRK_REQUIRE(srk_psf_ks_ok(ks), SRK_E_SHAPE, "filter2d: ks must be odd and in 1..21 (got %d)", ks);
+  SRK_REQUIRE(srk_filter2d_shape_ok(B, C, Hp, Wp, ks), SRK_E_SHAPE,
+              "filter2d: B=%d C=%d must be >= 1, Hp=%d Wp=%d above R=%d (the reflection needs an extent > R), and the size must fit one launch", B, C,
+              Hp, Wp, ks / 2);
+  SRK_REQUIRE(srk_quant_bits_ok(quant_bits), SRK_E_SHAPE, "filter2d: quant_bits must be 0 or 8 (got %d)", quant_bits);
+  const size_t bytes = (size_t)(4.0 * B * C * Hp * Wp), kb = sizeof(float) * (size_t)B * ks * ks, eb = ext ? sizeof(int32_t) * 2 * (size_t)B : 0;
+  SRK_REQUIRE(!srk_ranges_overlap(x, bytes, out, bytes) && !srk_ranges_overlap(tab, kb, out, bytes) && !srk_ranges_overlap(ext, eb, out, bytes),
+              SRK_E_SHAPE, "filter2d: out overlaps x, tab or ext (the filter is not run in place)");
+  return srk_launch_filter2d_f32(x, tab, out, reinterpret_cast<const int*>(ext), B, C, Hp, Wp, ks, quant_bits, (hipStream_t)stream);
+}
+
+int srk_resize_aa_ragged_f32(const float* x, const int32_t* ext_in, float* out, const int32_t* ext_out, int B, int C, int Hp, int Wp, int Hop,
+                             int Wop, int quant_bits, srk_stream_t stream) {
+  REQ_PTR(x); REQ_PTR(out);
+  SRK_REQUIRE(srk_resize_ragged_shape_ok(B, C, Hp, Wp, Hop, Wop), SRK_E_SHAPE,
+              "resize_aa_ragged: B=%d C=%d Hp=%d Wp=%d Hop=%d Wop=%d must all be >= 1 and fit one launch", B, C, Hp, Wp, Hop, Wop);
+  SRK_REQUIRE(srk_quant_bits_ok(quant_bits), SRK_E_SHAPE, "resize_aa_ragged: quant_bits must be 0 or 8 (got %d)", quant_bits);
+  const size_t ib = (size_t)(4.0 * B * C * Hp * Wp), ob = (size_t)(4.0 * B * C * Hop * Wop), eb = sizeof(int32_t) * 2 * (size_t)B;
+  SRK_REQUIRE(!srk_ranges_overlap(x, ib, out, ob) && !srk_ranges_overlap(ext_in, ext_in ? eb : 0, out, ob) &&
+                  !srk_ranges_overlap(ext_out, ext_out ? eb : 0, out, ob),
+              SRK_E_SHAPE, "resize_aa_ragged: out overlaps x or an extent table (the resize is not done in place)");
+  // the extents live in device memory: a dense batch is checked here, a ragged one by the caller that wrote the tables
+  if (!ext_in && !ext_out)
+    SRK_REQUIRE(srk_resize_factor_ok(Hp, Hop) && srk_resize_factor_ok(Wp, Wop), SRK_E_UNSUPPORTED,
+                "resize_aa_ragged: %d x %d -> %d x %d shrinks an axis by more than 8x (more than 33 taps)", Hp, Wp, Hop, Wop);
+  return srk_launch_resize_aa_ragged_f32(x, reinterpret_cast<const int*>(ext_in), out, reinterpret_cast<const int*>(ext_out), B, C, Hp, Wp, Hop,
+                                         Wop, quant_bits, (hipStream_t)stream);
+}
+
+int srk_jpeg_roundtrip_ragged_f32(const float* x, float* out, const int32_t* quality, const int32_t* ext, int B, int C, int Hp, int Wp,
+                                  int subsample, srk_stream_t stream) {
+  REQ_PTR(x); REQ_PTR(out); REQ_PTR(quality);
+  SRK_REQUIRE(srk_noise_shape_ok(B, C, Hp, Wp), SRK_E_SHAPE,
+              "jpeg_roundtrip_ragged: B=%d Hp=%d Wp=%d must all be >= 1, C=%d must be 1 or 3, and the size must fit one launch", B, Hp, Wp, C);
+  SRK_REQUIRE(srk_flag01_ok(subsample), SRK_E_SHAPE, "jpeg_roundtrip_ragged: subsample must be 0 (4:4:4) or 1 (4:2:0) (got %d)", subsample);
+  const size_t bytes = (size_t)(4.0 * B * C * Hp * Wp);
+  SRK_REQUIRE(!srk_ranges_overlap(x, bytes, out, bytes), SRK_E_SHAPE, "jpeg_roundtrip_ragged: x and out overlap (the blocks are not transformed in place)");
+  return srk_launch_jpeg_roundtrip_ragged_f32(x, out, reinterpret_cast<const int*>(quality), reinterpret_cast<const int*>(ext), B, C, Hp, Wp,
+                                              subsample, (hipStream_t)stream);
 }
 
 int srk_crop_restore_u8(const uint8_t* pool, const int64_t* desc10, float* clean_out, float* degraded_out, int B, int patch, int out_chans,

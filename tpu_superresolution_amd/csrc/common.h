@@ -133,6 +133,18 @@ static inline bool srk_crop_restore_shape_ok(int B, int patch, int out_chans) {
 }
 static inline bool srk_flag01_ok(int v) { return v == 0 || v == 1; }
 static inline bool srk_quant_bits_ok(int v) { return v == 0 || v == 8; }
+// second-order degradation (filter2d.hip, ragged.hip, srk.h "Ragged batches"): the padded shapes srk_filter2d_f32 takes -- those of
+// srk_blur2d_f32 with both padded extents above R = ks / 2, so that an extent the reflection can serve exists -- and the pair of padded
+// shapes srk_resize_aa_ragged_f32 takes (planes index an int, both byte counts stay below 2^63).  One sample's extents against its
+// padded buffer, and its resize against the 33-tap rows, for callers that hold host copies of ext.
+static inline bool srk_filter2d_shape_ok(int B, int C, int Hp, int Wp, int ks) {
+  return srk_psf_ks_ok(ks) && srk_blur2d_shape_ok(B, C, Hp, Wp) && Hp > ks / 2 && Wp > ks / 2;
+}
+static inline bool srk_resize_ragged_shape_ok(int B, int C, int Hp, int Wp, int Hop, int Wop) {
+  return srk_blur2d_shape_ok(B, C, Hp, Wp) && srk_blur2d_shape_ok(B, C, Hop, Wop);
+}
+static inline bool srk_ragged_extent_ok(int h, int w, int Hp, int Wp) { return h >= 1 && h <= Hp && w >= 1 && w <= Wp; }
+static inline bool srk_resize_factor_ok(int n_in, int n_out) { return n_in >= 1 && n_out >= 1 && (long long)n_in <= 8LL * n_out; }
 
 // ---------------------------------------------------------------------------------------------
 // bf16 helpers (device)

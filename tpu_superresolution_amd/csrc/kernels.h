@@ -81,6 +81,16 @@ int srk_launch_jpeg_roundtrip_f32(const float* x, float* out, const int* quality
 int srk_launch_noise_f32(const float* x, float* out, const long long* par, int B, int C, int H, int W, int quant_bits, hipStream_t stream);
 int srk_launch_crop_restore_u8(const unsigned char* pool, const long long* desc, float* clean_out, float* degraded_out, int B, int P,
                                int out_chans, int subsample, int quant_bits, hipStream_t stream);
+// filter2d.hip: a signed per-sample ks x ks table as a correlation with a reflect-101 border, on a dense or ragged batch (arguments
+// checked by srk_filter2d_f32)
+int srk_launch_filter2d_f32(const float* x, const float* tab, float* out, const int* ext, int B, int C, int Hp, int Wp, int ks, int quant_bits,
+                            hipStream_t stream);
+// ragged.hip: the resize and the JPEG round trip at per-sample extents (arguments checked by srk_resize_aa_ragged_f32 /
+// srk_jpeg_roundtrip_ragged_f32)
+int srk_launch_resize_aa_ragged_f32(const float* x, const int* ext_in, float* out, const int* ext_out, int B, int C, int Hp, int Wp, int Hop,
+                                    int Wop, int quant_bits, hipStream_t stream);
+int srk_launch_jpeg_roundtrip_ragged_f32(const float* x, float* out, const int* quality, const int* ext, int B, int C, int Hp, int Wp,
+                                         int subsample, hipStream_t stream);
 // tile.hip: tiled inference (arguments checked by srk_tile_gather_f32 / srk_tile_merge_f32).  One axis of the tile grid: extent n,
 // tile t (1 <= t <= n), stride s (1 <= s <= t), k = ceil((n - t) / s) + 1 tiles, origin o_i = min(i * s, n - t)
 struct TileAxis { int n, t, s, k; };

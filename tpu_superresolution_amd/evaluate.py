@@ -21,6 +21,8 @@ DESIGN 7n); ``main(argv)`` is callable from tests.  SSIM is ``metrics.ssim`` (re
 ``--bench_metric y | rgb [--crop_border N]`` (any --arch, any of the options above: it looks at (pred, hr) only) adds ``[bench]`` lines
 and ``bench_*`` keys with the scores of the papers' protocol -- 8-bit, border-cropped (default: the scale), BT.601 luma or RGB, 0..255
 scale, mean over images (metrics.bench_metrics); the other lines and keys stay as they are.
+``--synth_lr --degrade second_order`` degrades the HR images with the fixed second-order chain (SecondOrderSpec.fixed, ops.degrade_second_order,
+DESIGN 7p).
 ``--task dn | car --scale X1 --arch swinir [--channels 1|3 --dn_sigma S --jpeg_quality Q]`` scores the scale-1 restoration models: the clean test
 images are noised / JPEG-coded as whole images on the device (ops.restore_degrade) and the baseline line is the degraded input itself.
 """
@@ -123,9 +125,12 @@ def parse_args(argv=None):
                          "bicubic (PIL BICUBIC convention) downscale, formed on the device (ops.resize_aa)")
     ap.add_argument("--synth_lr_bits", type=int, choices=[0, 8], default=8,
                     help="additive, with --synth_lr: 8 = LR rounded to k / 255 as an 8-bit LR file would hold it, 0 = the filtered values")
-    ap.add_argument("--degrade", type=str, choices=["bicubic", "blind"], default="bicubic",
+    ap.add_argument("--degrade", type=str, choices=["bicubic", "blind", "second_order"], default="bicubic",
                     help="additive, with --synth_lr: blind = LR is blurred and noised with the fixed parameters below (ops.degrade_blind; "
-                         "the noise id of an image is its index in the split)")
+                         "the noise id of an image is its index in the split); second_order = the fixed second-order chain "
+                         "(sr_datasets.SecondOrderSpec.fixed, ops.degrade_second_order, DESIGN 7p): that blur and noise as stage 1, "
+                         "--jpeg_quality Q as the first JPEG's quality (default: the middle of 30..95), then the documented midpoints; it "
+                         "needs --synth_lr_bits 8")
     ap.add_argument("--blur_sigma", type=float, nargs=2, default=[1.1, 1.1], metavar=("SY", "SX"),
                     help="additive, with --degrade blind: sigma of the Gaussian blur in HR pixels along y and x, within [0, 2.5]")
     ap.add_argument("--noise_sigma", type=float, default=5.0, help="additive, with --degrade blind: noise sigma in 8-bit levels")
@@ -181,16 +186,18 @@ def parse_args(argv=None):
             ap.error(f"--crop_border must be >= 0 (got {args.crop_border})")
     if args.synth_lr and args.arch == "ms_resunet":
         ap.error("--synth_lr is an option of --arch swinir | hat | dat (MS_ResUNet takes the pre-upscaled LR of the eval transform)")
-    if args.degrade == "blind":
+    if args.degrade == "second_order" and args.synth_lr_bits != 8:
+        ap.error("--degrade second_order codes 8-bit LR images: it needs --synth_lr_bits 8")
+    if args.degrade in ("blind", "second_order"):
         if not args.synth_lr:
-            ap.error("--degrade blind degrades the HR images on the device: it needs --synth_lr")
+            ap.error(f"--degrade {args.degrade} degrades the HR images on the device: it needs --synth_lr")
         try:
             from .ops import pack_degrade_params
             pack_degrade_params(args.blur_sigma, (args.noise_sigma / 255.0, args.noise_gain), 0, False)
         except ValueError as e:
-            ap.error(f"--degrade blind: {e}")
-    if (args.blur_theta is not None or args.blur_psf is not None) and args.degrade != "blind":
-        ap.error("--blur_theta and --blur_psf shape the blur of --degrade blind: they need it")
+            ap.error(f"--degrade {args.degrade}: {e}")
+    if (args.blur_theta is not None or args.blur_psf is not None) and args.degrade not in ("blind", "second_order"):
+        ap.error("--blur_theta and --blur_psf shape the blur of --degrade blind | second_order: they need it")
     if args.blur_theta is not None and args.blur_psf is not None:
         ap.error("--blur_psf FILE replaces the Gaussian: it does not go with --blur_theta")
     try:
@@ -198,7 +205,7 @@ def parse_args(argv=None):
     except (ValueError, OSError) as e:
         ap.error(f"--blur_theta / --blur_psf: {e}")
     if args.jpeg_quality is None:
-        if args.jpeg_subsample != "444":
+        if args.jpeg_subsample != "444" and args.degrade != "second_order":
             ap.error("--jpeg_subsample is an option of the JPEG stage: it needs --jpeg_quality Q")
     elif args.task == "sr":
         if not args.synth_lr:
@@ -278,12 +285,16 @@ def main(argv=None):
         print(f"[task {args.task}] {args.channels} channel(s); degraded = whole image on the device: noise sigma={fx.sigma * 255.0:.4g} / 255 "
               f"({args.dn_bits or 'no'}-bit rounding), jpeg quality {fx.jpeg_quality or 'none'} chroma {args.jpeg_subsample}, noise id = image index")
     if args.synth_lr:          # (lr, hr) batches formed on the device, before the peek, the baseline and the prediction loop
-        fixed = None
-        if args.degrade == "blind":
+        fixed = second = None
+        if args.degrade in ("blind", "second_order"):
             from .sr_datasets import FixedDegrade
             fixed = FixedDegrade(tuple(args.blur_sigma), (args.noise_sigma / 255.0, args.noise_gain))
-        test_loader = SynthLRBatches(test_loader, scale_int, args.synth_lr_bits, device, degrade=fixed, jpeg=args.jpeg_quality,
-                                     jpeg_subsample=args.jpeg_subsample == "420", psf=eval_psf(args))
+        if args.degrade == "second_order":
+            from .sr_datasets import SecondOrderSpec
+            second = SecondOrderSpec() if args.jpeg_quality is None else SecondOrderSpec(jpeg_quality=(args.jpeg_quality,) * 2)
+        test_loader = SynthLRBatches(test_loader, scale_int, args.synth_lr_bits, device, degrade=fixed,
+                                     jpeg=None if second is not None else args.jpeg_quality, jpeg_subsample=args.jpeg_subsample == "420",
+                                     psf=eval_psf(args), second_order=second)
         print(f"[synth_lr] LR = antialiased bicubic /{scale_int} of HR on the device, {args.synth_lr_bits or 'no'}-bit rounding")
         if fixed is not None:
             print(f"[degrade] blind: blur sigma=({fixed.blur[0]:.4g}, {fixed.blur[1]:.4g}) HR px, noise sigma={args.noise_sigma:.4g} / 255 "
@@ -292,7 +303,11 @@ def main(argv=None):
             k = eval_psf(args)
             print(f"[degrade] blur kernel: {k.shape[0]} x {k.shape[0]} table, " + (f"table 0 of {args.blur_psf}" if args.blur_psf is not None else
                                                                                     f"the Gaussian turned by {args.blur_theta:g} degrees"))
-        if args.jpeg_quality is not None:
+        if second is not None:
+            fx2 = second.fixed(None, fixed.noise)
+            print(f"[degrade] second order, fixed: resize x{fx2.r1:.4g}, jpeg {fx2.q1}, blur 2 {fx2.k2.shape[0]} taps, resize x{fx2.r2:.4g} of LR, "
+                  f"noise sigma={fx2.noise2[0] * 255.0:.4g} / 255, jpeg {fx2.q2}, final filter {fx2.k3.shape[0]} taps, chroma {args.jpeg_subsample}")
+        elif args.jpeg_quality is not None:
             print(f"[degrade] jpeg: quality {args.jpeg_quality}, chroma {args.jpeg_subsample}")
     print(f"[data] test samples: {len(test_ds)} | steps: {len(test_loader)}")
 

@@ -24,6 +24,8 @@ compression-artifact reduction with --jpeg_quality LO HI) from the HR directorie
 window of the whole-image degradation, JPEG blocks anchored at the image's (0, 0) (sr_datasets.DeviceRestorePool, csrc/restore.hip).
 `--jpeg_quality LO HI [--jpeg_p P --jpeg_subsample 444|420]` (with either --degrade) sends every 8-bit LR patch through a baseline JPEG
 round trip at a random per-sample quality in a second launch (csrc/jpeg.hip); validation uses the middle of the range.
+`--degrade second_order` runs Real-ESRGAN's chain on the device instead -- blur, resize, noise, JPEG, twice, every sample at its own
+intermediate sizes, then a sinc filter (sr_datasets.DeviceHR2Pool, csrc/filter2d.hip, csrc/ragged.hip).
 `--blur_kernel rotated|mixed` or `--blur_psf FILE` (with --degrade blind) blurs every patch with a 2-D table -- a rotated, generalized or
 plateau Gaussian, or a measured point-spread function -- in the same single launch (csrc/blur2d.hip).
 
@@ -304,10 +306,14 @@ def parse_args(argv=None):
     ap.add_argument("--synth_lr_bits", type=int, choices=[0, 8], default=8,
                     help="additive, with --synth_lr: 8 = round the LR values to k / 255, as an 8-bit LR file would hold them; 0 = keep "
                          "the filtered fp32 values")
-    ap.add_argument("--degrade", type=str, choices=["bicubic", "blind"], default="bicubic",
+    ap.add_argument("--degrade", type=str, choices=["bicubic", "blind", "second_order"], default="bicubic",
                     help="additive, with --synth_lr: blind = every LR training patch is blurred (Gaussian, composed into the bicubic "
                          "taps) and noised with random per-sample parameters on the device (sr_datasets.DegradeSpec, csrc/degrade.hip); "
-                         "validation uses the midpoints of the ranges and fixed noise, the same LR images every epoch")
+                         "validation uses the midpoints of the ranges and fixed noise, the same LR images every epoch.  second_order = "
+                         "Real-ESRGAN's chain on the device -- blur, resize, noise, JPEG, twice, each sample at its own intermediate sizes, "
+                         "then a sinc filter (sr_datasets.SecondOrderSpec / DeviceHR2Pool, csrc/filter2d.hip, csrc/ragged.hip; DESIGN 7p).  "
+                         "Stage 1 takes the options of blind (--blur_sigma, --blur_kernel*, --noise_sigma, --noise_gain, --gray_noise_p, "
+                         "--jpeg_quality); it needs --synth_lr_bits 8")
     ap.add_argument("--blur_sigma", type=float, nargs=2, default=[0.2, 2.0], metavar=("LO", "HI"),
                     help="additive, with --degrade blind: range of the blur sigma in HR pixels, within [0, 2.5]")
     ap.add_argument("--blur_aniso_p", type=float, default=0.5,
@@ -345,6 +351,28 @@ def parse_args(argv=None):
     ap.add_argument("--blur_psf", type=str, default=None, metavar="FILE",
                     help="additive, with --degrade blind: a measured point-spread function, .npy [k][k] or [n][k][k] (k odd <= 21, taps >= 0 "
                          "summing to 1); every training patch is blurred with one of its tables, validation with table 0")
+    ap.add_argument("--blur2_sigma", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="additive, with --degrade second_order: range of the sigmas of the second blur, a rotated Gaussian (default 0.2 1.5)")
+    ap.add_argument("--blur2_p", type=float, default=None,
+                    help="additive, with --degrade second_order: probability of the second blur (default 0.8)")
+    ap.add_argument("--noise2_sigma", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="additive, with --degrade second_order: range of the second noise sigma in 8-bit levels (default 1 25)")
+    ap.add_argument("--jpeg2_quality", type=int, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="additive, with --degrade second_order: quality range of the second JPEG (default 30 95; --jpeg_quality is the first's)")
+    ap.add_argument("--resize_range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="additive, with --degrade second_order: factors of the first resize, LO <= 1 <= HI (default 0.15 1.5)")
+    ap.add_argument("--resize_prob", type=float, nargs=3, default=None, metavar=("UP", "DOWN", "KEEP"),
+                    help="additive, with --degrade second_order: probabilities of the first resize going up, down, or staying (default 0.2 0.7 0.1)")
+    ap.add_argument("--resize2_range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="additive, with --degrade second_order: factors of the second resize, relative to the LR size (default 0.3 1.2)")
+    ap.add_argument("--resize2_prob", type=float, nargs=3, default=None, metavar=("UP", "DOWN", "KEEP"),
+                    help="additive, with --degrade second_order: probabilities of the second resize (default 0.3 0.4 0.3)")
+    ap.add_argument("--sinc_p", type=float, default=None,
+                    help="additive, with --degrade second_order: probability that a blur is a sinc (ringing) filter, at both stages (default 0.1)")
+    ap.add_argument("--final_sinc_p", type=float, default=None,
+                    help="additive, with --degrade second_order: probability of the final sinc filter (default 0.8)")
+    ap.add_argument("--degrade_margin", type=int, default=None,
+                    help="additive, with --degrade second_order: LR pixels around the patch that the chain also runs on (default 8)")
     ap.add_argument("--task", type=str, choices=["sr", "dn", "car"], default="sr",
                     help="additive: sr = super-resolution (as ever); dn = denoising, car = JPEG compression-artifact reduction: the published "
                          "scale-1 SwinIR models (build_restoration_model), trained from the HR directories alone -- every patch is cut at "
@@ -390,16 +418,30 @@ def parse_args(argv=None):
         args.gpu_data = True          # the pairs are made on the device; the HR directories alone are read
     if args.synth_lr and not args.gpu_data:
         ap.error("--synth_lr forms the LR patches on the device: it needs --gpu_data")
-    if args.degrade == "blind":
+    if args.degrade in ("blind", "second_order"):
         if not args.synth_lr:
-            ap.error("--degrade blind degrades HR patches on the device: it needs --synth_lr")
+            ap.error(f"--degrade {args.degrade} degrades HR patches on the device: it needs --synth_lr")
         try:
             degrade_spec(args)
         except ValueError as e:
-            ap.error(f"--degrade blind: {e}")
+            ap.error(f"--degrade {args.degrade}: {e}")
+    second = [n for n in SECOND_ORDER_FLAGS if getattr(args, n) is not None]
+    if args.degrade == "second_order":
+        if args.synth_lr_bits != 8:
+            ap.error("--degrade second_order codes 8-bit LR images: it needs --synth_lr_bits 8")
+        if args.jpeg_p != 1.0:
+            ap.error("--jpeg_p is an option of the single JPEG stage; --degrade second_order codes every patch twice")
+        try:
+            second_order_spec(args)
+        except ValueError as e:
+            ap.error(f"--degrade second_order: {e}")
+        if args.degrade_margin is not None and not 0 <= args.degrade_margin <= 64:
+            ap.error(f"--degrade_margin must be in 0..64 LR pixels (got {args.degrade_margin})")
+    elif second:
+        ap.error(f"--{second[0]} is an option of --degrade second_order")
     mixed_opts = [n for n in ("blur_kernel_prob", "blur_beta_g", "blur_beta_p", "blur_ksize") if getattr(args, n) is not None]
-    if (args.blur_kernel != "axis" or args.blur_psf is not None) and args.degrade != "blind":
-        ap.error("--blur_kernel and --blur_psf shape the blur of --degrade blind: they need it")
+    if (args.blur_kernel != "axis" or args.blur_psf is not None) and args.degrade not in ("blind", "second_order"):
+        ap.error("--blur_kernel and --blur_psf shape the blur of --degrade blind | second_order: they need it")
     if args.blur_psf is not None and args.blur_kernel != "axis":
         ap.error("--blur_psf FILE replaces the generated kernels: it does not go with --blur_kernel rotated | mixed")
     if mixed_opts and args.blur_kernel != "mixed":
@@ -409,7 +451,7 @@ def parse_args(argv=None):
     except (ValueError, OSError) as e:
         ap.error(f"--blur_kernel / --blur_psf: {e}")
     if args.jpeg_quality is None:
-        if args.jpeg_p != 1.0 or args.jpeg_subsample != "444":
+        if args.jpeg_p != 1.0 or (args.jpeg_subsample != "444" and args.degrade != "second_order"):
             ap.error("--jpeg_p and --jpeg_subsample are options of the JPEG stage: they need --jpeg_quality LO HI")
     elif args.task == "sr":
         if not (args.gpu_data and args.synth_lr):
@@ -446,7 +488,7 @@ def parse_args(argv=None):
 
 def degrade_spec(args):
     """The DegradeSpec of the command line (None for --degrade bicubic); --noise_sigma is given in 8-bit levels."""
-    if args.degrade != "blind":
+    if args.degrade not in ("blind", "second_order"):
         return None
     from .sr_datasets import DegradeSpec
     return DegradeSpec(blur_sigma=tuple(args.blur_sigma), blur_aniso_p=args.blur_aniso_p, noise_sigma=tuple(v / 255.0 for v in args.noise_sigma),
@@ -466,11 +508,32 @@ def psf_spec(args):
 
 
 def jpeg_spec(args):
-    """The JpegSpec of the command line (None without --jpeg_quality); it reuses --degrade_seed."""
-    if args.jpeg_quality is None:
+    """The JpegSpec of the command line (None without --jpeg_quality, and with --degrade second_order, whose first JPEG takes the
+    range); it reuses --degrade_seed."""
+    if args.jpeg_quality is None or args.degrade == "second_order":
         return None
     from .sr_datasets import JpegSpec
     return JpegSpec(quality=tuple(args.jpeg_quality), p=args.jpeg_p, subsample=args.jpeg_subsample == "420", seed=args.degrade_seed)
+
+
+SECOND_ORDER_FLAGS = ("blur2_sigma", "blur2_p", "noise2_sigma", "jpeg2_quality", "resize_range", "resize_prob", "resize2_range", "resize2_prob",
+                      "sinc_p", "final_sinc_p", "degrade_margin")
+
+
+def second_order_spec(args):
+    """The SecondOrderSpec of the command line (None unless --degrade second_order): the flags that were given replace Real-ESRGAN's
+    defaults; --noise2_sigma is given in 8-bit levels, --jpeg_quality is the first JPEG's range; it reuses --degrade_seed,
+    --gray_noise_p and --blur_ksize."""
+    if args.degrade != "second_order":
+        return None
+    from .sr_datasets import SecondOrderSpec
+    opts = {k: (v if isinstance(v, float) else tuple(v)) for k, v in (
+        ("blur2_sigma", args.blur2_sigma), ("blur2_p", args.blur2_p), ("jpeg2_quality", args.jpeg2_quality), ("resize_range", args.resize_range),
+        ("resize_prob", args.resize_prob), ("resize2_range", args.resize2_range), ("resize2_prob", args.resize2_prob), ("sinc_p", args.sinc_p),
+        ("final_sinc_p", args.final_sinc_p), ("jpeg_quality", args.jpeg_quality), ("ksize", args.blur_ksize)) if v is not None}
+    if args.noise2_sigma is not None:
+        opts["noise2_sigma"] = tuple(v / 255.0 for v in args.noise2_sigma)
+    return SecondOrderSpec(gray_noise_p=args.gray_noise_p, seed=args.degrade_seed, **opts)
 
 
 def restore_spec(args):
@@ -500,6 +563,7 @@ def saved_args(args) -> dict:
                   "val_bench_metric": args.val_bench_metric is None,
                   "val_crop_border": args.val_crop_border is None, "task": args.task == "sr", "channels": args.channels == 3,
                   "dn_sigma": args.dn_sigma is None, "dn_bits": args.dn_bits == 0}
+    at_default.update({n: getattr(args, n) is None for n in SECOND_ORDER_FLAGS})
     return {k: v for k, v in vars(args).items() if not at_default.get(k, False)}
 
 
@@ -538,17 +602,29 @@ def main(argv=None):
                   f"rounding), jpeg quality in {args.jpeg_quality} chroma {args.jpeg_subsample}, blocks on the image's grid, seed "
                   f"{args.degrade_seed}; validation: sigma={fx.sigma * 255.0:.4g} / 255 quality {fx.jpeg_quality or 'none'}, noise id = image index")
     elif args.synth_lr:
-        from .sr_datasets import DeviceHRPool, Shuffled2DHR, SynthLRBatches, hr_to_tensor3
+        from .sr_datasets import DeviceHR2Pool, DeviceHRPool, Shuffled2DHR, SynthLRBatches, hr_to_tensor3
         raw = Shuffled2DHR(args.data_root, split="train")
-        pool = DeviceHRPool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, device=device,
-                            shard_bytes=(args.gpu_data_shard_mb << 20) or None, augment=args.augment, quant_bits=args.synth_lr_bits,
-                            degrade=degrade_spec(args), rank=rank, jpeg=jpeg_spec(args), psf=psf_spec(args))
+        if args.degrade == "second_order":
+            pool = DeviceHR2Pool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, second_order_spec(args), degrade_spec(args),
+                                 device=device, shard_bytes=(args.gpu_data_shard_mb << 20) or None, augment=args.augment, rank=rank,
+                                 psf=psf_spec(args), margin=8 if args.degrade_margin is None else args.degrade_margin,
+                                 subsample=args.jpeg_subsample == "420", names=[f.name for f in raw.files])
+        else:
+            pool = DeviceHRPool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, device=device,
+                                shard_bytes=(args.gpu_data_shard_mb << 20) or None, augment=args.augment, quant_bits=args.synth_lr_bits,
+                                degrade=degrade_spec(args), rank=rank, jpeg=jpeg_spec(args), psf=psf_spec(args))
         train_loader = sampler = DevicePoolLoader(pool, args.batch_size, rank, world, args.seed)
         valid_ds = Shuffled2DHR(args.data_root, split="valid", transform=hr_to_tensor3)
         if rank == 0:
             print(f"[synth_lr] {len(pool)} HR images in {pool.num_shards} shard(s), {sum(t.numel() for t in pool._host) / 2**20:.1f} MiB "
                   f"decoded; LR = antialiased bicubic /{scale_int} on the device, {args.synth_lr_bits or 'no'}-bit rounding")
-            if args.degrade == "blind":
+            if args.degrade == "second_order":
+                so = second_order_spec(args)
+                print(f"[degrade] second order: window {pool.extent} x {pool.extent} HR px (margin {pool.margin} LR px), resize {list(so.resize_range)} "
+                      f"p={list(so.resize_prob)} then {list(so.resize2_range)} p={list(so.resize2_prob)}, blur 2 p={so.blur2_p:g}, sinc p={so.sinc_p:g} "
+                      f"final p={so.final_sinc_p:g}, jpeg {list(so.jpeg_quality)} then {list(so.jpeg2_quality)} chroma {args.jpeg_subsample}, seed "
+                      f"{args.degrade_seed}; validation: the fixed chain (SecondOrderSpec.fixed), noise id = image index")
+            if args.degrade in ("blind", "second_order"):
                 fx = degrade_spec(args).fixed()
                 print(f"[degrade] blind: blur sigma in {args.blur_sigma} HR px (aniso p={args.blur_aniso_p}), noise sigma in "
                       f"{args.noise_sigma} / 255, gain in {args.noise_gain}, gray p={args.gray_noise_p}, seed {args.degrade_seed}; "
@@ -584,7 +660,7 @@ def main(argv=None):
         valid_loader = RestoreBatches(valid_loader, args.channels, restore_spec(args), args.dn_bits, device)
     if args.synth_lr:
         valid_loader = SynthLRBatches(valid_loader, scale_int, args.synth_lr_bits, device, degrade=degrade_spec(args), jpeg=jpeg_spec(args),
-                                      psf=psf_spec(args))
+                                      jpeg_subsample=args.jpeg_subsample == "420", psf=psf_spec(args), second_order=second_order_spec(args))
 
     if args.task != "sr":
         model = build_restoration_model(args.task, args.channels, args.drop_path_rate, args.window_size)

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import numbers
 import struct
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import threading
 
@@ -817,6 +817,234 @@ def restore_degrade(x: torch.Tensor, noise, noise_ids, gray_noise=False, jpeg_qu
     if any((isinstance(q, bool) or q != 0) for q in qs):
         y = jpeg_roundtrip(y, qs, subsample)
     return y
+
+
+# ---- second-order degradation: signed tables and ragged batches (csrc/filter2d.hip, csrc/ragged.hip) -----------------
+class RaggedExt:
+    """The extents of a ragged batch (include/srk.h "Ragged batches"): `host`, a list of B (h, w), and `dev`, the int32 [B][2] copy the
+    kernels read.  The host copy is what the checks run on: nothing is read back from the device."""
+
+    def __init__(self, ext, device):
+        try:
+            self.host = [(int(h), int(w)) for h, w in ext]
+        except (TypeError, ValueError):
+            raise ValueError(f"extents must be B pairs (h, w) (got {ext!r})") from None
+        if not self.host or any(h < 1 or w < 1 for h, w in self.host):
+            raise ValueError(f"every extent must be >= 1 (got {self.host})")
+        self.dev = torch.tensor(self.host, dtype=torch.int32).to(device)
+
+    def pad(self) -> Tuple[int, int]:
+        return max(h for h, _ in self.host), max(w for _, w in self.host)
+
+
+def _ragged(ext, B: int, Hp: int, Wp: int, device, what: str) -> Optional[RaggedExt]:
+    """ext (None = dense, a list of pairs, or a RaggedExt) checked against a padded [B][.][Hp][Wp] buffer."""
+    if ext is None:
+        return None
+    if not isinstance(ext, RaggedExt):
+        ext = RaggedExt(ext, device)
+    if len(ext.host) != B or any(h > Hp or w > Wp for h, w in ext.host):
+        raise ValueError(f"{what}: {B} extents inside the padded {Hp} x {Wp} are needed (got {ext.host})")
+    return ext
+
+
+def _ext_ptr(ext: Optional[RaggedExt]):
+    return None if ext is None else _p(ext.dev)
+
+
+def _padded_out(out: Optional[torch.Tensor], shape, like: torch.Tensor) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=like.device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or out.device != like.device or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous fp32 {tuple(shape)} on {like.device} (got {out.dtype} {tuple(out.shape)} on {out.device})")
+    return out
+
+
+def pack_filter_tables(tab, B: int):
+    """tab: one [ks][ks] table or B of them (mixed odd sizes allowed) -> (fp32 numpy [B][ks][ks], ks, the B sizes before padding), each
+    checked by blur_kernels.check_filter_table -- finite, sum within 1e-3 of 1, any sign -- and zero-padded, centred, to the largest ks."""
+    from . import blur_kernels as bk
+    import numpy as np
+    if isinstance(tab, torch.Tensor):
+        tab = tab.detach().cpu().numpy()
+    if isinstance(tab, np.ndarray) and tab.ndim == 2:
+        tabs = [bk.check_filter_table(tab)] * B
+    else:
+        tabs = [bk.check_filter_table(t, f"table[{i}]") for i, t in enumerate(tab)]
+    if len(tabs) != B:
+        raise ValueError(f"filter tables: one table or one per sample (B={B}; got {len(tabs)})")
+    ks = max(t.shape[0] for t in tabs)
+    return np.stack([bk.pad_to(t, ks) for t in tabs]), ks, [t.shape[0] for t in tabs]
+
+
+def filter2d(x: torch.Tensor, tab, ext=None, quant_bits: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x CUDA fp32 [B,C,Hp,Wp] filtered with one signed ks x ks table or one per sample (csrc/filter2d.hip, srk_filter2d_f32): a
+    correlation with a reflect-101 border and no normalisation, cv2.filter2D's default and Real-ESRGAN's filter2D -- the rule sinc
+    tables need, and the one every 2-D filter of the second-order chain takes.  ext: None (dense) or the (h, w) of every sample in the
+    padded batch; each must exceed the R = ks // 2 of its sample's OWN table (zero-padding a table to the batch's largest ks adds taps
+    that multiply in-extent pixels by 0: no bit changes).  A delta table passes its sample through bit for bit.  quant_bits 8 rounds to
+    k / 255.  One launch after one small upload."""
+    if x.dim() != 4 or not x.is_cuda or x.dtype != torch.float32 or min(x.shape) < 1:
+        raise ValueError(f"filter2d takes a non-empty CUDA fp32 [B,C,H,W] batch (got {x.dtype} {tuple(x.shape)} on {x.device})")
+    if quant_bits not in (0, 8):
+        raise ValueError(f"filter2d: quant_bits must be 0 or 8 (got {quant_bits!r})")
+    x = x.contiguous()
+    B, Cc, Hp, Wp = x.shape
+    tabs, ks, own = pack_filter_tables(tab, B)
+    e = _ragged(ext, B, Hp, Wp, x.device, "filter2d")
+    for b, (h, w) in enumerate([(Hp, Wp)] * B if e is None else e.host):
+        if min(h, w) <= own[b] // 2:
+            raise ValueError(f"filter2d: sample {b} of {h} x {w} does not exceed the R = {own[b] // 2} of its table")
+    out = _padded_out(out, x.shape, x)
+    k = torch.from_numpy(tabs).to(x.device)
+    check(lib().srk_filter2d_f32(_p(x), _p(k), _p(out), _ext_ptr(e), B, Cc, Hp, Wp, ks, int(quant_bits), _stream()))
+    return out
+
+
+def resize_aa_ragged(x: torch.Tensor, ext_in, ext_out, pad_out=None, quant_bits: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`resize_aa` with a size per sample (csrc/ragged.hip, srk_resize_aa_ragged_f32): sample b of the padded x [B,C,Hp,Wp] is resized
+    from ext_in[b] to ext_out[b] into the top-left of out [B,C,Hop,Wop], bit-identical to `resize_aa` on that sample alone; the rest of
+    out keeps its bits.  ext_in / ext_out: None (dense) or B pairs; pad_out = (Hop, Wop), by default the largest output extents.  The
+    8x limit of `resize_aa` is checked here, on the host copies of the extents (SrkUnsupported).  One launch."""
+    if x.dim() != 4 or not x.is_cuda or x.dtype != torch.float32 or min(x.shape) < 1:
+        raise ValueError(f"resize_aa_ragged takes a non-empty CUDA fp32 [B,C,H,W] batch (got {x.dtype} {tuple(x.shape)} on {x.device})")
+    if quant_bits not in (0, 8):
+        raise ValueError(f"resize_aa_ragged: quant_bits must be 0 or 8 (got {quant_bits!r})")
+    x = x.contiguous()
+    B, Cc, Hp, Wp = x.shape
+    ei = _ragged(ext_in, B, Hp, Wp, x.device, "resize_aa_ragged: ext_in")
+    if ext_out is None and pad_out is None:
+        raise ValueError("resize_aa_ragged: a dense output needs pad_out = (Hop, Wop)")
+    if ext_out is not None and not isinstance(ext_out, RaggedExt):
+        ext_out = RaggedExt(ext_out, x.device)
+    try:
+        Hop, Wop = ext_out.pad() if pad_out is None else (int(v) for v in pad_out)
+    except (TypeError, ValueError):
+        raise ValueError(f"resize_aa_ragged: pad_out must be (Hop, Wop) (got {pad_out!r})") from None
+    if Hop < 1 or Wop < 1:
+        raise ValueError(f"resize_aa_ragged: pad_out must be >= 1 (got {(Hop, Wop)})")
+    eo = _ragged(ext_out, B, Hop, Wop, x.device, "resize_aa_ragged: ext_out")
+    for (h, w), (ho, wo) in zip([(Hp, Wp)] * B if ei is None else ei.host, [(Hop, Wop)] * B if eo is None else eo.host):
+        if h > 8 * ho or w > 8 * wo:
+            raise _lib.SrkUnsupported(f"resize_aa_ragged: {h} x {w} -> {ho} x {wo} shrinks an axis by more than 8x (more than 33 taps)")
+    out = _padded_out(out, (B, Cc, Hop, Wop), x)
+    check(lib().srk_resize_aa_ragged_f32(_p(x), _ext_ptr(ei), _p(out), _ext_ptr(eo), B, Cc, Hp, Wp, Hop, Wop, int(quant_bits), _stream()))
+    return out
+
+
+def _qualities(quality, B: int, what: str):
+    qs = [quality] * B if isinstance(quality, numbers.Real) else list(quality)
+    if len(qs) != B:
+        raise ValueError(f"{what}: one quality or one per sample (B={B}; got {len(qs)})")
+    return [0 if (not isinstance(q, bool) and q == 0) else check_jpeg_quality(q) for q in qs]
+
+
+def jpeg_roundtrip_ragged(x: torch.Tensor, quality, ext=None, subsample: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`jpeg_roundtrip` with a size per sample (csrc/ragged.hip, srk_jpeg_roundtrip_ragged_f32): the block grid and the edge replication
+    of sample b are those of its own extents ext[b], so it is bit-identical to `jpeg_roundtrip` on that sample alone; quality 0 copies
+    the in-extent words.  The padding of out keeps its bits.  One launch after one small upload."""
+    if x.dim() != 4 or not x.is_cuda or x.dtype != torch.float32:
+        raise ValueError(f"jpeg_roundtrip_ragged takes a CUDA fp32 [B,C,H,W] batch (got {x.dtype} {tuple(x.shape)} on {x.device})")
+    B, Cc, Hp, Wp = x.shape
+    if Cc not in (1, 3) or min(B, Hp, Wp) < 1:
+        raise ValueError(f"jpeg_roundtrip_ragged: C must be 1 or 3 and every extent >= 1 (got {tuple(x.shape)})")
+    qs = _qualities(quality, B, "jpeg_roundtrip_ragged")
+    x = x.contiguous()
+    e = _ragged(ext, B, Hp, Wp, x.device, "jpeg_roundtrip_ragged")
+    out = _padded_out(out, x.shape, x)
+    qd = torch.tensor(qs, dtype=torch.int32).to(x.device)
+    check(lib().srk_jpeg_roundtrip_ragged_f32(_p(x), _p(out), _p(qd), _ext_ptr(e), B, Cc, Hp, Wp, int(bool(subsample)), _stream()))
+    return out
+
+
+class SecondOrder(NamedTuple):
+    """The second-order degradation of ONE sample (Real-ESRGAN's chain; sr_datasets.SecondOrderSpec draws it): tables k1 / k2 / k3 for
+    the three filters (blur_kernels; a delta = no filter), resize factors r1 / r2 of the two intermediate sizes, noise1 / noise2 =
+    (sigma_n, gain) with their gray flags, JPEG qualities q1 (stage 1) and q2 (stage 2), `jpeg_last`: False = order A (JPEG 2, final
+    resize, final filter), True = order B (final resize, final filter, JPEG 2); the Philox key of noise 1 (noise 2 takes its
+    complement)."""
+    k1: object
+    r1: float
+    noise1: Tuple[float, float]
+    gray1: bool
+    q1: int
+    k2: object
+    r2: float
+    noise2: Tuple[float, float]
+    gray2: bool
+    q2: int
+    jpeg_last: bool
+    k3: object
+    noise_id: int
+
+
+def second_order_sizes(H: int, W: int, scale: int, p: SecondOrder):
+    """((h1, w1), (h2, w2), (ho, wo)) of one sample: round-half-up of H r1, of (H / scale) r2, and the dense output H / scale."""
+    rnd = lambda v: max(1, int(v + 0.5))          # noqa: E731
+    s = int(scale)
+    return (rnd(H * p.r1), rnd(W * p.r1)), (rnd(H / s * p.r2), rnd(W / s * p.r2)), (H // s, W // s)
+
+
+def second_order_noise_ids(p: SecondOrder) -> Tuple[int, int]:
+    i = int(p.noise_id) & 0xFFFFFFFFFFFFFFFF
+    return i, i ^ 0xFFFFFFFFFFFFFFFF
+
+
+def degrade_second_order(x: torch.Tensor, scale: int, params, subsample: bool = False, pads=None, bufs: Optional[dict] = None) -> torch.Tensor:
+    """The second-order blind degradation on a batch x CUDA fp32 [B,C,H,W] (C = 1 or 3; H, W multiples of `scale` in 1..4), one
+    `SecondOrder` per sample -> the LR batch [B,C,H/scale,W/scale] in 8-bit levels:
+        filter k1 -> resize to (H, W) r1 -> noise 1 -> JPEG q1 -> filter k2 -> resize to (H, W) / scale r2 -> noise 2
+        -> [order A: JPEG q2] -> resize to (H, W) / scale -> filter k3, rounded to 8 bits -> [order B: JPEG q2]
+    Every filter is `filter2d` (reflect border), every intermediate is a ragged batch in a padded buffer, so every sample has its own
+    sizes and every stage is ONE launch: eleven launches and their small uploads, no host read, no intermediate copy.  Each sample is
+    bit-identical to the composition of the dense ops on that sample alone.  pads = ((Hp1, Wp1), (Hp2, Wp2)) fixes the padded sizes
+    (default: the batch's largest); bufs: a dict that keeps the work buffers between calls."""
+    if x.dim() != 4 or not x.is_cuda or x.dtype != torch.float32:
+        raise ValueError(f"degrade_second_order takes a CUDA fp32 [B,C,H,W] batch (got {x.dtype} {tuple(x.shape)} on {x.device})")
+    s = int(scale)
+    B, Cc, H, W = x.shape
+    if not 1 <= s <= 4 or H % s or W % s or Cc not in (1, 3) or min(B, H // s, W // s) < 1:
+        raise ValueError(f"degrade_second_order: scale in 1..4 dividing H and W, C 1 or 3 (got scale {scale!r}, {tuple(x.shape)})")
+    ps = list(params)
+    if len(ps) != B or not all(isinstance(p, SecondOrder) for p in ps):
+        raise ValueError(f"degrade_second_order: one SecondOrder per sample (B={B}; got {len(ps)})")
+    sizes = [second_order_sizes(H, W, s, p) for p in ps]
+    e1, e2 = RaggedExt([z[0] for z in sizes], x.device), RaggedExt([z[1] for z in sizes], x.device)
+    (Hp1, Wp1), (Hp2, Wp2) = (e1.pad(), e2.pad()) if pads is None else pads
+    Ho, Wo = H // s, W // s
+    bufs = {} if bufs is None else bufs
+
+    def buf(name, *shape):
+        t = bufs.get(name)
+        if t is None or tuple(t.shape) != shape or t.device != x.device:
+            t = bufs[name] = torch.empty(shape, dtype=torch.float32, device=x.device)
+        return t
+
+    ids = [second_order_noise_ids(p) for p in ps]
+    qa = [0 if p.jpeg_last else p.q2 for p in ps]
+    qb = [p.q2 if p.jpeg_last else 0 for p in ps]
+    x = x.contiguous()
+    a = filter2d(x, [p.k1 for p in ps], out=buf("f1", B, Cc, H, W))
+    a = resize_aa_ragged(a, None, e1, (Hp1, Wp1), out=buf("a1", B, Cc, Hp1, Wp1))
+    a = _noise_into(a, [p.noise1 for p in ps], [i[0] for i in ids], [p.gray1 for p in ps], buf("b1", B, Cc, Hp1, Wp1))
+    a = jpeg_roundtrip_ragged(a, [p.q1 for p in ps], e1, subsample, out=buf("a1", B, Cc, Hp1, Wp1))
+    a = filter2d(a, [p.k2 for p in ps], e1, out=buf("b1", B, Cc, Hp1, Wp1))
+    a = resize_aa_ragged(a, e1, e2, (Hp2, Wp2), out=buf("a2", B, Cc, Hp2, Wp2))
+    a = _noise_into(a, [p.noise2 for p in ps], [i[1] for i in ids], [p.gray2 for p in ps], buf("b2", B, Cc, Hp2, Wp2))
+    a = jpeg_roundtrip_ragged(a, qa, e2, subsample, out=buf("a2", B, Cc, Hp2, Wp2))
+    a = resize_aa_ragged(a, e2, None, (Ho, Wo), out=buf("lr0", B, Cc, Ho, Wo))
+    a = filter2d(a, [p.k3 for p in ps], quant_bits=8, out=buf("lr1", B, Cc, Ho, Wo))
+    return jpeg_roundtrip(a, qb, subsample)
+
+
+def _noise_into(x: torch.Tensor, amp, noise_ids, gray, out: torch.Tensor) -> torch.Tensor:
+    """`noise` into a given buffer: on a padded batch the counter is (x, y, ch) only, so inside a sample's extents the bits are those of
+    the dense call on that sample; what lands in the padding is never read."""
+    B, Cc, H, W = x.shape
+    rows = [pack_restore_params(0, n, i, g) for n, i, g in zip(amp, noise_ids, gray)]
+    par = torch.tensor(rows, dtype=torch.int64).to(x.device)
+    check(lib().srk_noise_f32(_p(x), _p(out), _p(par), B, Cc, H, W, 0, _stream()))
+    return out
 
 
 LUMA_COEF = (4899, 9617, 1868)          # /16384: full-range BT.601 in 14-bit fixed point, the sum is 16384

@@ -499,6 +499,165 @@ class PsfSpec:
         return self._tables[0] if self._tables is not None else None
 
 
+def _check_prob3(name: str, p) -> Tuple[float, float, float]:
+    try:
+        prob = tuple(float(v) for v in p)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be three numbers UP DOWN KEEP (got {p!r})") from None
+    if len(prob) != 3 or not all(0.0 <= v <= 1.0 for v in prob) or abs(sum(prob) - 1.0) > 1e-6:
+        raise ValueError(f"{name} must be three probabilities UP DOWN KEEP that sum to 1 (got {p!r})")
+    return prob
+
+
+def _check_factors(name: str, r) -> Tuple[float, float]:
+    try:
+        lo, hi = (float(v) for v in r)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be two numbers LO HI (got {r!r})") from None
+    if not 0.125 <= lo <= 1.0 <= hi <= 2.0:          # also refuses NaN; below 1/8 the resize has more than 33 taps
+        raise ValueError(f"{name} must satisfy 0.125 <= LO <= 1 <= HI <= 2 (got {lo} {hi})")
+    return lo, hi
+
+
+SECOND_ORDER_VARIATES = 23          # per SecondOrderSpec.draw, whatever they decide
+
+
+@dataclass(frozen=True)
+class SecondOrderSpec:
+    """The random second-order degradation of `--degrade second_order` (Real-ESRGAN's chain and defaults): what one
+    `ops.SecondOrder` is drawn from, on top of the first-order draws that stage 1 reuses -- the blur table of the 7n pool (PsfSpec on
+    DegradeSpec's sigmas) and DegradeSpec's noise, gray flag and noise id.
+    Stage 1: with probability `sinc_p` the table is a sinc filter instead; a resize by a factor that goes up / down / stays with
+    probabilities `resize_prob`, uniform in [1, HI] / [LO, 1] of `resize_range`; JPEG at a quality uniform in `jpeg_quality`.
+    Stage 2: with probability `blur2_p` a filter -- a sinc with probability `sinc_p`, else a rotated anisotropic Gaussian with sigmas
+    uniform in `blur2_sigma` -- else none (a table that would not fit the size it filters, R >= an extent, is dropped at any stage);
+    `resize2_prob` / `resize2_range` relative to the LR size; noise uniform in `noise2_sigma` / `noise2_gain`, gray with `gray_noise_p`;
+    JPEG at `jpeg2_quality`, before or after the final resize and filter with equal probability.
+    Final: with probability `final_sinc_p` a sinc filter.  A sinc table has an odd side uniform in `ksize` and a cutoff uniform in
+    [pi/3, pi] for sides below 13, else [pi/5, pi].
+    Everything comes from the spec's OWN generator `random.Random(f"degrade2:{seed + rank}")`, 23 variates per draw whatever they
+    decide: the global `random` state and the other specs' generators never see it."""
+    resize_prob: Tuple[float, float, float] = (0.2, 0.7, 0.1)
+    resize_range: Tuple[float, float] = (0.15, 1.5)
+    resize2_prob: Tuple[float, float, float] = (0.3, 0.4, 0.3)
+    resize2_range: Tuple[float, float] = (0.3, 1.2)
+    blur2_p: float = 0.8
+    blur2_sigma: Tuple[float, float] = (0.2, 1.5)
+    sinc_p: float = 0.1
+    final_sinc_p: float = 0.8
+    ksize: Tuple[int, int] = (7, 21)
+    noise2_sigma: Tuple[float, float] = (1.0 / 255.0, 25.0 / 255.0)
+    noise2_gain: Tuple[float, float] = (0.0, 0.0)
+    gray_noise_p: float = 0.4
+    jpeg_quality: Tuple[int, int] = (30, 95)
+    jpeg2_quality: Tuple[int, int] = (30, 95)
+    seed: int = 0
+
+    def __post_init__(self):
+        from . import blur_kernels as bk
+        from .ops import check_jpeg_quality
+        object.__setattr__(self, "resize_prob", _check_prob3("resize_prob", self.resize_prob))
+        object.__setattr__(self, "resize2_prob", _check_prob3("resize2_prob", self.resize2_prob))
+        object.__setattr__(self, "resize_range", _check_factors("resize_range", self.resize_range))
+        object.__setattr__(self, "resize2_range", _check_factors("resize2_range", self.resize2_range))
+        for name in ("blur2_p", "sinc_p", "final_sinc_p", "gray_noise_p"):
+            if not 0.0 <= float(getattr(self, name)) <= 1.0:          # also refuses NaN
+                raise ValueError(f"{name} must be a probability (got {getattr(self, name)!r})")
+        lo, hi = _check_range("blur2_sigma", self.blur2_sigma, 10.0)
+        if lo <= 0.0:
+            raise ValueError(f"blur2_sigma must be > 0 (got {lo} {hi})")
+        object.__setattr__(self, "blur2_sigma", (lo, hi))
+        object.__setattr__(self, "noise2_sigma", _check_range("noise2_sigma", self.noise2_sigma, 1.0))
+        object.__setattr__(self, "noise2_gain", _check_range("noise2_gain", self.noise2_gain, 1.0))
+        try:
+            lo, hi = self.ksize
+            lo, hi = bk.check_ks(lo), bk.check_ks(hi)
+        except (TypeError, ValueError):
+            raise ValueError(f"ksize must be two odd integers LO HI in 1..{bk.KS_MAX} (got {self.ksize!r})") from None
+        if lo > hi:
+            raise ValueError(f"ksize must satisfy LO <= HI (got {lo} {hi})")
+        object.__setattr__(self, "ksize", (lo, hi))
+        for name in ("jpeg_quality", "jpeg2_quality"):
+            try:
+                lo, hi = getattr(self, name)
+            except (TypeError, ValueError):
+                raise ValueError(f"{name} must be two integers LO HI (got {getattr(self, name)!r})") from None
+            lo, hi = check_jpeg_quality(lo, f"{name} LO"), check_jpeg_quality(hi, f"{name} HI")
+            if lo > hi:
+                raise ValueError(f"{name} must satisfy 1 <= LO <= HI <= 100 (got {lo} {hi})")
+            object.__setattr__(self, name, (lo, hi))
+
+    def rng(self, rank: int = 0) -> random.Random:
+        return random.Random(f"degrade2:{int(self.seed) + int(rank)}")
+
+    def _ks(self, u: float) -> int:
+        lo, hi = self.ksize
+        n = (hi - lo) // 2 + 1
+        return lo + 2 * min(int(u * n), n - 1)
+
+    @staticmethod
+    def _cutoff(ks: int, u: float) -> float:
+        lo = math.pi / 3.0 if ks < 13 else math.pi / 5.0
+        return lo + u * (math.pi - lo)
+
+    @staticmethod
+    def _factor(prob, rng_, u_kind: float, u: float) -> float:
+        lo, hi = rng_
+        if u_kind < prob[0]:
+            return 1.0 + u * (hi - 1.0)
+        if u_kind < prob[0] + prob[1]:
+            return lo + u * (1.0 - lo)
+        return 1.0
+
+    @staticmethod
+    def _quality(q, u: float) -> int:
+        return min(q[0] + int(u * (q[1] - q[0] + 1)), q[1])
+
+    def draw(self, rng: random.Random, table1, noise1, noise_id: int, gray1: bool, colour: bool, extent: int, scale: int):
+        """-> the `ops.SecondOrder` of one sample.  table1, noise1, noise_id, gray1: the first-order draws (PsfSpec.draw or a Gaussian
+        of DegradeSpec's sigmas; DegradeSpec.draw).  extent: the side of the square window the chain runs on at factor `scale`: it
+        bounds filter 2, and factor 2 is raised where the second resize would shrink by more than the resampler's 8x (an upscale by
+        1.5 followed by 0.3 / 4 is 20x; Real-ESRGAN's resize has no such limit because it does not antialias)."""
+        from . import blur_kernels as bk
+        from .ops import SecondOrder
+        u = [rng.random() for _ in range(SECOND_ORDER_VARIATES)]
+        ks1 = self._ks(u[2])
+        k1 = bk.sinc(self._cutoff(ks1, u[1]), ks1) if (u[0] < self.sinc_p and ks1 // 2 < extent) else table1
+        r1 = self._factor(self.resize_prob, self.resize_range, u[3], u[4])
+        ks2 = self._ks(u[9])
+        if u[6] >= self.blur2_p or ks2 // 2 >= max(1, int(extent * r1 + 0.5)):
+            k2 = bk.delta()
+        elif u[7] < self.sinc_p:
+            k2 = bk.sinc(self._cutoff(ks2, u[8]), ks2)
+        else:
+            lo, hi = self.blur2_sigma
+            k2 = bk.gaussian(ks2, lo + u[10] * (hi - lo), lo + u[11] * (hi - lo), math.pi * (u[12] - 0.5))
+        r2 = self._factor(self.resize2_prob, self.resize2_range, u[13], u[14])
+        h1 = max(1, int(extent * r1 + 0.5))
+        r2 = max(r2, (-(-h1 // 8) * int(scale) + 1e-6) / extent)
+        noise2 = (self.noise2_sigma[0] + u[15] * (self.noise2_sigma[1] - self.noise2_sigma[0]),
+                  self.noise2_gain[0] + u[16] * (self.noise2_gain[1] - self.noise2_gain[0]))
+        ks3 = self._ks(u[22])
+        k3 = bk.sinc(self._cutoff(ks3, u[21]), ks3) if (u[20] < self.final_sinc_p and ks3 // 2 < extent // int(scale)) else bk.delta()
+        return SecondOrder(k1, r1, tuple(noise1), bool(gray1), self._quality(self.jpeg_quality, u[5]), k2, r2, noise2,
+                           u[17] < self.gray_noise_p or not colour, self._quality(self.jpeg2_quality, u[18]), u[19] < 0.5, k3, int(noise_id))
+
+    def fixed(self, table1, noise1, gray1: bool = False, noise_id: int = 0):
+        """What validation scores, every epoch and every run: no sinc at stages 1 and 2 (sinc_p < 0.5, else a sinc at the middle
+        cutoff of a 13-tap table), the middle of the DOWN range at both resizes, an isotropic Gaussian at the middle `blur2_sigma`
+        when blur2_p >= 0.5, the middle noise and qualities, order A (JPEG before the final resize), and when final_sinc_p >= 0.5 a
+        13-tap final sinc at the middle of its cutoff range.  table1 / noise1 / gray1: the fixed first-order stage (FixedDegrade)."""
+        from . import blur_kernels as bk
+        from .ops import SecondOrder
+        mid = lambda r: 0.5 * (r[0] + r[1])          # noqa: E731
+        sinc13 = bk.sinc(self._cutoff(13, 0.5), 13)
+        k2 = bk.delta() if self.blur2_p < 0.5 else (sinc13 if self.sinc_p >= 0.5 else bk.gaussian(13, mid(self.blur2_sigma), mid(self.blur2_sigma)))
+        return SecondOrder(sinc13 if self.sinc_p >= 0.5 else table1, 0.5 * (self.resize_range[0] + 1.0), tuple(noise1), bool(gray1),
+                           round(mid(self.jpeg_quality)), k2, 0.5 * (self.resize2_range[0] + 1.0),
+                           (mid(self.noise2_sigma), mid(self.noise2_gain)), self.gray_noise_p >= 0.5, round(mid(self.jpeg2_quality)), False,
+                           sinc13 if self.final_sinc_p >= 0.5 else bk.delta(), int(noise_id))
+
+
 class DeviceHRPool(_DeviceImagePool):
     """Training pairs from HR images only (`--synth_lr`): the pool holds the decoded HR images -- half the device memory of a
     DevicePairPool at x2, no LR files to keep in sync -- and `sample` makes the HR patch AND its antialiased bicubic degradation
@@ -623,6 +782,105 @@ class DeviceHRPool(_DeviceImagePool):
         return lr, hr
 
 
+def stage1_table(blur):
+    """The stage-1 table of the second-order chain when no PsfSpec shapes it: the axis-aligned Gaussian of DegradeSpec's
+    (sigma_y, sigma_x), R = min(ceil(3 sigma), 10), as a 2-D table (the chain filters with `ops.filter2d` only)."""
+    from . import blur_kernels as bk
+    sy, sx = (float(v) for v in blur)
+    ks = 2 * min(math.ceil(3.0 * max(0.0, sy, sx)), 10) + 1
+    return bk.gaussian(ks, max(sx, PSF_SIGMA_FLOOR), max(sy, PSF_SIGMA_FLOOR), 0.0)
+
+
+def second_order_window(top: int, left: int, Hr: int, Wr: int, s: int, P: int, m: int):
+    """The E x E window, E = s (P + 2 m), that the chain of an HR patch at (top, left) runs on, inside the image's Hr x Wr region: cut
+    at the patch origin minus s m, then clamped into the region.  -> (window top, window left, LR row, LR column of the patch in it)."""
+    E = s * (P + 2 * m)
+    wt, wl = min(max(top - s * m, 0), Hr - E), min(max(left - s * m, 0), Wr - E)
+    return wt, wl, (top - wt) // s, (left - wl) // s
+
+
+class DeviceHR2Pool(DeviceHRPool):
+    """Training pairs under the second-order degradation (`--degrade second_order`).  `draw` is DeviceHRPool's: from one
+    `random` state both pools cut the same HR patches and D4 codes, and the HR patch is `srk_crop_u8`'s -- bit-identical to
+    srk_paired_crop_u8's.  The chain changes sizes per sample and filters with a reflect border, so it cannot run on a window of the
+    whole image bit for bit; it runs on an EXTENDED window of E = s (P + 2 m) HR pixels around the patch (`margin` m LR pixels, cut at
+    the patch origin minus s m and clamped into the image's (H - H % s, W - W % s) region), and the LR patch is the P x P window of
+    `ops.degrade_second_order`'s output at the patch's offset: the margin keeps the reflected border, the JPEG grid's edge and the
+    resize's border taps away from the patch.  Noise is keyed on window coordinates.
+    Stage 1 reuses ``degrade`` (a DegradeSpec: sigmas, noise, gray flag, noise id) and ``psf`` (a PsfSpec shaping the table; None =
+    the axis-aligned Gaussian as a table); ``spec`` (a SecondOrderSpec) draws the rest from its own generator.  An image whose region
+    is smaller than E is refused at construction.  The padded work buffers have the spec's largest sizes and are kept between calls:
+    the launches and their shapes are the same every step."""
+
+    def __init__(self, images, lr_patch: int, scale: int, spec: "SecondOrderSpec", degrade: Optional[DegradeSpec] = None, device="cuda",
+                 shard_bytes: Optional[int] = None, augment: str = "none", rank: int = 0, psf: Optional[PsfSpec] = None, margin: int = 8,
+                 subsample: bool = False, names=None):
+        if not isinstance(spec, SecondOrderSpec):
+            raise ValueError(f"spec must be a SecondOrderSpec (got {type(spec).__name__})")
+        if isinstance(margin, bool) or int(margin) != margin or not 0 <= int(margin) <= 64:
+            raise ValueError(f"margin must be an integer in 0..64 LR pixels (got {margin!r})")
+        self.spec, self._spec_rng, self.margin, self.subsample = spec, spec.rng(rank), int(margin), bool(subsample)
+        self.extent = int(scale) * (int(lr_patch) + 2 * self.margin)
+        self._names = None if names is None else list(names)
+        self._bufs: dict = {}
+        super().__init__(images, lr_patch, scale, device, shard_bytes, augment, 8, degrade if degrade is not None else DegradeSpec(), rank, None, psf)
+        rnd = lambda v: max(1, int(v + 0.5))          # noqa: E731
+        E, s = self.extent, self.scale
+        self.pads = ((rnd(E * spec.resize_range[1]),) * 2, (rnd(E / s * spec.resize2_range[1]),) * 2)
+
+    def _check_group(self, hr) -> None:
+        super()._check_group(hr)
+        _, hh, hw, _ = hr
+        s, E = self.scale, self.extent
+        if hh - hh % s < E or hw - hw % s < E:
+            i = len(self.meta)
+            name = self._names[i] if self._names is not None and i < len(self._names) else f"image {i}"
+            raise ValueError(f"{name}: its ({hh - hh % s},{hw - hw % s}) region is smaller than the {E} x {E} window of the second-order "
+                             f"degradation (LR patch {self.lr_patch} + 2 x margin {self.margin}, scale {s})")
+
+    def draw_second_order(self, hd):
+        """-> (window descriptors, LR offsets of the patches in their windows, one ops.SecondOrder per sample): DegradeSpec's and
+        PsfSpec's draws in DeviceHRPool's order, then SecondOrderSpec's; the global `random` state is not touched."""
+        P, s, m = self.lr_patch, self.scale, self.margin
+        wd, offs, params = [], [], []
+        for ho, hh, hw, hc, top, left in hd:
+            wt, wl, oy, ox = second_order_window(top, left, hh - hh % s, hw - hw % s, s, P, m)
+            wd.append((ho, hh, hw, hc, wt, wl))
+            offs.append((oy, ox))
+            colour = (hc & 0xff) == 3
+            blur, noise, nid, gray = self.degrade.draw(self._degrade_rng, colour=colour)
+            table1 = self.psf.draw(self._psf_rng, blur) if self.psf is not None else stage1_table(blur)
+            params.append(self.spec.draw(self._spec_rng, table1, noise, nid, gray, colour, self.extent, s))
+        return wd, offs, params
+
+    def _crop(self, pool, rows, patch: int) -> torch.Tensor:
+        from ._lib import check, lib
+        desc = torch.tensor(rows, dtype=torch.int64).to(self.device)
+        out = torch.empty(len(rows), 3, patch, patch, dtype=torch.float32, device=self.device)
+        check(lib().srk_crop_u8(pool.data_ptr(), desc.data_ptr(), out.data_ptr(), len(rows), patch, torch.cuda.current_stream(self.device).cuda_stream))
+        return out
+
+    def sample(self, indices):
+        """-> (lr [B,3,P,P], hr [B,3,P*s,P*s]) fp32 on the device."""
+        from .ops import degrade_second_order
+        P, s = self.lr_patch, self.scale
+        pool = self._batch_pool(indices)
+        hd, codes = self.draw(indices)
+        wd, offs, params = self.draw_second_order(hd)
+        hr = self._crop(pool, hd, P * s)
+        whole = degrade_second_order(self._crop(pool, wd, self.extent), s, params, self.subsample, self.pads, self._bufs)
+        if len(set(offs)) == 1:
+            (oy, ox), = set(offs)
+            lr = whole[:, :, oy:oy + P, ox:ox + P].contiguous()
+        else:
+            lr = torch.stack([whole[b, :, oy:oy + P, ox:ox + P] for b, (oy, ox) in enumerate(offs)])
+        if any(codes):
+            from .augment import dihedral
+            ops = torch.tensor(codes, dtype=torch.int32).to(self.device)
+            lr, hr = dihedral(lr, ops), dihedral(hr, ops)
+        return lr, hr
+
+
 class SynthLRBatches:
     """Wraps a loader of HR batches [B,3,H,W] into the (lr, hr) batches of `--synth_lr` validation / evaluation: each HR batch goes to
     the device, is cropped to a multiple of the factor and degraded there (ops.degrade_aa) -- the whole-image form of what
@@ -636,10 +894,21 @@ class SynthLRBatches:
     no such stage): the whole degraded LR image goes through `ops.jpeg_roundtrip`, the same every epoch.  Needs ``quant_bits`` 8.
 
     ``psf`` (one ks x ks table, or a PsfSpec standing for its `fixed()` table -- table 0 of a PSF file, None otherwise; needs
-    ``degrade``): the table replaces the Gaussian of ``degrade`` (ops.degrade_psf); the noise stays."""
+    ``degrade``): the table replaces the Gaussian of ``degrade`` (ops.degrade_psf); the noise stays.
 
-    def __init__(self, loader, scale: int, quant_bits: int, device, degrade=None, jpeg=None, jpeg_subsample: bool = False, psf=None):
+    ``second_order`` (a SecondOrderSpec standing for its `fixed()` chain; needs ``degrade`` and ``quant_bits`` 8, takes no ``jpeg``):
+    the whole cropped image goes through `ops.degrade_second_order` with ``degrade`` / ``psf`` as its stage 1; the noise id is the
+    image's index in the split, the same every epoch."""
+
+    def __init__(self, loader, scale: int, quant_bits: int, device, degrade=None, jpeg=None, jpeg_subsample: bool = False, psf=None,
+                 second_order=None):
         self.loader, self.scale, self.quant_bits, self.device = loader, int(scale), int(quant_bits), torch.device(device)
+        if second_order is not None:
+            if not isinstance(second_order, SecondOrderSpec):
+                raise ValueError(f"second_order must be a SecondOrderSpec (got {type(second_order).__name__})")
+            if degrade is None or self.quant_bits != 8 or jpeg is not None:
+                raise ValueError("second_order= needs degrade= (its stage 1), quant_bits 8, and takes its JPEG qualities from the spec (no jpeg=)")
+        self.second_order = second_order
         if isinstance(psf, PsfSpec):
             psf = psf.fixed()
         if psf is not None:
@@ -681,7 +950,14 @@ class SynthLRBatches:
             gray = [True] * B
             if hr.shape[1] == 3 and not self.degrade.gray_noise:
                 gray = ((hr[:, 0] == hr[:, 1]) & (hr[:, 0] == hr[:, 2])).flatten(1).all(dim=1).tolist()
-            if self.psf is not None:
+            if self.second_order is not None:
+                from .ops import degrade_second_order
+                H, W = hr.shape[-2:]
+                hr = hr[..., :H - H % self.scale, :W - W % self.scale].contiguous()
+                table1 = self.psf if self.psf is not None else stage1_table(self.degrade.blur)
+                params = [self.second_order.fixed(table1, self.degrade.noise, gray[b], first + b) for b in range(B)]
+                yield degrade_second_order(hr, self.scale, params, self.jpeg_subsample), hr
+            elif self.psf is not None:
                 yield degrade_psf(hr, self.scale, self.psf, self.degrade.noise, range(first, first + B), gray, self.quant_bits)
             else:
                 yield degrade_blind(hr, self.scale, self.degrade.blur, self.degrade.noise, range(first, first + B), gray, self.quant_bits)
