@@ -434,6 +434,32 @@ int srk_jpeg_roundtrip_ragged_f32(const float* x, float* out, const int32_t* qua
                                   int subsample, srk_stream_t stream);
 /* The noise stage of a ragged chain is srk_noise_f32 on the padded buffer: its counter is (x, y, ch) only, so inside the extents its
  * bits are those of the dense call on the sample alone; what it writes into the padding is never read. */
+/* Blur and sinc tables built on the device (csrc/tables.hip): n tables of srk_blur2d_f32 / srk_crop_degrade_psf_u8 / srk_filter2d_f32
+ * from a few numbers each, so that the host draws variates and uploads no table.  tab = DEVICE fp32 [n][ks][ks], ks odd in 1..21;
+ * desc = DEVICE fp64 [n][8] = (kind, ks_own, A, B2, C, beta, cutoff, bank_index), the integers carried exactly as doubles; bank =
+ * DEVICE fp32 [n_bank][kb][kb] (measured PSFs the host has checked) or NULL with n_bank = kb = 0.
+ * Table i has side ks_own <= ks (kind 5: kb), centred in its ks x ks slot and surrounded by +0 words.  With R = (ks_own - 1) / 2,
+ * row a <-> y = a - R, column b <-> x = b - R, the unnormalised tap e(x, y) in fp64 is
+ *   kind 0 delta        the centre tap 1, every other tap +0; written as such
+ *   kind 1 gaussian     exp(-0.5 q)
+ *   kind 2 generalized  exp(-0.5 pow(q, beta))
+ *   kind 3 plateau      1 / (pow(q, beta) + 1)
+ *   kind 4 sinc         cutoff J1(cutoff r) / (2 pi r), r = sqrt(x^2 + y^2); the centre tap cutoff^2 / (4 pi)
+ *   kind 5 bank         the words of bank[bank_index], copied: no arithmetic, -0 / denormals / NaN payloads kept
+ * q = (A x^2 + B2 x y) + C y^2 with the integer products exact and no contraction: A, B2, C are the coefficients of the inverse
+ * covariance, which the host forms (blur_kernels._quad_coef), so q has the host's bits.  J1(z) is the trapezoid rule on Bessel's
+ * integral, (sum over j = 1..511 ascending of f_j, + 0.5 (f_0 + f_512)) / 512 with f_j = cos(t_j - z sin t_j), t_j = j (pi / 512),
+ * t_512 = pi; it is evaluated ONCE per distinct x^2 + y^2 of the grid and looked up by that integer, so a sinc table is exactly 8-fold
+ * symmetric.  Kinds 1..4: S = the fp64 sum of e over the own ks_own^2 taps, sequential, row-major ascending from 0; the tap is
+ * (float)(e / S), one IEEE division and one rounding; fp32 denormal results are kept.  This order is the contract: it does not depend
+ * on the launch shape, and equal descriptors give equal words wherever they stand in the batch.
+ * The host that wrote desc checks it (ops.kernel_tables does); for ANY bit pattern in desc the kernel stays inside its buffers:
+ * kind outside [0, 6) or NaN counts as 0, kind 5 with a NULL bank as 0, ks_own is clamped into 1..ks (NaN: 1) and an even value lowered
+ * by one, bank_index is clamped into 0..n_bank-1 (NaN: 0); a NaN parameter gives a NaN table.  One launch, one workgroup per table, no
+ * device allocation; nothing outside tab[0 .. n*ks*ks) is written.  tab must overlap neither desc nor bank.
+ * SRK_E_NULL: null desc / tab; SRK_E_SHAPE: n < 1, ks even or outside 1..21, a bank triple that is neither (NULL, 0, 0) nor
+ * (pointer, n_bank >= 1, kb odd in 1..ks), an overlap. */
+int srk_kernel_tables_f32(const double* desc, const float* bank, int n_bank, int kb, float* tab, int n, int ks, srk_stream_t stream);
 /* Tiled inference (csrc/tile.hip): crop a chunk of overlapping tiles out of an fp32 NCHW batch, run a model on them as a batch of
  * n * B, and merge the chunk's outputs into the output image.
  * Tile grid, per axis with extent N, tile t (1 <= t <= N) and stride s (1 <= s <= t; overlap = t - s): k = ceil((N - t) / s) + 1

@@ -117,6 +117,7 @@ _SIGNATURES = {
     "srk_noise_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "srk_crop_restore_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "srk_filter2d_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "srk_kernel_tables_f32": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     "srk_resize_aa_ragged_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "srk_jpeg_roundtrip_ragged_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "srk_tile_gather_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

@@ -12,6 +12,7 @@ correlation, so what matters for an asymmetric table is this orientation and not
 from __future__ import annotations
 
 import math
+from typing import NamedTuple, Tuple
 
 import numpy as np
 
@@ -36,16 +37,23 @@ def _grid(ks: int):
     return _GRIDS[ks]
 
 
-def _quad(ks: int, s1: float, s2: float, theta: float) -> np.ndarray:
-    """q^T Sigma^-1 q with Sigma^-1 = Rot diag(1 / s1^2, 1 / s2^2) Rot^T written out: A x^2 + 2 B x y + C y^2."""
-    ks = check_ks(ks)
+def _quad_coef(s1: float, s2: float, theta: float):
+    """(A, B2, C) of q^T Sigma^-1 q = A x^2 + B2 x y + C y^2 with Sigma^-1 = Rot diag(1 / s1^2, 1 / s2^2) Rot^T written out.  The
+    device builds its tables from these three doubles (TableDesc.row), so its q has the bits of `_quad`'s."""
     s1, s2, theta = float(s1), float(s2), float(theta)
     if not (s1 > 0.0 and s2 > 0.0 and math.isfinite(s1) and math.isfinite(s2) and math.isfinite(theta)):
         raise ValueError(f"blur sigmas must be finite and > 0, theta finite (got {(s1, s2, theta)})")
     c, s = math.cos(theta), math.sin(theta)
     i1, i2 = 1.0 / (s1 * s1), 1.0 / (s2 * s2)
+    return c * c * i1 + s * s * i2, 2.0 * c * s * (i1 - i2), s * s * i1 + c * c * i2
+
+
+def _quad(ks: int, s1: float, s2: float, theta: float) -> np.ndarray:
+    """q^T Sigma^-1 q on the grid of a ks x ks table: (A x^2 + B2 x y) + C y^2."""
+    ks = check_ks(ks)
+    a, b2, c = _quad_coef(s1, s2, theta)
     xx, xy, yy = _grid(ks)
-    return (c * c * i1 + s * s * i2) * xx + (2.0 * c * s * (i1 - i2)) * xy + (s * s * i1 + c * c * i2) * yy
+    return a * xx + b2 * xy + c * yy
 
 
 def _finish(k: np.ndarray) -> np.ndarray:
@@ -163,3 +171,83 @@ def load_psf_file(path: str) -> np.ndarray:
     if a.ndim != 3 or a.shape[0] < 1:
         raise ValueError(f"{path}: a PSF file holds [k][k] or [n][k][k] (got shape {a.shape})")
     return np.stack([check_table(t, f"{path}[{i}]") for i, t in enumerate(a)])
+
+
+# ---- descriptors: a table as eight numbers, for the device to build (include/srk.h: srk_kernel_tables_f32; ops.kernel_tables) ------
+KIND_DELTA, KIND_GAUSSIAN, KIND_GENERALIZED, KIND_PLATEAU, KIND_SINC, KIND_BANK = range(6)
+
+
+class TableDesc(NamedTuple):
+    """What one table is made from: the arguments of `delta` / `gaussian` / `generalized` / `plateau` / `sinc`, or the index of a
+    measured PSF in a bank (`load_psf_file`).  The constructors below take the arguments of those functions and refuse what they
+    refuse, with their errors; `table()` IS that function's table, `row()` the eight doubles the device reads."""
+    kind: int
+    ks: int
+    s1: float = 1.0
+    s2: float = 1.0
+    theta: float = 0.0
+    beta: float = 1.0
+    cutoff: float = 0.0
+    bank_index: int = 0
+
+    @classmethod
+    def delta(cls, ks: int = 1) -> "TableDesc":
+        return cls(KIND_DELTA, check_ks(ks))
+
+    @classmethod
+    def gaussian(cls, ks: int, s1: float, s2: float, theta: float = 0.0) -> "TableDesc":
+        ks = check_ks(ks)
+        _quad_coef(s1, s2, theta)
+        return cls(KIND_GAUSSIAN, ks, float(s1), float(s2), float(theta))
+
+    @classmethod
+    def generalized(cls, ks: int, s1: float, s2: float, theta: float, beta: float) -> "TableDesc":
+        ks = check_ks(ks)
+        _quad_coef(s1, s2, theta)
+        return cls(KIND_GENERALIZED, ks, float(s1), float(s2), float(theta), _beta(beta))
+
+    @classmethod
+    def plateau(cls, ks: int, s1: float, s2: float, theta: float, beta: float) -> "TableDesc":
+        ks = check_ks(ks)
+        _quad_coef(s1, s2, theta)
+        return cls(KIND_PLATEAU, ks, float(s1), float(s2), float(theta), _beta(beta))
+
+    @classmethod
+    def sinc(cls, cutoff: float, ks: int) -> "TableDesc":
+        ks = check_ks(ks)
+        cutoff = float(cutoff)
+        if not 0.0 < cutoff <= math.pi:          # also refuses NaN
+            raise ValueError(f"sinc: the cutoff must be in (0, pi] (got {cutoff!r})")
+        return cls(KIND_SINC, ks, cutoff=cutoff)
+
+    @classmethod
+    def bank(cls, index: int, ks: int) -> "TableDesc":
+        """Table `index` of a bank of checked ks x ks tables (PsfSpec's `file`)."""
+        if isinstance(index, bool) or int(index) != index or int(index) < 0:
+            raise ValueError(f"a bank index is an integer >= 0 (got {index!r})")
+        return cls(KIND_BANK, check_ks(ks), bank_index=int(index))
+
+    def table(self, bank=None) -> np.ndarray:
+        """The host table: the very function of this module (kind 5: the bank's table, which `bank` must then hold)."""
+        if self.kind == KIND_DELTA:
+            return delta(self.ks)
+        if self.kind == KIND_GAUSSIAN:
+            return gaussian(self.ks, self.s1, self.s2, self.theta)
+        if self.kind == KIND_GENERALIZED:
+            return generalized(self.ks, self.s1, self.s2, self.theta, self.beta)
+        if self.kind == KIND_PLATEAU:
+            return plateau(self.ks, self.s1, self.s2, self.theta, self.beta)
+        if self.kind == KIND_SINC:
+            return sinc(self.cutoff, self.ks)
+        if self.kind == KIND_BANK:
+            if bank is None or not 0 <= self.bank_index < len(bank) or tuple(np.shape(bank[self.bank_index])) != (self.ks, self.ks):
+                raise ValueError(f"a bank descriptor needs the bank that holds its {self.ks} x {self.ks} table {self.bank_index}")
+            return np.asarray(bank[self.bank_index], dtype=np.float32)
+        raise ValueError(f"unknown table kind {self.kind!r}")
+
+    def row(self) -> Tuple[float, ...]:
+        """(kind, ks, A, B2, C, beta, cutoff, bank_index) as eight doubles; A, B2, C are `_quad`'s coefficients."""
+        if not (isinstance(self.kind, int) and KIND_DELTA <= self.kind <= KIND_BANK):
+            raise ValueError(f"unknown table kind {self.kind!r}")
+        a, b2, c = _quad_coef(self.s1, self.s2, self.theta) if KIND_GAUSSIAN <= self.kind <= KIND_PLATEAU else (0.0, 0.0, 0.0)
+        return (float(self.kind), float(check_ks(self.ks)), a, b2, c, float(self.beta), float(self.cutoff), float(self.bank_index))

@@ -6,6 +6,7 @@
 
 #include "adamw.h"
 #include "kernels.h"
+#include "tables.h"
 #include "wgrad.h"
 
 static thread_local char g_err[512] = "";
@@ -614,6 +615,17 @@ int srk_filter2d_f32(const float* x, const float* tab, float* out, const int32_t
   SRK_REQUIRE(!srk_ranges_overlap(x, bytes, out, bytes) && !srk_ranges_overlap(tab, kb, out, bytes) && !srk_ranges_overlap(ext, eb, out, bytes),
               SRK_E_SHAPE, "filter2d: out overlaps x, tab or ext (the filter is not run in place)");
   return srk_launch_filter2d_f32(x, tab, out, reinterpret_cast<const int*>(ext), B, C, Hp, Wp, ks, quant_bits, (hipStream_t)stream);
+}
+
+int srk_kernel_tables_f32(const double* desc, const float* bank, int n_bank, int kb, float* tab, int n, int ks, srk_stream_t stream) {
+  REQ_PTR(desc); REQ_PTR(tab);
+  SRK_REQUIRE(srk_psf_ks_ok(ks), SRK_E_SHAPE, "kernel_tables: ks must be odd and in 1..21 (got %d)", ks);
+  SRK_REQUIRE(srk_tables_shape_ok(n, ks, bank != nullptr, n_bank, kb), SRK_E_SHAPE,
+              "kernel_tables: n=%d must be >= 1, and the bank is absent (NULL, 0, 0) or has n_bank=%d >= 1 and kb=%d odd in 1..ks=%d", n, n_bank, kb, ks);
+  const size_t tb = srk_tables_bytes(n, ks, sizeof(float)), db = sizeof(double) * 8 * (size_t)n, bb = bank ? srk_tables_bytes(n_bank, kb, sizeof(float)) : 0;
+  SRK_REQUIRE(!srk_ranges_overlap(desc, db, tab, tb) && !srk_ranges_overlap(bank, bb, tab, tb), SRK_E_SHAPE,
+              "kernel_tables: tab overlaps desc or bank");
+  return srk_launch_kernel_tables_f32(desc, bank, n_bank, kb, tab, n, ks, (hipStream_t)stream);
 }
 
 int srk_resize_aa_ragged_f32(const float* x, const int32_t* ext_in, float* out, const int32_t* ext_out, int B, int C, int Hp, int Wp, int Hop,

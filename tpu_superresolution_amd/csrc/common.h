@@ -145,6 +145,13 @@ static inline bool srk_resize_ragged_shape_ok(int B, int C, int Hp, int Wp, int 
 }
 static inline bool srk_ragged_extent_ok(int h, int w, int Hp, int Wp) { return h >= 1 && h <= Hp && w >= 1 && w <= Wp; }
 static inline bool srk_resize_factor_ok(int n_in, int n_out) { return n_in >= 1 && n_out >= 1 && (long long)n_in <= 8LL * n_out; }
+// tables built on the device (tables.hip, srk.h "Blur and sinc tables built on the device"): n tables of side ks, and the bank triple --
+// absent (no pointer, n_bank = kb = 0) or present with kb odd in 1..ks.  n * 21 * 21 * 8 and n_bank * 21 * 21 * 4 stay below 2^63 for
+// every int, so the byte counts the entry forms (srk_tables_bytes, in 64 bits) cannot wrap.
+static inline bool srk_tables_shape_ok(int n, int ks, bool has_bank, int n_bank, int kb) {
+  return n >= 1 && srk_psf_ks_ok(ks) && (has_bank ? (n_bank >= 1 && srk_psf_ks_ok(kb) && kb <= ks) : (n_bank == 0 && kb == 0));
+}
+static inline size_t srk_tables_bytes(int n, int ks, size_t elem) { return elem * (size_t)n * (size_t)ks * (size_t)ks; }
 
 // ---------------------------------------------------------------------------------------------
 // bf16 helpers (device)

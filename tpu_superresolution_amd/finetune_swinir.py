@@ -26,6 +26,8 @@ window of the whole-image degradation, JPEG blocks anchored at the image's (0, 0
 round trip at a random per-sample quality in a second launch (csrc/jpeg.hip); validation uses the middle of the range.
 `--degrade second_order` runs Real-ESRGAN's chain on the device instead -- blur, resize, noise, JPEG, twice, every sample at its own
 intermediate sizes, then a sinc filter (sr_datasets.DeviceHR2Pool, csrc/filter2d.hip, csrc/ragged.hip).
+`--degrade_tables device` (with the 2-D kernels of --degrade blind, or --degrade second_order) builds the blur and sinc tables of every
+training batch on the device instead of in numpy on the training thread (csrc/tables.hip).
 `--blur_kernel rotated|mixed` or `--blur_psf FILE` (with --degrade blind) blurs every patch with a 2-D table -- a rotated, generalized or
 plateau Gaussian, or a measured point-spread function -- in the same single launch (csrc/blur2d.hip).
 
@@ -351,6 +353,11 @@ def parse_args(argv=None):
     ap.add_argument("--blur_psf", type=str, default=None, metavar="FILE",
                     help="additive, with --degrade blind: a measured point-spread function, .npy [k][k] or [n][k][k] (k odd <= 21, taps >= 0 "
                          "summing to 1); every training patch is blurred with one of its tables, validation with table 0")
+    ap.add_argument("--degrade_tables", type=str, choices=["host", "device"], default="host",
+                    help="additive, with --degrade blind and --blur_kernel rotated | mixed or --blur_psf, or with --degrade second_order: "
+                         "where the blur and sinc tables of a training batch are evaluated -- 'host': in fp64 numpy, then uploaded; 'device': "
+                         "on the GPU from eight numbers per table (csrc/tables.hip, DESIGN 7q), the same draws and decisions, every tap "
+                         "within one fp32 spacing of the host's.  Validation keeps its fixed host tables")
     ap.add_argument("--blur2_sigma", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                     help="additive, with --degrade second_order: range of the sigmas of the second blur, a rotated Gaussian (default 0.2 1.5)")
     ap.add_argument("--blur2_p", type=float, default=None,
@@ -450,6 +457,10 @@ def parse_args(argv=None):
         psf_spec(args)
     except (ValueError, OSError) as e:
         ap.error(f"--blur_kernel / --blur_psf: {e}")
+    if args.degrade_tables != "host" and not (args.degrade == "second_order" or
+                                              (args.degrade == "blind" and (args.blur_kernel != "axis" or args.blur_psf is not None))):
+        ap.error("--degrade_tables device builds the 2-D tables of --degrade blind with --blur_kernel rotated | mixed or --blur_psf, or of "
+                 "--degrade second_order: it needs one of them")
     if args.jpeg_quality is None:
         if args.jpeg_p != 1.0 or (args.jpeg_subsample != "444" and args.degrade != "second_order"):
             ap.error("--jpeg_p and --jpeg_subsample are options of the JPEG stage: they need --jpeg_quality LO HI")
@@ -560,7 +571,7 @@ def saved_args(args) -> dict:
                   "jpeg_subsample": args.jpeg_subsample == "444", "blur_kernel": args.blur_kernel == "axis",
                   "blur_kernel_prob": args.blur_kernel_prob is None, "blur_beta_g": args.blur_beta_g is None,
                   "blur_beta_p": args.blur_beta_p is None, "blur_ksize": args.blur_ksize is None, "blur_psf": args.blur_psf is None,
-                  "val_bench_metric": args.val_bench_metric is None,
+                  "degrade_tables": args.degrade_tables == "host", "val_bench_metric": args.val_bench_metric is None,
                   "val_crop_border": args.val_crop_border is None, "task": args.task == "sr", "channels": args.channels == 3,
                   "dn_sigma": args.dn_sigma is None, "dn_bits": args.dn_bits == 0}
     at_default.update({n: getattr(args, n) is None for n in SECOND_ORDER_FLAGS})
@@ -608,11 +619,11 @@ def main(argv=None):
             pool = DeviceHR2Pool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, second_order_spec(args), degrade_spec(args),
                                  device=device, shard_bytes=(args.gpu_data_shard_mb << 20) or None, augment=args.augment, rank=rank,
                                  psf=psf_spec(args), margin=8 if args.degrade_margin is None else args.degrade_margin,
-                                 subsample=args.jpeg_subsample == "420", names=[f.name for f in raw.files])
+                                 subsample=args.jpeg_subsample == "420", names=[f.name for f in raw.files], tables=args.degrade_tables)
         else:
             pool = DeviceHRPool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, device=device,
                                 shard_bytes=(args.gpu_data_shard_mb << 20) or None, augment=args.augment, quant_bits=args.synth_lr_bits,
-                                degrade=degrade_spec(args), rank=rank, jpeg=jpeg_spec(args), psf=psf_spec(args))
+                                degrade=degrade_spec(args), rank=rank, jpeg=jpeg_spec(args), psf=psf_spec(args), tables=args.degrade_tables)
         train_loader = sampler = DevicePoolLoader(pool, args.batch_size, rank, world, args.seed)
         valid_ds = Shuffled2DHR(args.data_root, split="valid", transform=hr_to_tensor3)
         if rank == 0:
@@ -635,6 +646,8 @@ def main(argv=None):
                 what = (f"{len(ps.tables)} measured table(s) of {args.blur_psf}, {ps.tables.shape[-1]} x {ps.tables.shape[-1]}; validation: table 0"
                         if ps.mode == "file" else f"{ps.mode} 2-D kernels; validation: the isotropic midpoints")
                 print(f"[degrade] blur kernel: {what}, seed {args.degrade_seed}")
+            if args.degrade_tables == "device":
+                print("[degrade] tables: built on the device from descriptors (csrc/tables.hip)")
             if args.jpeg_quality is not None:
                 js = jpeg_spec(args)
                 print(f"[degrade] jpeg: quality in {list(js.quality)} with p={js.p:g}, chroma {args.jpeg_subsample}, seed {args.degrade_seed}; "

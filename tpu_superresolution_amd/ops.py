@@ -701,21 +701,99 @@ def pack_psf(psf, B: int, checked: bool = False):
     return np.stack([bk.pad_to(t, ks) for t in tabs]), ks
 
 
+class DeviceTables(NamedTuple):
+    """Tables the device built (`kernel_tables`): `tab`, CUDA fp32 [n][ks][ks]; `ks`; `own`, the host list of the n sides before
+    padding (what the radius-versus-extent checks run on: nothing is read back); `signed`: a sinc table is among them, so the batch
+    goes through `filter2d` only."""
+    tab: torch.Tensor
+    ks: int
+    own: Tuple[int, ...]
+    signed: bool
+
+
+def kernel_tables(descs, ks=None, bank=None, signed: bool = True, device=None) -> DeviceTables:
+    """The tables of n `blur_kernels.TableDesc` built ON THE DEVICE (csrc/tables.hip, srk_kernel_tables_f32): one upload of n x 8
+    doubles and one launch, in place of n fp64 numpy evaluations and an upload of n ks^2 floats.  ks: the side of the slots, by default
+    the largest own side (smaller tables are centred in +0, `blur_kernels.pad_to`).  bank: the CUDA fp32 [n_bank][kb][kb] tables that
+    kind-5 descriptors index (a numpy array is checked by `blur_kernels.check_table` and uploaded; keep the tensor to upload once).
+    signed=False refuses sinc descriptors: what `blur2d` / `degrade_psf` need, whose mass rule has no negative taps.  Each tap is
+    within one fp32 spacing of `TableDesc.table()`'s (tests/tables_ref.py derives the bound)."""
+    from . import blur_kernels as bk
+    ds = list(descs)
+    if not ds or not all(isinstance(d, bk.TableDesc) for d in ds):
+        raise ValueError(f"kernel_tables takes a non-empty list of blur_kernels.TableDesc (got {len(ds)} entries)")
+    rows = [d.row() for d in ds]                                     # refuses what the table functions refuse
+    for d in ds:                                                     # a NamedTuple built by hand gets the constructors' checks
+        if d.kind == bk.KIND_SINC:
+            bk.TableDesc.sinc(d.cutoff, d.ks)
+        elif d.kind in (bk.KIND_GENERALIZED, bk.KIND_PLATEAU):
+            bk._beta(d.beta)
+    if not signed and any(d.kind == bk.KIND_SINC for d in ds):
+        raise ValueError("kernel_tables(signed=False): a sinc table has negative taps (ops.filter2d takes it, ops.blur2d cannot)")
+    own = tuple(d.ks for d in ds)
+    ks = max(own) if ks is None else bk.check_ks(ks)
+    if max(own) > ks:
+        raise ValueError(f"kernel_tables: a table of side {max(own)} does not fit ks = {ks}")
+    n_bank = kb = 0
+    if bank is not None and isinstance(bank, torch.Tensor) and not any(d.kind == bk.KIND_BANK for d in ds):
+        device, bank = bank.device, None                             # nothing indexes it: its side need not fit ks
+    if bank is not None and not isinstance(bank, torch.Tensor):
+        import numpy as np
+        arr = np.asarray(bank)
+        if arr.ndim != 3:
+            raise ValueError(f"kernel_tables: a bank is [n][kb][kb] (got shape {arr.shape})")
+        bank = torch.from_numpy(np.stack([bk.check_table(t, f"bank[{i}]") for i, t in enumerate(arr)])).to(_default_device(device))
+    if bank is not None:
+        if bank.dim() != 3 or not bank.is_cuda or bank.dtype != torch.float32 or bank.shape[1] != bank.shape[2] or bank.shape[0] < 1 or \
+                not bank.is_contiguous():
+            raise ValueError(f"kernel_tables: a bank is a contiguous CUDA fp32 [n][kb][kb] tensor (got {bank.dtype} {tuple(bank.shape)} on {bank.device})")
+        n_bank, kb = int(bank.shape[0]), bk.check_ks(int(bank.shape[1]))
+        if kb > ks:
+            raise ValueError(f"kernel_tables: the bank's tables of side {kb} do not fit ks = {ks}")
+    for i, d in enumerate(ds):
+        if d.kind == bk.KIND_BANK and (bank is None or d.ks != kb or not 0 <= d.bank_index < n_bank):
+            raise ValueError(f"kernel_tables: descriptor {i} names table {d.bank_index} of side {d.ks}, which the bank "
+                             f"({n_bank} tables of side {kb}) does not hold")
+    dev = bank.device if bank is not None else _default_device(device)
+    desc = torch.tensor(rows, dtype=torch.float64).to(dev)
+    tab = torch.empty(len(ds), ks, ks, dtype=torch.float32, device=dev)
+    check(lib().srk_kernel_tables_f32(_p(desc), _p(bank), n_bank, kb, _p(tab), len(ds), ks, _stream()))
+    return DeviceTables(tab, ks, own, any(d.kind == bk.KIND_SINC for d in ds))
+
+
+def _default_device(device):
+    return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+
+
+def _device_tables(t: DeviceTables, B: int, x: torch.Tensor, what: str) -> DeviceTables:
+    if t.tab.dim() != 3 or t.tab.shape[0] != B or tuple(t.tab.shape[1:]) != (t.ks, t.ks) or len(t.own) != B or t.tab.device != x.device or \
+            t.tab.dtype != torch.float32 or not t.tab.is_contiguous():
+        raise ValueError(f"{what}: DeviceTables of one fp32 table per sample on {x.device} are needed (B={B}; got {tuple(t.tab.shape)} on {t.tab.device})")
+    return t
+
+
 def blur2d(x: torch.Tensor, psf, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x CUDA fp32 [B,C,H,W] blurred with one ks x ks table or one per sample (csrc/blur2d.hip, srk_blur2d_f32): a correlation (no flip,
     cv2.filter2D's convention) in which taps outside the image are dropped and the rest renormalised per pixel.  Tables: odd ks <= 21,
     taps finite and >= 0, centre > 0, sum within 1e-3 of 1 (ValueError otherwise); mixed sizes are zero-padded to the largest.  One
-    launch after one small upload."""
+    launch after one small upload.  psf may be `DeviceTables` made with signed=False (one per sample): nothing is checked, packed or
+    uploaded then."""
     if x.dim() != 4 or not x.is_cuda or x.dtype != torch.float32 or min(x.shape) < 1:
         raise ValueError(f"blur2d takes a non-empty CUDA fp32 [B,C,H,W] batch (got {x.dtype} {tuple(x.shape)} on {x.device})")
     x = x.contiguous()
     B, Cc, H, W = x.shape
-    tabs, ks = pack_psf(psf, B)
+    if isinstance(psf, DeviceTables):
+        if psf.signed:
+            raise ValueError("blur2d: these DeviceTables hold a sinc table (negative taps); build them with kernel_tables(signed=False)")
+        k, ks = _device_tables(psf, B, x, "blur2d").tab, psf.ks
+    else:
+        tabs, ks = pack_psf(psf, B)
     if out is None:
         out = torch.empty_like(x)
     elif tuple(out.shape) != tuple(x.shape) or out.dtype != torch.float32 or out.device != x.device or not out.is_contiguous():
         raise ValueError(f"out must be contiguous fp32 {tuple(x.shape)} on {x.device} (got {out.dtype} {tuple(out.shape)} on {out.device})")
-    k = torch.from_numpy(tabs).to(x.device)
+    if not isinstance(psf, DeviceTables):
+        k = torch.from_numpy(tabs).to(x.device)
     check(lib().srk_blur2d_f32(_p(x), _p(k), _p(out), B, Cc, H, W, ks, _stream()))
     return out
 
@@ -883,20 +961,24 @@ def filter2d(x: torch.Tensor, tab, ext=None, quant_bits: int = 0, out: Optional[
     tables need, and the one every 2-D filter of the second-order chain takes.  ext: None (dense) or the (h, w) of every sample in the
     padded batch; each must exceed the R = ks // 2 of its sample's OWN table (zero-padding a table to the batch's largest ks adds taps
     that multiply in-extent pixels by 0: no bit changes).  A delta table passes its sample through bit for bit.  quant_bits 8 rounds to
-    k / 255.  One launch after one small upload."""
+    k / 255.  One launch after one small upload.  tab may be `DeviceTables` (one per sample): nothing is checked, packed or uploaded
+    then, and the extent check runs on their host list of own sizes."""
     if x.dim() != 4 or not x.is_cuda or x.dtype != torch.float32 or min(x.shape) < 1:
         raise ValueError(f"filter2d takes a non-empty CUDA fp32 [B,C,H,W] batch (got {x.dtype} {tuple(x.shape)} on {x.device})")
     if quant_bits not in (0, 8):
         raise ValueError(f"filter2d: quant_bits must be 0 or 8 (got {quant_bits!r})")
     x = x.contiguous()
     B, Cc, Hp, Wp = x.shape
-    tabs, ks, own = pack_filter_tables(tab, B)
+    if isinstance(tab, DeviceTables):
+        tabs, ks, own = None, tab.ks, _device_tables(tab, B, x, "filter2d").own
+    else:
+        tabs, ks, own = pack_filter_tables(tab, B)
     e = _ragged(ext, B, Hp, Wp, x.device, "filter2d")
     for b, (h, w) in enumerate([(Hp, Wp)] * B if e is None else e.host):
         if min(h, w) <= own[b] // 2:
             raise ValueError(f"filter2d: sample {b} of {h} x {w} does not exceed the R = {own[b] // 2} of its table")
     out = _padded_out(out, x.shape, x)
-    k = torch.from_numpy(tabs).to(x.device)
+    k = tab.tab if tabs is None else torch.from_numpy(tabs).to(x.device)
     check(lib().srk_filter2d_f32(_p(x), _p(k), _p(out), _ext_ptr(e), B, Cc, Hp, Wp, ks, int(quant_bits), _stream()))
     return out
 
@@ -959,7 +1041,7 @@ def jpeg_roundtrip_ragged(x: torch.Tensor, quality, ext=None, subsample: bool = 
 
 class SecondOrder(NamedTuple):
     """The second-order degradation of ONE sample (Real-ESRGAN's chain; sr_datasets.SecondOrderSpec draws it): tables k1 / k2 / k3 for
-    the three filters (blur_kernels; a delta = no filter), resize factors r1 / r2 of the two intermediate sizes, noise1 / noise2 =
+    the three filters (blur_kernels; a delta = no filter; or `blur_kernels.TableDesc` descriptors, which the device turns into tables), resize factors r1 / r2 of the two intermediate sizes, noise1 / noise2 =
     (sigma_n, gain) with their gray flags, JPEG qualities q1 (stage 1) and q2 (stage 2), `jpeg_last`: False = order A (JPEG 2, final
     resize, final filter), True = order B (final resize, final filter, JPEG 2); the Philox key of noise 1 (noise 2 takes its
     complement)."""
@@ -990,7 +1072,20 @@ def second_order_noise_ids(p: SecondOrder) -> Tuple[int, int]:
     return i, i ^ 0xFFFFFFFFFFFFFFFF
 
 
-def degrade_second_order(x: torch.Tensor, scale: int, params, subsample: bool = False, pads=None, bufs: Optional[dict] = None) -> torch.Tensor:
+def _stage_tables(ks_list, bank, device, what: str):
+    """One stage's tables of `degrade_second_order`: arrays as they are (filter2d checks, packs and uploads them), descriptors built by
+    ONE `kernel_tables` launch."""
+    from .blur_kernels import TableDesc
+    n = sum(isinstance(k, TableDesc) for k in ks_list)
+    if n == 0:
+        return ks_list
+    if n != len(ks_list):
+        raise ValueError(f"degrade_second_order: {what} mixes tables and TableDesc descriptors in one batch ({n} of {len(ks_list)} are descriptors)")
+    return kernel_tables(ks_list, bank=bank, device=device)
+
+
+def degrade_second_order(x: torch.Tensor, scale: int, params, subsample: bool = False, pads=None, bufs: Optional[dict] = None,
+                         bank=None) -> torch.Tensor:
     """The second-order blind degradation on a batch x CUDA fp32 [B,C,H,W] (C = 1 or 3; H, W multiples of `scale` in 1..4), one
     `SecondOrder` per sample -> the LR batch [B,C,H/scale,W/scale] in 8-bit levels:
         filter k1 -> resize to (H, W) r1 -> noise 1 -> JPEG q1 -> filter k2 -> resize to (H, W) / scale r2 -> noise 2
@@ -998,7 +1093,10 @@ def degrade_second_order(x: torch.Tensor, scale: int, params, subsample: bool = 
     Every filter is `filter2d` (reflect border), every intermediate is a ragged batch in a padded buffer, so every sample has its own
     sizes and every stage is ONE launch: eleven launches and their small uploads, no host read, no intermediate copy.  Each sample is
     bit-identical to the composition of the dense ops on that sample alone.  pads = ((Hp1, Wp1), (Hp2, Wp2)) fixes the padded sizes
-    (default: the batch's largest); bufs: a dict that keeps the work buffers between calls."""
+    (default: the batch's largest); bufs: a dict that keeps the work buffers between calls.
+    k1 / k2 / k3 may be `blur_kernels.TableDesc` descriptors in place of tables -- per stage all or none of the batch -- and the
+    stage's tables are then built on the device by one `kernel_tables` launch (three more tiny launches, three fewer table uploads);
+    bank: the CUDA tensor that kind-5 descriptors index."""
     if x.dim() != 4 or not x.is_cuda or x.dtype != torch.float32:
         raise ValueError(f"degrade_second_order takes a CUDA fp32 [B,C,H,W] batch (got {x.dtype} {tuple(x.shape)} on {x.device})")
     s = int(scale)
@@ -1024,16 +1122,17 @@ def degrade_second_order(x: torch.Tensor, scale: int, params, subsample: bool = 
     qa = [0 if p.jpeg_last else p.q2 for p in ps]
     qb = [p.q2 if p.jpeg_last else 0 for p in ps]
     x = x.contiguous()
-    a = filter2d(x, [p.k1 for p in ps], out=buf("f1", B, Cc, H, W))
+    t1, t2, t3 = (_stage_tables([getattr(p, k) for p in ps], bank, x.device, k) for k in ("k1", "k2", "k3"))
+    a = filter2d(x, t1, out=buf("f1", B, Cc, H, W))
     a = resize_aa_ragged(a, None, e1, (Hp1, Wp1), out=buf("a1", B, Cc, Hp1, Wp1))
     a = _noise_into(a, [p.noise1 for p in ps], [i[0] for i in ids], [p.gray1 for p in ps], buf("b1", B, Cc, Hp1, Wp1))
     a = jpeg_roundtrip_ragged(a, [p.q1 for p in ps], e1, subsample, out=buf("a1", B, Cc, Hp1, Wp1))
-    a = filter2d(a, [p.k2 for p in ps], e1, out=buf("b1", B, Cc, Hp1, Wp1))
+    a = filter2d(a, t2, e1, out=buf("b1", B, Cc, Hp1, Wp1))
     a = resize_aa_ragged(a, e1, e2, (Hp2, Wp2), out=buf("a2", B, Cc, Hp2, Wp2))
     a = _noise_into(a, [p.noise2 for p in ps], [i[1] for i in ids], [p.gray2 for p in ps], buf("b2", B, Cc, Hp2, Wp2))
     a = jpeg_roundtrip_ragged(a, qa, e2, subsample, out=buf("a2", B, Cc, Hp2, Wp2))
     a = resize_aa_ragged(a, e2, None, (Ho, Wo), out=buf("lr0", B, Cc, Ho, Wo))
-    a = filter2d(a, [p.k3 for p in ps], quant_bits=8, out=buf("lr1", B, Cc, Ho, Wo))
+    a = filter2d(a, t3, quant_bits=8, out=buf("lr1", B, Cc, Ho, Wo))
     return jpeg_roundtrip(a, qb, subsample)
 
 

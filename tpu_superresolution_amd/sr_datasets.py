@@ -406,6 +406,7 @@ class JpegSpec:
 
 
 PSF_MODES = ("rotated", "mixed", "file")
+TABLE_MODES = ("host", "device")          # where a pool's blur / sinc tables are evaluated
 PSF_SIGMA_FLOOR = 1e-3          # a sigma of 0 (no blur on that axis) as a Gaussian: every tap off the axis underflows to 0
 
 
@@ -466,12 +467,17 @@ class PsfSpec:
         """The checked tables of `file`, fp32 [n][k][k] (None in the other modes)."""
         return self._tables
 
-    def draw(self, rng: random.Random, blur):
-        """-> the fp32 table of one sample with blur = (sigma_y, sigma_x); always the same six variates, whatever they decide."""
+    def draw(self, rng: random.Random, blur, as_desc: bool = False):
+        """-> the fp32 table of one sample with blur = (sigma_y, sigma_x); always the same six variates, whatever they decide.
+        as_desc: the `blur_kernels.TableDesc` of that table instead (`file`: a kind-5 descriptor into `tables`), for
+        `ops.kernel_tables` to build on the device; same variates, same decisions."""
         from . import blur_kernels as bk
+        if as_desc:
+            bk = bk.TableDesc
         u_kind, u_theta, u_bg, u_bp, u_ks, u_idx = (rng.random() for _ in range(6))
         if self.mode == "file":
-            return self._tables[min(int(u_idx * len(self._tables)), len(self._tables) - 1)]
+            idx = min(int(u_idx * len(self._tables)), len(self._tables) - 1)
+            return bk.bank(idx, self._tables.shape[1]) if as_desc else self._tables[idx]
         s2, s1 = (max(float(v), PSF_SIGMA_FLOOR) for v in blur)
         theta = math.pi * (u_theta - 0.5)
         if self.mode == "rotated":
@@ -613,13 +619,17 @@ class SecondOrderSpec:
     def _quality(q, u: float) -> int:
         return min(q[0] + int(u * (q[1] - q[0] + 1)), q[1])
 
-    def draw(self, rng: random.Random, table1, noise1, noise_id: int, gray1: bool, colour: bool, extent: int, scale: int):
-        """-> the `ops.SecondOrder` of one sample.  table1, noise1, noise_id, gray1: the first-order draws (PsfSpec.draw or a Gaussian
+    def draw(self, rng: random.Random, table1, noise1, noise_id: int, gray1: bool, colour: bool, extent: int, scale: int,
+             as_desc: bool = False):
+        """-> the `ops.SecondOrder` of one sample (as_desc: with `blur_kernels.TableDesc` descriptors for k1 / k2 / k3 -- table1 is then
+        one too -- from the same variates and decisions).  table1, noise1, noise_id, gray1: the first-order draws (PsfSpec.draw or a Gaussian
         of DegradeSpec's sigmas; DegradeSpec.draw).  extent: the side of the square window the chain runs on at factor `scale`: it
         bounds filter 2, and factor 2 is raised where the second resize would shrink by more than the resampler's 8x (an upscale by
         1.5 followed by 0.3 / 4 is 20x; Real-ESRGAN's resize has no such limit because it does not antialias)."""
         from . import blur_kernels as bk
         from .ops import SecondOrder
+        if as_desc:
+            bk = bk.TableDesc
         u = [rng.random() for _ in range(SECOND_ORDER_VARIATES)]
         ks1 = self._ks(u[2])
         k1 = bk.sinc(self._cutoff(ks1, u[1]), ks1) if (u[0] < self.sinc_p and ks1 // 2 < extent) else table1
@@ -680,11 +690,15 @@ class DeviceHRPool(_DeviceImagePool):
     ``psf`` (a PsfSpec; None = the axis-aligned Gaussian composed into the cubic tables, today's launch; needs ``degrade``): every
     sample is blurred with a 2-D table made from the sigmas of its `DegradeSpec.draw` and the PsfSpec's own generator, uploaded as one
     [B][ks][ks] block, in one `srk_crop_degrade_psf_u8` launch.  The DegradeSpec's draws, `draw` and the global `random` state are the
-    same with and without it."""
+    same with and without it.
+
+    ``tables`` "host" (default): the tables are evaluated in fp64 numpy and uploaded.  "device": `PsfSpec.draw` returns descriptors
+    and `ops.kernel_tables` builds the block on the device (eight doubles per sample go up instead of ks^2 floats; a `file` bank is
+    uploaded once, here); the draws are the same, the taps agree to one fp32 spacing."""
 
     def __init__(self, images, lr_patch: int, scale: int, device="cuda", shard_bytes: Optional[int] = None, augment: str = "none",
                  quant_bits: int = 8, degrade: Optional[DegradeSpec] = None, rank: int = 0, jpeg: Optional[JpegSpec] = None,
-                 psf: Optional[PsfSpec] = None):
+                 psf: Optional[PsfSpec] = None, tables: str = "host"):
         """images: iterable of HR PIL images or uint8 / uint16 arrays [H,W] / [H,W,1|3]."""
         if augment not in AUGMENT_MODES:
             raise ValueError(f"augment must be one of {AUGMENT_MODES} (got {augment!r})")
@@ -706,7 +720,13 @@ class DeviceHRPool(_DeviceImagePool):
         if psf is not None and degrade is None:
             raise ValueError("psf= shapes the blur of degrade=: it needs a DegradeSpec")
         self.psf, self._psf_rng, self._psf_buf = psf, (psf.rng(rank) if psf is not None else None), None
+        if tables not in TABLE_MODES:
+            raise ValueError(f"tables must be one of {TABLE_MODES} (got {tables!r})")
+        self.tables = tables
         self.lr_patch, self.scale, self.device = int(lr_patch), int(scale), torch.device(device)
+        self._bank = None
+        if tables == "device" and psf is not None and psf.tables is not None:
+            self._bank = torch.from_numpy(psf.tables).to(self.device)
         self._pack(((img,) for img in images), shard_bytes)
 
     def _check_group(self, hr) -> None:
@@ -733,13 +753,17 @@ class DeviceHRPool(_DeviceImagePool):
 
     def draw_psf(self, hd):
         """(ten-slot descriptors, fp32 numpy [B][ks][ks], ks) of a batch: `draw_degrade`'s draws, in its order, plus one `PsfSpec.draw`
-        per sample on the sigmas of that sample; slot 6 keeps the sigmas, which the PSF entry ignores."""
-        from .ops import pack_degrade_params, pack_psf
+        per sample on the sigmas of that sample; slot 6 keeps the sigmas, which the PSF entry ignores.  With tables = "device":
+        (descriptors, the batch's `ops.DeviceTables`, ks), built by one `ops.kernel_tables` launch."""
+        from .ops import kernel_tables, pack_degrade_params, pack_psf
         rows, tabs = [], []
         for d in hd:
             drawn = self.degrade.draw(self._degrade_rng, colour=(d[3] & 0xff) == 3)
             rows.append(tuple(d) + tuple(pack_degrade_params(*drawn)))
-            tabs.append(self.psf.draw(self._psf_rng, drawn[0]))
+            tabs.append(self.psf.draw(self._psf_rng, drawn[0], as_desc=self.tables == "device"))
+        if self.tables == "device":
+            built = kernel_tables(tabs, bank=self._bank, signed=False, device=self.device)
+            return rows, built, built.ks
         return (rows,) + pack_psf(tabs, len(tabs), checked=True)
 
     def _psf_upload(self, tabs) -> torch.Tensor:
@@ -767,7 +791,8 @@ class DeviceHRPool(_DeviceImagePool):
         hr = torch.empty(B, 3, P * s, P * s, dtype=torch.float32, device=self.device)
         st = torch.cuda.current_stream(self.device).cuda_stream
         if tabs is not None:
-            check(lib().srk_crop_degrade_psf_u8(pool.data_ptr(), desc.data_ptr(), self._psf_upload(tabs).data_ptr(), ks, lr.data_ptr(),
+            k = tabs.tab if self.tables == "device" else self._psf_upload(tabs)
+            check(lib().srk_crop_degrade_psf_u8(pool.data_ptr(), desc.data_ptr(), k.data_ptr(), ks, lr.data_ptr(),
                                                 hr.data_ptr(), B, P, s, self.quant_bits, st))
         else:
             entry = lib().srk_crop_degrade_u8 if self.degrade is None else lib().srk_crop_degrade_blind_u8
@@ -782,10 +807,13 @@ class DeviceHRPool(_DeviceImagePool):
         return lr, hr
 
 
-def stage1_table(blur):
+def stage1_table(blur, as_desc: bool = False):
     """The stage-1 table of the second-order chain when no PsfSpec shapes it: the axis-aligned Gaussian of DegradeSpec's
-    (sigma_y, sigma_x), R = min(ceil(3 sigma), 10), as a 2-D table (the chain filters with `ops.filter2d` only)."""
+    (sigma_y, sigma_x), R = min(ceil(3 sigma), 10), as a 2-D table (the chain filters with `ops.filter2d` only).  as_desc: its
+    `blur_kernels.TableDesc`."""
     from . import blur_kernels as bk
+    if as_desc:
+        bk = bk.TableDesc
     sy, sx = (float(v) for v in blur)
     ks = 2 * min(math.ceil(3.0 * max(0.0, sy, sx)), 10) + 1
     return bk.gaussian(ks, max(sx, PSF_SIGMA_FLOOR), max(sy, PSF_SIGMA_FLOOR), 0.0)
@@ -810,11 +838,12 @@ class DeviceHR2Pool(DeviceHRPool):
     Stage 1 reuses ``degrade`` (a DegradeSpec: sigmas, noise, gray flag, noise id) and ``psf`` (a PsfSpec shaping the table; None =
     the axis-aligned Gaussian as a table); ``spec`` (a SecondOrderSpec) draws the rest from its own generator.  An image whose region
     is smaller than E is refused at construction.  The padded work buffers have the spec's largest sizes and are kept between calls:
-    the launches and their shapes are the same every step."""
+    the launches and their shapes are the same every step.  ``tables`` "device": every stage's tables are built on the device from
+    descriptors (DeviceHRPool's switch; three `ops.kernel_tables` launches per batch, no table evaluated or uploaded by the host)."""
 
     def __init__(self, images, lr_patch: int, scale: int, spec: "SecondOrderSpec", degrade: Optional[DegradeSpec] = None, device="cuda",
                  shard_bytes: Optional[int] = None, augment: str = "none", rank: int = 0, psf: Optional[PsfSpec] = None, margin: int = 8,
-                 subsample: bool = False, names=None):
+                 subsample: bool = False, names=None, tables: str = "host"):
         if not isinstance(spec, SecondOrderSpec):
             raise ValueError(f"spec must be a SecondOrderSpec (got {type(spec).__name__})")
         if isinstance(margin, bool) or int(margin) != margin or not 0 <= int(margin) <= 64:
@@ -823,7 +852,8 @@ class DeviceHR2Pool(DeviceHRPool):
         self.extent = int(scale) * (int(lr_patch) + 2 * self.margin)
         self._names = None if names is None else list(names)
         self._bufs: dict = {}
-        super().__init__(images, lr_patch, scale, device, shard_bytes, augment, 8, degrade if degrade is not None else DegradeSpec(), rank, None, psf)
+        super().__init__(images, lr_patch, scale, device, shard_bytes, augment, 8, degrade if degrade is not None else DegradeSpec(), rank, None, psf,
+                         tables)
         rnd = lambda v: max(1, int(v + 0.5))          # noqa: E731
         E, s = self.extent, self.scale
         self.pads = ((rnd(E * spec.resize_range[1]),) * 2, (rnd(E / s * spec.resize2_range[1]),) * 2)
@@ -849,8 +879,9 @@ class DeviceHR2Pool(DeviceHRPool):
             offs.append((oy, ox))
             colour = (hc & 0xff) == 3
             blur, noise, nid, gray = self.degrade.draw(self._degrade_rng, colour=colour)
-            table1 = self.psf.draw(self._psf_rng, blur) if self.psf is not None else stage1_table(blur)
-            params.append(self.spec.draw(self._spec_rng, table1, noise, nid, gray, colour, self.extent, s))
+            dev = self.tables == "device"
+            table1 = self.psf.draw(self._psf_rng, blur, dev) if self.psf is not None else stage1_table(blur, dev)
+            params.append(self.spec.draw(self._spec_rng, table1, noise, nid, gray, colour, self.extent, s, dev))
         return wd, offs, params
 
     def _crop(self, pool, rows, patch: int) -> torch.Tensor:
@@ -868,7 +899,7 @@ class DeviceHR2Pool(DeviceHRPool):
         hd, codes = self.draw(indices)
         wd, offs, params = self.draw_second_order(hd)
         hr = self._crop(pool, hd, P * s)
-        whole = degrade_second_order(self._crop(pool, wd, self.extent), s, params, self.subsample, self.pads, self._bufs)
+        whole = degrade_second_order(self._crop(pool, wd, self.extent), s, params, self.subsample, self.pads, self._bufs, self._bank)
         if len(set(offs)) == 1:
             (oy, ox), = set(offs)
             lr = whole[:, :, oy:oy + P, ox:ox + P].contiguous()
