@@ -434,6 +434,37 @@ int srk_jpeg_roundtrip_ragged_f32(const float* x, float* out, const int32_t* qua
                                   int subsample, srk_stream_t stream);
 /* The noise stage of a ragged chain is srk_noise_f32 on the padded buffer: its counter is (x, y, ch) only, so inside the extents its
  * bits are those of the dense call on the sample alone; what it writes into the padding is never read. */
+/* srk_resize_aa_ragged_f32 with a resize rule per sample (csrc/resize_modes.hip): the ragged contract, the arguments, the tile grid and
+ * the filter (resize.h: rs_filter, horizontal pass first, ascending-tap fmaf chains from 0) are those of srk_resize_aa_ragged_f32; only
+ * the per-output tap list differs.  mode = DEVICE int32 [B], NULL = every sample mode 0; any other bit pattern is clamped into 0..2.
+ * Per axis n_in -> n_out, the table arithmetic in fp64 (contraction off), the weights rounded once to fp32:
+ *   0 cubic, antialiased     the taps of srk_resize_aa_f32: the sample is BIT-IDENTICAL to srk_resize_aa_ragged_f32
+ *   1 bilinear, not antialiased   scale = n_in / n_out, src = max(scale (i + 0.5) - 0.5, 0), i0 = min(floor(src), n_in - 1),
+ *                            l = src - i0; taps i0 and min(i0 + 1, n_in - 1) with weights 1 - l and l; where both are one pixel, one
+ *                            tap of weight 1 (F.interpolate(mode='bilinear', align_corners=False) on an explicit size)
+ *   2 area                   lo = (i n_in) / n_out, hi = ((i + 1) n_in + n_out - 1) / n_out in 64-bit integers; hi - lo taps of
+ *                            weight 1 / (hi - lo) (adaptive average pooling)
+ * An axis shrinking by more than 8x is not supported in ANY mode (the tile staging needs it, not the tap count): checked as
+ * srk_resize_aa_ragged_f32 checks it -- by the entry for a dense call, by the caller for ragged tables.
+ * SRK_E_NULL: null x / out; SRK_E_SHAPE: a non-positive extent, quant_bits other than 0 / 8, out overlapping x, a table or mode, a
+ * size that does not fit one launch; SRK_E_UNSUPPORTED: a dense call shrinking an axis by more than 8x. */
+int srk_resize_ragged_mode_f32(const float* x, const int32_t* ext_in, float* out, const int32_t* ext_out, const int32_t* mode, int B, int C,
+                               int Hp, int Wp, int Hop, int Wop, int quant_bits, srk_stream_t stream);
+/* Unsharp mask of a dense batch (csrc/usm.hip), Real-ESRGAN's USMSharp with its table k k^T evaluated separably.  x, out: fp32
+ * [B][C][H][W], C 1 or 3; taps = DEVICE fp32 [ks], ks odd in 1..51, R = (ks - 1) / 2, H, W > R; work = DEVICE fp32 [B][C][H][W]
+ * (SRK_USM_WORK_FLOATS(B, C, H, W) floats), provided by the caller: the library allocates nothing.  The contract -- contraction off,
+ * every sum an ascending-tap chain acc = fmaf(taps[j], v, acc) from 0, rho the reflect-101 index of srk_filter2d_f32, clamped:
+ *   G(v)(p, q) = the horizontal pass h(p, q) = sum_j taps[j] v(p, rho(q + j - R, W)), then sum_i taps[i] h(rho(p + i - R, H), q)
+ *   blur = G(x);  res = x - blur;  mask = (fabsf(res) * 255.0f > threshold) ? 1.f : 0.f;  soft = G(mask)
+ *   sharp = fminf(fmaxf(x + weight * res, 0.f), 1.f);  out = soft * sharp + (1.0f - soft) * x
+ * Two launches of one kernel: the first leaves res in out and mask in work, the second reads both and writes out.  Nothing outside
+ * out and work is written; x, taps, out and work are pairwise distinct.
+ * SRK_E_NULL: null x / taps / out / work; SRK_E_SHAPE: B, H or W < 1, C not 1 or 3, ks even or outside 1..51, an overlap, a size that
+ * does not fit one launch; SRK_E_UNSUPPORTED: H or W <= R. */
+#define SRK_USM_MAX_KS 51
+#define SRK_USM_WORK_FLOATS(B, C, H, W) ((size_t)(B) * (size_t)(C) * (size_t)(H) * (size_t)(W))
+int srk_usm_sharpen_f32(const float* x, const float* taps, float* out, float* work, int B, int C, int H, int W, int ks, float weight,
+                        float threshold, srk_stream_t stream);
 /* Blur and sinc tables built on the device (csrc/tables.hip): n tables of srk_blur2d_f32 / srk_crop_degrade_psf_u8 / srk_filter2d_f32
  * from a few numbers each, so that the host draws variates and uploads no table.  tab = DEVICE fp32 [n][ks][ks], ks odd in 1..21;
  * desc = DEVICE fp64 [n][8] = (kind, ks_own, A, B2, C, beta, cutoff, bank_index), the integers carried exactly as doubles; bank =

@@ -64,6 +64,23 @@ def gaussian(ks: int, s1: float, s2: float, theta: float = 0.0) -> np.ndarray:
     return _finish(np.exp(-0.5 * _quad(ks, s1, s2, theta)))
 
 
+USM_KS_MAX = 51
+
+
+def gaussian1d(ks: int, sigma: float) -> np.ndarray:
+    """The 1-D Gaussian taps of the unsharp mask (ops.usm_sharpen), cv2.getGaussianKernel's closed form: exp(-(i - R)^2 / (2 sigma^2)),
+    ks odd in 1..51, normalised in fp64 and rounded once to fp32.  The 2-D table of Real-ESRGAN's USMSharp is the outer product."""
+    if isinstance(ks, bool) or int(ks) != ks or not 1 <= int(ks) <= USM_KS_MAX or int(ks) % 2 == 0:
+        raise ValueError(f"unsharp-mask taps: ks odd in 1..{USM_KS_MAX} (got {ks!r})")
+    sigma = float(sigma)
+    if not (sigma > 0.0 and math.isfinite(sigma)):
+        raise ValueError(f"unsharp-mask taps: sigma must be finite and > 0 (got {sigma!r})")
+    r = (int(ks) - 1) // 2
+    d = np.arange(-r, r + 1, dtype=np.float64)
+    k = np.exp(-(d * d) / (2.0 * sigma * sigma))
+    return (k / k.sum()).astype(np.float32)
+
+
 def _beta(beta) -> float:
     beta = float(beta)
     if not (beta > 0.0 and np.isfinite(beta)):

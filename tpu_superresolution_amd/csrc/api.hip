@@ -658,6 +658,37 @@ int srk_jpeg_roundtrip_ragged_f32(const float* x, float* out, const int32_t* qua
                                               subsample, (hipStream_t)stream);
 }
 
+int srk_resize_ragged_mode_f32(const float* x, const int32_t* ext_in, float* out, const int32_t* ext_out, const int32_t* mode, int B, int C,
+                               int Hp, int Wp, int Hop, int Wop, int quant_bits, srk_stream_t stream) {
+  REQ_PTR(x); REQ_PTR(out);
+  SRK_REQUIRE(srk_resize_ragged_shape_ok(B, C, Hp, Wp, Hop, Wop), SRK_E_SHAPE,
+              "resize_ragged_mode: B=%d C=%d Hp=%d Wp=%d Hop=%d Wop=%d must all be >= 1 and fit one launch", B, C, Hp, Wp, Hop, Wop);
+  SRK_REQUIRE(srk_quant_bits_ok(quant_bits), SRK_E_SHAPE, "resize_ragged_mode: quant_bits must be 0 or 8 (got %d)", quant_bits);
+  const size_t ib = (size_t)(4.0 * B * C * Hp * Wp), ob = (size_t)(4.0 * B * C * Hop * Wop), eb = sizeof(int32_t) * 2 * (size_t)B;
+  SRK_REQUIRE(!srk_ranges_overlap(x, ib, out, ob) && !srk_ranges_overlap(ext_in, ext_in ? eb : 0, out, ob) &&
+                  !srk_ranges_overlap(ext_out, ext_out ? eb : 0, out, ob) && !srk_ranges_overlap(mode, mode ? eb / 2 : 0, out, ob),
+              SRK_E_SHAPE, "resize_ragged_mode: out overlaps x, an extent table or mode (the resize is not done in place)");
+  if (!ext_in && !ext_out)
+    SRK_REQUIRE(srk_resize_factor_ok(Hp, Hop) && srk_resize_factor_ok(Wp, Wop), SRK_E_UNSUPPORTED,
+                "resize_ragged_mode: %d x %d -> %d x %d shrinks an axis by more than 8x (the tile staging covers 8x)", Hp, Wp, Hop, Wop);
+  return srk_launch_resize_ragged_mode_f32(x, reinterpret_cast<const int*>(ext_in), out, reinterpret_cast<const int*>(ext_out),
+                                           reinterpret_cast<const int*>(mode), B, C, Hp, Wp, Hop, Wop, quant_bits, (hipStream_t)stream);
+}
+
+int srk_usm_sharpen_f32(const float* x, const float* taps, float* out, float* work, int B, int C, int H, int W, int ks, float weight,
+                        float threshold, srk_stream_t stream) {
+  REQ_PTR(x); REQ_PTR(taps); REQ_PTR(out); REQ_PTR(work);
+  SRK_REQUIRE(srk_usm_shape_ok(B, C, H, W, ks), SRK_E_SHAPE,
+              "usm_sharpen: B=%d H=%d W=%d must all be >= 1, C=%d must be 1 or 3, ks=%d odd and in 1..%d, and the size must fit one launch", B, H, W,
+              C, ks, SRK_USM_MAX_KS);
+  SRK_REQUIRE(srk_usm_extent_ok(H, W, ks), SRK_E_UNSUPPORTED, "usm_sharpen: a %d x %d image is not larger than R = %d (ks=%d)", H, W, ks / 2, ks);
+  const size_t bytes = (size_t)(4.0 * B * C * H * W), kb = sizeof(float) * (size_t)ks;
+  SRK_REQUIRE(!srk_ranges_overlap(x, bytes, out, bytes) && !srk_ranges_overlap(x, bytes, work, bytes) && !srk_ranges_overlap(out, bytes, work, bytes) &&
+                  !srk_ranges_overlap(taps, kb, out, bytes) && !srk_ranges_overlap(taps, kb, work, bytes),
+              SRK_E_SHAPE, "usm_sharpen: x, taps, out and work must not overlap");
+  return srk_launch_usm_sharpen_f32(x, taps, out, work, B, C, H, W, ks, weight, threshold, (hipStream_t)stream);
+}
+
 int srk_crop_restore_u8(const uint8_t* pool, const int64_t* desc10, float* clean_out, float* degraded_out, int B, int patch, int out_chans,
                         int subsample, int quant_bits, srk_stream_t stream) {
   REQ_PTR(pool); REQ_PTR(desc10); REQ_PTR(clean_out); REQ_PTR(degraded_out);

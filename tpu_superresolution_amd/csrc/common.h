@@ -145,6 +145,10 @@ static inline bool srk_resize_ragged_shape_ok(int B, int C, int Hp, int Wp, int 
 }
 static inline bool srk_ragged_extent_ok(int h, int w, int Hp, int Wp) { return h >= 1 && h <= Hp && w >= 1 && w <= Wp; }
 static inline bool srk_resize_factor_ok(int n_in, int n_out) { return n_in >= 1 && n_out >= 1 && (long long)n_in <= 8LL * n_out; }
+// unsharp mask (usm.hip, srk.h srk_usm_sharpen_f32): the 1-D taps, the shapes (those of srk_noise_f32), and both extents above R = ks / 2
+static inline bool srk_usm_ks_ok(int ks) { return ks >= 1 && ks <= SRK_USM_MAX_KS && (ks & 1) == 1; }
+static inline bool srk_usm_shape_ok(int B, int C, int H, int W, int ks) { return srk_usm_ks_ok(ks) && srk_noise_shape_ok(B, C, H, W); }
+static inline bool srk_usm_extent_ok(int H, int W, int ks) { return H > ks / 2 && W > ks / 2; }
 // tables built on the device (tables.hip, srk.h "Blur and sinc tables built on the device"): n tables of side ks, and the bank triple --
 // absent (no pointer, n_bank = kb = 0) or present with kb odd in 1..ks.  n * 21 * 21 * 8 and n_bank * 21 * 21 * 4 stay below 2^63 for
 // every int, so the byte counts the entry forms (srk_tables_bytes, in 64 bits) cannot wrap.

@@ -91,6 +91,12 @@ int srk_launch_resize_aa_ragged_f32(const float* x, const int* ext_in, float* ou
                                     int Wop, int quant_bits, hipStream_t stream);
 int srk_launch_jpeg_roundtrip_ragged_f32(const float* x, float* out, const int* quality, const int* ext, int B, int C, int Hp, int Wp,
                                          int subsample, hipStream_t stream);
+// resize_modes.hip: the ragged resize with a rule per sample (arguments checked by srk_resize_ragged_mode_f32)
+int srk_launch_resize_ragged_mode_f32(const float* x, const int* ext_in, float* out, const int* ext_out, const int* mode, int B, int C, int Hp,
+                                      int Wp, int Hop, int Wop, int quant_bits, hipStream_t stream);
+// usm.hip: the separable unsharp mask (arguments checked by srk_usm_sharpen_f32)
+int srk_launch_usm_sharpen_f32(const float* x, const float* taps, float* out, float* work, int B, int C, int H, int W, int ks, float weight,
+                               float threshold, hipStream_t stream);
 // tile.hip: tiled inference (arguments checked by srk_tile_gather_f32 / srk_tile_merge_f32).  One axis of the tile grid: extent n,
 // tile t (1 <= t <= n), stride s (1 <= s <= t), k = ceil((n - t) / s) + 1 tiles, origin o_i = min(i * s, n - t)
 struct TileAxis { int n, t, s, k; };

@@ -22,7 +22,8 @@ DESIGN 7n); ``main(argv)`` is callable from tests.  SSIM is ``metrics.ssim`` (re
 and ``bench_*`` keys with the scores of the papers' protocol -- 8-bit, border-cropped (default: the scale), BT.601 luma or RGB, 0..255
 scale, mean over images (metrics.bench_metrics); the other lines and keys stay as they are.
 ``--synth_lr --degrade second_order`` degrades the HR images with the fixed second-order chain (SecondOrderSpec.fixed, ops.degrade_second_order,
-DESIGN 7p).
+DESIGN 7p); with ``--gt_usm [--usm_weight W --usm_threshold T --usm_radius R]`` the HR images are unsharp-masked first (ops.usm_sharpen), the chain
+runs on the sharpened images and every score is taken against them.
 ``--task dn | car --scale X1 --arch swinir [--channels 1|3 --dn_sigma S --jpeg_quality Q]`` scores the scale-1 restoration models: the clean test
 images are noised / JPEG-coded as whole images on the device (ops.restore_degrade) and the baseline line is the degraded input itself.
 """
@@ -146,6 +147,13 @@ def parse_args(argv=None):
                          "JPEG at quality Q in 1..100 on the device (ops.jpeg_roundtrip, csrc/jpeg.hip), before any tiling or self-ensemble")
     ap.add_argument("--jpeg_subsample", type=str, choices=["444", "420"], default="444",
                     help="additive, with --jpeg_quality: chroma at 4:4:4, or 4:2:0 (2 x 2 means, upsampled by replication)")
+    ap.add_argument("--gt_usm", action="store_true",
+                    help="additive, with --degrade second_order: score a model trained with finetune_swinir --gt_usm -- the HR image is "
+                         "unsharp-masked on the device (ops.usm_sharpen, csrc/usm.hip, DESIGN 7r), the fixed chain (bicubic resizes) runs "
+                         "on the sharpened image and every score is taken against it")
+    ap.add_argument("--usm_radius", type=int, default=None, help="additive, with --gt_usm: Real-ESRGAN's radius, 1..51 (default 50)")
+    ap.add_argument("--usm_weight", type=float, default=None, help="additive, with --gt_usm: weight of the residual (default 0.5)")
+    ap.add_argument("--usm_threshold", type=float, default=None, help="additive, with --gt_usm: threshold of the mask in 8-bit levels (default 10)")
     ap.add_argument("--bench_metric", type=str, choices=["y", "rgb"], default=None,
                     help="additive: also report PSNR / SSIM by the protocol of the SwinIR / HAT / DAT papers (metrics.bench_metrics): "
                          "8-bit, border-cropped, y = BT.601 luma of RGB (a single-channel image is its own luma), rgb = every channel, "
@@ -196,6 +204,15 @@ def parse_args(argv=None):
             pack_degrade_params(args.blur_sigma, (args.noise_sigma / 255.0, args.noise_gain), 0, False)
         except ValueError as e:
             ap.error(f"--degrade {args.degrade}: {e}")
+    usm_opts = [n for n in ("usm_radius", "usm_weight", "usm_threshold") if getattr(args, n) is not None]
+    if args.gt_usm and args.degrade != "second_order":
+        ap.error("--gt_usm sharpens the target of --degrade second_order: it needs it")
+    if usm_opts and not args.gt_usm:
+        ap.error(f"--{usm_opts[0]} is an option of --gt_usm")
+    try:
+        eval_usm(args)
+    except ValueError as e:
+        ap.error(f"--gt_usm: {e}")
     if (args.blur_theta is not None or args.blur_psf is not None) and args.degrade not in ("blind", "second_order"):
         ap.error("--blur_theta and --blur_psf shape the blur of --degrade blind | second_order: they need it")
     if args.blur_theta is not None and args.blur_psf is not None:
@@ -231,6 +248,14 @@ def eval_restore(args):
     fx = FixedRestore((args.dn_sigma or 0.0) / 255.0, args.jpeg_quality or 0, False, args.jpeg_subsample == "420")
     pack_restore_params(fx.jpeg_quality, (fx.sigma, 0.0), 0, False)          # the ranges
     return fx
+
+
+def eval_usm(args):
+    """The UsmSpec of the command line (None without --gt_usm)."""
+    if not args.gt_usm:
+        return None
+    from .sr_datasets import UsmSpec
+    return UsmSpec(**{k: v for k, v in (("radius", args.usm_radius), ("weight", args.usm_weight), ("threshold", args.usm_threshold)) if v is not None})
 
 
 def eval_psf(args):
@@ -294,7 +319,7 @@ def main(argv=None):
             second = SecondOrderSpec() if args.jpeg_quality is None else SecondOrderSpec(jpeg_quality=(args.jpeg_quality,) * 2)
         test_loader = SynthLRBatches(test_loader, scale_int, args.synth_lr_bits, device, degrade=fixed,
                                      jpeg=None if second is not None else args.jpeg_quality, jpeg_subsample=args.jpeg_subsample == "420",
-                                     psf=eval_psf(args), second_order=second)
+                                     psf=eval_psf(args), second_order=second, usm=eval_usm(args))
         print(f"[synth_lr] LR = antialiased bicubic /{scale_int} of HR on the device, {args.synth_lr_bits or 'no'}-bit rounding")
         if fixed is not None:
             print(f"[degrade] blind: blur sigma=({fixed.blur[0]:.4g}, {fixed.blur[1]:.4g}) HR px, noise sigma={args.noise_sigma:.4g} / 255 "
@@ -307,6 +332,10 @@ def main(argv=None):
             fx2 = second.fixed(None, fixed.noise)
             print(f"[degrade] second order, fixed: resize x{fx2.r1:.4g}, jpeg {fx2.q1}, blur 2 {fx2.k2.shape[0]} taps, resize x{fx2.r2:.4g} of LR, "
                   f"noise sigma={fx2.noise2[0] * 255.0:.4g} / 255, jpeg {fx2.q2}, final filter {fx2.k3.shape[0]} taps, chroma {args.jpeg_subsample}")
+            if args.gt_usm:
+                us = eval_usm(args)
+                print(f"[degrade] gt_usm: HR is unsharp-masked ({us.ks} taps, weight {us.weight:g}, threshold {us.threshold:g} / 255); LR is "
+                      f"degraded from it and every score is taken against it")
         elif args.jpeg_quality is not None:
             print(f"[degrade] jpeg: quality {args.jpeg_quality}, chroma {args.jpeg_subsample}")
     print(f"[data] test samples: {len(test_ds)} | steps: {len(test_loader)}")

@@ -28,6 +28,9 @@ round trip at a random per-sample quality in a second launch (csrc/jpeg.hip, DES
 intermediate sizes, then a sinc filter (sr_datasets.DeviceHR2Pool, csrc/filter2d.hip, csrc/ragged.hip).
 `--degrade_tables device` (with the 2-D kernels of --degrade blind, or --degrade second_order) builds the blur and sinc tables of every
 training batch on the device instead of in numpy on the training thread (csrc/tables.hip).
+`--gt_usm [--usm_weight W --usm_threshold T --usm_radius R]` (with --degrade second_order) unsharp-masks the HR window on the device, degrades
+the LR patch from the sharpened window and takes the loss against it; `--resize_mode_prob AREA BILINEAR BICUBIC` draws the rule of each of
+the chain's three resizes per sample (csrc/usm.hip, csrc/resize_modes.hip).
 `--blur_kernel rotated|mixed` or `--blur_psf FILE` (with --degrade blind) blurs every patch with a 2-D table -- a rotated, generalized or
 plateau Gaussian, or a measured point-spread function -- in the same single launch (csrc/blur2d.hip).
 
@@ -380,6 +383,18 @@ def parse_args(argv=None):
                     help="additive, with --degrade second_order: probability of the final sinc filter (default 0.8)")
     ap.add_argument("--degrade_margin", type=int, default=None,
                     help="additive, with --degrade second_order: LR pixels around the patch that the chain also runs on (default 8)")
+    ap.add_argument("--resize_mode_prob", type=float, nargs=3, default=None, metavar=("AREA", "BILINEAR", "BICUBIC"),
+                    help="additive, with --degrade second_order: probabilities of the rule of each of the three resizes of a training patch "
+                         "(csrc/resize_modes.hip, DESIGN 7r; Real-ESRGAN draws among the three; default 0 0 1, the antialiased cubic).  "
+                         "Validation keeps the cubic")
+    ap.add_argument("--gt_usm", action="store_true",
+                    help="additive, with --degrade second_order: Real-ESRGAN's gt_usm -- the HR window is unsharp-masked once on the device "
+                         "(csrc/usm.hip, DESIGN 7r), the LR patch is degraded from the sharpened window and the loss is taken against it; "
+                         "validation scores against the sharpened image.  --degrade_margin 13 at X4 (25 at X2) keeps the window's reflected "
+                         "edge out of the patch")
+    ap.add_argument("--usm_radius", type=int, default=None, help="additive, with --gt_usm: Real-ESRGAN's radius, 1..51 (default 50: 51 taps, sigma 8)")
+    ap.add_argument("--usm_weight", type=float, default=None, help="additive, with --gt_usm: weight of the residual (default 0.5)")
+    ap.add_argument("--usm_threshold", type=float, default=None, help="additive, with --gt_usm: threshold of the mask in 8-bit levels (default 10)")
     ap.add_argument("--task", type=str, choices=["sr", "dn", "car"], default="sr",
                     help="additive: sr = super-resolution (as ever); dn = denoising, car = JPEG compression-artifact reduction: the published "
                          "scale-1 SwinIR models (build_restoration_model), trained from the HR directories alone -- every patch is cut at "
@@ -446,6 +461,15 @@ def parse_args(argv=None):
             ap.error(f"--degrade_margin must be in 0..64 LR pixels (got {args.degrade_margin})")
     elif second:
         ap.error(f"--{second[0]} is an option of --degrade second_order")
+    usm_opts = [n for n in USM_FLAGS if getattr(args, n) is not None]
+    if args.gt_usm and args.degrade != "second_order":
+        ap.error("--gt_usm sharpens the target of --degrade second_order: it needs it")
+    if usm_opts and not args.gt_usm:
+        ap.error(f"--{usm_opts[0]} is an option of --gt_usm")
+    try:
+        usm_spec(args)
+    except ValueError as e:
+        ap.error(f"--gt_usm: {e}")
     mixed_opts = [n for n in ("blur_kernel_prob", "blur_beta_g", "blur_beta_p", "blur_ksize") if getattr(args, n) is not None]
     if (args.blur_kernel != "axis" or args.blur_psf is not None) and args.degrade not in ("blind", "second_order"):
         ap.error("--blur_kernel and --blur_psf shape the blur of --degrade blind | second_order: they need it")
@@ -528,7 +552,16 @@ def jpeg_spec(args):
 
 
 SECOND_ORDER_FLAGS = ("blur2_sigma", "blur2_p", "noise2_sigma", "jpeg2_quality", "resize_range", "resize_prob", "resize2_range", "resize2_prob",
-                      "sinc_p", "final_sinc_p", "degrade_margin")
+                      "sinc_p", "final_sinc_p", "degrade_margin", "resize_mode_prob")
+USM_FLAGS = ("usm_radius", "usm_weight", "usm_threshold")
+
+
+def usm_spec(args):
+    """The UsmSpec of the command line (None without --gt_usm): the flags that were given replace Real-ESRGAN's defaults."""
+    if not args.gt_usm:
+        return None
+    from .sr_datasets import UsmSpec
+    return UsmSpec(**{k: v for k, v in (("radius", args.usm_radius), ("weight", args.usm_weight), ("threshold", args.usm_threshold)) if v is not None})
 
 
 def second_order_spec(args):
@@ -541,7 +574,8 @@ def second_order_spec(args):
     opts = {k: (v if isinstance(v, float) else tuple(v)) for k, v in (
         ("blur2_sigma", args.blur2_sigma), ("blur2_p", args.blur2_p), ("jpeg2_quality", args.jpeg2_quality), ("resize_range", args.resize_range),
         ("resize_prob", args.resize_prob), ("resize2_range", args.resize2_range), ("resize2_prob", args.resize2_prob), ("sinc_p", args.sinc_p),
-        ("final_sinc_p", args.final_sinc_p), ("jpeg_quality", args.jpeg_quality), ("ksize", args.blur_ksize)) if v is not None}
+        ("final_sinc_p", args.final_sinc_p), ("jpeg_quality", args.jpeg_quality), ("ksize", args.blur_ksize),
+        ("resize_mode_prob", args.resize_mode_prob)) if v is not None}
     if args.noise2_sigma is not None:
         opts["noise2_sigma"] = tuple(v / 255.0 for v in args.noise2_sigma)
     return SecondOrderSpec(gray_noise_p=args.gray_noise_p, seed=args.degrade_seed, **opts)
@@ -574,7 +608,8 @@ def saved_args(args) -> dict:
                   "degrade_tables": args.degrade_tables == "host", "val_bench_metric": args.val_bench_metric is None,
                   "val_crop_border": args.val_crop_border is None, "task": args.task == "sr", "channels": args.channels == 3,
                   "dn_sigma": args.dn_sigma is None, "dn_bits": args.dn_bits == 0}
-    at_default.update({n: getattr(args, n) is None for n in SECOND_ORDER_FLAGS})
+    at_default.update({n: getattr(args, n) is None for n in SECOND_ORDER_FLAGS + USM_FLAGS})
+    at_default["gt_usm"] = not args.gt_usm
     return {k: v for k, v in vars(args).items() if not at_default.get(k, False)}
 
 
@@ -619,7 +654,8 @@ def main(argv=None):
             pool = DeviceHR2Pool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, second_order_spec(args), degrade_spec(args),
                                  device=device, shard_bytes=(args.gpu_data_shard_mb << 20) or None, augment=args.augment, rank=rank,
                                  psf=psf_spec(args), margin=8 if args.degrade_margin is None else args.degrade_margin,
-                                 subsample=args.jpeg_subsample == "420", names=[f.name for f in raw.files], tables=args.degrade_tables)
+                                 subsample=args.jpeg_subsample == "420", names=[f.name for f in raw.files], tables=args.degrade_tables,
+                                 usm=usm_spec(args))
         else:
             pool = DeviceHRPool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, device=device,
                                 shard_bytes=(args.gpu_data_shard_mb << 20) or None, augment=args.augment, quant_bits=args.synth_lr_bits,
@@ -635,6 +671,14 @@ def main(argv=None):
                       f"p={list(so.resize_prob)} then {list(so.resize2_range)} p={list(so.resize2_prob)}, blur 2 p={so.blur2_p:g}, sinc p={so.sinc_p:g} "
                       f"final p={so.final_sinc_p:g}, jpeg {list(so.jpeg_quality)} then {list(so.jpeg2_quality)} chroma {args.jpeg_subsample}, seed "
                       f"{args.degrade_seed}; validation: the fixed chain (SecondOrderSpec.fixed), noise id = image index")
+                if so.resize_mode_prob != (0.0, 0.0, 1.0):
+                    print(f"[degrade] resize rules: area / bilinear / bicubic with p={list(so.resize_mode_prob)} at each of the three resizes; "
+                          f"validation: bicubic")
+                if args.gt_usm:
+                    us = usm_spec(args)
+                    print(f"[degrade] gt_usm: the HR window is unsharp-masked ({us.ks} taps, weight {us.weight:g}, threshold {us.threshold:g} / 255); "
+                          f"LR is degraded from it and the loss is taken against it; margin {pool.margin} x scale {scale_int} "
+                          f"{'>=' if pool.margin * scale_int >= us.ks - 1 else '<'} 2R = {us.ks - 1}")
             if args.degrade in ("blind", "second_order"):
                 fx = degrade_spec(args).fixed()
                 print(f"[degrade] blind: blur sigma in {args.blur_sigma} HR px (aniso p={args.blur_aniso_p}), noise sigma in "
@@ -673,7 +717,8 @@ def main(argv=None):
         valid_loader = RestoreBatches(valid_loader, args.channels, restore_spec(args), args.dn_bits, device)
     if args.synth_lr:
         valid_loader = SynthLRBatches(valid_loader, scale_int, args.synth_lr_bits, device, degrade=degrade_spec(args), jpeg=jpeg_spec(args),
-                                      jpeg_subsample=args.jpeg_subsample == "420", psf=psf_spec(args), second_order=second_order_spec(args))
+                                      jpeg_subsample=args.jpeg_subsample == "420", psf=psf_spec(args), second_order=second_order_spec(args),
+                                      usm=usm_spec(args))
 
     if args.task != "sr":
         model = build_restoration_model(args.task, args.channels, args.drop_path_rate, args.window_size)
@@ -776,6 +821,8 @@ def main(argv=None):
         if val_border is not None:
             tag = args.val_bench_metric.upper()
             val_more += f", bench PSNR-{tag}={val[-3]:.2f}dB SSIM-{tag}={val[-2]:.4f} (8-bit, border {val_border})"
+        if args.gt_usm:
+            val_more += " [against the USM-sharpened target]"
         print(f"[{args.scale}] epoch {epoch:03d}/{args.epochs} | lr={opt.param_groups[0]['lr']:.2e} | "
               f"train {train_name}={tr_loss:.6f} ({tr_t:.1f}s) | val L1={val_loss:.6f}, PSNR={val_psnr:.2f}dB{val_more} ({val_t:.1f}s)")
         sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}     # un-prefixed keys, like the reference

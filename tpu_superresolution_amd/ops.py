@@ -1014,6 +1014,103 @@ def resize_aa_ragged(x: torch.Tensor, ext_in, ext_out, pad_out=None, quant_bits:
     return out
 
 
+RESIZE_MODES = ("cubic", "bilinear", "area")          # the mode words of srk_resize_ragged_mode_f32
+
+
+def resize_ragged(x: torch.Tensor, ext_in, ext_out, modes, pad_out=None, quant_bits: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`resize_aa_ragged` with a resize rule per sample (csrc/resize_modes.hip, srk_resize_ragged_mode_f32): modes = None or B words,
+    0 the antialiased cubic (that sample has the bits of `resize_aa_ragged`), 1 bilinear without antialiasing (F.interpolate,
+    align_corners=False), 2 area (adaptive average pooling).  None or all zeros IS `resize_aa_ragged`: the same launch.  The 8x limit
+    holds for every mode.  One launch after one small upload."""
+    if modes is None:
+        return resize_aa_ragged(x, ext_in, ext_out, pad_out, quant_bits, out)
+    try:
+        ms = [int(m) for m in modes]
+    except (TypeError, ValueError):
+        raise ValueError(f"resize_ragged: modes must be None or one word in 0..2 per sample (got {modes!r})") from None
+    if any(m not in (0, 1, 2) or isinstance(v, bool) for m, v in zip(ms, modes)):
+        raise ValueError(f"resize_ragged: a mode is 0 (cubic), 1 (bilinear) or 2 (area) (got {ms})")
+    if x.dim() != 4 or len(ms) != x.shape[0]:
+        raise ValueError(f"resize_ragged: one mode per sample of a [B,C,H,W] batch (got {len(ms)} for {tuple(x.shape)})")
+    if not any(ms):
+        return resize_aa_ragged(x, ext_in, ext_out, pad_out, quant_bits, out)
+    if not x.is_cuda or x.dtype != torch.float32 or min(x.shape) < 1:
+        raise ValueError(f"resize_ragged takes a non-empty CUDA fp32 [B,C,H,W] batch (got {x.dtype} {tuple(x.shape)} on {x.device})")
+    if quant_bits not in (0, 8):
+        raise ValueError(f"resize_ragged: quant_bits must be 0 or 8 (got {quant_bits!r})")
+    x = x.contiguous()
+    B, Cc, Hp, Wp = x.shape
+    ei = _ragged(ext_in, B, Hp, Wp, x.device, "resize_ragged: ext_in")
+    if ext_out is None and pad_out is None:
+        raise ValueError("resize_ragged: a dense output needs pad_out = (Hop, Wop)")
+    if ext_out is not None and not isinstance(ext_out, RaggedExt):
+        ext_out = RaggedExt(ext_out, x.device)
+    try:
+        Hop, Wop = ext_out.pad() if pad_out is None else (int(v) for v in pad_out)
+    except (TypeError, ValueError):
+        raise ValueError(f"resize_ragged: pad_out must be (Hop, Wop) (got {pad_out!r})") from None
+    if Hop < 1 or Wop < 1:
+        raise ValueError(f"resize_ragged: pad_out must be >= 1 (got {(Hop, Wop)})")
+    eo = _ragged(ext_out, B, Hop, Wop, x.device, "resize_ragged: ext_out")
+    for (h, w), (ho, wo) in zip([(Hp, Wp)] * B if ei is None else ei.host, [(Hop, Wop)] * B if eo is None else eo.host):
+        if h > 8 * ho or w > 8 * wo:
+            raise _lib.SrkUnsupported(f"resize_ragged: {h} x {w} -> {ho} x {wo} shrinks an axis by more than 8x (the tile staging covers 8x)")
+    out = _padded_out(out, (B, Cc, Hop, Wop), x)
+    md = torch.tensor(ms, dtype=torch.int32).to(x.device)
+    check(lib().srk_resize_ragged_mode_f32(_p(x), _ext_ptr(ei), _p(out), _ext_ptr(eo), _p(md), B, Cc, Hp, Wp, Hop, Wop, int(quant_bits),
+                                           _stream()))
+    return out
+
+
+_USM_TAPS: dict = {}
+
+
+def usm_ks(radius: int) -> int:
+    """The tap count of `usm_sharpen` for Real-ESRGAN's `radius`: radius + 1 if it is even, else radius."""
+    if isinstance(radius, bool) or not isinstance(radius, numbers.Integral) or not 1 <= radius <= 51:
+        raise ValueError(f"usm: radius must be an integer in 1..51 (got {radius!r})")
+    return int(radius) + 1 if radius % 2 == 0 else int(radius)
+
+
+def usm_taps(ks: int, sigma: float, device) -> torch.Tensor:
+    """The fp32 taps `blur_kernels.gaussian1d(ks, sigma)` on `device`: uploaded once per (device, ks, sigma) and kept."""
+    from . import blur_kernels as bk
+    device = torch.device(device)
+    key = (device.type, device.index if device.index is not None else torch.cuda.current_device(), int(ks), float(sigma))
+    t = _USM_TAPS.get(key)
+    if t is None:
+        t = _USM_TAPS[key] = torch.from_numpy(bk.gaussian1d(ks, sigma)).to(device)
+    return t
+
+
+def usm_sharpen(x: torch.Tensor, radius: int = 50, sigma: float = 0.0, weight: float = 0.5, threshold: float = 10.0,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Real-ESRGAN's USMSharp on x CUDA fp32 [B,C,H,W] in [0, 1], C 1 or 3 (csrc/usm.hip, srk_usm_sharpen_f32; include/srk.h states the
+    arithmetic): blur = G(x), res = x - blur, mask = |res| 255 > threshold, soft = G(mask), out = soft clamp(x + weight res, 0, 1) +
+    (1 - soft) x, G the separable Gaussian of ks = radius + 1 (radius even) or radius taps under a reflect-101 border.  sigma <= 0 takes
+    OpenCV's rule 0.3 ((ks - 1) / 2 - 1) + 0.8: the defaults are 51 taps at sigma 8.  H and W must exceed (ks - 1) / 2.  Two launches;
+    one work buffer of x's size is allocated per call by torch."""
+    if x.dim() != 4 or not x.is_cuda or x.dtype != torch.float32 or min(x.shape) < 1 or x.shape[1] not in (1, 3):
+        raise ValueError(f"usm_sharpen takes a non-empty CUDA fp32 [B,C,H,W] batch with C 1 or 3 (got {x.dtype} {tuple(x.shape)} on {x.device})")
+    ks = usm_ks(radius)
+    sigma = float(sigma)
+    if not sigma == sigma or sigma == float("inf"):
+        raise ValueError(f"usm_sharpen: sigma must be finite (got {sigma!r})")
+    if sigma <= 0.0:
+        sigma = 0.3 * ((ks - 1) / 2 - 1) + 0.8
+    weight, threshold = float(weight), float(threshold)
+    if not (weight == weight and threshold == threshold) or abs(weight) == float("inf"):
+        raise ValueError(f"usm_sharpen: weight and threshold must be numbers (got {weight!r}, {threshold!r})")
+    x = x.contiguous()
+    B, Cc, H, W = x.shape
+    if min(H, W) <= ks // 2:
+        raise _lib.SrkUnsupported(f"usm_sharpen: a {H} x {W} image is not larger than R = {ks // 2} (radius {radius})")
+    out = _padded_out(out, x.shape, x)
+    work = torch.empty_like(x)
+    check(lib().srk_usm_sharpen_f32(_p(x), _p(usm_taps(ks, sigma, x.device)), _p(out), _p(work), B, Cc, H, W, ks, weight, threshold, _stream()))
+    return out
+
+
 def _qualities(quality, B: int, what: str):
     qs = [quality] * B if isinstance(quality, numbers.Real) else list(quality)
     if len(qs) != B:
@@ -1044,7 +1141,8 @@ class SecondOrder(NamedTuple):
     the three filters (blur_kernels; a delta = no filter; or `blur_kernels.TableDesc` descriptors, which the device turns into tables), resize factors r1 / r2 of the two intermediate sizes, noise1 / noise2 =
     (sigma_n, gain) with their gray flags, JPEG qualities q1 (stage 1) and q2 (stage 2), `jpeg_last`: False = order A (JPEG 2, final
     resize, final filter), True = order B (final resize, final filter, JPEG 2); the Philox key of noise 1 (noise 2 takes its
-    complement)."""
+    complement).  modes: the rule of resize 1, resize 2 and the final resize (`resize_ragged`: 0 antialiased cubic, 1 bilinear,
+    2 area); the default is the cubic of every earlier release."""
     k1: object
     r1: float
     noise1: Tuple[float, float]
@@ -1058,6 +1156,7 @@ class SecondOrder(NamedTuple):
     jpeg_last: bool
     k3: object
     noise_id: int
+    modes: Tuple[int, int, int] = (0, 0, 0)
 
 
 def second_order_sizes(H: int, W: int, scale: int, p: SecondOrder):
@@ -1084,6 +1183,17 @@ def _stage_tables(ks_list, bank, device, what: str):
     return kernel_tables(ks_list, bank=bank, device=device)
 
 
+def _stage_modes(ps):
+    """The mode lists of the three resizes of `degrade_second_order`; None for a stage whose samples all take the cubic (the launch of
+    `resize_aa_ragged`, and no upload)."""
+    if all(p.modes == (0, 0, 0) for p in ps):          # the chain of every earlier release: nothing to check, build or upload
+        return None, None, None
+    for p in ps:
+        if len(p.modes) != 3 or any(isinstance(m, bool) or m not in (0, 1, 2) for m in p.modes):
+            raise ValueError(f"degrade_second_order: modes must be three words in 0..2 (got {p.modes!r})")
+    return tuple(([p.modes[k] for p in ps] if any(p.modes[k] for p in ps) else None) for k in range(3))
+
+
 def degrade_second_order(x: torch.Tensor, scale: int, params, subsample: bool = False, pads=None, bufs: Optional[dict] = None,
                          bank=None) -> torch.Tensor:
     """The second-order blind degradation on a batch x CUDA fp32 [B,C,H,W] (C = 1 or 3; H, W multiples of `scale` in 1..4), one
@@ -1096,7 +1206,9 @@ def degrade_second_order(x: torch.Tensor, scale: int, params, subsample: bool = 
     (default: the batch's largest); bufs: a dict that keeps the work buffers between calls.
     k1 / k2 / k3 may be `blur_kernels.TableDesc` descriptors in place of tables -- per stage all or none of the batch -- and the
     stage's tables are then built on the device by one `kernel_tables` launch (three more tiny launches, three fewer table uploads);
-    bank: the CUDA tensor that kind-5 descriptors index."""
+    bank: the CUDA tensor that kind-5 descriptors index.
+    `SecondOrder.modes` picks the rule of each of the three resizes per sample (`resize_ragged`); a stage whose samples all take mode 0
+    is the launch of `resize_aa_ragged`, so the default is the chain of every earlier release."""
     if x.dim() != 4 or not x.is_cuda or x.dtype != torch.float32:
         raise ValueError(f"degrade_second_order takes a CUDA fp32 [B,C,H,W] batch (got {x.dtype} {tuple(x.shape)} on {x.device})")
     s = int(scale)
@@ -1124,14 +1236,15 @@ def degrade_second_order(x: torch.Tensor, scale: int, params, subsample: bool = 
     x = x.contiguous()
     t1, t2, t3 = (_stage_tables([getattr(p, k) for p in ps], bank, x.device, k) for k in ("k1", "k2", "k3"))
     a = filter2d(x, t1, out=buf("f1", B, Cc, H, W))
-    a = resize_aa_ragged(a, None, e1, (Hp1, Wp1), out=buf("a1", B, Cc, Hp1, Wp1))
+    m1, m2, m3 = _stage_modes(ps)
+    a = resize_ragged(a, None, e1, m1, (Hp1, Wp1), out=buf("a1", B, Cc, Hp1, Wp1))
     a = _noise_into(a, [p.noise1 for p in ps], [i[0] for i in ids], [p.gray1 for p in ps], buf("b1", B, Cc, Hp1, Wp1))
     a = jpeg_roundtrip_ragged(a, [p.q1 for p in ps], e1, subsample, out=buf("a1", B, Cc, Hp1, Wp1))
     a = filter2d(a, t2, e1, out=buf("b1", B, Cc, Hp1, Wp1))
-    a = resize_aa_ragged(a, e1, e2, (Hp2, Wp2), out=buf("a2", B, Cc, Hp2, Wp2))
+    a = resize_ragged(a, e1, e2, m2, (Hp2, Wp2), out=buf("a2", B, Cc, Hp2, Wp2))
     a = _noise_into(a, [p.noise2 for p in ps], [i[1] for i in ids], [p.gray2 for p in ps], buf("b2", B, Cc, Hp2, Wp2))
     a = jpeg_roundtrip_ragged(a, qa, e2, subsample, out=buf("a2", B, Cc, Hp2, Wp2))
-    a = resize_aa_ragged(a, e2, None, (Ho, Wo), out=buf("lr0", B, Cc, Ho, Wo))
+    a = resize_ragged(a, e2, None, m3, (Ho, Wo), out=buf("lr0", B, Cc, Ho, Wo))
     a = filter2d(a, t3, quant_bits=8, out=buf("lr1", B, Cc, Ho, Wo))
     return jpeg_roundtrip(a, qb, subsample)
 

@@ -505,13 +505,13 @@ class PsfSpec:
         return self._tables[0] if self._tables is not None else None
 
 
-def _check_prob3(name: str, p) -> Tuple[float, float, float]:
+def _check_prob3(name: str, p, what: str = "UP DOWN KEEP") -> Tuple[float, float, float]:
     try:
         prob = tuple(float(v) for v in p)
     except (TypeError, ValueError):
-        raise ValueError(f"{name} must be three numbers UP DOWN KEEP (got {p!r})") from None
+        raise ValueError(f"{name} must be three numbers {what} (got {p!r})") from None
     if len(prob) != 3 or not all(0.0 <= v <= 1.0 for v in prob) or abs(sum(prob) - 1.0) > 1e-6:
-        raise ValueError(f"{name} must be three probabilities UP DOWN KEEP that sum to 1 (got {p!r})")
+        raise ValueError(f"{name} must be three probabilities {what} that sum to 1 (got {p!r})")
     return prob
 
 
@@ -523,6 +523,38 @@ def _check_factors(name: str, r) -> Tuple[float, float]:
     if not 0.125 <= lo <= 1.0 <= hi <= 2.0:          # also refuses NaN; below 1/8 the resize has more than 33 taps
         raise ValueError(f"{name} must satisfy 0.125 <= LO <= 1 <= HI <= 2 (got {lo} {hi})")
     return lo, hi
+
+
+@dataclass(frozen=True)
+class UsmSpec:
+    """The unsharp mask of `--gt_usm` (Real-ESRGAN's `gt_usm`; `ops.usm_sharpen`): `radius` 1..51 (ks = radius + 1 if it is even),
+    `sigma` (<= 0: OpenCV's rule from ks), `weight` of the residual, `threshold` of the mask in 8-bit levels."""
+    radius: int = 50
+    sigma: float = 0.0
+    weight: float = 0.5
+    threshold: float = 10.0
+
+    def __post_init__(self):
+        from .ops import usm_ks
+        usm_ks(self.radius)
+        for name, lo, hi in (("sigma", -math.inf, 100.0), ("weight", 0.0, 10.0), ("threshold", 0.0, 255.0)):
+            try:
+                v = float(getattr(self, name))
+            except (TypeError, ValueError):
+                raise ValueError(f"usm {name} must be a number (got {getattr(self, name)!r})") from None
+            if not (lo <= v <= hi) or (name == "sigma" and not math.isfinite(v)):          # also refuses NaN
+                raise ValueError(f"usm {name} must be in [{lo}, {hi}] (got {v!r})")
+            object.__setattr__(self, name, v)
+        object.__setattr__(self, "radius", int(self.radius))
+
+    @property
+    def ks(self) -> int:
+        from .ops import usm_ks
+        return usm_ks(self.radius)
+
+    def sharpen(self, x: torch.Tensor) -> torch.Tensor:
+        from .ops import usm_sharpen
+        return usm_sharpen(x, self.radius, self.sigma, self.weight, self.threshold)
 
 
 SECOND_ORDER_VARIATES = 23          # per SecondOrderSpec.draw, whatever they decide
@@ -542,7 +574,11 @@ class SecondOrderSpec:
     Final: with probability `final_sinc_p` a sinc filter.  A sinc table has an odd side uniform in `ksize` and a cutoff uniform in
     [pi/3, pi] for sides below 13, else [pi/5, pi].
     Everything comes from the spec's OWN generator `random.Random(f"degrade2:{seed + rank}")`, 23 variates per draw whatever they
-    decide: the global `random` state and the other specs' generators never see it."""
+    decide: the global `random` state and the other specs' generators never see it.
+    `resize_mode_prob` = the probabilities AREA BILINEAR BICUBIC of the rule of each of the three resizes (`ops.resize_ragged`;
+    Real-ESRGAN draws among the three), from a generator of their own, `random.Random(f"degrade2mode:{seed + rank}")`, three variates
+    per draw: the 23 variates above and their generator are the same whatever it holds.  The default (0, 0, 1) is the antialiased
+    cubic at every resize."""
     resize_prob: Tuple[float, float, float] = (0.2, 0.7, 0.1)
     resize_range: Tuple[float, float] = (0.15, 1.5)
     resize2_prob: Tuple[float, float, float] = (0.3, 0.4, 0.3)
@@ -558,10 +594,12 @@ class SecondOrderSpec:
     jpeg_quality: Tuple[int, int] = (30, 95)
     jpeg2_quality: Tuple[int, int] = (30, 95)
     seed: int = 0
+    resize_mode_prob: Tuple[float, float, float] = (0.0, 0.0, 1.0)
 
     def __post_init__(self):
         from . import blur_kernels as bk
         from .ops import check_jpeg_quality
+        object.__setattr__(self, "resize_mode_prob", _check_prob3("resize_mode_prob", self.resize_mode_prob, "AREA BILINEAR BICUBIC"))
         object.__setattr__(self, "resize_prob", _check_prob3("resize_prob", self.resize_prob))
         object.__setattr__(self, "resize2_prob", _check_prob3("resize2_prob", self.resize2_prob))
         object.__setattr__(self, "resize_range", _check_factors("resize_range", self.resize_range))
@@ -596,6 +634,18 @@ class SecondOrderSpec:
     def rng(self, rank: int = 0) -> random.Random:
         return random.Random(f"degrade2:{int(self.seed) + int(rank)}")
 
+    def mode_rng(self, rank: int = 0) -> random.Random:
+        return random.Random(f"degrade2mode:{int(self.seed) + int(rank)}")
+
+    def draw_modes(self, mode_rng: Optional[random.Random]) -> Tuple[int, int, int]:
+        """The `ops.SecondOrder.modes` of one sample: three variates of `mode_rng`, whatever they decide; None = the cubic."""
+        if mode_rng is None:
+            return (0, 0, 0)
+        pa, pb, _ = self.resize_mode_prob
+        pb += pa
+        u0, u1, u2 = mode_rng.random(), mode_rng.random(), mode_rng.random()
+        return (2 if u0 < pa else (1 if u0 < pb else 0), 2 if u1 < pa else (1 if u1 < pb else 0), 2 if u2 < pa else (1 if u2 < pb else 0))
+
     def _ks(self, u: float) -> int:
         lo, hi = self.ksize
         n = (hi - lo) // 2 + 1
@@ -620,12 +670,13 @@ class SecondOrderSpec:
         return min(q[0] + int(u * (q[1] - q[0] + 1)), q[1])
 
     def draw(self, rng: random.Random, table1, noise1, noise_id: int, gray1: bool, colour: bool, extent: int, scale: int,
-             as_desc: bool = False):
+             as_desc: bool = False, mode_rng: Optional[random.Random] = None):
         """-> the `ops.SecondOrder` of one sample (as_desc: with `blur_kernels.TableDesc` descriptors for k1 / k2 / k3 -- table1 is then
         one too -- from the same variates and decisions).  table1, noise1, noise_id, gray1: the first-order draws (PsfSpec.draw or a Gaussian
         of DegradeSpec's sigmas; DegradeSpec.draw).  extent: the side of the square window the chain runs on at factor `scale`: it
         bounds filter 2, and factor 2 is raised where the second resize would shrink by more than the resampler's 8x (an upscale by
-        1.5 followed by 0.3 / 4 is 20x; Real-ESRGAN's resize has no such limit because it does not antialias)."""
+        1.5 followed by 0.3 / 4 is 20x; Real-ESRGAN's resize has no such limit because it does not antialias).  mode_rng: the
+        generator of `mode_rng()`, which `draw_modes` reads; None leaves every resize the cubic."""
         from . import blur_kernels as bk
         from .ops import SecondOrder
         if as_desc:
@@ -650,7 +701,8 @@ class SecondOrderSpec:
         ks3 = self._ks(u[22])
         k3 = bk.sinc(self._cutoff(ks3, u[21]), ks3) if (u[20] < self.final_sinc_p and ks3 // 2 < extent // int(scale)) else bk.delta()
         return SecondOrder(k1, r1, tuple(noise1), bool(gray1), self._quality(self.jpeg_quality, u[5]), k2, r2, noise2,
-                           u[17] < self.gray_noise_p or not colour, self._quality(self.jpeg2_quality, u[18]), u[19] < 0.5, k3, int(noise_id))
+                           u[17] < self.gray_noise_p or not colour, self._quality(self.jpeg2_quality, u[18]), u[19] < 0.5, k3, int(noise_id),
+                           self.draw_modes(mode_rng))
 
     def fixed(self, table1, noise1, gray1: bool = False, noise_id: int = 0):
         """What validation scores, every epoch and every run: no sinc at stages 1 and 2 (sinc_p < 0.5, else a sinc at the middle
@@ -839,17 +891,29 @@ class DeviceHR2Pool(DeviceHRPool):
     the axis-aligned Gaussian as a table); ``spec`` (a SecondOrderSpec) draws the rest from its own generator.  An image whose region
     is smaller than E is refused at construction.  The padded work buffers have the spec's largest sizes and are kept between calls:
     the launches and their shapes are the same every step.  ``tables`` "device": every stage's tables are built on the device from
-    descriptors (DeviceHRPool's switch; three `ops.kernel_tables` launches per batch, no table evaluated or uploaded by the host)."""
+    descriptors (DeviceHRPool's switch; three `ops.kernel_tables` launches per batch, no table evaluated or uploaded by the host).
+    ``usm`` (a UsmSpec): the E x E window is unsharp-masked once, the chain runs on the sharpened window, and the HR patch is
+    the P s window of the SHARPENED WINDOW at the patch's offset (not `srk_crop_u8`'s patch): a pixel of it depends on HR pixels up to
+    2R away, so margin * scale >= 2R keeps the window's reflected edge out of the patch (13 at x4 for the default R = 25; the default
+    margin of 8 does not).  None leaves `sample` as it was.  `spec.resize_mode_prob` draws the resize rules from a generator of its own."""
 
     def __init__(self, images, lr_patch: int, scale: int, spec: "SecondOrderSpec", degrade: Optional[DegradeSpec] = None, device="cuda",
                  shard_bytes: Optional[int] = None, augment: str = "none", rank: int = 0, psf: Optional[PsfSpec] = None, margin: int = 8,
-                 subsample: bool = False, names=None, tables: str = "host"):
+                 subsample: bool = False, names=None, tables: str = "host", usm: Optional["UsmSpec"] = None):
         if not isinstance(spec, SecondOrderSpec):
             raise ValueError(f"spec must be a SecondOrderSpec (got {type(spec).__name__})")
+        if usm is not None and not isinstance(usm, UsmSpec):
+            raise ValueError(f"usm must be a UsmSpec (got {type(usm).__name__})")
         if isinstance(margin, bool) or int(margin) != margin or not 0 <= int(margin) <= 64:
             raise ValueError(f"margin must be an integer in 0..64 LR pixels (got {margin!r})")
         self.spec, self._spec_rng, self.margin, self.subsample = spec, spec.rng(rank), int(margin), bool(subsample)
+        # at the default (0, 0, 1) every draw is the cubic whatever the variates: the generator is not consulted and `draw` costs what it did
+        self._mode_rng = spec.mode_rng(rank) if spec.resize_mode_prob != (0.0, 0.0, 1.0) else None
+        self.usm = usm
         self.extent = int(scale) * (int(lr_patch) + 2 * self.margin)
+        if usm is not None and self.extent <= usm.ks // 2:
+            raise ValueError(f"the {self.extent} x {self.extent} window of the second-order degradation is not larger than the R = "
+                             f"{usm.ks // 2} of the unsharp mask (LR patch {lr_patch} + 2 x margin {margin}, scale {scale})")
         self._names = None if names is None else list(names)
         self._bufs: dict = {}
         super().__init__(images, lr_patch, scale, device, shard_bytes, augment, 8, degrade if degrade is not None else DegradeSpec(), rank, None, psf,
@@ -881,7 +945,7 @@ class DeviceHR2Pool(DeviceHRPool):
             blur, noise, nid, gray = self.degrade.draw(self._degrade_rng, colour=colour)
             dev = self.tables == "device"
             table1 = self.psf.draw(self._psf_rng, blur, dev) if self.psf is not None else stage1_table(blur, dev)
-            params.append(self.spec.draw(self._spec_rng, table1, noise, nid, gray, colour, self.extent, s, dev))
+            params.append(self.spec.draw(self._spec_rng, table1, noise, nid, gray, colour, self.extent, s, dev, self._mode_rng))
         return wd, offs, params
 
     def _crop(self, pool, rows, patch: int) -> torch.Tensor:
@@ -898,13 +962,21 @@ class DeviceHR2Pool(DeviceHRPool):
         pool = self._batch_pool(indices)
         hd, codes = self.draw(indices)
         wd, offs, params = self.draw_second_order(hd)
-        hr = self._crop(pool, hd, P * s)
-        whole = degrade_second_order(self._crop(pool, wd, self.extent), s, params, self.subsample, self.pads, self._bufs, self._bank)
+        if self.usm is None:
+            hr = self._crop(pool, hd, P * s)
+            win = self._crop(pool, wd, self.extent)
+        else:          # the target is a window of the sharpened WINDOW, and the chain runs on the sharpened window
+            win = self.usm.sharpen(self._crop(pool, wd, self.extent))
+        whole = degrade_second_order(win, s, params, self.subsample, self.pads, self._bufs, self._bank)
         if len(set(offs)) == 1:
             (oy, ox), = set(offs)
             lr = whole[:, :, oy:oy + P, ox:ox + P].contiguous()
+            if self.usm is not None:
+                hr = win[:, :, oy * s:(oy + P) * s, ox * s:(ox + P) * s].contiguous()
         else:
             lr = torch.stack([whole[b, :, oy:oy + P, ox:ox + P] for b, (oy, ox) in enumerate(offs)])
+            if self.usm is not None:
+                hr = torch.stack([win[b, :, oy * s:(oy + P) * s, ox * s:(ox + P) * s] for b, (oy, ox) in enumerate(offs)])
         if any(codes):
             from .augment import dihedral
             ops = torch.tensor(codes, dtype=torch.int32).to(self.device)
@@ -929,11 +1001,17 @@ class SynthLRBatches:
 
     ``second_order`` (a SecondOrderSpec standing for its `fixed()` chain; needs ``degrade`` and ``quant_bits`` 8, takes no ``jpeg``):
     the whole cropped image goes through `ops.degrade_second_order` with ``degrade`` / ``psf`` as its stage 1; the noise id is the
-    image's index in the split, the same every epoch."""
+    image's index in the split, the same every epoch.  The fixed chain resizes with the cubic.
+
+    ``usm`` (a UsmSpec; needs ``second_order``): the whole cropped image is unsharp-masked (ops.usm_sharpen), the chain runs on the
+    sharpened image, and the yielded HR is the sharpened image -- the target `--gt_usm` trains against."""
 
     def __init__(self, loader, scale: int, quant_bits: int, device, degrade=None, jpeg=None, jpeg_subsample: bool = False, psf=None,
-                 second_order=None):
+                 second_order=None, usm=None):
         self.loader, self.scale, self.quant_bits, self.device = loader, int(scale), int(quant_bits), torch.device(device)
+        if usm is not None and (not isinstance(usm, UsmSpec) or second_order is None):
+            raise ValueError("usm= takes a UsmSpec and sharpens the target of the second-order chain: it needs second_order=")
+        self.usm = usm
         if second_order is not None:
             if not isinstance(second_order, SecondOrderSpec):
                 raise ValueError(f"second_order must be a SecondOrderSpec (got {type(second_order).__name__})")
@@ -985,6 +1063,8 @@ class SynthLRBatches:
                 from .ops import degrade_second_order
                 H, W = hr.shape[-2:]
                 hr = hr[..., :H - H % self.scale, :W - W % self.scale].contiguous()
+                if self.usm is not None:
+                    hr = self.usm.sharpen(hr)
                 table1 = self.psf if self.psf is not None else stage1_table(self.degrade.blur)
                 params = [self.second_order.fixed(table1, self.degrade.noise, gray[b], first + b) for b in range(B)]
                 yield degrade_second_order(hr, self.scale, params, self.jpeg_subsample), hr
