@@ -207,6 +207,24 @@ int srk_pixel_loss_fwd_bwd(const float* pred, const float* target, float* d_pred
 int64_t srk_ssim_loss_workspace(int B, int C, int H, int W);
 int srk_ssim_loss_fwd_bwd(const float* x, const float* y, void* workspace, int B, int C, int H, int W, float data_range, float alpha,
                           float* d_x, int accumulate, float* ssim_mean, float* loss, srk_stream_t stream);
+/* Frequency loss as a training term (csrc/fft_loss.hip): the L1 distance between the 2-D real FFTs of x and y (fp32
+ * [B][C][H][W]), the basicsr-style FFTLoss.  With d = x - y, D = rfft2(d) unnormalised, Wh = W / 2 + 1, s = 1 (ortho == 0) or
+ * 1 / sqrt(H W) (ortho == 1) and N = 2 B C H Wh:  L = (s / N) sum_{u < H, v < Wh} |Re D| + |Im D|, which equals
+ * F.l1_loss(stack([rfft2(x).real, rfft2(x).imag], -1), the same of y).  value[0] = L (may be null); loss[0] += alpha * L (may be
+ * null); d_x (fp32 [B][C][H][W], may be null for a value-only call) receives alpha * dL/dx, stored when accumulate == 0 and added
+ * when accumulate == 1; there is no gradient for y.  The gradient is the true adjoint over the half spectrum,
+ * (s / N) Re sum_{u, v < Wh} G[u][v] exp(+2 pi i (u y / H + v x / W)) with G = sign(Re D) + i sign(Im D), sign(0) = 0: no Hermitian
+ * doubling of the interior columns.  At the self-conjugate bins (u in {0, H/2}, v in {0, W/2}; halves of even extents only) the
+ * imaginary part is structurally zero and contributes neither to L nor to the gradient.  One transform of d, as fp32 matrix
+ * products on the fp32-input MFMA with twiddle tables built on the device by the same call (fp64 sincospi, rounded once); D itself
+ * never goes to memory.  Fixed-order sums, no float atomics, no host read: reproducible and capturable.  Nothing outside
+ * d_x[0 .. B*C*H*W), the two scalars and the workspace is written.  workspace: srk_fft_loss_workspace(B, C, H, W) bytes (0 for a
+ * shape the entry refuses).  Any 1 <= H, W <= 512, odd sizes included.
+ * SRK_E_NULL: null x / y / workspace; SRK_E_SHAPE: B, C, H or W <= 0, B*C >= 65536, a non-finite alpha, ortho or accumulate not
+ * 0 / 1, accumulate with a null d_x, d_x overlapping x or y; SRK_E_UNSUPPORTED: H or W > 512. */
+int64_t srk_fft_loss_workspace(int B, int C, int H, int W);
+int srk_fft_loss_fwd_bwd(const float* x, const float* y, void* workspace, int B, int C, int H, int W, int ortho, float alpha,
+                         float* d_x, int accumulate, float* value, float* loss, srk_stream_t stream);
 /* Optional workspace of the stand-alone weight-gradient entry points (srk_linear_wgrad_bf16, srk_conv3x3_wgrad_bf16):
  * srk_wgrad_workspace_bytes() bytes of device memory owned by the caller, registered for the CALLING THREAD until replaced
  * (null / 0 unregisters).  With it the row-splits of a weight-gradient tile are summed in a fixed order (reproducible dW);

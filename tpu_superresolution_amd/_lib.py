@@ -102,6 +102,8 @@ _SIGNATURES = {
     "srk_pixel_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _f, _i, _vp, _vp]),
     "srk_ssim_loss_workspace": (_i64, [_i, _i, _i, _i]),
     "srk_ssim_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _i, _vp, _vp, _vp]),
+    "srk_fft_loss_workspace": (_i64, [_i, _i, _i, _i]),
+    "srk_fft_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _vp, _vp]),
     "srk_wgrad_workspace_bytes": (_i64, []),
     "srk_set_wgrad_workspace": (_i, [_vp, _i64]),
     "srk_paired_crop_u8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

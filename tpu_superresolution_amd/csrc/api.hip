@@ -474,6 +474,23 @@ int srk_l1_loss_fwd_bwd(const float* pred, const float* target, float* d_pred, f
   return srk_launch_l1_loss(pred, target, d_pred, loss, nonfinite, n, grad_scale, (hipStream_t)stream);
 }
 
+int64_t srk_fft_loss_workspace(int B, int C, int H, int W) { return (int64_t)srk_fft_loss_workspace_bytes(B, C, H, W); }
+
+int srk_fft_loss_fwd_bwd(const float* x, const float* y, void* workspace, int B, int C, int H, int W, int ortho, float alpha, float* d_x,
+                         int accumulate, float* value, float* loss, srk_stream_t stream) {
+  SRK_REQUIRE(x && y && workspace, SRK_E_NULL, "fft_loss: null pointer (x, y and workspace are required)");
+  SRK_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && (long long)B * C < 65536, SRK_E_SHAPE, "fft_loss: B=%d C=%d H=%d W=%d", B, C, H, W);
+  SRK_REQUIRE(std::isfinite(alpha), SRK_E_SHAPE, "fft_loss: alpha=%g", (double)alpha);
+  SRK_REQUIRE((ortho == 0 || ortho == 1) && (accumulate == 0 || accumulate == 1), SRK_E_SHAPE,
+              "fft_loss: ortho and accumulate must be 0 or 1 (got %d, %d)", ortho, accumulate);
+  SRK_REQUIRE(!accumulate || d_x, SRK_E_SHAPE, "fft_loss: accumulate needs the d_x to add to");
+  SRK_REQUIRE(H <= 512 && W <= 512, SRK_E_UNSUPPORTED, "fft_loss: H, W <= 512 (got %dx%d)", H, W);
+  const size_t n = sizeof(float) * (size_t)B * C * H * W;
+  SRK_REQUIRE(!d_x || (!srk_ranges_overlap(d_x, n, x, n) && !srk_ranges_overlap(d_x, n, y, n)), SRK_E_SHAPE, "fft_loss: d_x overlaps x or y");
+  return srk_launch_fft_loss(x, y, static_cast<float*>(workspace), B, C, H, W, ortho, alpha, d_x, accumulate, value, loss,
+                             (hipStream_t)stream);
+}
+
 int64_t srk_wgrad_workspace_bytes(void) { return (int64_t)WS_WORKSPACE_BYTES; }
 
 int srk_set_wgrad_workspace(void* workspace, int64_t bytes) {

@@ -128,6 +128,10 @@ int srk_launch_pixel_loss(const float* pred, const float* target, float* dpred, 
                           float eps, float grad_scale, int accumulate, float* partial, hipStream_t stream);
 int srk_launch_ssim_loss(const float* x, const float* y, float* partial, int B, int C, int H, int W, float data_range, float alpha, float* d_x,
                          int accumulate, float* ssim_mean, float* loss, hipStream_t stream);
+// fft_loss.hip: the frequency loss (arguments checked by srk_fft_loss_fwd_bwd); ws holds srk_fft_loss_workspace_bytes(B, C, H, W) bytes
+long long srk_fft_loss_workspace_bytes(int B, int C, int H, int W);
+int srk_launch_fft_loss(const float* x, const float* y, float* ws, int B, int C, int H, int W, int ortho, float alpha, float* d_x,
+                        int accumulate, float* value, float* loss, hipStream_t stream);
 int srk_launch_sumsq(const float* g, long long n, float* out, hipStream_t stream);
 int srk_launch_adamw(float* p, const float* g, float* m, float* v, long long n, const float* sumsq, const int* nonfinite, float max_norm, float grad_div, float lr, float beta1, float beta2, float eps, float wd, int step, hipStream_t stream);
 int srk_launch_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, long long n, const float* sumsq, const int* nonfinite, float max_norm, float grad_div, float lr, float beta1, float beta2, float eps, float wd, int step, float ema_decay, hipStream_t stream);

@@ -12,6 +12,8 @@ context), the step uses the fused L1 / clip / AdamW kernels, `--weights` may be 
 on flipped / rotated patches (augment.py; on the device with `--gpu_data`).  `--loss l1|mse|charbonnier` (default l1) and
 `--ssim_weight W` (default 0) choose the objective: the pixel loss plus W * (1 - SSIM), value and gradient from the fused kernels of
 csrc/loss.hip (training.make_loss); with W > 0 validation also reports the mean per-image SSIM and checkpoints gain 'val_ssim'.
+`--fft_weight W [--fft_norm backward|ortho]` (default 0) adds W * mean(|Re D| + |Im D|), D = rfft2(pred - hr): the frequency loss of the
+SwinFIR / HAT recipes (csrc/fft_loss.hip; HR patches of at most 512 x 512).
 `--val_tile N` (default 0 = whole images) validates on overlapping N x N LR tiles merged on the device (tiling.tiled_forward).
 `--val_bench_metric y|rgb [--val_crop_border N]` adds the papers' scores to the epoch line and the checkpoints ('val_bench_psnr',
 'val_bench_ssim'): 8-bit, border-cropped (default: the scale), BT.601 luma or RGB, 0..255 scale (metrics.bench_metrics).
@@ -294,6 +296,12 @@ def parse_args(argv=None):
     ap.add_argument("--ssim_weight", type=float, default=0.0,
                     help="additive: add ssim_weight * (1 - SSIM(pred, hr)) to the objective (0 = off; needs HR patches of at least "
                          "11 x 11); validation then also reports the SSIM and checkpoints gain 'val_ssim'")
+    ap.add_argument("--fft_weight", type=float, default=0.0,
+                    help="additive: add fft_weight * mean(|Re D| + |Im D|), D = rfft2(pred - hr), to the objective: the frequency "
+                         "loss of the SwinFIR / HAT fine-tuning recipes (0 = off; typical 0.05 .. 0.1; needs HR patches of at most "
+                         "512 x 512; csrc/fft_loss.hip)")
+    ap.add_argument("--fft_norm", type=str, choices=["backward", "ortho"], default="backward",
+                    help="additive, with --fft_weight: the normalisation of the transform (ortho divides by sqrt(H W))")
     ap.add_argument("--val_tile", type=int, default=0,
                     help="additive: validate on overlapping tiles of N x N LR pixels merged by their mean (tiling.tiled_forward; 0 = "
                          "off, the whole image in one call)")
@@ -504,6 +512,11 @@ def parse_args(argv=None):
         ap.error(f"--val_crop_border must be >= 0 and is an option of --val_bench_metric y | rgb (got {args.val_crop_border})")
     if not 0.0 <= args.ssim_weight < float("inf"):          # also refuses NaN
         ap.error(f"--ssim_weight must be a finite number >= 0 (got {args.ssim_weight})")
+    if not 0.0 <= args.fft_weight < float("inf"):          # also refuses NaN
+        ap.error(f"--fft_weight must be a finite number >= 0 (got {args.fft_weight})")
+    if args.fft_weight > 0 and args.lr_patch * SCALES[args.scale.upper()] > 512:
+        ap.error(f"--fft_weight needs HR patches of at most 512 x 512 (lr_patch * scale = "
+                 f"{args.lr_patch * SCALES[args.scale.upper()]})")
     if not args.charbonnier_eps > 0.0:
         ap.error(f"--charbonnier_eps must be > 0 (got {args.charbonnier_eps})")
     if args.ssim_weight > 0 and args.lr_patch * SCALES[args.scale.upper()] < 11:
@@ -595,7 +608,8 @@ def restore_spec(args):
 def saved_args(args) -> dict:
     """What a checkpoint keeps of the command line: additive flags leave no trace in the files at their defaults."""
     at_default = {"ema_decay": not args.ema_decay, "loss": args.loss == "l1", "charbonnier_eps": args.charbonnier_eps == 1e-3,
-                  "ssim_weight": args.ssim_weight == 0, "val_tile": args.val_tile == 0,
+                  "ssim_weight": args.ssim_weight == 0, "fft_weight": args.fft_weight == 0,
+                  "fft_norm": args.fft_weight == 0 or args.fft_norm == "backward", "val_tile": args.val_tile == 0,
                   "val_tile_overlap": args.val_tile == 0 or args.val_tile_overlap == 32, "synth_lr": not args.synth_lr,
                   "synth_lr_bits": not args.synth_lr or args.synth_lr_bits == 8, "degrade": args.degrade == "bicubic",
                   "blur_sigma": args.blur_sigma == [0.2, 2.0], "blur_aniso_p": args.blur_aniso_p == 0.5,
@@ -777,8 +791,9 @@ def main(argv=None):
                      ema_decay=args.ema_decay or None)
     sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=args.epochs, eta_min=args.min_lr) if args.scheduler == "Cosine" else None
 
-    custom = args.loss != "l1" or args.ssim_weight > 0          # at the defaults: the L1 step, lines and files of ever
-    loss_fn = make_loss(args.loss, args.charbonnier_eps, args.ssim_weight) if custom else None
+    custom = args.loss != "l1" or args.ssim_weight > 0 or args.fft_weight > 0          # at the defaults: the L1 step, lines and files of ever
+    loss_fn = make_loss(args.loss, args.charbonnier_eps, args.ssim_weight, fft_weight=args.fft_weight,
+                        fft_norm=args.fft_norm) if custom else None
     with_ssim = args.ssim_weight > 0
     graphed = None
     if args.graph:
@@ -816,7 +831,7 @@ def main(argv=None):
             sched.step()
         if rank != 0:
             continue
-        train_name = f"loss[{loss_name(args.loss, args.ssim_weight)}]" if custom else "L1"
+        train_name = f"loss[{loss_name(args.loss, args.ssim_weight, args.fft_weight)}]" if custom else "L1"
         val_more = f", SSIM={val[2]:.4f}" if with_ssim else ""
         if val_border is not None:
             tag = args.val_bench_metric.upper()

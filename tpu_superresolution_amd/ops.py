@@ -573,6 +573,30 @@ def ssim_loss_fwd_bwd(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0,
     return mean, d_x, loss
 
 
+def fft_loss_fwd_bwd(x: torch.Tensor, y: torch.Tensor, norm: str = "backward", alpha: float = 1.0, d_x: Optional[torch.Tensor] = None,
+                     accumulate: bool = False, loss: Optional[torch.Tensor] = None, want_grad: bool = True):
+    """The frequency loss (csrc/fft_loss.hip): L = mean(|Re D| + |Im D|) over the half spectrum D = rfft2(x - y, norm=norm), norm
+    'backward' | 'ortho' -> (L fp32 [1], d_x | None, loss | None) with d_x = alpha dL/dx (stored, or added to a given d_x with
+    accumulate=True; want_grad=False without a d_x: value only) and, when `loss` is given, loss[0] += alpha L.  H, W <= 512.
+    Fixed-order sums, no host read: capturable."""
+    if norm not in ("backward", "ortho"):
+        raise ValueError(f"fft loss: norm must be 'backward' or 'ortho' (got {norm!r})")
+    if x.shape != y.shape or x.ndim != 4 or x.dtype != torch.float32 or y.dtype != torch.float32:
+        raise ValueError(f"fft loss: x / y must be fp32 [B, C, H, W] of one shape (got {x.dtype} {tuple(x.shape)}, {y.dtype} {tuple(y.shape)})")
+    B, Cc, H, W = x.shape
+    if d_x is None and want_grad:
+        if accumulate:
+            raise ValueError("fft loss: accumulate=True needs the d_x to add to")
+        d_x = torch.empty_like(x)
+    if d_x is not None and (d_x.shape != x.shape or d_x.dtype != torch.float32):
+        raise ValueError(f"fft loss: d_x must be fp32 {tuple(x.shape)} (got {d_x.dtype} {tuple(d_x.shape)})")
+    ws = torch.empty(max(4, int(lib().srk_fft_loss_workspace(B, Cc, H, W))), dtype=torch.uint8, device=x.device)
+    value = torch.empty(1, dtype=torch.float32, device=x.device)
+    check(lib().srk_fft_loss_fwd_bwd(_p(x), _p(y), _p(ws), B, Cc, H, W, int(norm == "ortho"), float(alpha), _p(d_x), int(bool(accumulate)),
+                                     _p(value), _p(loss), _stream()))
+    return value, d_x, loss
+
+
 def resize_aa(x: torch.Tensor, size, quant_bits: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Antialiased bicubic resize of a CUDA fp32 batch x [B,C,H,W] to size = (Ho, Wo), up or down (csrc/resize.hip,
     srk_resize_aa_f32): the Keys cubic with a = -0.5 in the convention of PIL's Image.BICUBIC and of

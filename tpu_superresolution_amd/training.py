@@ -38,29 +38,40 @@ def l1_loss_checked(pred: torch.Tensor, target: torch.Tensor) -> Tuple[torch.Ten
 LOSS_KINDS = ("l1", "mse", "charbonnier")
 
 
-def loss_name(kind: str = "l1", ssim_weight: float = 0.0) -> str:
-    """'l1', 'charbonnier+0.2*(1-ssim)', ...: how the scripts name the objective"""
-    return kind + (f"+{ssim_weight:g}*(1-ssim)" if ssim_weight else "")
+FFT_NORMS = ("backward", "ortho")
+FFT_MAX_SIDE = 512          # the frequency loss takes H, W <= 512 (csrc/fft_loss.hip)
 
 
-def make_loss(kind: str = "l1", charbonnier_eps: float = 1e-3, ssim_weight: float = 0.0, data_range: float = 1.0):
+def loss_name(kind: str = "l1", ssim_weight: float = 0.0, fft_weight: float = 0.0) -> str:
+    """'l1', 'charbonnier+0.2*(1-ssim)', 'l1+0.05*fft', ...: how the scripts name the objective"""
+    return kind + (f"+{ssim_weight:g}*(1-ssim)" if ssim_weight else "") + (f"+{fft_weight:g}*fft" if fft_weight else "")
+
+
+def make_loss(kind: str = "l1", charbonnier_eps: float = 1e-3, ssim_weight: float = 0.0, data_range: float = 1.0,
+              fft_weight: float = 0.0, fft_norm: str = "backward"):
     """-> callable (pred, target) -> (loss, nonfinite_count), both device tensors, for train_step / GraphedTrainStep(loss_fn=...).
 
     kind 'l1' | 'mse' | 'charbonnier' (mean sqrt(d^2 + charbonnier_eps^2)); ssim_weight > 0 adds ssim_weight * (1 - SSIM(pred, target))
     with the SSIM of metrics.ssim at `data_range` (4-D batches, H, W >= 11).  One autograd Function: its forward runs the pixel kernel
     and then the SSIM kernel, which accumulates into the same loss scalar and the same d(pred) (csrc/loss.hip: fixed-order sums, no host
     read, capturable); the non-finite counter is the one optim.FusedAdamW.step(nonfinite=...) gates on.  The target gets no gradient.
-    kind 'l1' without an SSIM term returns l1_loss_checked itself."""
+    fft_weight > 0 adds fft_weight * mean(|Re D| + |Im D|), D = rfft2(pred - target) with norm `fft_norm` ('backward' | 'ortho'): the
+    frequency loss of csrc/fft_loss.hip (4-D batches, H, W <= 512), run after the other two kernels into the same scalar and d(pred).
+    kind 'l1' without an SSIM or frequency term returns l1_loss_checked itself."""
     if kind not in LOSS_KINDS:
         raise ValueError(f"loss kind must be one of {LOSS_KINDS} (got {kind!r})")
-    eps, w, dr = float(charbonnier_eps), float(ssim_weight), float(data_range)
+    eps, w, dr, fw = float(charbonnier_eps), float(ssim_weight), float(data_range), float(fft_weight)
     if not w >= 0.0 or w == float("inf"):          # also refuses NaN
         raise ValueError(f"ssim_weight must be a finite number >= 0 (got {ssim_weight!r})")
+    if not fw >= 0.0 or fw == float("inf"):
+        raise ValueError(f"fft_weight must be a finite number >= 0 (got {fft_weight!r})")
+    if fft_norm not in FFT_NORMS:
+        raise ValueError(f"fft_norm must be one of {FFT_NORMS} (got {fft_norm!r})")
     if kind == "charbonnier" and not eps > 0.0:
         raise ValueError(f"charbonnier_eps must be > 0 (got {charbonnier_eps!r})")
     if not dr > 0.0:
         raise ValueError(f"data_range must be > 0 (got {data_range!r})")
-    if kind == "l1" and w == 0.0:
+    if kind == "l1" and w == 0.0 and fw == 0.0:
         return l1_loss_checked
 
     class _Loss(torch.autograd.Function):
@@ -70,6 +81,8 @@ def make_loss(kind: str = "l1", charbonnier_eps: float = 1e-3, ssim_weight: floa
             loss, d_pred, bad = ops.pixel_loss_fwd_bwd(p, t, kind, eps, want_grad=True)
             if w > 0.0:
                 ops.ssim_loss_fwd_bwd(p, t, dr, alpha=w, d_x=d_pred, accumulate=True, loss=loss)
+            if fw > 0.0:
+                ops.fft_loss_fwd_bwd(p, t, fft_norm, alpha=fw, d_x=d_pred, accumulate=True, loss=loss)
             ctx.save_for_backward(d_pred)
             ctx.mark_non_differentiable(bad)
             return loss.reshape(()), bad
@@ -84,9 +97,11 @@ def make_loss(kind: str = "l1", charbonnier_eps: float = 1e-3, ssim_weight: floa
             raise ValueError("make_loss: the target gets no gradient (detach it)")
         if w > 0.0 and (pred.ndim != 4 or pred.shape[2] < 11 or pred.shape[3] < 11):
             raise ValueError(f"make_loss: the SSIM term needs [B, C, H, W] batches with H, W >= 11 (got {tuple(pred.shape)})")
+        if fw > 0.0 and (pred.ndim != 4 or pred.shape[2] > FFT_MAX_SIDE or pred.shape[3] > FFT_MAX_SIDE):
+            raise ValueError(f"make_loss: the frequency term needs [B, C, H, W] batches with H, W <= {FFT_MAX_SIDE} (got {tuple(pred.shape)})")
         return _Loss.apply(pred, target)
 
-    loss_fn.__name__ = loss_fn.__qualname__ = f"loss[{loss_name(kind, w)}]"
+    loss_fn.__name__ = loss_fn.__qualname__ = f"loss[{loss_name(kind, w, fw)}]"
     return loss_fn
 
 
