@@ -4,7 +4,9 @@ from __future__ import annotations
 import ctypes as C
 import os
 import re
-from typing import List
+from typing import List, Optional
+
+import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SRK_LIB_PATH") or os.path.join(HERE, "libsrk.so")   # SRK_LIB_PATH: developer A/B builds
@@ -265,6 +267,25 @@ def lib() -> C.CDLL:
             fn.argtypes = args
         _lib = l
     return _lib
+
+
+# ---- the calling convention: raw device pointers of contiguous tensors on the current device, the current torch stream ---------------
+def _stream() -> int:
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _p(t: Optional[torch.Tensor]) -> Optional[int]:
+    if t is None:
+        return None
+    if not t.is_cuda:
+        raise RuntimeError("libsrk operates on GPU tensors only (got a CPU tensor); there is no CPU fallback")
+    if t.device.index != torch.cuda.current_device():
+        # the kernel would launch on the current device with another device's pointers (a GPU fault, not a Python error)
+        raise RuntimeError(f"tensor on {t.device} but the current device is cuda:{torch.cuda.current_device()}; "
+                           "libsrk ops launch on the current device (torch.cuda.set_device / one process per GPU)")
+    if not t.is_contiguous():
+        raise RuntimeError("libsrk needs contiguous tensors")
+    return t.data_ptr()
 
 
 _claimed_device = None

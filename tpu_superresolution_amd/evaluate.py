@@ -251,11 +251,9 @@ def eval_restore(args):
 
 
 def eval_usm(args):
-    """The UsmSpec of the command line (None without --gt_usm)."""
-    if not args.gt_usm:
-        return None
-    from .sr_datasets import UsmSpec
-    return UsmSpec(**{k: v for k, v in (("radius", args.usm_radius), ("weight", args.usm_weight), ("threshold", args.usm_threshold)) if v is not None})
+    """The UsmSpec of the command line (None without --gt_usm): training's rule, finetune_swinir.usm_spec."""
+    from .finetune_swinir import usm_spec
+    return usm_spec(args)
 
 
 def eval_psf(args):
