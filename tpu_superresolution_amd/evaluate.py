@@ -32,15 +32,18 @@ from __future__ import annotations
 import argparse
 import re
 import time
+from functools import partial
 from pathlib import Path
 
 import torch
 from PIL import Image
 from torch.utils.data import DataLoader
 
+from .data_cli import (BLIND, SCALES, SECOND, USM_FLAGS, default_window_size, eval_lines, eval_psf, eval_restore, eval_specs,          # noqa: F401
+                       flag, shared_flags, usm_spec as eval_usm)          # eval_usm: training's rule, the same object as finetune_swinir.usm_spec
 from .metrics import psnr, ssim
 from .ms_resunet import MS_ResUNet
-from .sr_datasets import Shuffled2DPaired
+from .sr_datasets import PairTransformValid, RestoreBatches, Shuffled2DHR, Shuffled2DPaired, SynthLRBatches, clean_to_tensor, hr_to_tensor3
 from .sr_transforms import build_pair_transform_eval
 
 
@@ -61,9 +64,9 @@ def save_tensor_as_png(x: torch.Tensor, path: Path, per_image_rescale: bool = Fa
 PARAM_KEYS = ("model", "params", "params_ema")          # envelopes, in the order 'auto' tries them
 
 
-def _load_state(path: str, param_key: str = "auto"):
-    """-> (state_dict, message).  'auto': the first of 'model', 'params', 'params_ema' the file has (the published HAT / DAT files hold
-    only 'params_ema', the exponential moving average of the weights), else the file is a raw state_dict.  A named key must exist."""
+def _load_state(path: str, param_key: str = "auto", keys=PARAM_KEYS):
+    """-> (state_dict, message).  'auto': the first of `keys` the file has (the published HAT / DAT files hold only 'params_ema', the
+    exponential moving average of the weights; finetune_swinir --weights tries 'params' first), else a raw state_dict.  A named key must exist."""
     ckpt = torch.load(path, map_location="cpu", weights_only=True)
     if param_key != "auto":
         if param_key not in PARAM_KEYS:
@@ -73,7 +76,7 @@ def _load_state(path: str, param_key: str = "auto"):
             raise KeyError(f"{path}: no '{param_key}' key; the file has {have[:12]}{' ...' if len(have) > 12 else ''}")
         return ckpt[param_key], f"[ckpt] loaded state_dict from '{param_key}' key"
     if isinstance(ckpt, dict):
-        for k in PARAM_KEYS:
+        for k in keys:
             if k in ckpt:
                 return ckpt[k], f"[ckpt] loaded state_dict from '{k}' key"
     return ckpt, "[ckpt] loaded raw state_dict"
@@ -99,17 +102,15 @@ def parse_args(argv=None):
     ap.add_argument("--device", type=str, default=None, help="additive: force 'cpu' / 'cuda' (default: cuda if available)")
     ap.add_argument("--window_size", type=int, default=None,
                     help="additive, --arch swinir: SwinIR(window_size=N), N in 2..8 (default: 8, or 7 with --task car)")
-    ap.add_argument("--task", type=str, choices=["sr", "dn", "car"], default="sr",
-                    help="additive, --arch swinir: dn = denoising, car = JPEG compression-artifact reduction -- the published scale-1 "
-                         "models (finetune_swinir.build_restoration_model), scored from the HR directory of the test split alone: each "
-                         "image is degraded on the device as a whole (ops.restore_degrade; the noise id of an image is its index in the "
-                         "split) and the baseline is the degraded input itself.  They need --scale X1")
-    ap.add_argument("--channels", type=int, choices=[1, 3], default=3,
-                    help="additive, with --task dn | car: 3 = colour, 1 = gray (an RGB file becomes its integer BT.601 luma, ops.to_gray)")
-    ap.add_argument("--dn_sigma", type=float, default=None, metavar="S",
-                    help="additive, with --task dn (required) | car: the Gaussian noise sigma on the 0..255 scale of the papers (15 / 25 / 50)")
-    ap.add_argument("--dn_bits", type=int, choices=[0, 8], default=0,
-                    help="additive, with --task dn | car: 0 = the noisy input is neither clipped nor rounded, 8 = rounded to k / 255")
+    flag(ap, "task", str, "sr", choices=["sr", "dn", "car"],
+         text="--arch swinir: dn = denoising, car = JPEG compression-artifact reduction -- the published scale-1 models "
+              "(finetune_swinir.build_restoration_model), scored from the HR directory of the test split alone: each image is degraded on the "
+              "device as a whole (ops.restore_degrade; the noise id of an image is its index in the split) and the baseline is the degraded input "
+              "itself.  They need --scale X1")
+    shared_flags(ap, "channels")
+    flag(ap, "dn_sigma", float, None, metavar="S",
+         text="with --task dn (required) | car: the Gaussian noise sigma on the 0..255 scale of the papers (15 / 25 / 50)")
+    shared_flags(ap, "dn_bits")
     ap.add_argument("--self_ensemble", action="store_true",
                     help="additive: predict with the x8 self-ensemble (the '+' of SwinIR+ / HAT+ / DAT+): the mean of the eight "
                          "inverse-transformed predictions on the flipped / rotated inputs (augment.self_ensemble)")
@@ -122,38 +123,33 @@ def parse_args(argv=None):
                     help="additive, with --tile: mean = average the tiles covering a pixel (SwinIR's test script), center = take each "
                          "pixel from the tile whose border is farthest (what the tile_pad of the HAT / DAT scripts aims at)")
     ap.add_argument("--synth_lr", action="store_true",
-                    help="additive, --arch swinir|hat|dat: evaluate from the HR directory of the test split alone; LR is its antialiased "
-                         "bicubic (PIL BICUBIC convention) downscale, formed on the device (ops.resize_aa)")
-    ap.add_argument("--synth_lr_bits", type=int, choices=[0, 8], default=8,
-                    help="additive, with --synth_lr: 8 = LR rounded to k / 255 as an 8-bit LR file would hold it, 0 = the filtered values")
-    ap.add_argument("--degrade", type=str, choices=["bicubic", "blind", "second_order"], default="bicubic",
-                    help="additive, with --synth_lr: blind = LR is blurred and noised with the fixed parameters below (ops.degrade_blind; "
-                         "the noise id of an image is its index in the split); second_order = the fixed second-order chain "
-                         "(sr_datasets.SecondOrderSpec.fixed, ops.degrade_second_order, DESIGN 7p): that blur and noise as stage 1, "
-                         "--jpeg_quality Q as the first JPEG's quality (default: the middle of 30..95), then the documented midpoints; it "
-                         "needs --synth_lr_bits 8")
-    ap.add_argument("--blur_sigma", type=float, nargs=2, default=[1.1, 1.1], metavar=("SY", "SX"),
-                    help="additive, with --degrade blind: sigma of the Gaussian blur in HR pixels along y and x, within [0, 2.5]")
-    ap.add_argument("--noise_sigma", type=float, default=5.0, help="additive, with --degrade blind: noise sigma in 8-bit levels")
-    ap.add_argument("--noise_gain", type=float, default=0.0, help="additive, with --degrade blind: gain of the signal-dependent noise")
-    ap.add_argument("--blur_theta", type=float, default=None, metavar="DEG",
-                    help="additive, with --degrade blind: the Gaussian of --blur_sigma turned by DEG degrees, applied as a 2-D table "
-                         "(blur_kernels.gaussian, ops.degrade_psf, csrc/blur2d.hip); 0 is the axis-aligned Gaussian on the 2-D path")
-    ap.add_argument("--blur_psf", type=str, default=None, metavar="FILE",
-                    help="additive, with --degrade blind: blur with table 0 of a measured point-spread function, .npy [k][k] or [n][k][k] "
-                         "(k odd <= 21, taps >= 0 summing to 1), instead of the Gaussian")
-    ap.add_argument("--jpeg_quality", type=int, default=None, metavar="Q",
-                    help="additive, with --synth_lr --synth_lr_bits 8 (either --degrade): the LR image makes a round trip through baseline "
-                         "JPEG at quality Q in 1..100 on the device (ops.jpeg_roundtrip, csrc/jpeg.hip), before any tiling or self-ensemble")
-    ap.add_argument("--jpeg_subsample", type=str, choices=["444", "420"], default="444",
-                    help="additive, with --jpeg_quality: chroma at 4:4:4, or 4:2:0 (2 x 2 means, upsampled by replication)")
+                    help="additive, --arch swinir|hat|dat: evaluate from the HR directory of the test split alone; LR is its antialiased bicubic "
+                         "(PIL BICUBIC convention) downscale, formed on the device (ops.resize_aa)")
+    shared_flags(ap, "synth_lr_bits")
+    flag(ap, "degrade", str, "bicubic", choices=["bicubic", "blind", "second_order"],
+         text="with --synth_lr: blind = LR is blurred and noised with the fixed parameters below (ops.degrade_blind; the noise id of an image is "
+              "its index in the split); second_order = the fixed second-order chain (sr_datasets.SecondOrderSpec.fixed, ops.degrade_second_order, "
+              "DESIGN 7p): that blur and noise as stage 1, --jpeg_quality Q as the first JPEG's quality (default: the middle of 30..95), then the "
+              "documented midpoints; it needs --synth_lr_bits 8")
+    flag(ap, "blur_sigma", float, [1.1, 1.1], BLIND + "sigma of the Gaussian blur in HR pixels along y and x, within [0, 2.5]", nargs=2,
+          metavar=("SY", "SX"))
+    flag(ap, "noise_sigma", float, 5.0, BLIND + "noise sigma in 8-bit levels")
+    flag(ap, "noise_gain", float, 0.0, BLIND + "gain of the signal-dependent noise")
+    flag(ap, "blur_theta", float, None, metavar="DEG",
+         text=BLIND + "the Gaussian of --blur_sigma turned by DEG degrees, applied as a 2-D table (blur_kernels.gaussian, ops.degrade_psf, "
+              "csrc/blur2d.hip); 0 is the axis-aligned Gaussian on the 2-D path")
+    flag(ap, "blur_psf", str, None, metavar="FILE",
+         text=BLIND + "blur with table 0 of a measured point-spread function, .npy [k][k] or [n][k][k] (k odd <= 21, taps >= 0 summing to 1), instead "
+              "of the Gaussian")
+    flag(ap, "jpeg_quality", int, None, metavar="Q",
+         text="with --synth_lr --synth_lr_bits 8 (either --degrade): the LR image makes a round trip through baseline JPEG at quality Q in 1..100 "
+              "on the device (ops.jpeg_roundtrip, csrc/jpeg.hip), before any tiling or self-ensemble")
+    shared_flags(ap, "jpeg_subsample")
     ap.add_argument("--gt_usm", action="store_true",
-                    help="additive, with --degrade second_order: score a model trained with finetune_swinir --gt_usm -- the HR image is "
-                         "unsharp-masked on the device (ops.usm_sharpen, csrc/usm.hip, DESIGN 7r), the fixed chain (bicubic resizes) runs "
-                         "on the sharpened image and every score is taken against it")
-    ap.add_argument("--usm_radius", type=int, default=None, help="additive, with --gt_usm: Real-ESRGAN's radius, 1..51 (default 50)")
-    ap.add_argument("--usm_weight", type=float, default=None, help="additive, with --gt_usm: weight of the residual (default 0.5)")
-    ap.add_argument("--usm_threshold", type=float, default=None, help="additive, with --gt_usm: threshold of the mask in 8-bit levels (default 10)")
+                    help="additive, " + SECOND + "score a model trained with finetune_swinir --gt_usm -- the HR image is unsharp-masked on the device "
+                         "(ops.usm_sharpen, csrc/usm.hip, DESIGN 7r), the fixed chain (bicubic resizes) runs on the sharpened image and every score "
+                         "is taken against it")
+    shared_flags(ap, *USM_FLAGS)
     ap.add_argument("--bench_metric", type=str, choices=["y", "rgb"], default=None,
                     help="additive: also report PSNR / SSIM by the protocol of the SwinIR / HAT / DAT papers (metrics.bench_metrics): "
                          "8-bit, border-cropped, y = BT.601 luma of RGB (a single-channel image is its own luma), rgb = every channel, "
@@ -162,75 +158,8 @@ def parse_args(argv=None):
                     help="additive, with --bench_metric: pixels cropped on every side before scoring (default: the scale)")
     args = ap.parse_args(argv)
     if args.window_size is None:
-        args.window_size = 7 if args.task == "car" else 8
-    if args.task == "sr":
-        if args.scale == "X1":
-            ap.error("--scale X1 is the scale of --task dn | car; --task sr takes X2 | X4")
-        if args.channels != 3 or args.dn_sigma is not None or args.dn_bits != 0:
-            ap.error("--channels, --dn_sigma and --dn_bits are options of --task dn | car")
-    else:
-        if args.scale != "X1":
-            ap.error(f"--task {args.task} restores at one size: it needs --scale X1 (got {args.scale})")
-        if args.arch != "swinir":
-            ap.error(f"--task {args.task} is built for --arch swinir only (HAT and DAT end in a pixel-shuffle tail; got --arch {args.arch})")
-        if args.synth_lr or args.degrade != "bicubic":
-            ap.error(f"--synth_lr and --degrade form LR images for --task sr; --task {args.task} degrades at scale 1 on its own")
-        if args.task == "dn" and args.dn_sigma is None:
-            ap.error("--task dn needs --dn_sigma S (0..255 scale, e.g. 25)")
-        if args.task == "dn" and args.jpeg_quality is not None:
-            ap.error("--jpeg_quality with noise is --task car --dn_sigma S; --task dn has no JPEG stage")
-        if args.task == "car" and args.jpeg_quality is None:
-            ap.error("--task car needs --jpeg_quality Q")
-        if args.bench_metric is not None and args.channels == 1:
-            ap.error("--bench_metric is not offered with --channels 1 (the benchmark-protocol scores take RGB predictions)")
-        try:
-            eval_restore(args)
-        except ValueError as e:
-            ap.error(f"--task {args.task}: {e}")
-    if args.crop_border is not None:
-        if args.bench_metric is None:
-            ap.error("--crop_border is an option of the benchmark-protocol scores: it needs --bench_metric y | rgb")
-        if args.crop_border < 0:
-            ap.error(f"--crop_border must be >= 0 (got {args.crop_border})")
-    if args.synth_lr and args.arch == "ms_resunet":
-        ap.error("--synth_lr is an option of --arch swinir | hat | dat (MS_ResUNet takes the pre-upscaled LR of the eval transform)")
-    if args.degrade == "second_order" and args.synth_lr_bits != 8:
-        ap.error("--degrade second_order codes 8-bit LR images: it needs --synth_lr_bits 8")
-    if args.degrade in ("blind", "second_order"):
-        if not args.synth_lr:
-            ap.error(f"--degrade {args.degrade} degrades the HR images on the device: it needs --synth_lr")
-        try:
-            from .ops import pack_degrade_params
-            pack_degrade_params(args.blur_sigma, (args.noise_sigma / 255.0, args.noise_gain), 0, False)
-        except ValueError as e:
-            ap.error(f"--degrade {args.degrade}: {e}")
-    usm_opts = [n for n in ("usm_radius", "usm_weight", "usm_threshold") if getattr(args, n) is not None]
-    if args.gt_usm and args.degrade != "second_order":
-        ap.error("--gt_usm sharpens the target of --degrade second_order: it needs it")
-    if usm_opts and not args.gt_usm:
-        ap.error(f"--{usm_opts[0]} is an option of --gt_usm")
-    try:
-        eval_usm(args)
-    except ValueError as e:
-        ap.error(f"--gt_usm: {e}")
-    if (args.blur_theta is not None or args.blur_psf is not None) and args.degrade not in ("blind", "second_order"):
-        ap.error("--blur_theta and --blur_psf shape the blur of --degrade blind | second_order: they need it")
-    if args.blur_theta is not None and args.blur_psf is not None:
-        ap.error("--blur_psf FILE replaces the Gaussian: it does not go with --blur_theta")
-    try:
-        eval_psf(args)
-    except (ValueError, OSError) as e:
-        ap.error(f"--blur_theta / --blur_psf: {e}")
-    if args.jpeg_quality is None:
-        if args.jpeg_subsample != "444" and args.degrade != "second_order":
-            ap.error("--jpeg_subsample is an option of the JPEG stage: it needs --jpeg_quality Q")
-    elif args.task == "sr":
-        if not args.synth_lr:
-            ap.error("--jpeg_quality codes the LR images formed on the device: it needs --synth_lr")
-        if args.synth_lr_bits != 8:
-            ap.error("--jpeg_quality codes 8-bit LR images: it needs --synth_lr_bits 8")
-        if not 1 <= args.jpeg_quality <= 100:
-            ap.error(f"--jpeg_quality must be in 1..100 (got {args.jpeg_quality})")
+        args.window_size = default_window_size(args.task)
+    eval_specs(args, ap.error)          # the data-path flags in their order; nothing is kept: main() builds the run's specs
     if args.tile < 0 or args.tile_batch < 1 or args.tile_overlap < 0 or (args.tile and args.tile_overlap >= args.tile):
         ap.error(f"--tile must be >= 0, --tile_batch >= 1 and 0 <= --tile_overlap < --tile (got --tile {args.tile} "
                  f"--tile_overlap {args.tile_overlap} --tile_batch {args.tile_batch})")
@@ -239,39 +168,25 @@ def parse_args(argv=None):
     return args
 
 
-def eval_restore(args):
-    """The FixedRestore of the command line (None for --task sr); --dn_sigma is given on the 0..255 scale."""
-    if args.task == "sr":
-        return None
-    from .ops import pack_restore_params
-    from .sr_datasets import FixedRestore
-    fx = FixedRestore((args.dn_sigma or 0.0) / 255.0, args.jpeg_quality or 0, False, args.jpeg_subsample == "420")
-    pack_restore_params(fx.jpeg_quality, (fx.sigma, 0.0), 0, False)          # the ranges
-    return fx
-
-
-def eval_usm(args):
-    """The UsmSpec of the command line (None without --gt_usm): training's rule, finetune_swinir.usm_spec."""
-    from .finetune_swinir import usm_spec
-    return usm_spec(args)
-
-
-def eval_psf(args):
-    """The 2-D blur table of the command line: table 0 of --blur_psf, the rotated Gaussian of --blur_theta (sigma_x along the columns at
-    0 degrees, as on the separable path; a sigma of 0 is floored as in sr_datasets.PsfSpec), or None."""
-    if args.blur_psf is not None:
-        from .blur_kernels import load_psf_file
-        return load_psf_file(args.blur_psf)[0]
-    if args.blur_theta is None:
-        return None
-    import math
-
-    from .blur_kernels import gaussian
-    from .sr_datasets import PSF_SIGMA_FLOOR
-    if not math.isfinite(args.blur_theta):
-        raise ValueError(f"--blur_theta must be finite (got {args.blur_theta})")
-    sy, sx = (max(float(v), PSF_SIGMA_FLOOR) for v in args.blur_sigma)
-    return gaussian(2 * min(math.ceil(3.0 * max(float(v) for v in args.blur_sigma)), 10) + 1, sx, sy, math.radians(args.blur_theta))
+def build_loader(args, specs, scale_int, swin, device):
+    """-> (test_ds, test_loader) of the run's branch (--task dn | car and --synth_lr read the HR directory alone); the loader is wrapped so
+    that the (degraded, clean) or (lr, hr) batches are formed on the device.  specs: the run's, from eval_specs."""
+    tf_test = PairTransformValid(scale_int) if swin else build_pair_transform_eval()
+    if specs.restore is not None:
+        test_ds = Shuffled2DHR(args.data_root, split="test", transform=partial(clean_to_tensor, out_chans=args.channels))
+    elif args.synth_lr:
+        test_ds = Shuffled2DHR(args.data_root, split="test", transform=hr_to_tensor3)
+    else:
+        test_ds = Shuffled2DPaired(args.data_root, split="test", scale=args.scale, transform_pair=tf_test)
+    test_loader = DataLoader(test_ds, batch_size=args.batch_size, shuffle=False, num_workers=args.workers,
+                             pin_memory=(device.type == "cuda"), persistent_workers=False)
+    if specs.restore is not None:
+        test_loader = RestoreBatches(test_loader, args.channels, specs.restore, args.dn_bits, device)
+    if args.synth_lr:
+        test_loader = SynthLRBatches(test_loader, scale_int, args.synth_lr_bits, device, degrade=specs.degrade,
+                                     jpeg=specs.jpeg, jpeg_subsample=args.jpeg_subsample == "420", psf=specs.psf, second_order=specs.second_order,
+                                     usm=specs.usm)
+    return test_ds, test_loader
 
 
 def main(argv=None):
@@ -282,60 +197,13 @@ def main(argv=None):
     swin = args.arch in ("swinir", "hat", "dat")
     if swin and device.type != "cuda":
         raise SystemExit(f"--arch {args.arch} runs on the MI355X HIP path only (no CPU fallback)")
-    scale_int = {"X1": 1, "X2": 2, "X4": 4}[args.scale.upper()]
-    restore = args.task != "sr"
+    scale_int = SCALES[args.scale.upper()]
+    specs = eval_specs(args)          # the run's fixed degradation, built once: the device wrapper and the lines share it
+    restore = specs.restore is not None
 
-    if swin:
-        from .sr_datasets import PairTransformValid
-        tf_test = PairTransformValid(scale_int)
-    else:
-        tf_test = build_pair_transform_eval()
-    if restore:
-        from functools import partial
-
-        from .sr_datasets import RestoreBatches, Shuffled2DHR, clean_to_tensor
-        test_ds = Shuffled2DHR(args.data_root, split="test", transform=partial(clean_to_tensor, out_chans=args.channels))
-    elif args.synth_lr:
-        from .sr_datasets import Shuffled2DHR, SynthLRBatches, hr_to_tensor3
-        test_ds = Shuffled2DHR(args.data_root, split="test", transform=hr_to_tensor3)
-    else:
-        test_ds = Shuffled2DPaired(args.data_root, split="test", scale=args.scale, transform_pair=tf_test)
-    test_loader = DataLoader(test_ds, batch_size=args.batch_size, shuffle=False, num_workers=args.workers,
-                             pin_memory=(device.type == "cuda"), persistent_workers=False)
-    if restore:          # (degraded, clean) batches formed on the device
-        fx = eval_restore(args)
-        test_loader = RestoreBatches(test_loader, args.channels, fx, args.dn_bits, device)
-        print(f"[task {args.task}] {args.channels} channel(s); degraded = whole image on the device: noise sigma={fx.sigma * 255.0:.4g} / 255 "
-              f"({args.dn_bits or 'no'}-bit rounding), jpeg quality {fx.jpeg_quality or 'none'} chroma {args.jpeg_subsample}, noise id = image index")
-    if args.synth_lr:          # (lr, hr) batches formed on the device, before the peek, the baseline and the prediction loop
-        fixed = second = None
-        if args.degrade in ("blind", "second_order"):
-            from .sr_datasets import FixedDegrade
-            fixed = FixedDegrade(tuple(args.blur_sigma), (args.noise_sigma / 255.0, args.noise_gain))
-        if args.degrade == "second_order":
-            from .sr_datasets import SecondOrderSpec
-            second = SecondOrderSpec() if args.jpeg_quality is None else SecondOrderSpec(jpeg_quality=(args.jpeg_quality,) * 2)
-        test_loader = SynthLRBatches(test_loader, scale_int, args.synth_lr_bits, device, degrade=fixed,
-                                     jpeg=None if second is not None else args.jpeg_quality, jpeg_subsample=args.jpeg_subsample == "420",
-                                     psf=eval_psf(args), second_order=second, usm=eval_usm(args))
-        print(f"[synth_lr] LR = antialiased bicubic /{scale_int} of HR on the device, {args.synth_lr_bits or 'no'}-bit rounding")
-        if fixed is not None:
-            print(f"[degrade] blind: blur sigma=({fixed.blur[0]:.4g}, {fixed.blur[1]:.4g}) HR px, noise sigma={args.noise_sigma:.4g} / 255 "
-                  f"gain={args.noise_gain:.4g}, noise id = image index")
-        if eval_psf(args) is not None:
-            k = eval_psf(args)
-            print(f"[degrade] blur kernel: {k.shape[0]} x {k.shape[0]} table, " + (f"table 0 of {args.blur_psf}" if args.blur_psf is not None else
-                                                                                    f"the Gaussian turned by {args.blur_theta:g} degrees"))
-        if second is not None:
-            fx2 = second.fixed(None, fixed.noise)
-            print(f"[degrade] second order, fixed: resize x{fx2.r1:.4g}, jpeg {fx2.q1}, blur 2 {fx2.k2.shape[0]} taps, resize x{fx2.r2:.4g} of LR, "
-                  f"noise sigma={fx2.noise2[0] * 255.0:.4g} / 255, jpeg {fx2.q2}, final filter {fx2.k3.shape[0]} taps, chroma {args.jpeg_subsample}")
-            if args.gt_usm:
-                us = eval_usm(args)
-                print(f"[degrade] gt_usm: HR is unsharp-masked ({us.ks} taps, weight {us.weight:g}, threshold {us.threshold:g} / 255); LR is "
-                      f"degraded from it and every score is taken against it")
-        elif args.jpeg_quality is not None:
-            print(f"[degrade] jpeg: quality {args.jpeg_quality}, chroma {args.jpeg_subsample}")
+    test_ds, test_loader = build_loader(args, specs, scale_int, swin, device)
+    for line in eval_lines(args, specs, scale_int):
+        print(line)
     print(f"[data] test samples: {len(test_ds)} | steps: {len(test_loader)}")
 
     def upscaled(lr, hr):
@@ -396,14 +264,10 @@ def main(argv=None):
     model = model.to(device).eval()
     predict = model
     if args.tile:
-        from functools import partial
-
         from .tiling import tiled_forward
         predict = partial(tiled_forward, model, tile=args.tile, overlap=args.tile_overlap, tile_batch=args.tile_batch, blend=args.tile_blend)
         print(f"[tile] {args.tile} overlap {args.tile_overlap} batch {args.tile_batch} blend {args.tile_blend}")
     if args.self_ensemble:
-        from functools import partial
-
         from .augment import self_ensemble
         predict = partial(self_ensemble, predict)
         print("[self_ensemble] x8")

@@ -35,6 +35,7 @@ the LR patch from the sharpened window and takes the loss against it; `--resize_
 the chain's three resizes per sample (csrc/usm.hip, csrc/resize_modes.hip).
 `--blur_kernel rotated|mixed` or `--blur_psf FILE` (with --degrade blind) blurs every patch with a 2-D table -- a rotated, generalized or
 plateau Gaussian, or a measured point-spread function -- in the same single launch (csrc/blur2d.hip).
+The flags from --synth_lr on are declared, checked, turned into specs and worded for the [degrade] lines in data_cli.py.
 
 Also additive: `--arch hat|dat` fine-tunes HAT / DAT (build_sr_model) through the same loop -- the fused, device-gated clip + AdamW step
 over their parameter lists (optim.FusedAdamW, csrc/optim_multi.hip), checkpoints "best_<arch>_finetune_<scale>.pt" /
@@ -48,16 +49,21 @@ import os
 import random
 import re
 import time
+from contextlib import nullcontext
 from datetime import timedelta
+from functools import partial
 
 import torch
 from torch.utils.data import DataLoader
 from torch.utils.data.distributed import DistributedSampler
 
-from . import SwinIR
+from . import SwinIR, data_cli
+from .data_cli import (RESTORATION_TASKS, SCALES, SECOND_ORDER_FLAGS, USM_FLAGS, add_train_data_flags,          # noqa: F401
+                       default_window_size, degrade_spec, jpeg_spec, psf_spec, restore_spec, second_order_spec, train_lines, train_specs, usm_spec)
 from .distributed import DataParallelSwinIR, init_from_env
 from .optim import FusedAdamW
-from .sr_datasets import PairTransformTrain, PairTransformValid, Shuffled2DPaired
+from .sr_datasets import (DeviceHR2Pool, DeviceHRPool, DevicePairPool, DeviceRestorePool, PairTransformTrain, PairTransformValid, RestoreBatches,
+                          Shuffled2DHR, Shuffled2DPaired, SynthLRBatches, clean_to_tensor, hr_to_tensor3)
 from .training import assert_finite_step, freeze_batchnorm, l1_loss, loss_name, make_loss, train_step
 
 
@@ -204,10 +210,6 @@ def build_model(scale_int: int, drop_path_rate: float = 0.1, window_size: int = 
                   drop_path_rate=drop_path_rate)
 
 
-RESTORATION_TASKS = {"dn": dict(window_size=8, img_size=128, img_range=1.0), "car": dict(window_size=7, img_size=126, img_range=255.0)}
-SCALES = {"X1": 1, "X2": 2, "X4": 4}
-
-
 def build_restoration_model(task: str, channels: int = 3, drop_path_rate: float = 0.1, window_size: int = None) -> SwinIR:
     """The published scale-1 SwinIR configurations: 'dn' (gray / colour denoising: window 8, img_size 128, img_range 1) and 'car' (JPEG
     compression-artifact reduction: window 7, img_size 126, img_range 255); upscale 1, upsampler '', in_chans = channels (1 | 3).
@@ -245,7 +247,8 @@ def build_sr_model(arch: str, scale_int: int, drop_path_rate: float = 0.1, windo
     raise ValueError(f"unknown arch {arch!r}")
 
 
-def parse_args(argv=None):
+def build_parser() -> argparse.ArgumentParser:
+    """The reference's flags and the additive ones of the training loop; the data-path flags (--synth_lr on) are data_cli's."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--data_root", type=str, required=True)
     ap.add_argument("--scale", type=str, choices=["X1", "X2", "X4"], required=True,
@@ -312,216 +315,32 @@ def parse_args(argv=None):
                          "images); checkpoints gain 'val_bench_psnr' / 'val_bench_ssim'; which checkpoint is best does not change")
     ap.add_argument("--val_crop_border", type=int, default=None, metavar="N",
                     help="additive, with --val_bench_metric: pixels cropped on every side before scoring (default: the scale)")
-    ap.add_argument("--synth_lr", action="store_true",
-                    help="additive, with --gpu_data: train and validate from the HR directories alone -- every LR patch is the "
-                         "antialiased bicubic (PIL BICUBIC convention) downscale of its HR image, computed on the device in the launch "
-                         "that crops the HR patch (sr_datasets.DeviceHRPool); no LR directory is required or read")
-    ap.add_argument("--synth_lr_bits", type=int, choices=[0, 8], default=8,
-                    help="additive, with --synth_lr: 8 = round the LR values to k / 255, as an 8-bit LR file would hold them; 0 = keep "
-                         "the filtered fp32 values")
-    ap.add_argument("--degrade", type=str, choices=["bicubic", "blind", "second_order"], default="bicubic",
-                    help="additive, with --synth_lr: blind = every LR training patch is blurred (Gaussian, composed into the bicubic "
-                         "taps) and noised with random per-sample parameters on the device (sr_datasets.DegradeSpec, csrc/degrade.hip); "
-                         "validation uses the midpoints of the ranges and fixed noise, the same LR images every epoch.  second_order = "
-                         "Real-ESRGAN's chain on the device -- blur, resize, noise, JPEG, twice, each sample at its own intermediate sizes, "
-                         "then a sinc filter (sr_datasets.SecondOrderSpec / DeviceHR2Pool, csrc/filter2d.hip, csrc/ragged.hip; DESIGN 7p).  "
-                         "Stage 1 takes the options of blind (--blur_sigma, --blur_kernel*, --noise_sigma, --noise_gain, --gray_noise_p, "
-                         "--jpeg_quality); it needs --synth_lr_bits 8")
-    ap.add_argument("--blur_sigma", type=float, nargs=2, default=[0.2, 2.0], metavar=("LO", "HI"),
-                    help="additive, with --degrade blind: range of the blur sigma in HR pixels, within [0, 2.5]")
-    ap.add_argument("--blur_aniso_p", type=float, default=0.5,
-                    help="additive, with --degrade blind: probability of an independent sigma_x (otherwise sigma_x = sigma_y)")
-    ap.add_argument("--noise_sigma", type=float, nargs=2, default=[0.0, 10.0], metavar=("LO", "HI"),
-                    help="additive, with --degrade blind: range of the signal-independent noise sigma in 8-bit levels (divided by 255)")
-    ap.add_argument("--noise_gain", type=float, nargs=2, default=[0.0, 0.0], metavar=("LO", "HI"),
-                    help="additive, with --degrade blind: range of the gain of the signal-dependent (Poisson-like) noise variance gain * v")
-    ap.add_argument("--gray_noise_p", type=float, default=0.4,
-                    help="additive, with --degrade blind: probability that a colour image gets one noise draw for its three channels")
-    ap.add_argument("--degrade_seed", type=int, default=0,
-                    help="additive, with --degrade blind: seed of the degradation parameters' own generator (+ rank)")
-    ap.add_argument("--jpeg_quality", type=int, nargs=2, default=None, metavar=("LO", "HI"),
-                    help="additive, with --synth_lr --synth_lr_bits 8 (either --degrade): every LR training patch makes a round trip through "
-                         "baseline JPEG on the device at a quality uniform in LO..HI (1..100; sr_datasets.JpegSpec, csrc/jpeg.hip; its own "
-                         "generator, seeded by --degrade_seed + rank); validation uses the middle of the range")
-    ap.add_argument("--jpeg_p", type=float, default=1.0,
-                    help="additive, with --jpeg_quality: probability that a training patch takes the JPEG stage (otherwise it passes through)")
-    ap.add_argument("--jpeg_subsample", type=str, choices=["444", "420"], default="444",
-                    help="additive, with --jpeg_quality: chroma at 4:4:4, or 4:2:0 (2 x 2 means, upsampled by replication)")
-    ap.add_argument("--blur_kernel", type=str, choices=["axis", "rotated", "mixed"], default="axis",
-                    help="additive, with --degrade blind: the blur of a training patch -- 'axis': the axis-aligned Gaussian composed into the "
-                         "bicubic taps; 'rotated': the same Gaussian turned by a random angle; 'mixed': Real-ESRGAN's pool of (an)isotropic, "
-                         "generalized and plateau kernels -- as a 2-D table on the device (sr_datasets.PsfSpec, csrc/blur2d.hip; its own "
-                         "generator, seeded by --degrade_seed + rank); validation keeps the isotropic midpoints")
-    ap.add_argument("--blur_kernel_prob", type=float, nargs=6, default=None, metavar="P",
-                    help="additive, with --blur_kernel mixed: probabilities of iso, aniso, generalized iso, generalized aniso, plateau iso, "
-                         "plateau aniso (default 0.45 0.25 0.12 0.03 0.12 0.03)")
-    ap.add_argument("--blur_beta_g", type=float, nargs=2, default=None, metavar=("LO", "HI"),
-                    help="additive, with --blur_kernel mixed: range of the generalized Gaussian's shape beta (default 0.5 4)")
-    ap.add_argument("--blur_beta_p", type=float, nargs=2, default=None, metavar=("LO", "HI"),
-                    help="additive, with --blur_kernel mixed: range of the plateau kernel's shape beta (default 1 2)")
-    ap.add_argument("--blur_ksize", type=int, nargs=2, default=None, metavar=("LO", "HI"),
-                    help="additive, with --blur_kernel mixed: range of the odd table size (default 7 21)")
-    ap.add_argument("--blur_psf", type=str, default=None, metavar="FILE",
-                    help="additive, with --degrade blind: a measured point-spread function, .npy [k][k] or [n][k][k] (k odd <= 21, taps >= 0 "
-                         "summing to 1); every training patch is blurred with one of its tables, validation with table 0")
-    ap.add_argument("--degrade_tables", type=str, choices=["host", "device"], default="host",
-                    help="additive, with --degrade blind and --blur_kernel rotated | mixed or --blur_psf, or with --degrade second_order: "
-                         "where the blur and sinc tables of a training batch are evaluated -- 'host': in fp64 numpy, then uploaded; 'device': "
-                         "on the GPU from eight numbers per table (csrc/tables.hip, DESIGN 7q), the same draws and decisions, every tap "
-                         "within one fp32 spacing of the host's.  Validation keeps its fixed host tables")
-    ap.add_argument("--blur2_sigma", type=float, nargs=2, default=None, metavar=("LO", "HI"),
-                    help="additive, with --degrade second_order: range of the sigmas of the second blur, a rotated Gaussian (default 0.2 1.5)")
-    ap.add_argument("--blur2_p", type=float, default=None,
-                    help="additive, with --degrade second_order: probability of the second blur (default 0.8)")
-    ap.add_argument("--noise2_sigma", type=float, nargs=2, default=None, metavar=("LO", "HI"),
-                    help="additive, with --degrade second_order: range of the second noise sigma in 8-bit levels (default 1 25)")
-    ap.add_argument("--jpeg2_quality", type=int, nargs=2, default=None, metavar=("LO", "HI"),
-                    help="additive, with --degrade second_order: quality range of the second JPEG (default 30 95; --jpeg_quality is the first's)")
-    ap.add_argument("--resize_range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
-                    help="additive, with --degrade second_order: factors of the first resize, LO <= 1 <= HI (default 0.15 1.5)")
-    ap.add_argument("--resize_prob", type=float, nargs=3, default=None, metavar=("UP", "DOWN", "KEEP"),
-                    help="additive, with --degrade second_order: probabilities of the first resize going up, down, or staying (default 0.2 0.7 0.1)")
-    ap.add_argument("--resize2_range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
-                    help="additive, with --degrade second_order: factors of the second resize, relative to the LR size (default 0.3 1.2)")
-    ap.add_argument("--resize2_prob", type=float, nargs=3, default=None, metavar=("UP", "DOWN", "KEEP"),
-                    help="additive, with --degrade second_order: probabilities of the second resize (default 0.3 0.4 0.3)")
-    ap.add_argument("--sinc_p", type=float, default=None,
-                    help="additive, with --degrade second_order: probability that a blur is a sinc (ringing) filter, at both stages (default 0.1)")
-    ap.add_argument("--final_sinc_p", type=float, default=None,
-                    help="additive, with --degrade second_order: probability of the final sinc filter (default 0.8)")
-    ap.add_argument("--degrade_margin", type=int, default=None,
-                    help="additive, with --degrade second_order: LR pixels around the patch that the chain also runs on (default 8)")
-    ap.add_argument("--resize_mode_prob", type=float, nargs=3, default=None, metavar=("AREA", "BILINEAR", "BICUBIC"),
-                    help="additive, with --degrade second_order: probabilities of the rule of each of the three resizes of a training patch "
-                         "(csrc/resize_modes.hip, DESIGN 7r; Real-ESRGAN draws among the three; default 0 0 1, the antialiased cubic).  "
-                         "Validation keeps the cubic")
-    ap.add_argument("--gt_usm", action="store_true",
-                    help="additive, with --degrade second_order: Real-ESRGAN's gt_usm -- the HR window is unsharp-masked once on the device "
-                         "(csrc/usm.hip, DESIGN 7r), the LR patch is degraded from the sharpened window and the loss is taken against it; "
-                         "validation scores against the sharpened image.  --degrade_margin 13 at X4 (25 at X2) keeps the window's reflected "
-                         "edge out of the patch")
-    ap.add_argument("--usm_radius", type=int, default=None, help="additive, with --gt_usm: Real-ESRGAN's radius, 1..51 (default 50: 51 taps, sigma 8)")
-    ap.add_argument("--usm_weight", type=float, default=None, help="additive, with --gt_usm: weight of the residual (default 0.5)")
-    ap.add_argument("--usm_threshold", type=float, default=None, help="additive, with --gt_usm: threshold of the mask in 8-bit levels (default 10)")
-    ap.add_argument("--task", type=str, choices=["sr", "dn", "car"], default="sr",
-                    help="additive: sr = super-resolution (as ever); dn = denoising, car = JPEG compression-artifact reduction: the published "
-                         "scale-1 SwinIR models (build_restoration_model), trained from the HR directories alone -- every patch is cut at "
-                         "any image pixel and degraded on the device as a window of the whole-image degradation (sr_datasets."
-                         "DeviceRestorePool, csrc/restore.hip).  They need --scale X1 and imply --gpu_data")
-    ap.add_argument("--channels", type=int, choices=[1, 3], default=3,
-                    help="additive, with --task dn | car: 3 = colour, 1 = gray (an RGB file becomes its integer BT.601 luma, ops.to_gray)")
-    ap.add_argument("--dn_sigma", type=float, nargs=2, default=None, metavar=("LO", "HI"),
-                    help="additive, with --task dn (required) | car: range of the Gaussian noise sigma on the 0..255 scale of the papers "
-                         "(15 / 25 / 50; divided by 255); validation uses the midpoint")
-    ap.add_argument("--dn_bits", type=int, choices=[0, 8], default=0,
-                    help="additive, with --task dn | car: 0 = the noisy input is neither clipped nor rounded, as the published training has "
-                         "it; 8 = rounded to k / 255")
+    add_train_data_flags(ap)
+    return ap
+
+
+def parse_args(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
     if args.window_size is None:
-        args.window_size = RESTORATION_TASKS[args.task]["window_size"] if args.task != "sr" else 8
-    if args.task == "sr":
-        if args.scale == "X1":
-            ap.error("--scale X1 is the scale of --task dn | car; --task sr takes X2 | X4")
-        if args.channels != 3 or args.dn_sigma is not None or args.dn_bits != 0:
-            ap.error("--channels, --dn_sigma and --dn_bits are options of --task dn | car")
-    else:
-        if args.scale != "X1":
-            ap.error(f"--task {args.task} restores at one size: it needs --scale X1 (got {args.scale})")
-        if args.arch != "swinir":
-            ap.error(f"--task {args.task} is built for --arch swinir only (HAT and DAT end in a pixel-shuffle tail; got --arch {args.arch})")
-        if args.synth_lr or args.degrade != "bicubic":
-            ap.error(f"--synth_lr and --degrade form LR images for --task sr; --task {args.task} degrades at scale 1 on its own")
-        if args.task == "dn" and args.dn_sigma is None:
-            ap.error("--task dn needs --dn_sigma LO HI (0..255 scale, e.g. 25 25)")
-        if args.task == "dn" and args.jpeg_quality is not None:
-            ap.error("--jpeg_quality with noise is --task car --dn_sigma LO HI; --task dn has no JPEG stage")
-        if args.task == "car" and args.jpeg_quality is None:
-            ap.error("--task car needs --jpeg_quality LO HI")
-        if args.jpeg_p != 1.0:
-            ap.error(f"--jpeg_p is an option of the JPEG stage of --synth_lr; with --task {args.task} every patch is coded")
-        if args.val_bench_metric is not None and args.channels == 1:
-            ap.error("--val_bench_metric is not offered with --channels 1 (the benchmark-protocol scores take RGB predictions)")
-        try:
-            restore_spec(args)
-        except ValueError as e:
-            ap.error(f"--task {args.task}: {e}")
-        args.gpu_data = True          # the pairs are made on the device; the HR directories alone are read
-    if args.synth_lr and not args.gpu_data:
-        ap.error("--synth_lr forms the LR patches on the device: it needs --gpu_data")
-    if args.degrade in ("blind", "second_order"):
-        if not args.synth_lr:
-            ap.error(f"--degrade {args.degrade} degrades HR patches on the device: it needs --synth_lr")
-        try:
-            degrade_spec(args)
-        except ValueError as e:
-            ap.error(f"--degrade {args.degrade}: {e}")
-    second = [n for n in SECOND_ORDER_FLAGS if getattr(args, n) is not None]
-    if args.degrade == "second_order":
-        if args.synth_lr_bits != 8:
-            ap.error("--degrade second_order codes 8-bit LR images: it needs --synth_lr_bits 8")
-        if args.jpeg_p != 1.0:
-            ap.error("--jpeg_p is an option of the single JPEG stage; --degrade second_order codes every patch twice")
-        try:
-            second_order_spec(args)
-        except ValueError as e:
-            ap.error(f"--degrade second_order: {e}")
-        if args.degrade_margin is not None and not 0 <= args.degrade_margin <= 64:
-            ap.error(f"--degrade_margin must be in 0..64 LR pixels (got {args.degrade_margin})")
-    elif second:
-        ap.error(f"--{second[0]} is an option of --degrade second_order")
-    usm_opts = [n for n in USM_FLAGS if getattr(args, n) is not None]
-    if args.gt_usm and args.degrade != "second_order":
-        ap.error("--gt_usm sharpens the target of --degrade second_order: it needs it")
-    if usm_opts and not args.gt_usm:
-        ap.error(f"--{usm_opts[0]} is an option of --gt_usm")
-    try:
-        usm_spec(args)
-    except ValueError as e:
-        ap.error(f"--gt_usm: {e}")
-    mixed_opts = [n for n in ("blur_kernel_prob", "blur_beta_g", "blur_beta_p", "blur_ksize") if getattr(args, n) is not None]
-    if (args.blur_kernel != "axis" or args.blur_psf is not None) and args.degrade not in ("blind", "second_order"):
-        ap.error("--blur_kernel and --blur_psf shape the blur of --degrade blind | second_order: they need it")
-    if args.blur_psf is not None and args.blur_kernel != "axis":
-        ap.error("--blur_psf FILE replaces the generated kernels: it does not go with --blur_kernel rotated | mixed")
-    if mixed_opts and args.blur_kernel != "mixed":
-        ap.error(f"--{mixed_opts[0]} is an option of --blur_kernel mixed")
-    try:
-        psf_spec(args)
-    except (ValueError, OSError) as e:
-        ap.error(f"--blur_kernel / --blur_psf: {e}")
-    if args.degrade_tables != "host" and not (args.degrade == "second_order" or
-                                              (args.degrade == "blind" and (args.blur_kernel != "axis" or args.blur_psf is not None))):
-        ap.error("--degrade_tables device builds the 2-D tables of --degrade blind with --blur_kernel rotated | mixed or --blur_psf, or of "
-                 "--degrade second_order: it needs one of them")
-    if args.jpeg_quality is None:
-        if args.jpeg_p != 1.0 or (args.jpeg_subsample != "444" and args.degrade != "second_order"):
-            ap.error("--jpeg_p and --jpeg_subsample are options of the JPEG stage: they need --jpeg_quality LO HI")
-    elif args.task == "sr":
-        if not (args.gpu_data and args.synth_lr):
-            ap.error("--jpeg_quality codes the LR patches formed on the device: it needs --gpu_data --synth_lr")
-        if args.synth_lr_bits != 8:
-            ap.error("--jpeg_quality codes 8-bit LR images: it needs --synth_lr_bits 8")
-        try:
-            jpeg_spec(args)
-        except ValueError as e:
-            ap.error(f"--jpeg_quality: {e}")
+        args.window_size = default_window_size(args.task)
+    train_specs(args, ap.error)          # the data-path flags in their order; nothing is kept: main() builds the run's specs
+    args.gpu_data |= args.task != "sr"          # dn | car: the pairs are made on the device; the HR directories alone are read
     if args.val_tile < 0 or args.val_tile_overlap < 0 or (args.val_tile and args.val_tile_overlap >= args.val_tile):
         ap.error(f"--val_tile must be >= 0 and 0 <= --val_tile_overlap < --val_tile (got --val_tile {args.val_tile} "
                  f"--val_tile_overlap {args.val_tile_overlap})")
     if args.val_crop_border is not None and (args.val_bench_metric is None or args.val_crop_border < 0):
         ap.error(f"--val_crop_border must be >= 0 and is an option of --val_bench_metric y | rgb (got {args.val_crop_border})")
-    if not 0.0 <= args.ssim_weight < float("inf"):          # also refuses NaN
-        ap.error(f"--ssim_weight must be a finite number >= 0 (got {args.ssim_weight})")
-    if not 0.0 <= args.fft_weight < float("inf"):          # also refuses NaN
-        ap.error(f"--fft_weight must be a finite number >= 0 (got {args.fft_weight})")
-    if args.fft_weight > 0 and args.lr_patch * SCALES[args.scale.upper()] > 512:
-        ap.error(f"--fft_weight needs HR patches of at most 512 x 512 (lr_patch * scale = "
-                 f"{args.lr_patch * SCALES[args.scale.upper()]})")
+    for n in ("ssim_weight", "fft_weight"):
+        if not 0.0 <= getattr(args, n) < float("inf"):          # also refuses NaN
+            ap.error(f"--{n} must be a finite number >= 0 (got {getattr(args, n)})")
+    hr_patch = args.lr_patch * SCALES[args.scale.upper()]
+    if args.fft_weight > 0 and hr_patch > 512:
+        ap.error(f"--fft_weight needs HR patches of at most 512 x 512 (lr_patch * scale = {hr_patch})")
     if not args.charbonnier_eps > 0.0:
         ap.error(f"--charbonnier_eps must be > 0 (got {args.charbonnier_eps})")
-    if args.ssim_weight > 0 and args.lr_patch * SCALES[args.scale.upper()] < 11:
-        ap.error(f"--ssim_weight needs HR patches of at least 11 x 11 (lr_patch * scale = "
-                 f"{args.lr_patch * SCALES[args.scale.upper()]})")
+    if args.ssim_weight > 0 and hr_patch < 11:
+        ap.error(f"--ssim_weight needs HR patches of at least 11 x 11 (lr_patch * scale = {hr_patch})")
     if not 0.0 <= args.ema_decay < 1.0:          # also refuses NaN
         ap.error(f"--ema_decay must be in [0, 1) (got {args.ema_decay})")
     if not 2 <= args.window_size <= 8:
@@ -534,97 +353,56 @@ def parse_args(argv=None):
     return args
 
 
-def degrade_spec(args):
-    """The DegradeSpec of the command line (None for --degrade bicubic); --noise_sigma is given in 8-bit levels."""
-    if args.degrade not in ("blind", "second_order"):
-        return None
-    from .sr_datasets import DegradeSpec
-    return DegradeSpec(blur_sigma=tuple(args.blur_sigma), blur_aniso_p=args.blur_aniso_p, noise_sigma=tuple(v / 255.0 for v in args.noise_sigma),
-                       noise_gain=tuple(args.noise_gain), gray_noise_p=args.gray_noise_p, seed=args.degrade_seed)
-
-
-def psf_spec(args):
-    """The PsfSpec of the command line (None for --blur_kernel axis without --blur_psf); it reuses --degrade_seed."""
-    if args.blur_kernel == "axis" and args.blur_psf is None:
-        return None
-    from .sr_datasets import PsfSpec
-    opts = {k: tuple(v) for k, v in (("kernel_prob", args.blur_kernel_prob), ("beta_g", args.blur_beta_g), ("beta_p", args.blur_beta_p),
-                                     ("ksize", args.blur_ksize)) if v is not None}
-    if args.blur_psf is not None:
-        return PsfSpec(mode="file", file=args.blur_psf, seed=args.degrade_seed)
-    return PsfSpec(mode=args.blur_kernel, seed=args.degrade_seed, **opts)
-
-
-def jpeg_spec(args):
-    """The JpegSpec of the command line (None without --jpeg_quality, and with --degrade second_order, whose first JPEG takes the
-    range); it reuses --degrade_seed."""
-    if args.jpeg_quality is None or args.degrade == "second_order":
-        return None
-    from .sr_datasets import JpegSpec
-    return JpegSpec(quality=tuple(args.jpeg_quality), p=args.jpeg_p, subsample=args.jpeg_subsample == "420", seed=args.degrade_seed)
-
-
-SECOND_ORDER_FLAGS = ("blur2_sigma", "blur2_p", "noise2_sigma", "jpeg2_quality", "resize_range", "resize_prob", "resize2_range", "resize2_prob",
-                      "sinc_p", "final_sinc_p", "degrade_margin", "resize_mode_prob")
-USM_FLAGS = ("usm_radius", "usm_weight", "usm_threshold")
-
-
-def usm_spec(args):
-    """The UsmSpec of the command line (None without --gt_usm): the flags that were given replace Real-ESRGAN's defaults."""
-    if not args.gt_usm:
-        return None
-    from .sr_datasets import UsmSpec
-    return UsmSpec(**{k: v for k, v in (("radius", args.usm_radius), ("weight", args.usm_weight), ("threshold", args.usm_threshold)) if v is not None})
-
-
-def second_order_spec(args):
-    """The SecondOrderSpec of the command line (None unless --degrade second_order): the flags that were given replace Real-ESRGAN's
-    defaults; --noise2_sigma is given in 8-bit levels, --jpeg_quality is the first JPEG's range; it reuses --degrade_seed,
-    --gray_noise_p and --blur_ksize."""
-    if args.degrade != "second_order":
-        return None
-    from .sr_datasets import SecondOrderSpec
-    opts = {k: (v if isinstance(v, float) else tuple(v)) for k, v in (
-        ("blur2_sigma", args.blur2_sigma), ("blur2_p", args.blur2_p), ("jpeg2_quality", args.jpeg2_quality), ("resize_range", args.resize_range),
-        ("resize_prob", args.resize_prob), ("resize2_range", args.resize2_range), ("resize2_prob", args.resize2_prob), ("sinc_p", args.sinc_p),
-        ("final_sinc_p", args.final_sinc_p), ("jpeg_quality", args.jpeg_quality), ("ksize", args.blur_ksize),
-        ("resize_mode_prob", args.resize_mode_prob)) if v is not None}
-    if args.noise2_sigma is not None:
-        opts["noise2_sigma"] = tuple(v / 255.0 for v in args.noise2_sigma)
-    return SecondOrderSpec(gray_noise_p=args.gray_noise_p, seed=args.degrade_seed, **opts)
-
-
-def restore_spec(args):
-    """The RestoreSpec of the command line (None for --task sr); --dn_sigma is given on the 0..255 scale; it reuses --degrade_seed and
-    --gray_noise_p is not consulted: a colour image gets colour noise, as in the published training."""
-    if args.task == "sr":
-        return None
-    from .sr_datasets import RestoreSpec
-    sigma = (0.0, 0.0) if args.dn_sigma is None else tuple(v / 255.0 for v in args.dn_sigma)
-    return RestoreSpec(sigma=sigma, jpeg_quality=None if args.jpeg_quality is None else tuple(args.jpeg_quality),
-                       subsample=args.jpeg_subsample == "420", seed=args.degrade_seed)
-
-
 def saved_args(args) -> dict:
-    """What a checkpoint keeps of the command line: additive flags leave no trace in the files at their defaults."""
-    at_default = {"ema_decay": not args.ema_decay, "loss": args.loss == "l1", "charbonnier_eps": args.charbonnier_eps == 1e-3,
-                  "ssim_weight": args.ssim_weight == 0, "fft_weight": args.fft_weight == 0,
-                  "fft_norm": args.fft_weight == 0 or args.fft_norm == "backward", "val_tile": args.val_tile == 0,
-                  "val_tile_overlap": args.val_tile == 0 or args.val_tile_overlap == 32, "synth_lr": not args.synth_lr,
-                  "synth_lr_bits": not args.synth_lr or args.synth_lr_bits == 8, "degrade": args.degrade == "bicubic",
-                  "blur_sigma": args.blur_sigma == [0.2, 2.0], "blur_aniso_p": args.blur_aniso_p == 0.5,
-                  "noise_sigma": args.noise_sigma == [0.0, 10.0], "noise_gain": args.noise_gain == [0.0, 0.0],
-                  "gray_noise_p": args.gray_noise_p == 0.4,
-                  "degrade_seed": args.degrade_seed == 0, "jpeg_quality": args.jpeg_quality is None, "jpeg_p": args.jpeg_p == 1.0,
-                  "jpeg_subsample": args.jpeg_subsample == "444", "blur_kernel": args.blur_kernel == "axis",
-                  "blur_kernel_prob": args.blur_kernel_prob is None, "blur_beta_g": args.blur_beta_g is None,
-                  "blur_beta_p": args.blur_beta_p is None, "blur_ksize": args.blur_ksize is None, "blur_psf": args.blur_psf is None,
-                  "degrade_tables": args.degrade_tables == "host", "val_bench_metric": args.val_bench_metric is None,
-                  "val_crop_border": args.val_crop_border is None, "task": args.task == "sr", "channels": args.channels == 3,
-                  "dn_sigma": args.dn_sigma is None, "dn_bits": args.dn_bits == 0}
-    at_default.update({n: getattr(args, n) is None for n in SECOND_ORDER_FLAGS + USM_FLAGS})
-    at_default["gt_usm"] = not args.gt_usm
-    return {k: v for k, v in vars(args).items() if not at_default.get(k, False)}
+    """What a checkpoint keeps of the command line: additive flags leave no trace in the files at the defaults their add_argument declared."""
+    return data_cli.saved_args(args, build_parser())
+
+
+def build_loaders(args, specs, scale_int, device, rank, world):
+    """-> (train_loader, sampler, valid_loader, lines): a DevicePoolLoader over the pool of the run's branch (--task dn | car, --synth_lr,
+    --gpu_data) or the host DataLoader; what takes set_epoch (or None); the validation loader with its device wrapper; the pool's lines
+    for rank 0 to print (data_cli.train_lines).  specs: the run's, from train_specs."""
+    shard_bytes, pool = (args.gpu_data_shard_mb << 20) or None, None
+    if specs.restore is not None:
+        raw = Shuffled2DHR(args.data_root, split="train")
+        pool = DeviceRestorePool((raw[i] for i in range(len(raw))), args.lr_patch, args.channels, specs.restore, device=device,
+                                 shard_bytes=shard_bytes, augment=args.augment, quant_bits=args.dn_bits, rank=rank)
+        train_loader = sampler = DevicePoolLoader(pool, args.batch_size, rank, world, args.seed)
+        valid_ds = Shuffled2DHR(args.data_root, split="valid", transform=partial(clean_to_tensor, out_chans=args.channels))
+    elif args.synth_lr:
+        raw = Shuffled2DHR(args.data_root, split="train")
+        if specs.second_order is not None:
+            pool = DeviceHR2Pool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, specs.second_order, specs.degrade, device=device,
+                                 shard_bytes=shard_bytes, augment=args.augment, rank=rank, psf=specs.psf,
+                                 margin=8 if args.degrade_margin is None else args.degrade_margin, subsample=args.jpeg_subsample == "420",
+                                 names=[f.name for f in raw.files], tables=args.degrade_tables, usm=specs.usm)
+        else:
+            pool = DeviceHRPool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, device=device,
+                                shard_bytes=shard_bytes, augment=args.augment, quant_bits=args.synth_lr_bits,
+                                degrade=specs.degrade, rank=rank, jpeg=specs.jpeg, psf=specs.psf, tables=args.degrade_tables)
+        train_loader = sampler = DevicePoolLoader(pool, args.batch_size, rank, world, args.seed)
+        valid_ds = Shuffled2DHR(args.data_root, split="valid", transform=hr_to_tensor3)
+    else:
+        train_ds = Shuffled2DPaired(args.data_root, split="train", scale=args.scale,
+                                    transform_pair=PairTransformTrain(args.lr_patch, scale_int, args.augment))
+        valid_ds = Shuffled2DPaired(args.data_root, split="valid", scale=args.scale, transform_pair=PairTransformValid(scale_int))
+        sampler = DistributedSampler(train_ds, num_replicas=world, rank=rank, shuffle=True, seed=args.seed) if world > 1 else None
+        train_loader = make_loader(train_ds, args.batch_size, args.workers, pin=not args.no_pin, shuffle=True, drop_last=True,
+                                   persistent=not args.no_persistent, sampler=sampler)
+        if args.gpu_data:
+            raw = Shuffled2DPaired(args.data_root, split="train", scale=args.scale, transform_pair=None)
+            pool = DevicePairPool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, device=device,
+                                  shard_bytes=shard_bytes, augment=args.augment)
+            train_loader = sampler = DevicePoolLoader(pool, args.batch_size, rank, world, args.seed)
+    valid_loader = make_loader(valid_ds, max(1, args.batch_size // 2), args.workers, pin=not args.no_pin, shuffle=False,
+                               drop_last=False, persistent=not args.no_persistent)
+    if specs.restore is not None:
+        valid_loader = RestoreBatches(valid_loader, args.channels, specs.restore, args.dn_bits, device)
+    if args.synth_lr:
+        valid_loader = SynthLRBatches(valid_loader, scale_int, args.synth_lr_bits, device, degrade=specs.degrade, jpeg=specs.jpeg,
+                                      jpeg_subsample=args.jpeg_subsample == "420", psf=specs.psf, second_order=specs.second_order,
+                                      usm=specs.usm)
+    return train_loader, sampler, valid_loader, [] if pool is None else train_lines(args, specs, scale_int, pool)
 
 
 def main(argv=None):
@@ -644,95 +422,10 @@ def main(argv=None):
         print("[device]", device, torch.cuda.get_device_name(local), f"world={world}")
     scale_int = SCALES[args.scale.upper()]
 
-    if args.task != "sr":
-        from functools import partial
-
-        from .sr_datasets import DeviceRestorePool, RestoreBatches, Shuffled2DHR, clean_to_tensor
-        raw = Shuffled2DHR(args.data_root, split="train")
-        spec = restore_spec(args)
-        pool = DeviceRestorePool((raw[i] for i in range(len(raw))), args.lr_patch, args.channels, spec, device=device,
-                                 shard_bytes=(args.gpu_data_shard_mb << 20) or None, augment=args.augment, quant_bits=args.dn_bits, rank=rank)
-        train_loader = sampler = DevicePoolLoader(pool, args.batch_size, rank, world, args.seed)
-        valid_ds = Shuffled2DHR(args.data_root, split="valid", transform=partial(clean_to_tensor, out_chans=args.channels))
-        if rank == 0:
-            fx = spec.fixed()
-            print(f"[task {args.task}] {len(pool)} clean images in {pool.num_shards} shard(s), {sum(t.numel() for t in pool._host) / 2**20:.1f} "
-                  f"MiB decoded; {args.channels} channel(s), patches of {args.lr_patch} cut at any pixel and degraded on the device")
-            print(f"[degrade] noise sigma in {[0.0, 0.0] if args.dn_sigma is None else args.dn_sigma} / 255 ({args.dn_bits or 'no'}-bit "
-                  f"rounding), jpeg quality in {args.jpeg_quality} chroma {args.jpeg_subsample}, blocks on the image's grid, seed "
-                  f"{args.degrade_seed}; validation: sigma={fx.sigma * 255.0:.4g} / 255 quality {fx.jpeg_quality or 'none'}, noise id = image index")
-    elif args.synth_lr:
-        from .sr_datasets import DeviceHR2Pool, DeviceHRPool, Shuffled2DHR, SynthLRBatches, hr_to_tensor3
-        raw = Shuffled2DHR(args.data_root, split="train")
-        if args.degrade == "second_order":
-            pool = DeviceHR2Pool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, second_order_spec(args), degrade_spec(args),
-                                 device=device, shard_bytes=(args.gpu_data_shard_mb << 20) or None, augment=args.augment, rank=rank,
-                                 psf=psf_spec(args), margin=8 if args.degrade_margin is None else args.degrade_margin,
-                                 subsample=args.jpeg_subsample == "420", names=[f.name for f in raw.files], tables=args.degrade_tables,
-                                 usm=usm_spec(args))
-        else:
-            pool = DeviceHRPool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, device=device,
-                                shard_bytes=(args.gpu_data_shard_mb << 20) or None, augment=args.augment, quant_bits=args.synth_lr_bits,
-                                degrade=degrade_spec(args), rank=rank, jpeg=jpeg_spec(args), psf=psf_spec(args), tables=args.degrade_tables)
-        train_loader = sampler = DevicePoolLoader(pool, args.batch_size, rank, world, args.seed)
-        valid_ds = Shuffled2DHR(args.data_root, split="valid", transform=hr_to_tensor3)
-        if rank == 0:
-            print(f"[synth_lr] {len(pool)} HR images in {pool.num_shards} shard(s), {sum(t.numel() for t in pool._host) / 2**20:.1f} MiB "
-                  f"decoded; LR = antialiased bicubic /{scale_int} on the device, {args.synth_lr_bits or 'no'}-bit rounding")
-            if args.degrade == "second_order":
-                so = second_order_spec(args)
-                print(f"[degrade] second order: window {pool.extent} x {pool.extent} HR px (margin {pool.margin} LR px), resize {list(so.resize_range)} "
-                      f"p={list(so.resize_prob)} then {list(so.resize2_range)} p={list(so.resize2_prob)}, blur 2 p={so.blur2_p:g}, sinc p={so.sinc_p:g} "
-                      f"final p={so.final_sinc_p:g}, jpeg {list(so.jpeg_quality)} then {list(so.jpeg2_quality)} chroma {args.jpeg_subsample}, seed "
-                      f"{args.degrade_seed}; validation: the fixed chain (SecondOrderSpec.fixed), noise id = image index")
-                if so.resize_mode_prob != (0.0, 0.0, 1.0):
-                    print(f"[degrade] resize rules: area / bilinear / bicubic with p={list(so.resize_mode_prob)} at each of the three resizes; "
-                          f"validation: bicubic")
-                if args.gt_usm:
-                    us = usm_spec(args)
-                    print(f"[degrade] gt_usm: the HR window is unsharp-masked ({us.ks} taps, weight {us.weight:g}, threshold {us.threshold:g} / 255); "
-                          f"LR is degraded from it and the loss is taken against it; margin {pool.margin} x scale {scale_int} "
-                          f"{'>=' if pool.margin * scale_int >= us.ks - 1 else '<'} 2R = {us.ks - 1}")
-            if args.degrade in ("blind", "second_order"):
-                fx = degrade_spec(args).fixed()
-                print(f"[degrade] blind: blur sigma in {args.blur_sigma} HR px (aniso p={args.blur_aniso_p}), noise sigma in "
-                      f"{args.noise_sigma} / 255, gain in {args.noise_gain}, gray p={args.gray_noise_p}, seed {args.degrade_seed}; "
-                      f"validation: sigma=({fx.blur[0]:.4g}, {fx.blur[1]:.4g}) noise sigma={fx.noise[0] * 255.0:.4g} / 255 "
-                      f"gain={fx.noise[1]:.4g}, noise id = image index")
-            if psf_spec(args) is not None:
-                ps = psf_spec(args)
-                what = (f"{len(ps.tables)} measured table(s) of {args.blur_psf}, {ps.tables.shape[-1]} x {ps.tables.shape[-1]}; validation: table 0"
-                        if ps.mode == "file" else f"{ps.mode} 2-D kernels; validation: the isotropic midpoints")
-                print(f"[degrade] blur kernel: {what}, seed {args.degrade_seed}")
-            if args.degrade_tables == "device":
-                print("[degrade] tables: built on the device from descriptors (csrc/tables.hip)")
-            if args.jpeg_quality is not None:
-                js = jpeg_spec(args)
-                print(f"[degrade] jpeg: quality in {list(js.quality)} with p={js.p:g}, chroma {args.jpeg_subsample}, seed {args.degrade_seed}; "
-                      f"validation: quality {js.fixed()}")
-    else:
-        train_ds = Shuffled2DPaired(args.data_root, split="train", scale=args.scale,
-                                    transform_pair=PairTransformTrain(args.lr_patch, scale_int, args.augment))
-        valid_ds = Shuffled2DPaired(args.data_root, split="valid", scale=args.scale, transform_pair=PairTransformValid(scale_int))
-        sampler = DistributedSampler(train_ds, num_replicas=world, rank=rank, shuffle=True, seed=args.seed) if world > 1 else None
-        train_loader = make_loader(train_ds, args.batch_size, args.workers, pin=not args.no_pin, shuffle=True, drop_last=True,
-                                   persistent=not args.no_persistent, sampler=sampler)
-    if args.gpu_data and not args.synth_lr and args.task == "sr":
-        from .sr_datasets import DevicePairPool
-        raw = Shuffled2DPaired(args.data_root, split="train", scale=args.scale, transform_pair=None)
-        pool = DevicePairPool((raw[i] for i in range(len(raw))), args.lr_patch, scale_int, device=device,
-                              shard_bytes=(args.gpu_data_shard_mb << 20) or None, augment=args.augment)
-        train_loader = sampler = DevicePoolLoader(pool, args.batch_size, rank, world, args.seed)
-        if rank == 0:
-            print(f"[gpu_data] {len(pool)} pairs in {pool.num_shards} shard(s), {sum(t.numel() for t in pool._host) / 2**20:.1f} MiB decoded")
-    valid_loader = make_loader(valid_ds, max(1, args.batch_size // 2), args.workers, pin=not args.no_pin, shuffle=False,
-                               drop_last=False, persistent=not args.no_persistent)
-    if args.task != "sr":
-        valid_loader = RestoreBatches(valid_loader, args.channels, restore_spec(args), args.dn_bits, device)
-    if args.synth_lr:
-        valid_loader = SynthLRBatches(valid_loader, scale_int, args.synth_lr_bits, device, degrade=degrade_spec(args), jpeg=jpeg_spec(args),
-                                      jpeg_subsample=args.jpeg_subsample == "420", psf=psf_spec(args), second_order=second_order_spec(args),
-                                      usm=usm_spec(args))
+    specs = train_specs(args)          # the run's degradation specs, built once: the pool, the validation wrapper and the lines share them
+    train_loader, sampler, valid_loader, lines = build_loaders(args, specs, scale_int, device, rank, world)
+    for line in lines if rank == 0 else ():
+        print(line)
 
     if args.task != "sr":
         model = build_restoration_model(args.task, args.channels, args.drop_path_rate, args.window_size)
@@ -743,10 +436,8 @@ def main(argv=None):
     if small:
         model.enable_small_window_training()          # before the optimizer is constructed: the model steps on the multi-tensor path
     if args.weights:
-        ckpt = torch.load(args.weights, map_location="cpu", weights_only=True)
-        state = ckpt
-        if isinstance(ckpt, dict):          # envelopes, in this order; 'params_ema' is what published HAT / DAT files hold
-            state = next((ckpt[k] for k in ("params", "model", "params_ema") if k in ckpt), ckpt)
+        from .evaluate import _load_state          # envelopes, in this script's order; 'params_ema' is what published HAT / DAT files hold
+        state, _ = _load_state(args.weights, keys=("params", "model", "params_ema"))
         missing, unexpected = model.load_state_dict(state, strict=True)
         if rank == 0:
             print(f"[weights] loaded: {args.weights}")
@@ -802,8 +493,6 @@ def main(argv=None):
 
     predict = None
     if args.val_tile:
-        from functools import partial
-
         from .tiling import tiled_forward
         predict = partial(tiled_forward, model, tile=args.val_tile, overlap=args.val_tile_overlap)
         if rank == 0:
@@ -811,7 +500,6 @@ def main(argv=None):
 
     validate_fn, val_border = validate, None          # without --val_bench_metric: the validation call of ever
     if args.val_bench_metric is not None:
-        from functools import partial
         val_border = scale_int if args.val_crop_border is None else args.val_crop_border
         validate_fn = partial(validate_bench, bench_metric=args.val_bench_metric, crop_border=val_border)
 
@@ -821,10 +509,7 @@ def main(argv=None):
             sampler.set_epoch(epoch)
         tr_loss, tr_t = train_one_epoch(model, train_loader, opt, device, dp if world > 1 else None, graphed=graphed,
                                         freeze_bn=args.freeze_bn, loss_fn=loss_fn)
-        if args.ema_decay:          # validate what gets shipped: the averaged weights (ranks hold identical averages)
-            with opt.swap_ema():
-                val = validate_fn(model, valid_loader, device, with_ssim=with_ssim, predict=predict)
-        else:
+        with opt.swap_ema() if args.ema_decay else nullcontext():          # validate what gets shipped: the averaged weights (the same on every rank)
             val = validate_fn(model, valid_loader, device, with_ssim=with_ssim, predict=predict)
         val_loss, val_psnr, val_t = val[0], val[1], val[-1]
         if sched is not None:
