@@ -532,6 +532,29 @@ int srk_tile_gather_f32(const float* x, float* tiles, int t0, int n, int B, int 
                         srk_stream_t stream);
 int srk_tile_merge_f32(const float* tiles, float* out, int t0, int n, int B, int C, int Ho, int Wo, int th, int tw, int sy, int sx,
                        int mode, srk_stream_t stream);
+/* Image files to and from the device (csrc/image_io.hip): B images of one size, interleaved 8- or 16-bit samples as a decoder
+ * delivers them <-> planar fp32 in [0, 1] as the models take it.  One launch each, no host read, no upload: capturable.
+ * srk_image_unpack: src [B][H][W][in_chans] of uint8 (bits 8) or uint16 in host byte order (bits 16) -> dst fp32 [B][out_chans][H][W],
+ *   out_chans 1 or 3; value = (float)s / 255.0f or / 65535.0f as an IEEE division (the convention of srk_paired_crop_u8).
+ *   in_chans 1 | 2 (gray, gray + alpha): the gray sample, once or three times; in_chans 3 | 4 (RGB, RGB + alpha): R, G, B at out_chans 3,
+ *   the integer luma (4899 R + 9617 G + 1868 B + 8192) >> 14 of the stored samples at out_chans 1.  The last sample of in_chans 2 | 4 is
+ *   alpha: it goes to alpha fp32 [B][1][H][W] when that pointer is non-null and is dropped otherwise (alpha is ignored at in_chans 1 | 3).
+ *   src needs no alignment beyond that of a sample.
+ * srk_image_pack: y fp32 [B][chans][H][W], chans 1 or 3 (+ alpha fp32 [B][1][H][W]) -> dst [B][H][W][out_chans] samples.
+ *   q(v), max = 255 or 65535: NaN -> 0, v <= 0 -> 0 (-0.0 and -Inf too), v >= 1 -> max, else rintf(v * max): one fp32 product, rounded
+ *   half-to-even -- the (x * 255).round() of the public test scripts, not a truncation.
+ *   out_chans 1: gray -- with chans 3 the integer luma above of the QUANTISED R, G, B (at either depth); 2: gray + q(alpha);
+ *   3: RGB -- with chans 1 the sample three times; 4: RGB + q(alpha).  alpha is read at out_chans 2 | 4 only.
+ *   counters: null, or DEVICE uint32[2] that the launch ADDS to -- [0] the non-finite input values, [1] the finite ones outside
+ *   [0, 1], over y and (at out_chans 2 | 4) alpha.  Integer sums: exact, whatever the order.
+ * Nothing outside dst[0 .. B*H*W*out_chans) samples (and alpha[0 .. B*H*W)) is written.  Checked on the host before any launch, in
+ * this order: SRK_E_SHAPE -- B, H or W < 1, B > 65535, in_chans outside 1..4, chans not 1 or 3, bits not 8 or 16, out_chans not
+ * 1 or 3 (unpack) / outside 1..4 (pack); SRK_E_NULL -- null src / dst / y, null alpha at out_chans 2 | 4 of pack; SRK_E_ALIGN -- an odd
+ * src (unpack) or dst (pack) at 16 bits, an fp32 array or counters not 4-byte aligned. */
+int srk_image_unpack(const void* src, float* dst, float* alpha, int B, int H, int W, int in_chans, int bits, int out_chans,
+                     srk_stream_t stream);
+int srk_image_pack(const float* y, const float* alpha, void* dst, uint32_t* counters, int B, int H, int W, int chans, int out_chans,
+                   int bits, srk_stream_t stream);
 /* Validation metrics of one batch in one pass (first slice): per-image PSNR of the images clamped to [0, 1]
  * (batch_psnr, finetune_swinir.py:69-74: 20 log10(max_val / sqrt(mse + 1e-8)), mse over the per_image = C*H*W elements of an
  * image) and the sum of |pred - target| over the batch for the validation L1 (F.l1_loss, :66-67, used by validate :181-207).

@@ -759,6 +759,32 @@ int srk_tile_merge_f32(const float* tiles, float* out, int t0, int n, int B, int
   return srk_launch_tile_merge_f32(tiles, out, t0, n, B * C, ay, ax, mode, (hipStream_t)stream);
 }
 
+int srk_image_unpack(const void* src, float* dst, float* alpha, int B, int H, int W, int in_chans, int bits, int out_chans,
+                     srk_stream_t stream) {
+  SRK_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && W >= 1, SRK_E_SHAPE, "image_unpack: B must be in 1..65535 and H, W >= 1 (got B=%d H=%d W=%d)",
+              B, H, W);
+  SRK_REQUIRE(in_chans >= 1 && in_chans <= 4 && (bits == 8 || bits == 16) && (out_chans == 1 || out_chans == 3), SRK_E_SHAPE,
+              "image_unpack: in_chans must be in 1..4, bits 8 or 16, out_chans 1 or 3 (got %d, %d, %d)", in_chans, bits, out_chans);
+  REQ_PTR(src); REQ_PTR(dst);
+  SRK_REQUIRE(bits == 8 || srk_aligned(src, 2), SRK_E_ALIGN, "image_unpack: 16-bit samples at an odd address");
+  SRK_REQUIRE(srk_aligned(dst, 4) && srk_aligned(alpha, 4), SRK_E_ALIGN, "image_unpack: 'dst' / 'alpha' is not 4-byte aligned");
+  return srk_launch_image_unpack(src, dst, alpha, B, H, W, in_chans, bits, out_chans, (hipStream_t)stream);
+}
+
+int srk_image_pack(const float* y, const float* alpha, void* dst, uint32_t* counters, int B, int H, int W, int chans, int out_chans,
+                   int bits, srk_stream_t stream) {
+  SRK_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && W >= 1, SRK_E_SHAPE, "image_pack: B must be in 1..65535 and H, W >= 1 (got B=%d H=%d W=%d)",
+              B, H, W);
+  SRK_REQUIRE((chans == 1 || chans == 3) && out_chans >= 1 && out_chans <= 4 && (bits == 8 || bits == 16), SRK_E_SHAPE,
+              "image_pack: chans must be 1 or 3, out_chans in 1..4, bits 8 or 16 (got %d, %d, %d)", chans, out_chans, bits);
+  REQ_PTR(y); REQ_PTR(dst);
+  SRK_REQUIRE((out_chans & 1) || alpha != nullptr, SRK_E_NULL, "image_pack: out_chans %d needs 'alpha'", out_chans);
+  SRK_REQUIRE(bits == 8 || srk_aligned(dst, 2), SRK_E_ALIGN, "image_pack: 16-bit samples at an odd address");
+  SRK_REQUIRE(srk_aligned(y, 4) && srk_aligned(alpha, 4) && srk_aligned(counters, 4), SRK_E_ALIGN,
+              "image_pack: 'y' / 'alpha' / 'counters' is not 4-byte aligned");
+  return srk_launch_image_pack(y, alpha, dst, counters, B, H, W, chans, out_chans, bits, (hipStream_t)stream);
+}
+
 int64_t srk_batch_psnr_workspace(int64_t per_image, int B) {
   if (per_image <= 0 || B <= 0) return 0;
   return (int64_t)2 * sizeof(float) * B * srk_batch_psnr_chunks(per_image);

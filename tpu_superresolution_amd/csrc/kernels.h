@@ -105,6 +105,11 @@ inline int srk_tile_origin(const TileAxis& a, int i) { const long long o = (long
 int srk_launch_tile_gather_f32(const float* x, float* tiles, int t0, int n, int planes, TileAxis ay, TileAxis ax, hipStream_t stream);
 int srk_launch_tile_merge_f32(const float* tiles, float* out, int t0, int n, int planes, TileAxis ay, TileAxis ax, int mode,
                               hipStream_t stream);
+// image_io.hip: interleaved 8- / 16-bit samples <-> planar fp32 (arguments checked by srk_image_unpack / srk_image_pack)
+int srk_launch_image_unpack(const void* src, float* dst, float* alpha, int B, int H, int W, int in_chans, int bits, int out_chans,
+                            hipStream_t stream);
+int srk_launch_image_pack(const float* y, const float* alpha, void* dst, unsigned* counters, int B, int H, int W, int chans, int out_chans,
+                          int bits, hipStream_t stream);
 int srk_launch_batch_psnr(const float* pred, const float* target, float* partial, int B, long long per_image, float max_val,
                           float* psnr, float* psnr_sum, float* abs_sum, hipStream_t stream);
 int srk_launch_zero_f32(float* p, long long n, hipStream_t stream);      // graph-safe zero fill (misc.hip)

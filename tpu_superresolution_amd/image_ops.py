@@ -1,6 +1,6 @@
 """The image-processing ops of the on-device data path: resizes, blurs and filters, noise, JPEG, unsharp mask, and the degradations
-composed of them.  Thin torch wrappers over libsrk.so like ops.py, which re-exports every public name here:
-`ops.<name>` stays the public spelling.
+composed of them, and the conversion between decoded image files and fp32 batches (7v).  Thin torch wrappers over
+libsrk.so like ops.py, which re-exports every public name here: `ops.<name>` stays the public spelling.
 
 One shape for every op: `_batch` tests the tensor, one helper tests each further argument (`_quant_bits`, `_factor_crop`, `_padded_out`,
 `_ids_and_grays`, `_qualities`, `_ragged`), the small tables go up in one `torch.tensor(...).to(device)` each, and ONE `check(lib()...)`
@@ -21,7 +21,8 @@ from ._lib import SrkUnsupported, _p, _stream, check, lib
 __all__ = ["resize_aa", "degrade_aa", "BLUR_SIGMA_MAX", "pack_degrade_params", "degrade_blind", "pack_psf", "DeviceTables", "kernel_tables", "blur2d",
            "degrade_psf", "check_jpeg_quality", "jpeg_roundtrip", "pack_restore_params", "noise", "restore_degrade", "RaggedExt",
            "pack_filter_tables", "filter2d", "resize_aa_ragged", "RESIZE_MODES", "resize_ragged", "usm_ks", "usm_taps", "usm_sharpen",
-           "jpeg_roundtrip_ragged", "SecondOrder", "second_order_sizes", "second_order_noise_ids", "degrade_second_order", "LUMA_COEF", "to_gray"]
+           "jpeg_roundtrip_ragged", "SecondOrder", "second_order_sizes", "second_order_noise_ids", "degrade_second_order", "LUMA_COEF", "to_gray",
+           "image_unpack", "image_pack"]
 
 
 # ---- the argument checks every op shares ---------------------------------------------------------------------------------------------
@@ -669,3 +670,122 @@ def to_gray(x):
     v = a.astype(np.uint32)          # 16384 * 65535 + 8192 < 2^32
     y = ((LUMA_COEF[0] * v[..., 0] + LUMA_COEF[1] * v[..., 1] + LUMA_COEF[2] * v[..., 2] + 8192) >> 14).astype(a.dtype)
     return torch.from_numpy(y) if is_t else y
+
+
+# ---- image files to and from the device (csrc/image_io.hip) -----------------------------------------------------------------
+_SAMPLE_MAX = {torch.uint8: 255, torch.uint16: 65535}
+
+
+def _samples_i32(a: torch.Tensor) -> torch.Tensor:
+    """Stored samples as int32 (torch has little arithmetic on uint16: its bits are read as int16 and the sign is undone)."""
+    return a.to(torch.int32) if a.dtype == torch.uint8 else a.view(torch.int16).to(torch.int32) & 0xFFFF
+
+
+def _luma_i32(r, g, b):
+    """`to_gray` on int32 samples: 16384 * 65535 + 8192 needs 31 bits, so the sum is formed in int64."""
+    y = (LUMA_COEF[0] * r.to(torch.int64) + LUMA_COEF[1] * g.to(torch.int64) + LUMA_COEF[2] * b.to(torch.int64) + 8192) >> 14
+    return y.to(torch.int32)
+
+
+def image_unpack(a: torch.Tensor, out_chans: int, want_alpha: bool = False):
+    """Decoded image samples -> (x, alpha | None): a uint8 / uint16 [B,H,W,ch], [H,W,ch] or [H,W] (ch 1..4: gray, gray + alpha, RGB,
+    RGB + alpha; a 3-D tensor is one image) -> x fp32 [B,out_chans,H,W] in [0, 1] (B = 1 for one image), out_chans 1 | 3.
+    Value = sample / 255 or / 65535 as an IEEE fp32 division -- the bits of `pil_to_tensor01`; gray is repeated into three channels
+    (`ensure_3ch`), RGB becomes one channel by the integer luma of the stored samples (`to_gray`, as `clean_to_tensor`).  want_alpha: the
+    last sample of ch 2 | 4 as fp32 [B,1,H,W] (None for ch 1 | 3, and when not asked for).  A CUDA tensor is one launch
+    (srk_image_unpack), capturable; a CPU tensor runs the same arithmetic in torch."""
+    if not isinstance(a, torch.Tensor) or a.dtype not in _SAMPLE_MAX:
+        raise ValueError(f"image_unpack takes a uint8 or uint16 tensor (got {getattr(a, 'dtype', type(a))})")
+    if out_chans not in (1, 3):
+        raise ValueError(f"image_unpack: out_chans must be 1 or 3 (got {out_chans!r})")
+    if a.dim() == 2:
+        a = a[None, :, :, None]
+    elif a.dim() == 3:
+        a = a[None]
+    if a.dim() != 4 or not 1 <= a.shape[3] <= 4 or min(a.shape) < 1:
+        raise ValueError(f"image_unpack takes non-empty [B,H,W,ch], [H,W,ch] or [H,W] samples with ch in 1..4 (got {tuple(a.shape)})")
+    B, H, W, ch = a.shape
+    has_alpha = bool(want_alpha) and ch in (2, 4)
+    if a.is_cuda:
+        a = a.contiguous()
+        x = torch.empty((B, out_chans, H, W), dtype=torch.float32, device=a.device)
+        alpha = torch.empty((B, 1, H, W), dtype=torch.float32, device=a.device) if has_alpha else None
+        check(lib().srk_image_unpack(_p(a), _p(x), _p(alpha), B, H, W, ch, 8 * a.element_size(), out_chans, _stream()))
+        return x, alpha
+    s = _samples_i32(a)
+    mx = float(_SAMPLE_MAX[a.dtype])
+    if ch <= 2:
+        planes = [s[..., 0]] * out_chans
+    elif out_chans == 3:
+        planes = [s[..., 0], s[..., 1], s[..., 2]]
+    else:
+        planes = [_luma_i32(s[..., 0], s[..., 1], s[..., 2])]
+    x = torch.stack(planes, 1).to(torch.float32) / mx
+    alpha = (s[..., ch - 1].to(torch.float32) / mx).unsqueeze(1) if has_alpha else None
+    return x.contiguous(), alpha
+
+
+def _quantise_i32(v: torch.Tensor, mx: int) -> torch.Tensor:
+    """q(v): NaN -> 0, v <= 0 -> 0, v >= 1 -> max, else round-half-to-even of the fp32 product v * max."""
+    q = torch.round(v * float(mx))                                          # NaN stays NaN here and fails `v > 0` below
+    q = torch.where(v >= 1.0, torch.full_like(q, float(mx)), q)
+    return torch.where(v > 0.0, q, torch.zeros_like(q)).to(torch.int32)
+
+
+def image_pack(y: torch.Tensor, alpha: Optional[torch.Tensor] = None, out_chans: Optional[int] = None, bits: int = 8,
+               counters: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A prediction as file samples: y fp32 [B,C,H,W] (or [C,H,W]: one image), C 1 | 3, + alpha fp32 [B,1,H,W] -> uint8 (bits 8) or
+    uint16 (bits 16) [B,H,W,out_chans] ([H,W,out_chans] for one image).  out_chans 1 gray, 2 gray + alpha, 3 RGB, 4 RGB + alpha (default: C,
+    plus 1 with an alpha).  Samples are q(v) = rint(v * max) of the clamped value (NaN -> 0): the `(x * 255).round()` of the public test
+    scripts, not the truncation of `evaluate.save_tensor_as_png`; RGB -> gray is the integer luma (`to_gray`) of the QUANTISED samples,
+    gray -> RGB repeats the sample.  counters: an int32 [2] tensor on y's device that the call ADDS to -- [0] the non-finite input values,
+    [1] the finite ones outside [0, 1] (y, and alpha where it is written).  A CUDA tensor is one launch (srk_image_pack), capturable;
+    a CPU tensor runs the same arithmetic in torch."""
+    if not isinstance(y, torch.Tensor) or y.dtype != torch.float32 or y.dim() not in (3, 4):
+        raise ValueError(f"image_pack takes an fp32 [B,C,H,W] or [C,H,W] tensor (got {getattr(y, 'dtype', type(y))} "
+                         f"{tuple(getattr(y, 'shape', ()))})")
+    single = y.dim() == 3
+    if single:
+        y = y[None]
+        alpha = alpha[None] if (alpha is not None and alpha.dim() == 3) else alpha
+    B, C, H, W = y.shape
+    if C not in (1, 3) or min(B, H, W) < 1:
+        raise ValueError(f"image_pack takes a non-empty batch with C 1 or 3 (got {tuple(y.shape)})")
+    if out_chans is None:
+        out_chans = C + (alpha is not None)
+    if out_chans not in (1, 2, 3, 4):
+        raise ValueError(f"image_pack: out_chans must be in 1..4 (got {out_chans!r})")
+    if bits not in (8, 16):
+        raise ValueError(f"image_pack: bits must be 8 or 16 (got {bits!r})")
+    with_alpha = out_chans in (2, 4)
+    if with_alpha and alpha is None:
+        raise ValueError(f"image_pack: out_chans {out_chans} needs an alpha plane")
+    if alpha is not None and (alpha.dtype != torch.float32 or tuple(alpha.shape) != (B, 1, H, W) or alpha.device != y.device):
+        raise ValueError(f"image_pack: alpha must be fp32 {(B, 1, H, W)} on {y.device} (got {alpha.dtype} {tuple(alpha.shape)} on {alpha.device})")
+    if counters is not None and (counters.dtype != torch.int32 or tuple(counters.shape) != (2,) or counters.device != y.device or
+                                 not counters.is_contiguous()):
+        raise ValueError(f"image_pack: counters must be a contiguous int32 [2] tensor on {y.device}")
+    dtype = torch.uint8 if bits == 8 else torch.uint16
+    if y.is_cuda:
+        y = y.contiguous()
+        a = alpha.contiguous() if with_alpha else None
+        out = torch.empty((B, H, W, out_chans), dtype=dtype, device=y.device)
+        check(lib().srk_image_pack(_p(y), _p(a), _p(out), _p(counters), B, H, W, C, out_chans, bits, _stream()))
+        return out[0] if single else out
+    mx = _SAMPLE_MAX[dtype]
+    vals = [y] + ([alpha] if with_alpha else [])
+    if counters is not None:
+        fin = [torch.isfinite(v) for v in vals]
+        counters += torch.tensor([sum(int((~f).sum()) for f in fin), sum(int((f & ((v < 0) | (v > 1))).sum()) for f, v in zip(fin, vals))],
+                                 dtype=torch.int32)
+    q = _quantise_i32(y, mx)
+    if out_chans <= 2:
+        chans = [_luma_i32(q[:, 0], q[:, 1], q[:, 2]) if C == 3 else q[:, 0]]
+    else:
+        chans = [q[:, c if C == 3 else 0] for c in range(3)]
+    if with_alpha:
+        chans.append(_quantise_i32(alpha, mx)[:, 0])
+    s = torch.stack(chans, -1)
+    out = s.to(torch.uint8) if bits == 8 else (s - ((s >= 32768).to(torch.int32) << 16)).to(torch.int16).view(torch.uint16)
+    out = out.contiguous()
+    return out[0] if single else out
