@@ -1141,7 +1141,9 @@ int srk_swinir_pack(srk_swinir_plan* plan, const float* params, void* packed, sr
 size_t srk_swinir_workspace_bytes(const srk_swinir_plan* plan, int B, int H0, int W0, int training);
 
 /* x fp32 NCHW [B][in_chans][H0][W0] in [0,1]  ->  y fp32 NCHW [B][in_chans][H0*s][W0*s].
- * training != 0 keeps the activations the backward needs in `workspace`.
+ * training != 0 keeps the activations the backward needs in `workspace`.  The one-step head (SRK_UPSAMPLER_PIXELSHUFFLEDIRECT) takes
+ * upscale^2 * in_chans <= 64 (plan_create refuses more); past 16 it is inference-only: training != 0, and srk_swinir_backward,
+ * return SRK_E_UNSUPPORTED before anything is launched.
  * drop_scale: null, or fp32 [n_blocks][2][B] per-sample DropPath factors (0 or 1/keep) for the
  * attention and MLP residual branches (timm DropPath in SwinTransformerBlock :276-277). */
 int srk_swinir_forward(srk_swinir_plan* plan, const float* params, const void* packed, const float* x, float* y,

@@ -4,7 +4,7 @@
 //
 // One 256-thread workgroup (4 waves as 2(M) x 2(N)) owns a 128 x BN output tile, BN = 32*NT
 // (NT = n-tiles of 16 per wave: 6/4/2 -> BN 192/128/64); a narrow variant (4 waves x 32 rows x 16
-// cols) serves N == 16 (3-channel image heads).  K is consumed in 64-wide chunks staged through
+// cols) serves N == 16 (3-channel image heads; the one-step upsample head runs N / 16 <= 4 of its n-blocks).  K is consumed in 64-wide chunks staged through
 // LDS with a register-staged double buffer (global->VGPR issued before the MFMA block of the
 // current chunk, VGPR->LDS after it, one barrier per chunk).  LDS tiles are [rows][64] bf16 with
 // the 16-byte chunk index XOR-swizzled by (row & 7), which makes every ds_read_b128 fragment read
@@ -428,7 +428,9 @@ int srk_launch_gemm(int loader, int epilogue, const GemmParams& p, hipStream_t s
   CASE(LD_CONV3_PS, EP_DLRELU)
 #undef CASE
   if (loader == LD_CONV3 && epilogue == EP_IMG && p.N == 16) return launch<LD_CONV3, EP_IMG, 1, true>(p, stream);
-  if (loader == LD_CONV3 && epilogue == EP_PS_IMG && p.N == 16) return launch<LD_CONV3, EP_PS_IMG, 1, true>(p, stream);
+  // one-step upsample head: N = round_up(upscale^2 * in_chans, 16) <= 64 runs as N / 16 n-blocks of the same narrow instance
+  // (n-block fastest in the tile order, so the blocks of one M-tile re-read its A rows from the XCD's L2)
+  if (loader == LD_CONV3 && epilogue == EP_PS_IMG && p.N % 16 == 0 && p.N <= 64) return launch<LD_CONV3, EP_PS_IMG, 1, true>(p, stream);
   srk_set_error("gemm: unsupported loader/epilogue combination %d/%d (N=%d)", loader, epilogue, p.N);
   return SRK_E_UNSUPPORTED;
 }

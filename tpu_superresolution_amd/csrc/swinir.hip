@@ -464,6 +464,11 @@ int run_conv(const Ctx& c, const ConvW& cw, int loader, int ep, const bf16_t* in
   return srk_launch_gemm(loader, ep, g, c.stream);
 }
 
+// one-step head wider than the 16 output channels the backward's small-conv kernels are built for: inference only
+bool wide_direct_head(const srk_swinir_plan* p) {
+  return p->cfg.upsampler == SRK_UPSAMPLER_PIXELSHUFFLEDIRECT && p->up_direct.Cout > 16;
+}
+
 }  // namespace
 
 extern "C" {
@@ -496,8 +501,8 @@ int srk_swinir_plan_create(const srk_swinir_config* cfg, srk_swinir_plan** out) 
       return SRK_E_SHAPE;
     }
   } else if (cfg->upsampler == SRK_UPSAMPLER_PIXELSHUFFLEDIRECT) {
-    SRK_REQUIRE(s >= 1 && s * s * cfg->in_chans <= 16, SRK_E_UNSUPPORTED,
-                "HIP 'pixelshuffledirect' path supports upscale^2 * in_chans <= 16 (got %d)", s * s * cfg->in_chans);
+    SRK_REQUIRE(s >= 1 && s * s * cfg->in_chans <= 64, SRK_E_UNSUPPORTED,
+                "HIP 'pixelshuffledirect' path supports upscale^2 * in_chans <= 64 (got %d)", s * s * cfg->in_chans);
   } else if (cfg->upsampler == SRK_UPSAMPLER_NEAREST_CONV) {
     // the reference applies conv_up1 always and conv_up2 only for upscale == 4 (network_swinir.py:831-834): x2 or x4
     SRK_REQUIRE(s == 2 || s == 4, SRK_E_UNSUPPORTED, "'nearest+conv' upsamples by 2 or 4 (got %d)", s);
@@ -607,7 +612,8 @@ int srk_swinir_plan_create(const srk_swinir_config* cfg, srk_swinir_plan** out) 
     }
     add_conv(p, p->conv_last, "conv_last", cfg->in_chans, 64, 16, 64, 1, 64, false);
   } else {
-    add_conv(p, p->up_direct, "upsample.0", s * s * cfg->in_chans, C, 16, CP, 1, 64, false);
+    // one-step head: 16 output columns per n-block of the narrow image-head kernel, up to four blocks (inference only past 16)
+    add_conv(p, p->up_direct, "upsample.0", s * s * cfg->in_chans, C, round_up(s * s * cfg->in_chans, 16), CP, 1, 64, false);
   }
   finish_group(p);
   *out = p;
@@ -920,6 +926,9 @@ int srk_swinir_forward(srk_swinir_plan* plan, const float* params, const void* p
   PlanOptionScope opts(plan);
   SRK_REQUIRE(B > 0 && H0 > 0 && W0 > 0, SRK_E_SHAPE, "forward: bad shape B=%d H=%d W=%d", B, H0, W0);
   srk_swinir_plan* p = plan;
+  SRK_REQUIRE(!(training && wide_direct_head(p)), SRK_E_UNSUPPORTED,
+              "forward: a 'pixelshuffledirect' head with upscale^2 * in_chans = %d > 16 is inference-only (the backward's small-conv "
+              "kernels cover 16 output channels); call with training = 0", p->up_direct.Cout);
   Workspace& w = p->ws;
   if (w.B != B || w.H0 != H0 || w.W0 != W0 || w.training != training || w.opt_sig != layout_option_sig())
     layout_workspace(p, w, B, H0, W0, training);
@@ -1093,6 +1102,8 @@ int srk_swinir_backward(srk_swinir_plan* plan, const float* params, const void* 
   SRK_REQUIRE(plan && params && packed && grads && d_y && workspace, SRK_E_NULL, "backward: null argument");
   PlanOptionScope opts(plan);
   srk_swinir_plan* p = plan;
+  SRK_REQUIRE(!wide_direct_head(p), SRK_E_UNSUPPORTED,
+              "backward: a 'pixelshuffledirect' head with upscale^2 * in_chans = %d > 16 is inference-only", p->up_direct.Cout);
   Workspace& w = p->ws;
   SRK_REQUIRE(w.B == B && w.H0 == H0 && w.W0 == W0 && w.training == 1, SRK_E_STATE,
               "backward: no matching training forward (have B=%d %dx%d training=%d)", w.B, w.H0, w.W0, w.training);

@@ -10,7 +10,7 @@ kernels behind the C ABI of ``include/srk.h``.  There is no CPU path: a CPU tens
 
 Covered by the HIP path: window_size 8, head_dim <= 32, embed_dim <= 256, in_chans 1/3, resi_connection '1conv' and
 '3conv', patch_norm=True, ape (at img_size), use_checkpoint, all four heads -- 'pixelshuffle' (x2/x3/x4/x8), 'pixelshuffledirect'
-(upscale^2 * in_chans <= 16), 'nearest+conv' (x2/x4) and '' (denoising, upscale 1) -- and ``forward_features`` as a callable
+(upscale^2 * in_chans <= 64 for inference, <= 16 for training), 'nearest+conv' (x2/x4) and '' (denoising, upscale 1) -- and ``forward_features`` as a callable
 (inference).  window_size 16 runs INFERENCE through the 256-token window attention of the HAT path (``swinir_w16.py``; the two
 pixel-shuffle heads, '1conv').  window_size 2..7 -- 7 is this constructor's default and the window of the SwinIR JPEG-artifact
 models -- runs INFERENCE through the same sequence with the small-window attention kernel (csrc/attn_small.hip; heads
@@ -455,12 +455,15 @@ class SwinIR(nn.Module):
                                      "model.enable_small_window_training())")
             from . import swinir_w16
             return swinir_w16.forward(self, x)
+        anchor = next((p for p in self.parameters() if p.requires_grad), None)
+        needs_grad = torch.is_grad_enabled() and anchor is not None
+        if needs_grad and self.upsampler == 'pixelshuffledirect' and self.upscale ** 2 * self.in_chans > 16:
+            raise SrkUnsupported(f"SwinIR 'pixelshuffledirect' with upscale^2 * in_chans = {self.upscale ** 2 * self.in_chans} > 16 on the HIP "
+                                 "path is inference-only: call it under torch.no_grad() (the backward's head kernels cover 16 output channels)")
         eng = self._bind(x.device)
         if not self._param_views_ok(eng):
             self._engine = None
             eng = self._bind(x.device)
-        anchor = next((p for p in self.parameters() if p.requires_grad), None)
-        needs_grad = torch.is_grad_enabled() and anchor is not None
         if self.training or needs_grad:
             eng.packed_valid = False          # parameters may have been stepped since the last call
             eng.pack_version = -1

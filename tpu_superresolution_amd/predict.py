@@ -1,7 +1,14 @@
 """Upscale image files that have no ground truth: the `--folder_lq` mode of the SwinIR test script, the HAT / DAT test configs without
 `dataroot_gt`, Real-ESRGAN's inference script.
 
-    python -m tpu_superresolution_amd.predict --input FILE|DIR --output DIR --arch swinir|hat|dat --scale X1|X2|X4 --ckpt F
+    python -m tpu_superresolution_amd.predict --input FILE|DIR --output DIR --arch swinir|hat|dat --scale X1|X2|X3|X4|X8 --ckpt F
+    python -m tpu_superresolution_amd.predict --input FILE|DIR --output DIR --arch auto --scale auto --ckpt F
+
+--arch auto: the checkpoint is the specification.  checkpoint_arch.build_from_state reads the family and the constructor
+keywords from the state_dict's key names and shapes, prints them on `[arch]` lines with the conventions it applied (img_range, HAT's
+conv_scale), and refuses what the HIP path does not cover with the package's own reason before anything runs.  --scale auto takes the
+file's scale; an explicit --scale must equal it.  --window_size, --task, --channels and --upsampler are refused (the file decides them);
+--img_range R overrides the img_range convention.  An explicit --arch builds one configuration per family, as before.
 
 Files: --input is one file or a directory (not recursive, sorted by name, only what PIL opens; anything else prints a `[skip]` line).
 Outputs are `<stem><--suffix, default _sr>.png` under --output; an output that would overwrite its input is refused.  Modes L, LA, RGB,
@@ -38,6 +45,7 @@ from . import ops
 from .data_cli import SCALES, default_window_size, flag, shared_flags
 from .evaluate import PARAM_KEYS, _load_state
 
+PREDICT_SCALES = dict(sorted({**SCALES, "X3": 3, "X8": 8}.items()))          # predict's own table: x3 for the three families, x8 for SwinIR (data_cli.SCALES is the training parsers')
 KEPT_MODES = ("L", "LA", "RGB", "RGBA", "I;16")          # kept as they are; every other mode is converted
 _CHANNELS = {"L": 1, "LA": 2, "RGB": 3, "RGBA": 4, "I;16": 1}
 _OUT_MODE = {1: "L", 2: "LA", 3: "RGB", 4: "RGBA"}
@@ -48,8 +56,12 @@ def parse_args(argv=None):
     ap.add_argument("--input", type=str, required=True, help="an image file, or a directory of them (not recursive, sorted by name)")
     ap.add_argument("--output", type=str, required=True, help="directory of the <stem><suffix>.png outputs (created)")
     ap.add_argument("--suffix", type=str, default="_sr", help="appended to the input's stem")
-    ap.add_argument("--arch", type=str, choices=["swinir", "hat", "dat"], required=True)
-    ap.add_argument("--scale", type=str, choices=list(SCALES), required=True, help="the model's scale; X1 with --task dn | car")
+    ap.add_argument("--arch", type=str, choices=["swinir", "hat", "dat", "auto"], required=True,
+                    help="auto: the constructor keywords are read from the checkpoint (checkpoint_arch.infer_arch)")
+    ap.add_argument("--scale", type=str, choices=[*PREDICT_SCALES, "auto"], required=True,
+                    help="the model's scale; X1 with --task dn | car; X8 with --arch swinir; auto (with --arch auto): the checkpoint's")
+    ap.add_argument("--img_range", type=float, default=None, metavar="R",
+                    help="with --arch auto: SwinIR(img_range=R) instead of the convention (255 for the scale-1 head at window 7, else 1.0)")
     ap.add_argument("--ckpt", type=str, required=True)
     ap.add_argument("--param_key", type=str, choices=["auto", *PARAM_KEYS], default="auto",
                     help="which envelope of the checkpoint to load (auto: model, then params, then params_ema)")
@@ -70,10 +82,27 @@ def parse_args(argv=None):
                     help="final size = input size x S (default: the model's scale): the fp32 prediction is resized with ops.resize_aa before it is quantised")
     ap.add_argument("--out_bits", type=str, choices=["auto", "8", "16"], default="auto", help="bit depth of the outputs (auto: the input's)")
     args = ap.parse_args(argv)
+    if args.img_range is not None and not (math.isfinite(args.img_range) and args.img_range > 0):
+        ap.error(f"--img_range must be a positive number (got {args.img_range})")
+    if args.arch == "auto":          # the file decides the model: its flags are refused off their defaults
+        given = [f"--{n} {getattr(args, n)}" for n, dflt in (("window_size", None), ("task", "sr"), ("channels", 3), ("upsampler", "pixelshuffle"))
+                 if getattr(args, n) != dflt]
+        if given:
+            ap.error(f"{', '.join(given)}: with --arch auto the checkpoint decides window_size, task, channels and upsampler")
+        args.window_size = default_window_size(args.task)
+    else:
+        if args.scale == "auto":
+            ap.error(f"--scale auto goes with --arch auto (--arch {args.arch} builds one configuration per scale: name it)")
+        if args.img_range is not None:
+            ap.error(f"--img_range is an option of --arch auto (--arch {args.arch} builds its configuration's own)")
+        if args.scale.upper() == "X8" and args.arch != "swinir":
+            ap.error(f"--scale X8 is an option of --arch swinir and --arch auto (got --arch {args.arch})")
+        if args.upsampler == "nearest+conv" and args.scale.upper() not in ("X2", "X4"):
+            ap.error(f"--upsampler nearest+conv upsamples by 2 or 4 (got --scale {args.scale})")
     if args.window_size is None:
         args.window_size = default_window_size(args.task)
     restore = args.task != "sr"
-    if restore != (args.scale.upper() == "X1"):
+    if args.arch != "auto" and restore != (args.scale.upper() == "X1"):
         ap.error(f"--task dn | car and --scale X1 go together (got --task {args.task} --scale {args.scale})")
     if restore and args.arch != "swinir":
         ap.error(f"--task {args.task} is an option of --arch swinir (got --arch {args.arch})")
@@ -303,14 +332,34 @@ def main(argv=None):
     print("[device]", device, torch.cuda.get_device_name(0) if device.type == "cuda" else "-")
     if device.type != "cuda":
         raise SystemExit(f"--arch {args.arch} runs on the MI355X HIP path only (no CPU fallback)")
-    scale_int = SCALES[args.scale.upper()]
-
-    model = build_model(args, scale_int)
-    state, msg = _load_state(args.ckpt, args.param_key)
-    model.load_state_dict(state, strict=True)
-    print(msg)
+    if args.arch == "auto":
+        model, scale_int = build_auto_model(args)
+    else:
+        scale_int = PREDICT_SCALES[args.scale.upper()]
+        model = build_model(args, scale_int)
+        state, msg = _load_state(args.ckpt, args.param_key)
+        model.load_state_dict(state, strict=True)
+        print(msg)
     model = model.to(device).eval()
     return run(model, args, scale_int, device)
+
+
+def build_auto_model(args, log: Callable = print):
+    """--arch auto: the model of checkpoint_arch.build_from_state on the state evaluate._load_state returns -> (model, scale).  Sets
+    args.channels to the file's in_chans (a scale-1 file thereby takes upscale()'s restoration path); an explicit --scale must be the file's.
+    Raises (SrkUnsupported, ValueError, SystemExit) before anything touches the GPU or the output directory."""
+    from .checkpoint_arch import build_from_state, format_call, infer_arch
+    state, msg = _load_state(args.ckpt, args.param_key)
+    log(msg)
+    file_scale = int(infer_arch(state).kwargs["upscale"])
+    if args.scale != "auto" and PREDICT_SCALES[args.scale.upper()] != file_scale:
+        raise SystemExit(f"--scale {args.scale} does not match the checkpoint: {args.ckpt} is a x{file_scale} model (name --scale X{file_scale} or --scale auto)")
+    model, spec = build_from_state(state, drop_path_rate=0.0, img_range=getattr(args, "img_range", None))
+    log(f"[arch] {spec.arch}: {format_call(spec)}")
+    for note in spec.notes:
+        log(f"[arch] note: {note}")
+    args.channels = int(spec.kwargs["in_chans"])
+    return model, file_scale
 
 
 def run(model, args, scale_int: int, device) -> dict:
