@@ -607,6 +607,45 @@ int srk_bench_planes_f32(const float* pred, const float* target, float* planes_p
                          int H, int W, int border, int mode, srk_stream_t stream);
 int srk_bench_psnr(const void* workspace, int B, int Cm, int Hc, int Wc, float* sqsum, float* psnr, float* psnr_sum,
                    srk_stream_t stream);
+/* No-reference quality (NIQE): Mittal et al., "Making a completely blind image quality analyzer", in the form of BasicSR's
+ * calculate_niqe, the score the Real-ESRGAN / BSRGAN / SwinIR real-SR papers print for files without ground truth.  Restated from the
+ * published algorithm: PARITY UNPINNED (neither BasicSR, pyiqa, OpenCV nor the MATLAB code is available to compare with); tests hold it
+ * against an independent fp64 restatement (tests/niqe_ref.py).  The device computes the four stages below; the AGGD fit, the
+ * 36-dimensional Gaussian and the distance are host fp64 (niqe.py).  One definition:
+ *   plane     x fp32 [B][C][H][W] in [0, 1], C 1 or 3.  q = rintf(c(x) * 255.0f), c the comparison clamp of srk_bench_planes_f32 (a NaN
+ *             stays).  C == 3: Y = rintf(16.0f + t / 255.0f), t the fma chain of srk_bench_planes_f32 (BasicSR rounds the luma); C == 1:
+ *             the plane is q.  `border` pixels are cropped on every side, then the top-left Hk x Wk is kept, Hk = floor((H - 2 border) /
+ *             bs) * bs, Wk likewise; bs is the block side (published: 96; any even bs >= 8).  The plane is integer-valued, 0..255.
+ *   half      scale 2 is the half-size antialiased cubic (a = -0.5) of the plane in the MATLAB imresize(., 0.5) convention: per axis
+ *             out[i] = sum_k T[k] in[2 i - 3 + k] / 256, T = [-3, -9, 29, 111, 111, 29, -9, -3], symmetric border (index -1-k -> k,
+ *             n+k -> n-1-k).  Both passes are formed in int32 (the plane holds integers: |S| <= 304^2 * 255, exact, so the order of the
+ *             passes does not show); out = (float)S * 2^-16, one rounding.  A plane that does not hold integers 0..255 gives no defined
+ *             value (and no fault: the samples are converted to int).
+ *   MSCN      under a 7 x 7 window w (49 fp32 taps in row-major order, device memory, not assumed separable; replicate border), in the
+ *             centred form: d = v - v_centre (exact); a = sum w d and b = sum w d^2 by fmaf over the taps in row-major order;
+ *             sigma = sqrtf(fabsf(b - a a)); m = -a / (sigma + 1.0f).  For sum w = 1 this is BasicSR's (v - mu) / (sqrt|E[v^2] - mu^2| + 1);
+ *             the naive form cancels at 255^2 in fp32 (max |dm| 7e-3 on smooth images against 2e-7 for the centred form).  One
+ *             divergence: on an exactly flat 7 x 7 neighbourhood m is exactly 0 (such a pixel counts on neither side below), where fp64
+ *             BasicSR yields +-1e-14 noise of either sign.
+ *   moments   blocks of bs x bs pixels (bs at scale 1, bs / 2 at scale 2: the same grid of nbh x nbw blocks).  Five maps per block: m, and
+ *             m * roll(m, s) for s = (0,1), (1,0), (1,1), (1,-1), the roll circular inside the block (np.roll of the block), each product
+ *             one fp32 multiply.  Per map five numbers: count of p < 0, sum of p^2 over p < 0, count of p > 0, sum of p^2 over p > 0,
+ *             sum of |p| -> mom fp32 [B][nbh nbw][5][5].  Sums are fp32 in a fixed order, no atomics: two runs give equal bits.  sharp
+ *             fp32 [B][nbh nbw]: the block mean of sigma (what the pristine fit selects blocks by).
+ * srk_niqe_plane_f32: x -> plane fp32 [B][Hk][Wk].  srk_niqe_half_f32: plane fp32 [B][H][W], H and W even and >= 4 -> half fp32
+ * [B][H/2][W/2].  srk_niqe_mscn_f32: plane [B][H][W], any H, W >= 1 -> mscn and (nullable) sigma, fp32 [B][H][W].
+ * srk_niqe_moments_f32: mscn (and sigma, nullable together with sharp) [B][H][W], H and W multiples of bs; bs in 4..4096 here, any parity
+ * (the scale-2 call passes half of an even block side >= 8; counts stay exact in fp32).  No workspace; nothing outside the stated outputs
+ * is written; the library allocates nothing.
+ * SRK_E_NULL: a null pointer (sigma without sharp or sharp without sigma included).  SRK_E_SHAPE: B outside 1..65535, an extent outside
+ * 1..2^20, C not 1 or 3, border < 0, bs odd or < 8 (plane; outside 4..4096 for moments), H or W odd or < 4 (half), H or W not a multiple
+ * of bs (moments), a grid that does not fit, an output overlapping another buffer.  SRK_E_UNSUPPORTED: fewer than one block (plane:
+ * after the border crop; moments: H or W < bs). */
+int srk_niqe_plane_f32(const float* x, float* plane, int B, int C, int H, int W, int border, int bs, srk_stream_t stream);
+int srk_niqe_half_f32(const float* plane, float* half, int B, int H, int W, srk_stream_t stream);
+int srk_niqe_mscn_f32(const float* plane, const float* win49, float* mscn, float* sigma, int B, int H, int W, srk_stream_t stream);
+int srk_niqe_moments_f32(const float* mscn, const float* sigma, float* mom, float* sharp, int B, int H, int W, int bs,
+                         srk_stream_t stream);
 /* sum of squares of a flat fp32 gradient, ACCUMULATED into sumsq[0] (for clip_grad_norm_ :170) */
 int srk_grad_sumsq(const float* grads, int64_t n, float* sumsq, srk_stream_t stream);
 /* clip_grad_norm_(max_norm) + AdamW step (:168-171, :303) on flat fp32 buffers.  The clip coefficient is

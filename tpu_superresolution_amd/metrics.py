@@ -13,6 +13,9 @@
                  luma or RGB, 0..255 scale, per image; include/srk.h) -> ``srk_bench_planes_f32`` / ``srk_bench_psnr`` and
                  ``srk_ssim`` on the planes; its SSIM shares the restatement above, parity with the third-party test scripts unpinned.
 
+``niqe``         nothing in the reference: the no-reference score of the real-SR papers (BasicSR's calculate_niqe restated, **parity
+                 unpinned**; niqe.py, include/srk.h) -> ``srk_niqe_*`` stages on the device, AGGD fit and distance in host fp64.
+
 CPU tensors use the torch-operator forms below (evaluate.py / train.py run BASELINE cfg1 on the CPU).  fp32 GPU tensors go to
 the libsrk kernels: ``psnr`` -> ``srk_eval_psnr``, ``batch_psnr`` -> ``srk_batch_psnr``, ``ssim`` (4-D,
 H, W >= 11, default window) -> ``srk_ssim`` (csrc/metrics.hip, csrc/misc.hip): one fused pass, fixed-order sums, no per-pixel
@@ -22,6 +25,9 @@ from __future__ import annotations
 
 import torch
 import torch.nn.functional as F
+
+from .niqe import (load_niqe_params, niqe, niqe_distance, niqe_features, niqe_fit, niqe_moments,          # noqa: F401  no-reference
+                   save_niqe_params)                                                                       # quality (niqe.py)
 
 
 def _on_device(*ts) -> bool:

@@ -27,6 +27,11 @@ optional resize, one pack launch (ops.image_pack: clamp, x max, round-half-to-ev
 one download of the packed samples and one read of the two counters.  A non-finite value in a prediction raises before anything of its
 group is written; the count of clipped values is printed.  `upscale()` is the function under the command line: it takes any callable as
 the model and any device; `main(argv)` is callable and returns a dict.
+
+--niqe F.npz [--niqe_crop_border N]: every output is scored with NIQE (niqe.py) against the parameter file, on the device,
+from the fp32 prediction after the optional resize and before the download -- the score of the 8-bit quantisation of what is written, also
+with --out_bits 16.  `[niqe] <name> <score>` lines, the mean in `[done]`, and 'niqe' in the result dict; without the flag nothing changes.
+The file is checked (keys, shapes, finite, symmetric covariance) while the arguments are parsed, before the checkpoint is read.
 """
 from __future__ import annotations
 
@@ -81,7 +86,21 @@ def parse_args(argv=None):
     ap.add_argument("--outscale", type=float, default=None, metavar="S",
                     help="final size = input size x S (default: the model's scale): the fp32 prediction is resized with ops.resize_aa before it is quantised")
     ap.add_argument("--out_bits", type=str, choices=["auto", "8", "16"], default="auto", help="bit depth of the outputs (auto: the input's)")
+    ap.add_argument("--niqe", type=str, default=None, metavar="F.npz",
+                    help="score every output with NIQE against this parameter file (niqe_pris_params.npz format; `python -m tpu_superresolution_amd.niqe fit` "
+                         "writes one): on the device, from the fp32 prediction quantised to 8 bits -- also with --out_bits 16, where the score is that of the "
+                         "8-bit quantisation of what is written")
+    ap.add_argument("--niqe_crop_border", type=int, default=0, metavar="N", help="with --niqe: pixels cropped on every side before the score")
     args = ap.parse_args(argv)
+    args.niqe_params = None
+    if args.niqe is not None:          # the file is read and checked here, before the checkpoint is opened
+        from .niqe import load_niqe_params
+        try:
+            args.niqe_params = load_niqe_params(args.niqe)
+        except ValueError as e:
+            ap.error(f"--niqe {e}")
+    if args.niqe_crop_border < 0 or (args.niqe_crop_border and args.niqe is None):
+        ap.error(f"--niqe_crop_border is an option of --niqe and must be >= 0 (got {args.niqe_crop_border})")
     if args.img_range is not None and not (math.isfinite(args.img_range) and args.img_range > 0):
         ap.error(f"--img_range must be a positive number (got {args.img_range})")
     if args.arch == "auto":          # the file decides the model: its flags are refused off their defaults
@@ -238,7 +257,7 @@ def _mode_label(ch: int, bits: int) -> str:
 
 def upscale(model, arrays: Sequence[np.ndarray], *, scale: int, device, channels: int = 3, outscale: Optional[float] = None,
             out_bits="auto", batch_size: int = 1, names: Optional[Sequence[str]] = None, modes: Optional[Sequence[str]] = None,
-            sink: Optional[Callable] = None, log: Callable = print) -> dict:
+            sink: Optional[Callable] = None, log: Callable = print, niqe_params: Optional[dict] = None, niqe_crop_border: int = 0) -> dict:
     """Runs `model` (any callable [B,channels,H,W] fp32 in [0, 1] -> [B,channels,H scale,W scale]) on decoded images.
 
     arrays: uint8 / uint16 [H,W] or [H,W,ch], ch 1..4 (gray, gray + alpha, RGB, RGB + alpha).  Consecutive arrays of equal shape and dtype,
@@ -246,7 +265,9 @@ def upscale(model, arrays: Sequence[np.ndarray], *, scale: int, device, channels
     out_size(H, W, outscale), ops.image_pack with the counters, one download, one read of the counters.  The output of an image has its
     channel count, and its depth unless out_bits is 8 or 16.  sink(index, samples [Ho,Wo,ch]) receives every output after its group's
     guard has passed (default: they are collected in the result's 'outputs').  A non-finite value raises RuntimeError before the sink sees
-    any image of the group."""
+    any image of the group.  niqe_params (niqe.load_niqe_params' dict): every prediction is scored with niqe.niqe after the resize and before
+    the download -- the 8-bit quantisation of the fp32 prediction, whatever the output depth; `[niqe]` lines, and the result gains 'niqe'
+    {index: score} (an image with fewer than 2 blocks is left out with a `skipped` line)."""
     if channels not in (1, 3):
         raise ValueError(f"channels must be 1 or 3 (got {channels!r})")
     if str(out_bits) not in ("auto", "8", "16"):
@@ -259,7 +280,7 @@ def upscale(model, arrays: Sequence[np.ndarray], *, scale: int, device, channels
     device = torch.device(device)
     names = [f"#{i}" for i in range(len(arrays))] if names is None else list(names)
     outputs = {} if sink is None else None
-    clipped_total, groups, pixels = 0, [], 0
+    clipped_total, groups, pixels, scores = 0, [], 0, {}
     i = 0
     while i < len(arrays):
         j = i + 1
@@ -285,6 +306,7 @@ def upscale(model, arrays: Sequence[np.ndarray], *, scale: int, device, channels
                 pred = _resize(pred, (Ho, Wo))
             if alpha is not None and tuple(alpha.shape[-2:]) != (Ho, Wo):
                 alpha = _resize(alpha, (Ho, Wo))
+            group_scores = _niqe_group(pred, niqe_params, niqe_crop_border) if niqe_params is not None else None
             counters = torch.zeros(2, dtype=torch.int32, device=device)
             packed = ops.image_pack(pred.contiguous(), alpha, out_chans=ch, bits=bits, counters=counters)
             host = _to_host(packed)
@@ -298,6 +320,12 @@ def upscale(model, arrays: Sequence[np.ndarray], *, scale: int, device, channels
             mode = modes[i + k] if modes is not None else _mode_label(ch, in_bits)
             log(f"[predict] {names[i + k]} {H}x{W} {mode} {in_bits} -> {Ho}x{Wo} | {ms / n:.1f} ms")
             pixels += Ho * Wo
+            if group_scores is not None:
+                if isinstance(group_scores[k], float):
+                    scores[i + k] = group_scores[k]
+                    log(f"[niqe] {names[i + k]} {group_scores[k]:.4f}")
+                else:
+                    log(f"[niqe] {names[i + k]}: skipped ({group_scores[k]})")
             if sink is None:
                 outputs[i + k] = host[k]
             else:
@@ -305,8 +333,33 @@ def upscale(model, arrays: Sequence[np.ndarray], *, scale: int, device, channels
         if clipped:
             log(f"[clipped] {clipped} values outside [0, 1] in {', '.join(names[i:j])}")
         i = j
-    return {"outputs": None if outputs is None else [outputs[k] for k in range(len(arrays))], "groups": groups, "clipped": clipped_total,
-            "pixels": pixels}
+    result = {"outputs": None if outputs is None else [outputs[k] for k in range(len(arrays))], "groups": groups, "clipped": clipped_total,
+              "pixels": pixels}
+    if niqe_params is not None:
+        result["niqe"] = scores
+    return result
+
+
+def _niqe_group(pred: torch.Tensor, params: dict, crop_border: int) -> list:
+    """NIQE of every prediction of a group -> per image the score (float) or the reason it has none (str)."""
+    from .niqe import NIQE_BLOCK, niqe_distance, niqe_moments, niqe_plane_shape, niqe_rows
+    n = pred.shape[0]
+    try:
+        _, _, nbh, nbw = niqe_plane_shape(pred.shape, crop_border)
+        if nbh * nbw < 2:
+            raise ValueError(f"{pred.shape[2]} x {pred.shape[3]} with a border of {crop_border} holds {nbh * nbw} block of {NIQE_BLOCK} x {NIQE_BLOCK}; "
+                             "the score needs at least 2")
+    except ValueError as e:
+        return [str(e)] * n
+    mom1, mom2, _ = niqe_moments(pred.contiguous(), crop_border, NIQE_BLOCK, params["window"])
+    rows = niqe_rows(mom1, mom2)
+    out = []
+    for b in range(n):
+        try:
+            out.append(niqe_distance(rows[b], params["mu"], params["cov"]))
+        except ValueError as e:
+            out.append(str(e))
+    return out
 
 
 # ---- the model --------------------------------------------------------------------------------------------------------------------------
@@ -376,7 +429,8 @@ def run(model, args, scale_int: int, device) -> dict:
     predict = make_predict(model, tile=args.tile, tile_overlap=args.tile_overlap, tile_batch=args.tile_batch, tile_blend=args.tile_blend,
                            self_ensemble=args.self_ensemble)
     t0 = time.time()
-    written, clipped, pixels, groups = [], 0, 0, []
+    written, clipped, pixels, groups, scores = [], 0, 0, [], {}
+    niqe_params = getattr(args, "niqe_params", None)
     # decode and predict one run of equal files at a time: a group is complete before its files are written, a directory is never held whole
     i, ahead = 0, None          # ahead: the decoded file that ended the previous run
     while i < len(files):
@@ -399,14 +453,22 @@ def run(model, args, scale_int: int, device) -> dict:
             written.append(str(targets[base + k]))
 
         r = upscale(predict, arrays, scale=scale_int, device=device, channels=args.channels, outscale=args.outscale, out_bits=args.out_bits,
-                    batch_size=args.batch_size, names=names, modes=modes, sink=sink)
+                    batch_size=args.batch_size, names=names, modes=modes, sink=sink,
+                    **({} if niqe_params is None else {"niqe_params": niqe_params, "niqe_crop_border": args.niqe_crop_border}))
+        scores.update({names[k]: v for k, v in r.get("niqe", {}).items()})
         clipped += r["clipped"]
         pixels += r["pixels"]
         groups += r["groups"]
         i += len(arrays)
     dt = time.time() - t0
-    print(f"[done] {len(written)} images | {dt:.1f} s | {pixels / 1e6 / max(dt, 1e-9):.2f} output MP/s")
-    return {"n": len(written), "written": written, "groups": groups, "clipped": clipped, "seconds": dt, "output_mp": pixels / 1e6}
+    result = {"n": len(written), "written": written, "groups": groups, "clipped": clipped, "seconds": dt, "output_mp": pixels / 1e6}
+    tail = ""
+    if niqe_params is not None:
+        mean = float(np.mean(list(scores.values()))) if scores else float("nan")
+        result["niqe"] = {"scores": scores, "mean": mean}
+        tail = f" | niqe mean {mean:.4f} over {len(scores)}"
+    print(f"[done] {len(written)} images | {dt:.1f} s | {pixels / 1e6 / max(dt, 1e-9):.2f} output MP/s{tail}")
+    return result
 
 
 if __name__ == "__main__":
