@@ -804,14 +804,26 @@ int srk_win_small_attention_bwd(const uint16_t* qkv, int ldq, int CA, const floa
                                 uint16_t* d_qkv, float* d_table, void* scratch, int B, int H, int W, int ws, int shift,
                                 int num_heads, float scale, srk_stream_t stream);
 /* ChannelAttention gate of CAB (:41-57): gate[b][c] = out_scale * sigmoid(W2 relu(W1 mean_b + b1) + b2), mean over the HW tokens
- * of x bf16 [B*HW][CP]; w1 [S][C], w2 [C][S] fp32 (the 1x1 convs).  workspace: srk_channel_gate_workspace bytes. */
+ * of x bf16 [B*HW][CP]; w1 [S][C], w2 [C][S] fp32 (the 1x1 convs).  workspace: srk_channel_gate_workspace bytes, fully written before
+ * it is read (needs no zeroing).  The pad columns C..CP-1 of x are read (their sums land in the workspace) but their means are never
+ * used: they may hold anything, NaN included.  Every element of gate fp32 [B][CP] is written: columns C..CP-1 receive +0.  The sums
+ * run in a fixed order without atomics: two calls give the same bits.  SRK_E_NULL: a null pointer; SRK_E_SHAPE unless 1 <= B < 65536,
+ * HW > 0, 1 <= C <= CP, CP % 64 == 0, CP <= 256, 1 <= S <= 64; SRK_E_ALIGN unless x is 16-byte aligned (eight bf16 per load).  All
+ * checked on the host before any launch. */
 size_t srk_channel_gate_workspace(int B, int HW, int CP);
 int srk_channel_gate(const uint16_t* x, void* workspace, const float* w1, const float* b1, const float* w2, const float* b2, float out_scale,
                      float* gate, int B, int HW, int C, int CP, int S, srk_stream_t stream);
 /* same with the hidden activation selectable: act 0 ReLU (HAT), 1 GELU (DAT's channel_interaction, dat_arch.py:315-321, BatchNorm folded) */
 int srk_channel_gate_act(const uint16_t* x, void* workspace, const float* w1, const float* b1, const float* w2, const float* b2, float out_scale,
                          float* gate, int B, int HW, int C, int CP, int S, int act, srk_stream_t stream);
-/* HAB.forward :322-323: x += conv * gate[sample] in place (fp32 [rows][CP]) and, if xn != null, xn = bf16(LayerNorm(x)) */
+/* HAB.forward :322-323: x += conv * gate[sample] in place (fp32 [rows][CP]) and, if xn != null, xn = bf16(LayerNorm(x)) over the C real
+ * columns (eps 1e-5, gamma / beta fp32 [C]); sample = row / rows_per_sample, gate fp32 [rows / rows_per_sample][CP] as srk_channel_gate
+ * wrote it (pad columns 0).  All CP columns of x and conv are read and all CP columns of x written: a pad column of x receives
+ * x + conv * 0, so the pad columns of conv must be finite.  The LayerNorm mean is taken from the sum over ALL CP columns: the pad columns
+ * of x must be zero on entry (they stay zero); the variance runs over the C real columns only.  xn bf16 [rows][CP]: pad columns +0.
+ * With xn == null gamma and beta may be null and only x is written.  SRK_E_NULL: null x / conv / gate, or xn without gamma / beta;
+ * SRK_E_SHAPE unless rows > 0, rows_per_sample > 0 dividing rows, 1 <= C <= CP; SRK_E_ALIGN unless x and gate are 16-byte and conv and
+ * xn 8-byte aligned; SRK_E_UNSUPPORTED for a CP other than 64 / 128 / 192 / 256.  All checked on the host before any launch. */
 int srk_cab_add_ln(float* x, const uint16_t* conv, const float* gate, const float* gamma, const float* beta, uint16_t* xn, int64_t rows,
                    int rows_per_sample, int C, int CP, srk_stream_t stream);
 
@@ -830,7 +842,13 @@ int srk_win256_attention_bwd(const uint16_t* qkv, int ldq, int CA, const float* 
                              float scale, int overlap, srk_stream_t stream);
 /* Gradient of `x += conv * gate[sample]`, gate = srk_channel_gate(conv) (HAB.forward :322 with CAB :41-75): g fp32 [B*HW][CP] is the
  * gradient of the sum, conv bf16 the second CAB conv's output, gate fp32 [B][CP] as the forward produced it.  d_conv bf16 [B*HW][CP] =
- * g * gate + (gradient through the average pool); dw1 [S][C], db1 [S], dw2 [C][S], db2 [C] are ACCUMULATED; dmean fp32 [B][CP] scratch. */
+ * g * gate + (gradient through the average pool); dw1 [S][C], db1 [S], dw2 [C][S], db2 [C] are ACCUMULATED (float atomics, one addend per
+ * sample); dmean fp32 [B][CP] scratch, fully written (the pool gradient per token; pad columns +0).  The hidden activation is ReLU.
+ * workspace: srk_cab_bwd_workspace bytes, fully written before it is read.  The pad columns C..CP-1 of conv are read but never used
+ * (anything, NaN included); those of g must be finite and those of gate zero: every column of d_conv is written and a pad column
+ * receives bf16(g * gate + 0).  SRK_E_NULL: a null pointer; SRK_E_SHAPE unless 1 <= B < 65536, HW > 0, 1 <= C <= CP, CP % 64 == 0,
+ * CP <= 256, 1 <= S <= 64; SRK_E_ALIGN unless conv, g, gate and dmean are 16-byte and d_conv 8-byte aligned.  All checked on the host
+ * before any launch. */
 size_t srk_cab_bwd_workspace(int B, int HW, int CP);
 int srk_cab_bwd(const uint16_t* conv, const float* g, const float* gate, void* workspace, const float* w1, const float* b1, const float* w2,
                 const float* b2, float out_scale, float* dw1, float* db1, float* dw2, float* db2, float* dmean, uint16_t* d_conv, int B, int HW,
@@ -1090,7 +1108,18 @@ int srk_chan_apply_mat(const float* M, const uint16_t* src, int ldsrc, const flo
  *     gram [B][heads][1088] = their sum (G | sum q^2 | sum k^2), A [B][heads][32][32] = softmax_j(temperature_h G_ij / (|q_i| |k_j|)) over the
  *     dh real channels (norms clamped at 1e-12 as F.normalize; padding rows / columns 0).  _bwd: dpartial = chunk partials of
  *     srk_chan_gram(d out, v) (= d A) -> dG, dGt (its transpose), dsq2 / dsk2 [B][heads][32] (the diagonal coefficients of d q / d k through
- *     the norms, as srk_chan_apply_mat takes them), dtemp [B][heads] (sum over B = d temperature). */
+ *     the norms, as srk_chan_apply_mat takes them), dtemp [B][heads] (sum over B = d temperature).
+ *   What is read and written.  Channel interaction, trained and frozen alike: of pooled only the positions pad_of names are read (the
+ *     others, and columns CA..ldp-1, may hold anything); every element of pm_out [B][C], cgate [B][CA] and dpool [B][CA] is written (the
+ *     positions pad_of does not name receive +0); the six parameter gradients dW1 [S][C], db1 [S], dgamma [S], dbeta [S], dW2 [C][S],
+ *     db2 [C] are OVERWRITTEN, not accumulated (the caller adds them to .grad).  The forms differ in the BatchNorm: the trained form
+ *     normalises with the biased batch variance, moves running_mean / running_var (both given or both null, else SRK_E_SHAPE) by
+ *     (1 - momentum) old + momentum new with the UNBIASED variance, and its backward carries the batch terms, so its db1 is a sum that is
+ *     zero but for rounding; the frozen form reads the running buffers, writes none, and its db1 = sum d y.  The matrix kernels write
+ *     every element of gram, A, dG, dGt, dsq2, dsk2 and dtemp, padding rows / columns (>= dh) +0; a channel whose sum of squares is
+ *     at most 1e-24 is normalised by the clamp and gets dsq2 / dsk2 = 0.  The sums over chunks run in a fixed order (no atomics).
+ *   SRK_E_NULL: a null pointer (the running buffers of the trained forward excepted); SRK_E_SHAPE: a (B, C, S) that is not covered, CA < C,
+ *     ldp < CA, ldg < CA, exactly one running buffer null; for the matrix B, num_heads, nchunk < 1 or dh outside 1..32. */
 int srk_channel_interaction_covered(int B, int C, int S);
 int srk_channel_interaction_fwd(const float* pooled, int ldp, float inv_hw, const int* pad_of, const float* W1, const float* b1,
                                 const float* gamma, const float* beta, float eps, const float* W2, const float* b2, float* running_mean,

@@ -47,7 +47,8 @@ from gemm_ex_ref import GELU_LIP, LN_EPS, U, Tol
 from oracle import dat_oracle as DO
 
 ATTN_TOL = 2e-2                      # x max|ref|: tests/test_gpu_hat.py, attention kernels alone
-GATE_TOL = 1e-6 * GELU_LIP           # tests/test_gpu_hat.py::test_channel_gate_and_cab_add_ln_vs_torch, through the GELU
+GATE_TOL = 1e-6 * GELU_LIP           # tests/test_gpu_hat.py::test_channel_gate_and_cab_add_ln_vs_torch, through the GELU; the derived
+                                     # per-element bound of the gate is tests/gate_ref.py (tests/test_gpu_gate_direct.py)
 
 
 @dataclass

@@ -331,6 +331,88 @@ def test_glue_entry_points_refuse_bad_arguments_without_a_gpu(lib):
            ("CP", 62, E_SHAPE), ("CP", -64, E_SHAPE), ("src", P + 2, E_ALIGN), ("dst", P + 4, E_ALIGN)])
 
 
+def test_gate_entry_points_refuse_bad_arguments_without_a_gpu(lib):
+    """HAT's CAB tail (srk_channel_gate / _act, srk_cab_add_ln, srk_cab_bwd) and DAT's small functions (srk_channel_interaction_fwd / _bwd,
+    their frozen forms, srk_chan_attn_matrix_fwd / _bwd) return on the host, before any launch: SRK_E_NULL, SRK_E_SHAPE, SRK_E_UNSUPPORTED
+    and SRK_E_ALIGN as include/srk.h states them at each entry point.  The addresses are dummies that are never dereferenced; every call
+    differs from a valid one in exactly the argument under test."""
+    h = lib.lib()
+    P = 4096
+    E_SHAPE, E_NULL, E_UNSUPPORTED, E_ALIGN = -1, -2, -3, -5
+
+    def sweep(fn, base, changes, tail=(None,)):
+        for name, bad, code in changes:
+            assert name in base, name
+            args = [bad if k == name else v for k, v in base.items()]
+            rc = fn(*args, *tail)
+            assert rc == code, (fn.__name__, name, bad, rc, code, h.srk_last_error())
+            assert h.srk_last_error(), "no message"
+
+    def nulls(base, but=()):
+        return [(k, None, E_NULL) for k, v in base.items() if v == P and k not in but]
+
+    gate_shape = [("S", 65, E_SHAPE), ("S", 0, E_SHAPE), ("C", 65, E_SHAPE), ("C", 0, E_SHAPE), ("CP", 96, E_SHAPE), ("CP", 320, E_SHAPE),
+                  ("B", 65536, E_SHAPE), ("B", 0, E_SHAPE), ("HW", 0, E_SHAPE)]
+    # srk_channel_gate(x, workspace, w1, b1, w2, b2, out_scale, gate, B, HW, C, CP, S, stream)  /  srk_channel_gate_act(..., S, act, stream)
+    base = dict(x=P, workspace=P, w1=P, b1=P, w2=P, b2=P, out_scale=0.01, gate=P, B=3, HW=700, C=60, CP=64, S=6)
+    faults = nulls(base) + gate_shape + [("x", P + 2, E_ALIGN), ("x", P + 8, E_ALIGN)]
+    sweep(h.srk_channel_gate, base, faults)
+    sweep(h.srk_channel_gate_act, dict(base, act=1), faults)
+
+    # srk_cab_add_ln(x, conv, gate, gamma, beta, xn, rows, rows_per_sample, C, CP, stream)
+    base = dict(x=P, conv=P, gate=P, gamma=P, beta=P, xn=P, rows=21, rps=7, C=60, CP=64)
+    sweep(h.srk_cab_add_ln, base, [("x", None, E_NULL), ("conv", None, E_NULL), ("gate", None, E_NULL), ("gamma", None, E_NULL),
+                                   ("beta", None, E_NULL), ("rows", 0, E_SHAPE), ("rows", 22, E_SHAPE), ("rps", 0, E_SHAPE), ("rps", 4, E_SHAPE),
+                                   ("C", 65, E_SHAPE), ("C", 0, E_SHAPE), ("CP", 320, E_UNSUPPORTED), ("CP", 96, E_UNSUPPORTED),
+                                   ("x", P + 4, E_ALIGN), ("x", P + 8, E_ALIGN), ("gate", P + 8, E_ALIGN), ("conv", P + 2, E_ALIGN),
+                                   ("conv", P + 4, E_ALIGN), ("xn", P + 2, E_ALIGN), ("xn", P + 12, E_ALIGN)])
+    assert h.srk_cab_add_ln(P, P, P, None, None, P, 21, 7, 60, 64, None) == E_NULL                       # xn without gamma / beta
+    assert h.srk_cab_add_ln(P, P, P, None, None, None, 21, 7, 60, 320, None) == E_UNSUPPORTED            # the xn == null form reaches the CP switch
+
+    # srk_cab_bwd(conv, g, gate, workspace, w1, b1, w2, b2, out_scale, dw1, db1, dw2, db2, dmean, d_conv, B, HW, C, CP, S, stream)
+    base = dict(conv=P, g=P, gate=P, workspace=P, w1=P, b1=P, w2=P, b2=P, out_scale=0.01, dw1=P, db1=P, dw2=P, db2=P, dmean=P, d_conv=P,
+                B=3, HW=700, C=60, CP=64, S=6)
+    sweep(h.srk_cab_bwd, base, nulls(base) + gate_shape + [("conv", P + 8, E_ALIGN), ("conv", P + 2, E_ALIGN), ("g", P + 4, E_ALIGN),
+                                                           ("gate", P + 8, E_ALIGN), ("dmean", P + 4, E_ALIGN), ("d_conv", P + 2, E_ALIGN),
+                                                           ("d_conv", P + 4, E_ALIGN)])
+
+    # the largest covered batch at C 180, S 22 and the first refused one (tests/gate_ref.py restates the LDS formula)
+    import gate_ref
+    bmax = gate_ref.ci_largest_B(180, 22)
+    assert h.srk_channel_interaction_covered(bmax, 180, 22) == 1 and h.srk_channel_interaction_covered(bmax + 1, 180, 22) == 0
+    assert h.srk_channel_interaction_covered(1, 180, 22) == 0 and h.srk_channel_interaction_frozen_covered(1, 180, 22) == 1
+    ci_shape = [("B", bmax + 1, E_SHAPE), ("B", 0, E_SHAPE), ("S", 65, E_SHAPE), ("S", 0, E_SHAPE), ("C", 0, E_SHAPE), ("CA", 179, E_SHAPE)]
+    # srk_channel_interaction_fwd(pooled, ldp, inv_hw, pad_of, W1, b1, gamma, beta, eps, W2, b2, running_mean, running_var, momentum, pm_out,
+    #                             cgate, B, C, S, CA, stream)
+    base = dict(pooled=P, ldp=192, inv_hw=0.01, pad_of=P, W1=P, b1=P, gamma=P, beta=P, eps=1e-5, W2=P, b2=P, running_mean=P, running_var=P,
+                momentum=0.1, pm_out=P, cgate=P, B=4, C=180, S=22, CA=192)
+    sweep(h.srk_channel_interaction_fwd, base, nulls(base, but=("running_mean", "running_var")) + ci_shape +
+          [("ldp", 191, E_SHAPE), ("running_mean", None, E_SHAPE), ("running_var", None, E_SHAPE), ("B", 1, E_SHAPE)])
+    # srk_channel_interaction_frozen_fwd(pooled, ..., b2, running_mean, running_var, pm_out, cgate, B, C, S, CA, stream)
+    fbase = {k: v for k, v in base.items() if k != "momentum"}
+    sweep(h.srk_channel_interaction_frozen_fwd, fbase, nulls(fbase) + ci_shape + [("ldp", 191, E_SHAPE)])
+    # srk_channel_interaction_bwd(pm, dcgate, ldg, inv_hw, pad_of, W1, b1, gamma, beta, eps, W2, b2, dW1, db1, dgamma, dbeta, dW2, db2, dpool,
+    #                             B, C, S, CA, stream)
+    base = dict(pm=P, dcgate=P, ldg=192, inv_hw=0.01, pad_of=P, W1=P, b1=P, gamma=P, beta=P, eps=1e-5, W2=P, b2=P, dW1=P, db1=P, dgamma=P,
+                dbeta=P, dW2=P, db2=P, dpool=P, B=4, C=180, S=22, CA=192)
+    sweep(h.srk_channel_interaction_bwd, base, nulls(base) + ci_shape + [("ldg", 191, E_SHAPE), ("B", 1, E_SHAPE)])
+    # srk_channel_interaction_frozen_bwd(pm, ..., b2, running_mean, running_var, dW1, ..., dpool, B, C, S, CA, stream)
+    fbase = {}
+    for k, v in base.items():
+        fbase[k] = v
+        if k == "b2":
+            fbase["running_mean"], fbase["running_var"] = P, P
+    sweep(h.srk_channel_interaction_frozen_bwd, fbase, nulls(fbase) + ci_shape + [("ldg", 191, E_SHAPE)])
+
+    # srk_chan_attn_matrix_fwd(partial, nchunk, temperature, gram, A, B, num_heads, dh, stream)
+    mat_shape = [("B", 0, E_SHAPE), ("nH", 0, E_SHAPE), ("nchunk", 0, E_SHAPE), ("dh", 0, E_SHAPE), ("dh", 33, E_SHAPE)]
+    base = dict(partial=P, nchunk=3, temperature=P, gram=P, A=P, B=2, nH=6, dh=30)
+    sweep(h.srk_chan_attn_matrix_fwd, base, nulls(base) + mat_shape)
+    # srk_chan_attn_matrix_bwd(dpartial, nchunk, gram, A, temperature, dG, dGt, dsq2, dsk2, dtemp, B, num_heads, dh, stream)
+    base = dict(dpartial=P, nchunk=3, gram=P, A=P, temperature=P, dG=P, dGt=P, dsq2=P, dsk2=P, dtemp=P, B=2, nH=6, dh=30)
+    sweep(h.srk_chan_attn_matrix_bwd, base, nulls(base) + mat_shape)
+
+
 def test_options_are_process_wide_with_per_plan_values():
     """SURVEY 8b 're-entrant': srk_set_option writes ONE process-wide value per option (every thread sees it -- the autograd engine runs
     the backward on its own thread); a plan carries its own values (srk_swinir_plan_set_option), applied in a thread-private copy of the

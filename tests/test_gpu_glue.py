@@ -9,7 +9,9 @@ Every case checks
   3. that nothing else is read: operands sit between NaN rows (a masked over-read would surface as NaN or as a non-zero pad column);
   4. pad columns (exactly +0, or unchanged under accumulate = 1), the accumulate contracts, and the return code.
 
-The comparators' ability to fail is pinned on the CPU (tests/test_glue_ref.py)."""
+The comparators' ability to fail is pinned on the CPU (tests/test_glue_ref.py).  srk_channel_gate_act runs here at the one shape of
+tests/test_gpu_hat.py; its direct coverage with a derived bound, and that of srk_channel_gate / srk_cab_add_ln / srk_cab_bwd, is
+tests/test_gpu_gate_direct.py."""
 import ctypes as C
 
 import pytest

@@ -3,7 +3,11 @@ reference of the same op, the CAB helper kernels, and the whole model against th
 CPU oracle (oracle/hat_oracle.py, pinned by tests/test_oracle_golden.py::test_g13_*).
 
 Tolerances as for SwinIR (tests/test_gpu_model.py): bf16 MFMA operands with fp32 accumulation / softmax / LayerNorm /
-residual stream -> forward max|err| <= 1.2e-2 * max|ref|; attention kernels alone (bf16 in, bf16 out) 2e-2 * max|ref|."""
+residual stream -> forward max|err| <= 1.2e-2 * max|ref|; attention kernels alone (bf16 in, bf16 out) 2e-2 * max|ref|.
+
+The CAB helper kernels (srk_channel_gate, srk_cab_add_ln, srk_cab_bwd) run here at one shape against fp32 torch; their direct coverage --
+fp64 references with derived per-element bounds, the chunk / channel / row / grid-wrap edges, guarded outputs -- is
+tests/test_gpu_gate_direct.py."""
 import numpy as np
 import pytest
 import torch

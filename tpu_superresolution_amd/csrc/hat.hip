@@ -151,6 +151,7 @@ int srk_channel_gate_act(const uint16_t* x, void* workspace, const float* w1, co
   SRK_REQUIRE(x && workspace && w1 && b1 && w2 && b2 && gate, SRK_E_NULL, "channel_gate: null pointer");
   SRK_REQUIRE(B > 0 && B < 65536 && HW > 0 && C > 0 && C <= CP && CP % 64 == 0 && CP <= 256 && S > 0 && S <= 64, SRK_E_SHAPE,
               "channel_gate: bad shape B=%d HW=%d C=%d CP=%d S=%d", B, HW, C, CP, S);
+  SRK_REQUIRE(srk_aligned(x, 16), SRK_E_ALIGN, "channel_gate: x is not 16-byte aligned");      // eight bf16 per load
   const int nchunk = (HW + TM_ROWS - 1) / TM_ROWS;
   hipLaunchKernelGGL(token_mean_partial_kernel, dim3(nchunk, B), dim3(256), 0, (hipStream_t)stream, x, static_cast<float*>(workspace), HW, CP);
   hipLaunchKernelGGL(channel_gate_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, static_cast<const float*>(workspace), nchunk, HW, C, CP, S,
@@ -163,6 +164,9 @@ int srk_cab_add_ln(float* x, const uint16_t* conv, const float* gate, const floa
   SRK_REQUIRE(x && conv && gate, SRK_E_NULL, "cab_add_ln: null pointer");
   SRK_REQUIRE(xn == nullptr || (gamma && beta), SRK_E_NULL, "cab_add_ln: LayerNorm output without gamma / beta");
   SRK_REQUIRE(rows > 0 && rows_per_sample > 0 && rows % rows_per_sample == 0 && C > 0 && C <= CP, SRK_E_SHAPE, "cab_add_ln: bad shape");
+  // float4 accesses of x / gate, uint2 (four bf16) accesses of conv / xn
+  SRK_REQUIRE(srk_aligned(x, 16) && srk_aligned(gate, 16) && srk_aligned(conv, 8) && srk_aligned(xn, 8), SRK_E_ALIGN,
+              "cab_add_ln: x / gate not 16-byte or conv / xn not 8-byte aligned");
   const int grid = (int)((rows + 15) / 16 < 8192 ? (rows + 15) / 16 : 8192);
   const float* gm = gamma ? gamma : gate;      // never dereferenced beyond C when xn is null (values unused)
   const float* bt = beta ? beta : gate;

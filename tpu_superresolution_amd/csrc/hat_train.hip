@@ -179,6 +179,9 @@ int srk_cab_bwd(const uint16_t* conv, const float* g, const float* gate, void* w
               "cab_bwd: null pointer");
   SRK_REQUIRE(B > 0 && B < 65536 && HW > 0 && C > 0 && C <= CP && CP % 64 == 0 && CP <= 256 && S > 0 && S <= 64, SRK_E_SHAPE,
               "cab_bwd: bad shape B=%d HW=%d C=%d CP=%d S=%d", B, HW, C, CP, S);
+  // uint4 (eight bf16) loads of conv, float4 accesses of g / gate / dmean, uint2 (four bf16) stores of d_conv
+  SRK_REQUIRE(srk_aligned(conv, 16) && srk_aligned(g, 16) && srk_aligned(gate, 16) && srk_aligned(dmean, 16) && srk_aligned(d_conv, 8),
+              SRK_E_ALIGN, "cab_bwd: conv / g / gate / dmean not 16-byte or d_conv not 8-byte aligned");
   const int nchunk = (HW + TM_ROWS - 1) / TM_ROWS;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(cab_pool_bwd_partial_kernel, dim3(nchunk, B), dim3(256), 0, st, conv, g, static_cast<float*>(workspace), HW, CP);
