@@ -748,7 +748,11 @@ int srk_mlp_fused_fwd(const uint16_t* xn, const uint16_t* w1, const float* b1, c
  * x, y: fp32 [B*H*W][64] token-major, channels >= C zero (y may alias x); y_bf16: optional bf16 copy of y.  Packed bf16 weights:
  * wqkv [3*192][64] (row = which*192 + head*32 + d), wproj [64][192] (column = head*32 + d), w1 [128][64], w2 [64][128]; fp32
  * biases in the same padded order; bias_dense [6][64][64] = table[rpi]; C <= 64, num_heads == 6, head_dim <= 16, hidden <= 128,
- * H and W multiples of 8, shift 0 or 4.  SRK_E_UNSUPPORTED for any other width. */
+ * H and W multiples of 8, shift 0 or 4.  Checked on the host before any launch: SRK_E_NULL for a null operand (y_bf16 and the four
+ * biases may be null: no copy, a zero bias); SRK_E_SHAPE unless B, H, W > 0, H and W multiples of 8, shift 0 or 4, 0 < C <= 64,
+ * 0 < hidden <= 128, num_heads * head_dim == C; SRK_E_ALIGN unless x, y, the four weights, the biases that are given and bias_dense
+ * are 16-byte aligned (float4 / eight-bf16 accesses) and y_bf16 is 8-byte aligned; SRK_E_UNSUPPORTED for any other width (heads
+ * other than 6, head_dim > 16) and when the option "block_light" is 0 (the message names the option). */
 int srk_swin_block_fwd(const float* x, float* y, uint16_t* y_bf16, const float* norm1_w, const float* norm1_b, const float* norm2_w,
                        const float* norm2_b, const uint16_t* wqkv, const float* bqkv, const uint16_t* wproj, const float* bproj,
                        const uint16_t* w1, const float* b1, const uint16_t* w2, const float* b2, const float* bias_dense, float scale,

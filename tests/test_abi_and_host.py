@@ -413,6 +413,43 @@ def test_gate_entry_points_refuse_bad_arguments_without_a_gpu(lib):
     sweep(h.srk_chan_attn_matrix_bwd, base, nulls(base) + mat_shape)
 
 
+def test_swin_block_entry_refuses_bad_arguments_without_a_gpu(lib):
+    """srk_swin_block_fwd (the whole-block kernel of the SwinIR-light width) returns on the host, before any launch: SRK_E_NULL,
+    SRK_E_SHAPE, SRK_E_ALIGN (its kernel issues 16-byte accesses on x, y, every weight, every bias and bias_dense, 8-byte stores on
+    y_bf16) and SRK_E_UNSUPPORTED as include/srk.h states them.  The addresses are dummies that are never dereferenced; every call differs
+    from a valid one in exactly the argument under test."""
+    h = lib.lib()
+    P = 4096
+    E_SHAPE, E_NULL, E_UNSUPPORTED, E_ALIGN = -1, -2, -3, -5
+    # srk_swin_block_fwd(x, y, y_bf16, norm1_w, norm1_b, norm2_w, norm2_b, wqkv, bqkv, wproj, bproj, w1, b1, w2, b2, bias_dense, scale,
+    #                    C, num_heads, head_dim, hidden, B, H, W, shift, stream)
+    base = dict(x=P, y=P, y_bf16=P, n1w=P, n1b=P, n2w=P, n2b=P, wqkv=P, bqkv=P, wproj=P, bproj=P, w1=P, b1=P, w2=P, b2=P, dense=P, scale=0.3,
+                C=60, nH=6, dh=10, hid=120, B=2, H=16, W=24, shift=4)
+    optional = ("y_bf16", "bqkv", "bproj", "b1", "b2")
+    changes = [(k, None, E_NULL) for k, v in base.items() if v == P and k not in optional]
+    changes += [("B", 0, E_SHAPE), ("H", 0, E_SHAPE), ("H", 12, E_SHAPE), ("W", 20, E_SHAPE), ("W", -8, E_SHAPE), ("shift", 2, E_SHAPE),
+                ("shift", -4, E_SHAPE), ("dh", 9, E_SHAPE), ("nH", 5, E_SHAPE), ("hid", 129, E_SHAPE), ("hid", 0, E_SHAPE), ("C", 68, E_SHAPE),
+                ("C", 0, E_SHAPE)]
+    for k in ("x", "y", "wqkv", "bqkv", "wproj", "bproj", "w1", "b1", "w2", "b2", "dense"):
+        changes += [(k, P + 4, E_ALIGN), (k, P + 8, E_ALIGN)]
+    changes += [("y_bf16", P + 2, E_ALIGN), ("y_bf16", P + 4, E_ALIGN), ("y_bf16", P + 12, E_ALIGN)]
+    for name, bad, code in changes:
+        rc = h.srk_swin_block_fwd(*[bad if k == name else v for k, v in base.items()], None)
+        assert rc == code, (name, bad, rc, code, h.srk_last_error())
+        assert h.srk_last_error(), "no message"
+    # widths without a whole-block kernel: 4 heads x 16, 3 heads x 20
+    for C_, nH, dh in ((64, 4, 16), (60, 3, 20)):
+        assert h.srk_swin_block_fwd(*dict(base, C=C_, nH=nH, dh=dh).values(), None) == E_UNSUPPORTED
+        assert b"light width" in h.srk_last_error()
+    # the option that switches the kernel off: the message names it
+    lib.check(h.srk_set_option(b"block_light", 0))
+    try:
+        assert h.srk_swin_block_fwd(*base.values(), None) == E_UNSUPPORTED
+        assert b"block_light" in h.srk_last_error()
+    finally:
+        lib.check(h.srk_set_option(b"block_light", 1))
+
+
 def test_options_are_process_wide_with_per_plan_values():
     """SURVEY 8b 're-entrant': srk_set_option writes ONE process-wide value per option (every thread sees it -- the autograd engine runs
     the backward on its own thread); a plan carries its own values (srk_swinir_plan_set_option), applied in a thread-private copy of the

@@ -205,13 +205,19 @@ int srk_swin_block_fwd(const float* x, float* y, uint16_t* y_bf16, const float* 
               "swin_block_fwd: B=%d H=%d W=%d shift=%d", B, H, W, shift);
   SRK_REQUIRE(C > 0 && C <= 64 && hidden > 0 && hidden <= 128 && num_heads * head_dim == C, SRK_E_SHAPE,
               "swin_block_fwd: C=%d heads=%d x %d hidden=%d", C, num_heads, head_dim, hidden);
+  // float4 accesses of x / y / the biases / bias_dense, eight bf16 per weight load, uint2 (four bf16) stores of y_bf16; null is aligned
+  SRK_REQUIRE(srk_aligned(x, 16) && srk_aligned(y, 16) && srk_aligned(wqkv, 16) && srk_aligned(wproj, 16) && srk_aligned(w1, 16) &&
+                  srk_aligned(w2, 16) && srk_aligned(bqkv, 16) && srk_aligned(bproj, 16) && srk_aligned(b1, 16) && srk_aligned(b2, 16) &&
+                  srk_aligned(bias_dense, 16) && srk_aligned(y_bf16, 8),
+              SRK_E_ALIGN, "swin_block_fwd: x / y / a weight / a bias / bias_dense not 16-byte or y_bf16 not 8-byte aligned");
   WinGeom g;
   g.H = H; g.W = W; g.nWw = W / 8; g.nW = (H / 8) * (W / 8); g.shift = shift;
   const int rc = srk_launch_swin_block_light(x, y, y_bf16, norm1_w, norm1_b, norm2_w, norm2_b, wqkv, wproj, w1, w2, bqkv, bproj, b1, b2,
                                              bias_dense, scale, C, 64, 128, num_heads, head_dim, hidden, (long long)B * g.nW, g,
                                              (hipStream_t)stream);
   if (rc == SRK_NOT_COVERED) {
-    srk_set_error("swin_block_fwd: only the light width (6 heads x d <= 16) has a whole-block kernel");
+    if (!srk_block_light_enabled()) srk_set_error("swin_block_fwd: the whole-block kernel is switched off (option \"block_light\" is 0)");
+    else srk_set_error("swin_block_fwd: only the light width (6 heads x d <= 16) has a whole-block kernel");
     return SRK_E_UNSUPPORTED;
   }
   return rc;
