@@ -646,6 +646,50 @@ int srk_niqe_half_f32(const float* plane, float* half, int B, int H, int W, srk_
 int srk_niqe_mscn_f32(const float* plane, const float* win49, float* mscn, float* sigma, int B, int H, int W, srk_stream_t stream);
 int srk_niqe_moments_f32(const float* mscn, const float* sigma, float* mom, float* sharp, int B, int H, int W, int bs,
                          srk_stream_t stream);
+/* Full-reference scores: PSNR-B, MS-SSIM: two scores of image files against ground truth that the papers this library follows
+ * print -- PSNR-B (Yim & Bovik, "Quality assessment of deblocked images") in the form of SwinIR's calculate_psnrb, beside PSNR and SSIM in
+ * every JPEG-artifact table, and MS-SSIM (Wang, Simoncelli & Bovik 2003) in the form of pytorch_msssim.ms_ssim, the package srk_ssim
+ * restates.  Neither the SwinIR / BasicSR test scripts nor pytorch_msssim is available to compare with: both are restated from the
+ * published algorithms, PARITY UNPINNED; tests hold them against an independent fp64 restatement (tests/fullref_ref.py).  Both work on
+ * the planes of srk_bench_planes_f32: 8-bit quantised, border-cropped, BT.601 luma or colour planes, scale 0..255, fp32 [B][Cm][Hc][Wc].
+ * PSNR-B, per image and plane c, p the RESTORED plane and t the target:
+ *   mse_c     mean of (p - t)^2
+ *   D sums    the boundary columns are x = 7, 15, 23, ... with x < Wc - 1, the boundary rows likewise with Hc.  Dh_b = sum over all rows
+ *             and boundary columns of (p[y][x] - p[y][x+1])^2, Dh_n the same sum over the other columns 0 <= x <= Wc - 2; Dv_b, Dv_n the
+ *             same two sums along the rows.  fp32, each term one fmaf, a fixed order, no atomics: two runs give equal bits
+ *   counts    AS PUBLISHED: n_bh = Hc (Wc / 8 - 1), n_bv = Wc (Hc / 8 - 1) (integer divisions), n_nh = Hc (Wc - 1) - n_bh,
+ *             n_nv = Wc (Hc - 1) - n_bv.  For an extent that is 1 (mod 8) the sums hold one more boundary line than n_b* counts
+ *             (Wc = 17: columns 7 and 15, n_bh = Hc); the published counts are kept
+ *   bef_c     D_b = (Dh_b + Dv_b) / (n_bh + n_bv), D_n = (Dh_n + Dv_n) / (n_nh + n_nv);
+ *             bef_c = (3 / log2(min(Hc, Wc))) (D_b - D_n) if D_b > D_n, else 0
+ *   psnrb     mean over c of 10 log10(255^2 / (mse_c + bef_c)); a zero denominator gives +inf; a NaN in a plane reaches the result
+ * srk_psnrb: one streaming pass (a workgroup takes a run of rows of one plane and reads the one row below it: every plane element is read
+ * by at most two workgroups) into workspace (srk_psnrb_workspace(B, Cm, Hc, Wc) bytes, caller-owned), then one finishing workgroup.
+ * sums fp32 [B][Cm][5] = (sum of (p - t)^2, Dh_b, Dh_n, Dv_b, Dv_n), psnrb fp32 [B]; either may be null.  Nothing outside the outputs and
+ * the workspace is written.  SRK_E_NULL: null planes / workspace, both outputs null.  SRK_E_SHAPE: B outside 1..1024, B Cm >= 65536, a
+ * non-positive extent, Cm * Hc beyond 2^31 - 1, an output or the workspace overlapping an input.  SRK_E_UNSUPPORTED: Hc < 16 or Wc < 16
+ * (no block boundary: the published code divides 0 by 0).  srk_psnrb_workspace returns 0 for all of these.
+ * MS-SSIM, `levels` levels (published: 5, weights 0.0448, 0.2856, 0.3001, 0.2363, 0.1333):
+ *   level s   srk_ssim's map quantities on the current planes: the same 11-tap Gaussian, VALID filter and K, C1 = (0.01 data_range)^2,
+ *             C2 = (0.03 data_range)^2.  Two per-channel means: S = mean of the SSIM map, CS = mean of (2 s12 + C2) / (s11 + s22 + C2)
+ *   between   both images pass through avg_pool2d(kernel 2, stride 2, padding = extent % 2, count_include_pad=True): an odd extent gains
+ *             one line of zeros in front, that cell is still divided by 4, the output extent is (n + n % 2) / 2; a pooled value is
+ *             ((a + b) + (c + d)) * 0.25f, row-major.  Integer planes 0..255 stay exactly representable through four poolings
+ *   score     per channel ms_c = prod_{s < levels - 1} max(CS_s,c, 0)^w_s * max(S_{levels-1},c, 0)^w_{levels-1}; per image the mean over the
+ *             channels.  The product is the caller's (metrics.ms_ssim forms it in host fp64)
+ * srk_msssim: x, y fp32 [B][C][H][W] -> means fp32 [levels][B][C][2] = (S, CS).  One launch per level -- it also writes the pooled planes of
+ * both images for the next level from the tile it holds, each pooled cell by exactly one workgroup -- and one finishing launch.  workspace:
+ * srk_msssim_workspace(B, C, H, W, levels) bytes, caller-owned; in floats, level s = 1 .. levels - 1 in order: the pooled x planes
+ * [B][C][H_s][W_s], then the pooled y planes; behind them the per-tile sums.  Fixed-order sums: two runs give equal bits.
+ * SRK_E_NULL: a null pointer.  SRK_E_SHAPE: B, C outside srk_ssim's limits (B <= 1024, B C < 65536), levels outside 1..5, H or W outside
+ * 1..2^20, data_range <= 0, means or the workspace overlapping an input or each other.  SRK_E_UNSUPPORTED: the smaller side not above
+ * 10 * 2^(levels - 1) (160 for five levels: the coarsest planes must hold the window).  srk_msssim_workspace returns 0 for all of these. */
+int64_t srk_psnrb_workspace(int B, int Cm, int Hc, int Wc);
+int srk_psnrb(const float* planes_pred, const float* planes_target, void* workspace, int B, int Cm, int Hc, int Wc, float* sums, float* psnrb,
+              srk_stream_t stream);
+int64_t srk_msssim_workspace(int B, int C, int H, int W, int levels);
+int srk_msssim(const float* x, const float* y, void* workspace, int B, int C, int H, int W, int levels, float data_range, float* means,
+               srk_stream_t stream);
 /* sum of squares of a flat fp32 gradient, ACCUMULATED into sumsq[0] (for clip_grad_norm_ :170) */
 int srk_grad_sumsq(const float* grads, int64_t n, float* sumsq, srk_stream_t stream);
 /* clip_grad_norm_(max_norm) + AdamW step (:168-171, :303) on flat fp32 buffers.  The clip coefficient is

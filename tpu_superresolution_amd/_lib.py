@@ -143,6 +143,10 @@ _SIGNATURES = {
     "srk_niqe_half_f32": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "srk_niqe_mscn_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "srk_niqe_moments_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "srk_psnrb_workspace": (_i64, [_i, _i, _i, _i]),
+    "srk_psnrb": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "srk_msssim_workspace": (_i64, [_i, _i, _i, _i, _i]),
+    "srk_msssim": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "srk_grad_sumsq": (_i, [_vp, _i64, _vp, _vp]),
     "srk_adamw_clip_step": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _f, _f, _f, _i, _vp, _vp]),
     "srk_adamw_clip_ema_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _f, _f, _f, _i, _f, _vp, _vp]),

@@ -407,6 +407,37 @@ def bench_psnr(ws: torch.Tensor, plane_shape, psnr_sum: Optional[torch.Tensor] =
     return sq, ps
 
 
+def psnrb_planes(planes_pred: torch.Tensor, planes_target: torch.Tensor):
+    """PSNR-B of benchmark-protocol planes (include/srk.h "Full-reference scores"; csrc/fullref.hip): fp32 [B, Cm, Hc, Wc]
+    planes of the restored image and of the target, Hc, Wc >= 16 -> (sums fp32 [B, Cm, 5] = squared error, Dh_b, Dh_n, Dv_b, Dv_n;
+    psnrb fp32 [B]).  Restated from the published algorithm, parity unpinned."""
+    if (planes_pred.shape != planes_target.shape or planes_pred.ndim != 4 or planes_pred.dtype != torch.float32
+            or planes_target.dtype != torch.float32):
+        raise ValueError(f"psnrb: planes must be fp32 [B, Cm, Hc, Wc] of one shape (got {planes_pred.dtype} {tuple(planes_pred.shape)}, "
+                         f"{planes_target.dtype} {tuple(planes_target.shape)})")
+    pp, pt = planes_pred.contiguous(), planes_target.contiguous()
+    B, Cm, Hc, Wc = pp.shape
+    ws = torch.empty(max(4, int(lib().srk_psnrb_workspace(B, Cm, Hc, Wc))), dtype=torch.uint8, device=pp.device)
+    sums = torch.empty((B, Cm, 5), dtype=torch.float32, device=pp.device)
+    out = torch.empty(B, dtype=torch.float32, device=pp.device)
+    check(lib().srk_psnrb(_p(pp), _p(pt), _p(ws), B, Cm, Hc, Wc, _p(sums), _p(out), _stream()))
+    return sums, out
+
+
+def msssim_means(x: torch.Tensor, y: torch.Tensor, levels: int = 5, data_range: float = 255.0) -> torch.Tensor:
+    """The per-level means of MS-SSIM (include/srk.h "Full-reference scores"; csrc/fullref.hip): fp32 [B, C, H, W] images ->
+    fp32 [levels, B, C, 2] = (mean of the SSIM map, mean of its contrast-structure factor) on the 2 x 2-pooled pyramid; one launch per
+    level and one to finish, no host read.  Restated from the published algorithm, parity unpinned."""
+    if x.shape != y.shape or x.ndim != 4 or x.dtype != torch.float32 or y.dtype != torch.float32:
+        raise ValueError(f"msssim: images must be fp32 [B, C, H, W] of one shape (got {x.dtype} {tuple(x.shape)}, {y.dtype} {tuple(y.shape)})")
+    x, y = x.contiguous(), y.contiguous()
+    B, Cc, H, W = x.shape
+    ws = torch.empty(max(4, int(lib().srk_msssim_workspace(B, Cc, H, W, int(levels)))), dtype=torch.uint8, device=x.device)
+    means = torch.empty((int(levels), B, Cc, 2), dtype=torch.float32, device=x.device)
+    check(lib().srk_msssim(_p(x), _p(y), _p(ws), B, Cc, H, W, int(levels), float(data_range), _p(means), _stream()))
+    return means
+
+
 class TensorTable:
     """Host table of a list of fp32 device tensors for the multi-tensor kernels (srk_multi_*): one ctypes array of data pointers per
     role plus the element counts.  Only pointers are kept; the caller keeps the tensors alive until the launches have run."""
