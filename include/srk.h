@@ -167,6 +167,11 @@ int srk_probe_end(double* total_ms, double* flops, double* bytes, int* launches)
  *   caller's workspace (srk_set_wgrad_workspace; the model executor uses a region of its own workspace) and a reduce
  *   kernel adds their sum to dW in a fixed order, or every split adds into dW with fp32 atomics (order-dependent
  *   rounding, ~20 us slower per launch; also what happens when no workspace is registered).
+ *   "wide_head_train" 0 (default) / 1: a SwinIR plan whose 'pixelshuffledirect' head has 17 .. 64 output channels (light x3: 27,
+ *   x4: 48) trains: srk_swinir_forward(training = 1) keeps what the backward reads and srk_swinir_backward runs the head through
+ *   srk_widehead_grad_prep / _wgrad / _dgrad (csrc/headconv_wide.hip); with 0 both calls return SRK_E_UNSUPPORTED for such a head.
+ *   The gradient of the head's output is then [T][round_up(Cout, 16)] fp32 in the workspace: the option changes the workspace
+ *   layout, so set it before the first srk_swinir_workspace_bytes query.  Heads of at most 16 channels are not affected.
  * Unknown names return SRK_E_UNSUPPORTED.
  * Scope: srk_set_option / srk_get_option act on ONE process-wide value per option (every thread reads it, including the autograd
  * engine's backward thread).  A plan carries its own values -- srk_swinir_plan_set_option -- which hold, in a thread-private copy of
@@ -929,6 +934,27 @@ int srk_smallconv_wgrad(const uint16_t* x, const float* gy, float* dw, float* db
                         srk_stream_t stream);
 int srk_smallconv_dgrad(const float* gy, const float* weight, uint16_t* dx, int B, int H, int W, int Cin, int CinP, int Co, int CoP,
                         srk_stream_t stream);
+/* The same three launches for a WIDE one-step head, 17 .. 64 output channels padded to CoP = 32, 48 or 64 (csrc/headconv_wide.hip);
+ * data contracts as above: d_pred fp32 NCHW, gy fp32 [B*H*W][CoP], x / dx bf16 NHWC [..][CinP], parameters fp32 [Co][Cin][3][3].
+ * srk_widehead_grad_prep: the function of srk_img_grad_prep (one fp32 multiply per element: bit-exact; columns >= Cimg*r*r and
+ * everything outside the Hc x Wc crop are zero).  srk_widehead_wgrad: dw and db [Co] are ACCUMULATED; every workgroup sums its run
+ * of pixels in registers and adds it with fp32 atomics, so the rounding of the last bits depends on the order the workgroups finish
+ * in (as the narrow kernel).  srk_widehead_dgrad: dx is WRITTEN, all CinP columns, the pad channels >= Cin as +0.  gy and the
+ * weights enter the matrix cores as the fp32 values they are (v_mfma_f32_*_f32: an fp32 fmaf chain; no hi + lo bf16 split, no split
+ * products); x converts exactly.  Any B, H, W > 0 gives the right answer, odd pixel counts included: the kernels walk flat pixel
+ * indices and mask the taps that leave the image.  srk_widehead_wgrad keeps the x window of a run in LDS and reads x once when
+ * W <= 95 (the light family's 64 x 64 training patches); wider images take the same kernel with the three 66-pixel row segments of
+ * every 64-pixel chunk staged afresh (x read three times; same sums per workgroup).  srk_widehead_dgrad has one path.
+ * SRK_E_NULL for any null pointer (db included); SRK_E_SHAPE unless B, H, W > 0, B*H*W < 2^31, CoP is 32, 48 or 64, and for the prep
+ * 1 <= r <= 8, 1 <= Cimg, Cimg*r*r <= CoP, 0 < Hc <= H*r, 0 < Wc <= W*r (H*r, W*r < 2^31), for the conv gradients 1 <= Co <= CoP,
+ * 1 <= Cin <= CinP, CinP % 64 == 0, CinP <= 256; SRK_E_ALIGN unless x, gy and dx are 16-byte aligned.  All checked on the host before
+ * any HIP call.  srk_img_grad_prep / srk_smallconv_* keep their contract (CoP 4 or 16). */
+int srk_widehead_grad_prep(const float* d_pred, float* gy, int B, int Cimg, int Hc, int Wc, int H, int W, int r, int CoP, float inv_range,
+                           srk_stream_t stream);
+int srk_widehead_wgrad(const uint16_t* x, const float* gy, float* dw, float* db, int B, int H, int W, int Cin, int CinP, int Co, int CoP,
+                       srk_stream_t stream);
+int srk_widehead_dgrad(const float* gy, const float* weight, uint16_t* dx, int B, int H, int W, int Cin, int CinP, int Co, int CoP,
+                       srk_stream_t stream);
 /* conv_first backwards: dw [C][Cin][3][3], db [C] ACCUMULATED from the padded NHWC4 image and gy fp32 [B*H*W][CP].  SRK_E_SHAPE unless
  * B, H, W > 0, 1 <= Cin <= 4, 1 <= C <= CP, C <= 256, CP % 4 == 0; SRK_E_ALIGN unless img4 and gy are 16-byte aligned.  With CP == 192, at
  * least 16384 pixels (a multiple of 32) and a registered workspace (srk_set_wgrad_workspace) the sums are formed in a fixed order. */

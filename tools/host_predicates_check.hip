@@ -1,5 +1,5 @@
-// Edge values for the host argument predicates of csrc/common.h (srk_aligned, srk_ranges_overlap, srk_qkv_layout_ok), as a
-// stand-alone program for a sanitizer build; needs no GPU:
+// Edge values for the host argument predicates of csrc/common.h (srk_aligned, srk_ranges_overlap, srk_qkv_layout_ok, the benchmark-plane shapes,
+// the wide-head shapes srk_widehead_cop_ok / _prep_shape_ok / _conv_shape_ok), as a stand-alone program for a sanitizer build; needs no GPU:
 //   hipcc --offload-arch=gfx950 --cuda-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
 //         -Xarch_host -fno-sanitize-recover=undefined tools/host_predicates_check.hip -o /tmp/host_predicates_check && /tmp/host_predicates_check
 #include <stdio.h>
@@ -51,6 +51,29 @@ int main() {
   EXPECT(srk_bench_plane_dims_ok(1, 1, 1, 1) && srk_bench_plane_dims_ok(1024, 3, 11, 11) && !srk_bench_plane_dims_ok(1025, 3, 11, 11));
   EXPECT(!srk_bench_plane_dims_ok(0, 1, 1, 1) && !srk_bench_plane_dims_ok(1, 0, 1, 1) && !srk_bench_plane_dims_ok(1, 1, 0, 1) && !srk_bench_plane_dims_ok(1, 1, 1, 0));
   EXPECT(srk_bench_plane_dims_ok(1, 1, 0x7fffffff, 0x7fffffff) && !srk_bench_plane_dims_ok(1, 2, 0x40000000, 1) && !srk_bench_plane_dims_ok(1, 0x7fffffff, 0x7fffffff, 1));
+  // wide one-step head backward: the three padded widths and nothing beside them
+  EXPECT(srk_widehead_cop_ok(32) && srk_widehead_cop_ok(48) && srk_widehead_cop_ok(64) && !srk_widehead_cop_ok(16) && !srk_widehead_cop_ok(4));
+  EXPECT(!srk_widehead_cop_ok(0) && !srk_widehead_cop_ok(-32) && !srk_widehead_cop_ok(40) && !srk_widehead_cop_ok(80) && !srk_widehead_cop_ok(0x7fffffff));
+  // gradient prep: the smallest and the widest valid shapes, each clause broken in turn, then the ends of the int range (no product wraps)
+  EXPECT(srk_widehead_prep_shape_ok(1, 1, 1, 1, 1, 1, 1, 32) && srk_widehead_prep_shape_ok(2, 3, 16, 32, 4, 8, 4, 48) && srk_widehead_prep_shape_ok(1, 1, 8, 8, 1, 1, 8, 64));
+  EXPECT(srk_widehead_prep_shape_ok(2, 3, 15, 29, 4, 8, 4, 48) && !srk_widehead_prep_shape_ok(2, 3, 17, 32, 4, 8, 4, 48) && !srk_widehead_prep_shape_ok(2, 3, 16, 33, 4, 8, 4, 48));
+  EXPECT(!srk_widehead_prep_shape_ok(0, 3, 16, 32, 4, 8, 4, 48) && !srk_widehead_prep_shape_ok(2, 0, 16, 32, 4, 8, 4, 48) && !srk_widehead_prep_shape_ok(2, 3, 0, 32, 4, 8, 4, 48));
+  EXPECT(!srk_widehead_prep_shape_ok(2, 3, 16, 0, 4, 8, 4, 48) && !srk_widehead_prep_shape_ok(2, 3, 16, 32, 0, 8, 4, 48) && !srk_widehead_prep_shape_ok(2, 3, 16, 32, 4, -8, 4, 48));
+  EXPECT(!srk_widehead_prep_shape_ok(2, 3, 16, 32, 4, 8, 0, 48) && !srk_widehead_prep_shape_ok(2, 3, 16, 32, 4, 8, 9, 48) && !srk_widehead_prep_shape_ok(2, 4, 16, 32, 4, 8, 4, 48));
+  EXPECT(!srk_widehead_prep_shape_ok(2, 3, 16, 32, 4, 8, 4, 16) && !srk_widehead_prep_shape_ok(2, 3, 16, 32, 4, 8, 4, 56) && !srk_widehead_prep_shape_ok(2, 3, 16, 32, 4, 8, 5, 64));
+  EXPECT(!srk_widehead_prep_shape_ok(2, 0x7fffffff, 16, 32, 4, 8, 4, 48) && !srk_widehead_prep_shape_ok(2, 3, 16, 32, 4, 8, 0x7fffffff, 48));
+  EXPECT(!srk_widehead_prep_shape_ok(0x7fffffff, 3, 16, 32, 4, 8, 4, 48) && !srk_widehead_prep_shape_ok(1, 1, 1, 1, 0x7fffffff, 0x7fffffff, 1, 32));
+  EXPECT(srk_widehead_prep_shape_ok(1, 1, 0x7fffffff, 1, 0x7fffffff, 1, 1, 32) && !srk_widehead_prep_shape_ok(1, 1, 1, 1, 0x40000000, 1, 2, 32));
+  EXPECT(srk_widehead_prep_shape_ok(1, 1, 0x7ffffff8, 1, 0x0fffffff, 1, 8, 64) && !srk_widehead_prep_shape_ok(1, 1, 1, 1, 0x10000000, 1, 8, 64));
+  // the two conv gradients: the narrow family's predicates at the wide widths
+  EXPECT(srk_widehead_conv_shape_ok(1, 1, 1, 1, 64, 1, 32) && srk_widehead_conv_shape_ok(32, 64, 64, 60, 64, 48, 48) && srk_widehead_conv_shape_ok(1, 4, 8, 256, 256, 64, 64));
+  EXPECT(!srk_widehead_conv_shape_ok(0, 4, 8, 60, 64, 48, 48) && !srk_widehead_conv_shape_ok(1, 0, 8, 60, 64, 48, 48) && !srk_widehead_conv_shape_ok(1, 4, -8, 60, 64, 48, 48));
+  EXPECT(!srk_widehead_conv_shape_ok(1, 4, 8, 0, 64, 48, 48) && !srk_widehead_conv_shape_ok(1, 4, 8, 65, 64, 48, 48) && !srk_widehead_conv_shape_ok(1, 4, 8, 60, 60, 48, 48));
+  EXPECT(!srk_widehead_conv_shape_ok(1, 4, 8, 60, 0, 48, 48) && !srk_widehead_conv_shape_ok(1, 4, 8, 60, 320, 48, 48) && !srk_widehead_conv_shape_ok(1, 4, 8, 60, 64, 0, 48));
+  EXPECT(!srk_widehead_conv_shape_ok(1, 4, 8, 60, 64, 49, 48) && !srk_widehead_conv_shape_ok(1, 4, 8, 60, 64, 12, 16) && !srk_widehead_conv_shape_ok(1, 4, 8, 60, 64, 3, 4));
+  EXPECT(!srk_widehead_conv_shape_ok(1, 4, 8, 60, 64, 48, 56) && !srk_widehead_conv_shape_ok(1, 4, 8, 60, 64, 48, 128) && !srk_widehead_conv_shape_ok(1, 4, 8, 60, 64, 48, -48));
+  EXPECT(srk_widehead_conv_shape_ok(1, 0x7fffffff, 1, 60, 64, 48, 48) && !srk_widehead_conv_shape_ok(2, 0x40000000, 1, 60, 64, 48, 48));
+  EXPECT(!srk_widehead_conv_shape_ok(0x7fffffff, 0x7fffffff, 0x7fffffff, 60, 64, 48, 48) && !srk_widehead_conv_shape_ok(1, 4, 8, 0x7fffffff, 64, 48, 48));
   printf("%d failure(s)\n", failures);
   return failures != 0;
 }

@@ -405,6 +405,7 @@ const OptEntry kOptions[] = {
     {"wgrad_stream", [] { return srk_wgrad_stream_enabled(); }, [](int v) { srk_wgrad_stream_enable(v); return (int)SRK_OK; }},
     {"conv_wgrad_taps", [] { return srk_conv_wgrad_taps_mode(); }, [](int v) { srk_conv_wgrad_taps_enable(v); return (int)SRK_OK; }},
     {"conv_wgrad_roll", [] { return srk_conv_wgrad_roll_enabled(); }, [](int v) { srk_conv_wgrad_roll_enable(v); return (int)SRK_OK; }},
+    {"wide_head_train", [] { return srk_wide_head_train_enabled(); }, [](int v) { srk_wide_head_train_enable(v); return (int)SRK_OK; }},
     {"wgrad_partials", [] { return srk_wgrad_partials_enabled(); }, [](int v) { srk_wgrad_partials_enable(v); return (int)SRK_OK; }},
     {"wgrad_stream_rows", [] { return wtune_get(0); },
      [](int v) {

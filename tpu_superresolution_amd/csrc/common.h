@@ -30,7 +30,7 @@ int srk_device_cus();         // multiProcessorCount of the current device (cach
 enum SrkOptId {
   OPT_MLP_FUSED, OPT_MLP_BWD_FUSED, OPT_GEMM_STREAM, OPT_TUNE_BM, OPT_TUNE_KS2, OPT_TUNE_SPLIT, OPT_TUNE_NB, OPT_ATTN_BWD_FUSED,
   OPT_ATTN_FUSED, OPT_BLOCK_LIGHT, OPT_TAPS_ENABLED, OPT_TAPS_DMA, OPT_WGRAD_STREAM, OPT_WGRAD_ROWS, OPT_WGRAD_NT, OPT_WGRAD_W8,
-  OPT_WGRAD_PARTIALS, OPT_MLP_DGELU_STORE, OPT_TAPS_ROLL, SRK_NUM_OPTS
+  OPT_WGRAD_PARTIALS, OPT_MLP_DGELU_STORE, OPT_TAPS_ROLL, OPT_WIDE_HEAD_TRAIN, SRK_NUM_OPTS
 };
 struct SrkOptTls {
   int v[SRK_NUM_OPTS];
@@ -156,6 +156,18 @@ static inline bool srk_tables_shape_ok(int n, int ks, bool has_bank, int n_bank,
   return n >= 1 && srk_psf_ks_ok(ks) && (has_bank ? (n_bank >= 1 && srk_psf_ks_ok(kb) && kb <= ks) : (n_bank == 0 && kb == 0));
 }
 static inline size_t srk_tables_bytes(int n, int ks, size_t elem) { return elem * (size_t)n * (size_t)ks * (size_t)ks; }
+// wide one-step head backward (headconv_wide.hip, srk.h srk_widehead_*): the padded output widths, the shapes the gradient prep takes
+// (the HR extents H r, W r and the pixel count B H W index an int) and the shapes the two conv gradients take
+static inline bool srk_widehead_cop_ok(int CoP) { return CoP == 32 || CoP == 48 || CoP == 64; }
+static inline bool srk_widehead_prep_shape_ok(int B, int Cimg, int Hc, int Wc, int H, int W, int r, int CoP) {
+  return B > 0 && H > 0 && W > 0 && r >= 1 && r <= 8 && (double)B * H * W <= 2147483647.0 && srk_widehead_cop_ok(CoP) && Cimg >= 1 &&
+         Cimg <= CoP && Cimg * r * r <= CoP && (long long)H * r <= 0x7fffffffLL && (long long)W * r <= 0x7fffffffLL && Hc > 0 && Wc > 0 &&
+         Hc <= H * r && Wc <= W * r;
+}
+static inline bool srk_widehead_conv_shape_ok(int B, int H, int W, int Cin, int CinP, int Co, int CoP) {
+  return B > 0 && H > 0 && W > 0 && (double)B * H * W <= 2147483647.0 && srk_widehead_cop_ok(CoP) && Co >= 1 && Co <= CoP && Cin >= 1 &&
+         Cin <= CinP && CinP % 64 == 0 && CinP <= 256;
+}
 
 // ---------------------------------------------------------------------------------------------
 // bf16 helpers (device)

@@ -49,6 +49,12 @@ int srk_launch_stem_wgrad(const float* in, const float* gy, float* dW, float* db
 int srk_launch_img_grad_prep(const float* dpred, float* gy, int B, int Cimg, int Hc, int Wc, int H, int W, int r, int CoP, float inv_range, hipStream_t stream);
 int srk_launch_smallconv_dgrad(const float* gy, const float* wgt, bf16_t* dx, int B, int H, int W, int Cin, int CinP, int Co, int CoP, hipStream_t stream);
 int srk_launch_smallconv_wgrad(const bf16_t* x, const float* gy, float* dW, float* db, int B, int H, int W, int Cin, int CinP, int Co, int CoP, hipStream_t stream);
+// headconv_wide.hip: the same two gradients for a one-step head of 17 .. 64 output channels (CoP 32, 48 or 64; fp32-input MFMA), and the
+// plan option that lets the SwinIR executor train through such a head
+int srk_launch_widehead_dgrad(const float* gy, const float* wgt, bf16_t* dx, int B, int H, int W, int Cin, int CinP, int Co, int CoP, hipStream_t stream);
+int srk_launch_widehead_wgrad(const bf16_t* x, const float* gy, float* dW, float* db, int B, int H, int W, int Cin, int CinP, int Co, int CoP, hipStream_t stream);
+void srk_wide_head_train_enable(int on);
+int srk_wide_head_train_enabled();
 // workgroups per image of the PSNR partial pass (8192 elements each, at most 64)
 inline int srk_batch_psnr_chunks(long long per_image) {
   const long long c = (per_image + 8191) / 8192;

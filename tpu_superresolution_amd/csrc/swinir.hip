@@ -252,8 +252,16 @@ struct PlanOptionScope {
   PlanOptionScope& operator=(const PlanOptionScope&) = delete;
 };
 
+// one-step head wider than the 16 output channels the backward's small-conv kernels are built for: inference only, unless the plan
+// option "wide_head_train" sends its backward through headconv_wide.hip (17 .. 64 channels, gyimg padded to a multiple of 16)
+bool wide_direct_head(const srk_swinir_plan* p) {
+  return p->cfg.upsampler == SRK_UPSAMPLER_PIXELSHUFFLEDIRECT && p->up_direct.Cout > 16;
+}
+bool wide_head_trains(const srk_swinir_plan* p) { return wide_direct_head(p) && p->up_direct.Cout <= 64 && srk_wide_head_train_enabled() != 0; }
+int wide_head_cop(const srk_swinir_plan* p) { return round_up(p->up_direct.Cout, 16); }
+
 // option values that change the workspace layout: a forward re-lays the workspace out when they differ from the laid-out ones
-int layout_option_sig() { return srk_attn_bwd_fused_enabled() | (srk_attn_fused_mode() << 1); }
+int layout_option_sig() { return srk_attn_bwd_fused_enabled() | (srk_attn_fused_mode() << 1) | (srk_wide_head_train_enabled() << 8); }
 
 void layout_workspace(const srk_swinir_plan* p, Workspace& w, int B, int H0, int W0, int training) {
   w = Workspace();
@@ -415,7 +423,7 @@ void layout_workspace(const srk_swinir_plan* p, Workspace& w, int B, int H0, int
       }
       w.gyimg = a.get("gyimg", px * 4 * 4);
     } else {
-      w.gyimg = a.get("gyimg", T * 16 * 4);
+      w.gyimg = a.get("gyimg", T * (wide_head_trains(p) ? (size_t)wide_head_cop(p) : (size_t)16) * 4);
     }
     w.gstage_w = a.get("gstage_w", (size_t)p->packed_elems * 4);
     w.gstage_side = a.get("gstage_side", (size_t)p->side_floats * 4);
@@ -462,11 +470,6 @@ int run_conv(const Ctx& c, const ConvW& cw, int loader, int ep, const bf16_t* in
   g.flops = 2.0 * g.M * cw.Cout * cw.Cin * 9;
   if (g.ldo == 0) g.ldo = cw.NP;
   return srk_launch_gemm(loader, ep, g, c.stream);
-}
-
-// one-step head wider than the 16 output channels the backward's small-conv kernels are built for: inference only
-bool wide_direct_head(const srk_swinir_plan* p) {
-  return p->cfg.upsampler == SRK_UPSAMPLER_PIXELSHUFFLEDIRECT && p->up_direct.Cout > 16;
 }
 
 }  // namespace
@@ -926,7 +929,7 @@ int srk_swinir_forward(srk_swinir_plan* plan, const float* params, const void* p
   PlanOptionScope opts(plan);
   SRK_REQUIRE(B > 0 && H0 > 0 && W0 > 0, SRK_E_SHAPE, "forward: bad shape B=%d H=%d W=%d", B, H0, W0);
   srk_swinir_plan* p = plan;
-  SRK_REQUIRE(!(training && wide_direct_head(p)), SRK_E_UNSUPPORTED,
+  SRK_REQUIRE(!(training && wide_direct_head(p) && !wide_head_trains(p)), SRK_E_UNSUPPORTED,
               "forward: a 'pixelshuffledirect' head with upscale^2 * in_chans = %d > 16 is inference-only (the backward's small-conv "
               "kernels cover 16 output channels); call with training = 0", p->up_direct.Cout);
   Workspace& w = p->ws;
@@ -1102,7 +1105,7 @@ int srk_swinir_backward(srk_swinir_plan* plan, const float* params, const void* 
   SRK_REQUIRE(plan && params && packed && grads && d_y && workspace, SRK_E_NULL, "backward: null argument");
   PlanOptionScope opts(plan);
   srk_swinir_plan* p = plan;
-  SRK_REQUIRE(!wide_direct_head(p), SRK_E_UNSUPPORTED,
+  SRK_REQUIRE(!wide_direct_head(p) || wide_head_trains(p), SRK_E_UNSUPPORTED,
               "backward: a 'pixelshuffledirect' head with upscale^2 * in_chans = %d > 16 is inference-only", p->up_direct.Cout);
   Workspace& w = p->ws;
   SRK_REQUIRE(w.B == B && w.H0 == H0 && w.W0 == W0 && w.training == 1, SRK_E_STATE,
@@ -1213,10 +1216,18 @@ int srk_swinir_backward(srk_swinir_plan* plan, const float* params, const void* 
       } else {
         // 'pixelshuffledirect' (s*s*in_chans output channels) and the denoising head (s == 1; its "+ x" has no parameters)
         const ConvW& cu = p->up_direct;
+        if (wide_head_trains(p)) {               // 17 .. 64 output channels: the fp32-input MFMA gradients of headconv_wide.hip
+          const int CoP = wide_head_cop(p);
+          SRK_REQUIRE(w.opt_sig == layout_option_sig(), SRK_E_STATE, "backward: option wide_head_train changed since the training forward");
+          RUN(srk_launch_img_grad_prep(d_y, c.at<float>(w.gyimg), B, p->Cimg, H0 * s, W0 * s, H, W, s, CoP, inv_range, st));
+          RUN(srk_launch_widehead_wgrad(c.at<bf16_t>(w.fb), c.at<float>(w.gyimg), grads + cu.w, grads + cu.b, B, H, W, C, CP, cu.Cout, CoP, st));
+          RUN(srk_launch_widehead_dgrad(c.at<float>(w.gyimg), params + cu.w, c.at<bf16_t>(w.gfb), B, H, W, C, CP, cu.Cout, CoP, st));
+        } else {
         RUN(srk_launch_img_grad_prep(d_y, c.at<float>(w.gyimg), B, p->Cimg, H0 * s, W0 * s, H, W, s, 16, inv_range, st));
         RUN(srk_launch_smallconv_wgrad(c.at<bf16_t>(w.fb), c.at<float>(w.gyimg), grads + cu.w, grads + cu.b, B, H, W, C, CP,
                                        cu.Cout, 16, st));
         RUN(srk_launch_smallconv_dgrad(c.at<float>(w.gyimg), params + cu.w, c.at<bf16_t>(w.gfb), B, H, W, C, CP, cu.Cout, 16, st));
+        }
       }
       // conv_after_body (gfb also feeds the long skip into f0, consumed by the head segment)
       {

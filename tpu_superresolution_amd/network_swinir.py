@@ -407,6 +407,36 @@ class SwinIR(nn.Module):
         self._small_window_training = True
         return self
 
+    # -- training through a wide one-step head (opt-in) -----------------------------------------------------------
+    def enable_wide_head_training(self):
+        """Opt in to training a 'pixelshuffledirect' head with 17..64 output channels (SwinIR-light x3: 27, x4: 48): sets the plan
+        option "wide_head_train", after which the engine keeps what the head's backward reads and runs it through the fp32-input
+        MFMA kernels of csrc/headconv_wide.hip.  The option changes the workspace layout, so an existing workspace is dropped.  Eval /
+        no_grad forwards give the same bits as before.  A no-op for heads of at most 16 channels (they train on the narrow kernels
+        either way).  Raises SrkUnsupported, with the reason, for what it does not cover.  Returns self."""
+        head = self.upscale ** 2 * self.in_chans
+        if self.upsampler != 'pixelshuffledirect':
+            raise SrkUnsupported(f"enable_wide_head_training: upsampler '{self.upsampler}' has no one-step head (only 'pixelshuffledirect' "
+                                 "has one; the other heads train without this call)")
+        if head > 64:
+            raise SrkUnsupported(f"enable_wide_head_training: upscale^2 * in_chans = {head} > 64 output channels; the wide head kernels "
+                                 "cover 17..64")
+        if self.window_size != 8 or getattr(self, "_small_window_training", False):
+            raise SrkUnsupported(f"enable_wide_head_training: window_size = {self.window_size} runs the host-orchestrated passes, whose shared "
+                                 "tail (host_pass.tail_forward) stops at 16 head channels; the wide head trains with window_size 8 on the engine")
+        if head <= 16:
+            return self
+        if self._plan is None:
+            opts = dict(getattr(self, "plan_options", None) or {})
+            opts["wide_head_train"] = 1
+            self.plan_options = opts
+        else:
+            self._plan.set_option("wide_head_train", 1)
+            if getattr(self, "_engine", None) is not None:
+                self._engine.workspace = None          # laid out without the wide gyimg
+        self._wide_head_training = True
+        return self
+
     def draw_drop_path(self, B: int, device) -> Optional[torch.Tensor]:
         """DropPath factors [n_blocks][2][B] of an enabled small-window model in train mode (``_drop_scale``), else None;
         ``training.GraphedTrainStep`` draws them outside its graph into ``_drop_override``."""
@@ -457,7 +487,8 @@ class SwinIR(nn.Module):
             return swinir_w16.forward(self, x)
         anchor = next((p for p in self.parameters() if p.requires_grad), None)
         needs_grad = torch.is_grad_enabled() and anchor is not None
-        if needs_grad and self.upsampler == 'pixelshuffledirect' and self.upscale ** 2 * self.in_chans > 16:
+        if (needs_grad and self.upsampler == 'pixelshuffledirect' and self.upscale ** 2 * self.in_chans > 16
+                and not getattr(self, "_wide_head_training", False)):
             raise SrkUnsupported(f"SwinIR 'pixelshuffledirect' with upscale^2 * in_chans = {self.upscale ** 2 * self.in_chans} > 16 on the HIP "
                                  "path is inference-only: call it under torch.no_grad() (the backward's head kernels cover 16 output channels)")
         eng = self._bind(x.device)
