@@ -495,12 +495,12 @@ def test_options_are_process_wide_with_per_plan_values():
 
 
 def test_batched_weight_packing_equals_one_tensor_at_a_time():
-    """hat_arch.batched_pack: the packed (bf16 / padded / permuted / transposed) weights of HAT, DAT (inference and training subsets) and
-    SwinIR window-16 built by one stack + scatter + cast per weight kind are bit-identical to the tensor-by-tensor pack (pure torch: runs
-    on the CPU)."""
+    """packing.batched_pack: the packed (bf16 / padded / permuted / transposed) weights of HAT, DAT (inference and training subsets) and
+    SwinIR (window 16 forward, window 7 transposed) built by one stack + scatter + cast per weight kind are bit-identical to the
+    tensor-by-tensor pack (pure torch: runs on the CPU)."""
     import torch
     import tpu_superresolution_amd as T
-    from tpu_superresolution_amd import dat_arch, dat_train, hat_arch as ha, hat_train, swinir_w16
+    from tpu_superresolution_amd import dat_train, hat_train, packing, swinir_small_train, swinir_w16
 
     class Eager:                      # a context whose helpers run eagerly (no active packer)
         def __enter__(self):
@@ -514,15 +514,12 @@ def test_batched_weight_packing_equals_one_tensor_at_a_time():
 
     def both(fn):
         a = fn()
-        mods = (ha, dat_arch, swinir_w16)
-        real = ha.batched_pack
-        for mod in mods:
-            mod.batched_pack = Eager
+        real = packing.batched_pack
+        packing.batched_pack = Eager
         try:
             b = fn()
         finally:
-            for mod in mods:
-                mod.batched_pack = real
+            packing.batched_pack = real
         assert a.keys() == b.keys()
         for k in a:
             assert isinstance(a[k], torch.Tensor), (k, type(a[k]))
@@ -536,35 +533,37 @@ def test_batched_weight_packing_equals_one_tensor_at_a_time():
     d = T.DAT(img_size=32, in_chans=3, embed_dim=48, split_size=[8, 32], depth=[3, 2], num_heads=[4, 4], expansion_factor=2.0, upscale=2, img_range=1.0)
     s = T.SwinIR(img_size=32, in_chans=3, embed_dim=24, depths=(2, 2), num_heads=(2, 2), window_size=16, mlp_ratio=2, img_range=1.0, upscale=2,
                  upsampler="pixelshuffle")
-
-    def reset(obj, *names):
-        for n in names:
-            setattr(obj, n, None)
+    s7 = T.SwinIR(img_size=28, in_chans=3, embed_dim=24, depths=(2, 2), num_heads=(2, 2), window_size=7, mlp_ratio=2, img_range=1.0, upscale=2,
+                  upsampler="pixelshuffle")
 
     def hat_p():
-        reset(m, "_packed")
+        packing.drop_packs(m)
         return dict(m._pack(dev))
 
     def hat_pt():
-        reset(m, "_packedT")
+        packing.drop_packs(m)
         return dict(hat_train.pack_transposed(m, dev))
 
     def dat_p(train):
         def f():
-            reset(d, "_packed")
+            packing.drop_packs(d)
             return dict(d._pack(dev, train))
         return f
 
     def dat_pt():
-        reset(d, "_packedT")
+        packing.drop_packs(d)
         return dict(dat_train.pack_train(d, dev))
 
     def w16_p():
-        reset(s, "_w16_packed")
+        packing.drop_packs(s)
         return dict(swinir_w16.pack(s, dev))
 
+    def ws_pt():
+        packing.drop_packs(s7)
+        return dict(swinir_small_train.pack_transposed(s7, dev))
+
     assert both(hat_p) == 93 and both(hat_pt) == 37 and both(dat_p(False)) == 131 and both(dat_p(True)) == 73 and both(dat_pt) == 58
-    assert both(w16_p) == 45
+    assert both(w16_p) == 45 and both(ws_pt) == 21
 
 
 def test_zero_arena_serves_the_second_pass_from_one_buffer():
@@ -644,11 +643,11 @@ def test_grad_sink_hands_every_gradient_over_once_in_creation_order():
 
 
 def test_unpack_inverts_pack_for_linear_and_conv_weights():
-    """host_pass._unpack_linear / _unpack_conv give back what hat_arch._pack_linear / _pack_conv packed -- plain, through the head / qkv /
+    """host_pass._unpack_linear / _unpack_conv give back what packing._pack_linear / _pack_conv packed -- plain, through the head / qkv /
     PixelShuffle index maps and transposed, at a width that is no multiple of 64 (C = 24, 2 heads, r = 3); integer-valued weights, so the
     bf16 packed copy is exact and the comparison is torch.equal."""
     import torch
-    from tpu_superresolution_amd import hat_arch as ha
+    from tpu_superresolution_amd import packing as ha
     from tpu_superresolution_amd.host_pass import _unpack_conv, _unpack_linear
     dev = torch.device("cpu")
     gen = torch.Generator().manual_seed(0)

@@ -55,7 +55,7 @@ def _block_weights(Cdim, nH, hid, seed):
 @pytest.mark.parametrize("dims", [(60, 6, 120), (48, 6, 96)])
 def test_whole_block_kernel_matches_oracle_block(shift, dims):
     from tpu_superresolution_amd._lib import check, lib
-    from tpu_superresolution_amd.hat_arch import _head_map, _pack_linear, _pack_vec
+    from tpu_superresolution_amd.packing import _head_map, _pack_linear, _pack_vec
     Cdim, nH, hid = dims
     dh = Cdim // nH
     B, H, W = 3, 24, 40                                   # 15 windows per image; masked border windows when shifted

@@ -405,7 +405,7 @@ def test_dat_channel_interaction_kernels_vs_autograd(B, C, S, nH):
     dat_arch.py:315-321 on a 1 x 1 map with BatchNorm batch statistics): gate, running buffers, all six parameter gradients and the
     pooled gradient, through the head-padded channel layout."""
     from tpu_superresolution_amd import dat_train as DT
-    from tpu_superresolution_amd import hat_arch as ha
+    from tpu_superresolution_amd import packing as ha
     check, L = _lib()
     g = torch.Generator().manual_seed(B * 1000 + C)
     dh = C // nH
@@ -603,6 +603,43 @@ def test_dat_train_step_pixelshuffledirect_vs_oracle():
     loss, yo, grads, _ = DO.loss_and_grads(sd, cfg, x, t)
     assert float((y.detach().cpu() - yo).abs().max()) <= 2e-2 * float(yo.abs().max())
     _check_grads(m, grads)
+
+
+def test_dat_train_step_packs_each_dictionary_once():
+    """A DAT train step (forward + backward + AdamW) enters the batched packer exactly twice: once for the `train` pack, once for `T`.
+    The training pack reads no buffer, so the BatchNorm counters that every training forward bumps do not invalidate it and the backward
+    gets the forward's pack.  (While the pack was keyed on the buffers' versions too, the same step entered the packer three times: the
+    backward rebuilt the training pack.)  Counts only: loss and gradients of this step are checked by the golden tests above."""
+    from test_oracle_golden import DAT_TINY
+    from tpu_superresolution_amd import packing
+    cfg = DO.DATConfig(**dict(DAT_TINY, depth=(2,), num_heads=(4,)))
+    m = _train_model(cfg, DO.random_state_dict(cfg, seed=23, scale=1.0))
+    assert any(isinstance(mod, torch.nn.BatchNorm2d) and mod.track_running_stats for mod in m.modules())
+    opt = torch.optim.AdamW(m.parameters(), lr=1e-4, weight_decay=0.0)
+    gen = torch.Generator().manual_seed(6)
+    x, t = torch.rand(2, 3, 32, 32, generator=gen).cuda(), torch.rand(2, 3, 64, 64, generator=gen).cuda()
+    entered = []
+
+    class Counting(packing.batched_pack):
+        def __enter__(self):
+            entered.append(1)
+            return super().__enter__()
+
+    real = packing.batched_pack
+    packing.batched_pack = Counting
+    try:
+        per_step = []
+        for _ in range(2):
+            before = len(entered)
+            opt.zero_grad(set_to_none=True)
+            F.l1_loss(m(x), t).backward()
+            opt.step()
+            per_step.append(len(entered) - before)
+    finally:
+        packing.batched_pack = real
+    print(f"packer entries per step: {per_step}")
+    assert per_step == [2, 2]
+    assert set(m.__dict__["_packs"]) == {"train", "T"}
 
 
 def test_graphed_train_step_matches_eager_steps():

@@ -224,7 +224,7 @@ def test_bn_frozen_coefficient_kernels_vs_fp64(Cn, ld, padded, R):
     partial rows.  Bounds: a handful of fp32 roundings on the forward (1e-6 relative to the magnitudes that enter), R + 4 roundings on the
     sums (eps = 6e-8 each, relative to the sum of the absolute terms).  Guard rows around both outputs; coef rows are ld wide, only the
     first Cn columns are written."""
-    from tpu_superresolution_amd import hat_arch as ha
+    from tpu_superresolution_amd import packing as ha
     check, L = _lib()
     g = torch.Generator().manual_seed(Cn + R)
     dev = torch.device("cuda")
@@ -290,7 +290,7 @@ def test_channel_interaction_frozen_kernels_vs_autograd(B):
     gradients (the bias in front of the BatchNorm has a real gradient here) and the pooled gradient, through the head-padded layout; no
     buffer written; guard rows around every output.  Bounds as test_dat_channel_interaction_kernels_vs_autograd."""
     from tpu_superresolution_amd import dat_train as DT
-    from tpu_superresolution_amd import hat_arch as ha
+    from tpu_superresolution_amd import packing as ha
     check, L = _lib()
     C, S, nH = 180, 22, 6
     g = torch.Generator().manual_seed(B * 1000 + C)

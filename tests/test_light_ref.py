@@ -50,7 +50,7 @@ def test_composed_restatement_is_the_oracle_block(c):
 
 
 def test_packing_is_the_projects_packing():
-    from tpu_superresolution_amd.hat_arch import _head_map, _pack_linear, _pack_vec
+    from tpu_superresolution_amd.packing import _head_map, _pack_linear, _pack_vec
     for C, dh, hid in L.WIDTHS:
         c = L.LCase(C, dh, hid, 1, 8, 8, 0)
         sd = L.make_weights(c)

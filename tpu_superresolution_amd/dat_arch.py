@@ -30,7 +30,9 @@ import torch.nn as nn
 
 from . import _lib, host_pass as hp, ops
 from ._lib import SrkUnsupported, check, lib
-from .hat_arch import Upsample, _cached_map, _gemm, _head_map, _holder_forward, _pack_conv, _pack_linear, _pack_vec, _qkv_rows, _rup, batched_pack
+from .hat_arch import Upsample, _holder_forward
+from .host_pass import _gemm
+from .packing import _cached_map, _head_map, _pack_conv, _pack_linear, _pack_vec, _rup, cached_pack, pack_attn
 
 
 class UpsampleOneStep(nn.Sequential):
@@ -119,6 +121,13 @@ def _fc1_rows(hid: int, half: int, HPh: int, device) -> torch.Tensor:
         rows = torch.arange(hid, device=device)
         return torch.where(rows < half, rows, rows - half + HPh)
     return _cached_map(("fc1", hid, half, HPh, str(device)), make)
+
+
+def _dw9(conv, rows, NP: int, device) -> torch.Tensor:
+    """depth-wise 3x3 weight [C][1][3][3] -> fp32 [NP][9], channel c in row rows[c]"""
+    w9 = torch.zeros(NP, 9, device=device)
+    w9[rows] = conv.weight.float().reshape(-1, 9)
+    return w9
 
 
 def is_shifted(rg_idx: int, b_idx: int) -> bool:
@@ -244,9 +253,6 @@ class DAT(nn.Module):
         elif upsampler == 'pixelshuffledirect':
             self.upsample = UpsampleOneStep(upscale, embed_dim, in_chans, (img_size, img_size))
         self.apply(self._init_weights)
-        self._packed: Optional[Dict[str, torch.Tensor]] = None
-        self._packed_version = -1
-        self._packed_device = None
 
     def _init_weights(self, m):
         if isinstance(m, nn.Linear):
@@ -279,78 +285,68 @@ class DAT(nn.Module):
 
     def _pack(self, device, for_training: bool = False) -> Dict[str, torch.Tensor]:
         """for_training: only what the training forward / backward read (no BatchNorm folds, no dense position bias: train mode
-        normalises with batch statistics and evaluates the bias MLP under autograd)."""
-        ver = sum(p._version for p in self.parameters()) + sum(b._version for b in self.buffers())
-        key = (ver, bool(for_training))
-        if self._packed is not None and self._packed_version == key and self._packed_device == device:
-            return self._packed
+        normalises with batch statistics and evaluates the bias MLP under autograd).  That pack reads no buffer; the inference pack
+        folds the BatchNorm running statistics, so the buffers' versions are part of its key."""
+        return cached_pack(self, "train" if for_training else "infer", device, lambda P: self._fill_pack(P, device, for_training),
+                           buffers=not for_training)
+
+    def _fill_pack(self, P: dict, device, for_training: bool) -> None:
         C_, CP = self.embed_dim, _rup(self.embed_dim, 64)
         hid = int(C_ * self.expansion_factor)
         half = hid // 2
         HPh = _rup(half, 64)
-        P: Dict[str, torch.Tensor] = {}
 
         def bn_fold(bn):
             s = (bn.weight / torch.sqrt(bn.running_var + bn.eps)).float()
             return s, (bn.bias - bn.running_mean * s).float()
 
-        with torch.no_grad(), batched_pack() as pk:
-            for li, layer in enumerate(self.layers):
-                nH = self.heads[li]
-                dh, CA = C_ // nH, nH * 32
-                hm = _head_map(nH, dh, device)
-                qkv_rows = _qkv_rows(nH, dh, device)
-                for bi, blk in enumerate(layer.blocks):
-                    pre = f"{li}.{bi}."
-                    at = blk.attn
-                    P[pre + "Wqkv"] = _pack_linear(at.qkv.weight, 3 * CA, CP, row_map=qkv_rows)
-                    P[pre + "bqkv"] = _pack_vec(at.qkv.bias, 3 * CA, row_map=qkv_rows, device=device)
-                    P[pre + "Wproj"] = _pack_linear(at.proj.weight, CP, CA, col_map=hm)
-                    P[pre + "bproj"] = _pack_vec(at.proj.bias, CP)
-                    # DW-conv branch: conv bias + BatchNorm(eval) folded into scale / shift, channels scattered to the head-padded layout
-                    w9 = torch.zeros(CA, 9, device=device)
-                    w9[hm] = at.dwconv[0].weight.float().reshape(C_, 9)
-                    P[pre + "dw_w"] = w9.contiguous()
-                    if for_training:
-                        self._pack_sgfn(P, pre, blk, hid, half, HPh, device)
-                        continue
-                    s, t = bn_fold(at.dwconv[1])
-                    P[pre + "dw_s"] = _pack_vec(s, CA, row_map=hm)
-                    P[pre + "dw_t"] = _pack_vec(t + at.dwconv[0].bias.float() * s, CA, row_map=hm)
-                    ci = at.channel_interaction
-                    s, t = bn_fold(ci[2])
-                    S1 = ci[1].weight.shape[0]
-                    w1 = torch.zeros(S1, CA, device=device)
-                    w1[:, hm] = ci[1].weight.float().reshape(S1, C_) * s[:, None]
-                    P[pre + "ci_w1"] = w1.contiguous()
-                    P[pre + "ci_b1"] = (ci[1].bias.float() * s + t).contiguous()
-                    w2 = torch.zeros(CA, S1, device=device)
-                    w2[hm] = ci[4].weight.float().reshape(C_, S1)
-                    P[pre + "ci_w2"] = w2.contiguous()
-                    P[pre + "ci_b2"] = _pack_vec(ci[4].bias, CA, row_map=hm)
-                    si = at.spatial_interaction
-                    s, t = bn_fold(si[1])
-                    S2 = si[0].weight.shape[0]
-                    w0 = torch.zeros(S2, CA, device=device)
-                    w0[:, hm] = si[0].weight.float().reshape(S2, C_) * s[:, None]
-                    P[pre + "si_w0"] = w0.contiguous()
-                    P[pre + "si_b0"] = (si[0].bias.float() * s + t).contiguous()
-                    P[pre + "si_w3"] = si[3].weight.float().reshape(S2).contiguous()
-                    P[pre + "si_b3"] = si[3].bias.float().reshape(1).contiguous()          # read by the kernel from device memory
-                    if bi % 2 == 0:
-                        for br, sa in enumerate(at.attns):      # dense bias of the branch: pos MLP on the offsets, gathered by the index
-                            pos = sa.pos(sa.rpe_biases.float())
-                            N = sa.H_sp * sa.W_sp
-                            P[pre + f"bias{br}"] = pos[sa.relative_position_index.reshape(-1)].reshape(N, N, -1).permute(2, 0, 1).float().contiguous()
-                    else:
-                        P[pre + "temp"] = at.temperature.float().reshape(-1).contiguous()
+        for li, layer in enumerate(self.layers):
+            nH = self.heads[li]
+            dh, CA = C_ // nH, nH * 32
+            hm = _head_map(nH, dh, device)
+            for bi, blk in enumerate(layer.blocks):
+                pre = f"{li}.{bi}."
+                at = blk.attn
+                pack_attn(P, pre, at.qkv, at.proj, nH, dh, CP, device)
+                # DW-conv branch: conv bias + BatchNorm(eval) folded into scale / shift, channels scattered to the head-padded layout
+                P[pre + "dw_w"] = _dw9(at.dwconv[0], hm, CA, device)
+                if for_training:
                     self._pack_sgfn(P, pre, blk, hid, half, HPh, device)
-                P[f"{li}.Wconv"] = _pack_conv(layer.conv.weight, CP, CP)
-                P[f"{li}.bconv"] = _pack_vec(layer.conv.bias, CP)
-            hp.pack_tail(P, self, CP, device)
-            pk.resolve(P)
-        self._packed, self._packed_version, self._packed_device = P, key, device
-        return P
+                    continue
+                s, t = bn_fold(at.dwconv[1])
+                P[pre + "dw_s"] = _pack_vec(s, CA, row_map=hm)
+                P[pre + "dw_t"] = _pack_vec(t + at.dwconv[0].bias.float() * s, CA, row_map=hm)
+                ci = at.channel_interaction
+                s, t = bn_fold(ci[2])
+                S1 = ci[1].weight.shape[0]
+                w1 = torch.zeros(S1, CA, device=device)
+                w1[:, hm] = ci[1].weight.float().reshape(S1, C_) * s[:, None]
+                P[pre + "ci_w1"] = w1.contiguous()
+                P[pre + "ci_b1"] = (ci[1].bias.float() * s + t).contiguous()
+                w2 = torch.zeros(CA, S1, device=device)
+                w2[hm] = ci[4].weight.float().reshape(C_, S1)
+                P[pre + "ci_w2"] = w2.contiguous()
+                P[pre + "ci_b2"] = _pack_vec(ci[4].bias, CA, row_map=hm)
+                si = at.spatial_interaction
+                s, t = bn_fold(si[1])
+                S2 = si[0].weight.shape[0]
+                w0 = torch.zeros(S2, CA, device=device)
+                w0[:, hm] = si[0].weight.float().reshape(S2, C_) * s[:, None]
+                P[pre + "si_w0"] = w0.contiguous()
+                P[pre + "si_b0"] = (si[0].bias.float() * s + t).contiguous()
+                P[pre + "si_w3"] = si[3].weight.float().reshape(S2).contiguous()
+                P[pre + "si_b3"] = si[3].bias.float().reshape(1).contiguous()          # read by the kernel from device memory
+                if bi % 2 == 0:
+                    for br, sa in enumerate(at.attns):      # dense bias of the branch: pos MLP on the offsets, gathered by the index
+                        pos = sa.pos(sa.rpe_biases.float())
+                        N = sa.H_sp * sa.W_sp
+                        P[pre + f"bias{br}"] = pos[sa.relative_position_index.reshape(-1)].reshape(N, N, -1).permute(2, 0, 1).float().contiguous()
+                else:
+                    P[pre + "temp"] = at.temperature.float().reshape(-1).contiguous()
+                self._pack_sgfn(P, pre, blk, hid, half, HPh, device)
+            P[f"{li}.Wconv"] = _pack_conv(layer.conv.weight, CP, CP)
+            P[f"{li}.bconv"] = _pack_vec(layer.conv.bias, CP)
+        hp.pack_tail(P, self, CP, device)
 
     def _pack_sgfn(self, P, pre, blk, hid, half, HPh, device):
         """SGFN: the two halves of the hidden vector each padded to HPh columns"""
@@ -361,9 +357,7 @@ class DAT(nn.Module):
         P[pre + "b1"] = _pack_vec(f.fc1.bias, 2 * HPh, row_map=rows)
         P[pre + "W2"] = _pack_linear(f.fc2.weight, CP, HPh)
         P[pre + "b2"] = _pack_vec(f.fc2.bias, CP)
-        sg9 = torch.zeros(HPh, 9, device=device)
-        sg9[:half] = f.sg.conv.weight.float().reshape(half, 9)
-        P[pre + "sg_w"] = sg9.contiguous()
+        P[pre + "sg_w"] = _dw9(f.sg.conv, slice(half), HPh, device)
         P[pre + "sg_s"] = _pack_vec(torch.ones(half, device=device), HPh)
         P[pre + "sg_t"] = _pack_vec(f.sg.conv.bias, HPh)
 

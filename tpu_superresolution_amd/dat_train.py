@@ -32,11 +32,11 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib, hat_arch as ha, host_pass as hp, ops
+from . import _lib, host_pass as hp, ops
 from ._lib import check, lib
-from .dat_arch import _fc1_rows
-from .hat_arch import _cached_map, _gemm, _head_map, _pack_conv_T, _pack_linear, _pack_vec, _qkv_rows, _rup
-from .host_pass import GradSink, _arange, _full
+from .dat_arch import _dw9, _fc1_rows
+from .host_pass import GradSink, _arange, _full, _gemm
+from .packing import _cached_map, _head_map, _pack_conv_T, _pack_linear, _pack_vec, _qkv_rows, _rup, cached_pack, pack_attn_T
 
 EPS = 1e-5
 
@@ -231,49 +231,39 @@ def _dense_bias(sa) -> torch.Tensor:
 
 # ---- packed operands of the backward pass -----------------------------------------------------------------------------------------------
 def pack_train(m, device) -> Dict[str, torch.Tensor]:
-    ver = sum(p._version for p in m.parameters())
-    if getattr(m, "_packedT", None) is not None and m._packedT_version == ver and m._packedT_device == device:
-        return m._packedT
+    return cached_pack(m, "T", device, lambda P: _fill_pack_train(P, m, device))
+
+
+def _fill_pack_train(P: dict, m, device) -> None:
     C_, CP = m.embed_dim, _rup(m.embed_dim, 64)
     hid = int(C_ * m.expansion_factor)
     half = hid // 2
     HPh = _rup(half, 64)
-    P: Dict[str, torch.Tensor] = {}
-    with torch.no_grad(), ha.batched_pack() as pk:      # the one name looked up on the module at every call (the packing test swaps it)
-        rows = _fc1_rows(hid, half, HPh, device)
-        P["fc1_rows"] = rows
-        for li, layer in enumerate(m.layers):
-            nH = m.heads[li]
-            dh, CA = C_ // nH, nH * 32
-            hm = _head_map(nH, dh, device)
-            qkv_rows = _qkv_rows(nH, dh, device)
-            for bi, blk in enumerate(layer.blocks):
-                pre = f"{li}.{bi}."
-                at = blk.attn
-                P[pre + "WqkvT"] = _pack_linear(at.qkv.weight.t(), CP, 3 * CA, col_map=qkv_rows)
-                P[pre + "WprojT"] = _pack_linear(at.proj.weight.t(), CA, CP, row_map=hm)
-                P[pre + "W1T"] = _pack_linear(blk.ffn.fc1.weight.t(), CP, 2 * HPh, col_map=rows)
-                P[pre + "W2T"] = _pack_linear(blk.ffn.fc2.weight.t(), HPh, CP)
-                w9 = torch.zeros(CA, 9, device=device)
-                w9[hm] = at.dwconv[0].weight.float().reshape(C_, 9)
-                P[pre + "dw_wf"] = w9.flip(1).contiguous()                         # the depth-wise dgrad: the same conv with flipped taps
-                P[pre + "dw_b"] = _pack_vec(at.dwconv[0].bias, CA, row_map=hm)
-                P[pre + "dw_gam"] = _pack_vec(at.dwconv[1].weight, CA, row_map=hm)          # BatchNorm affine in the head-padded layout
-                P[pre + "dw_bet"] = _pack_vec(at.dwconv[1].bias, CA, row_map=hm)
-                sg9 = torch.zeros(HPh, 9, device=device)
-                sg9[:half] = blk.ffn.sg.conv.weight.float().reshape(half, 9)
-                P[pre + "sg_wf"] = sg9.flip(1).contiguous()
-                S2 = at.spatial_interaction[0].weight.shape[0]
-                w0 = torch.zeros(S2, CA, device=device)
-                w0[:, hm] = at.spatial_interaction[0].weight.float().reshape(S2, C_)
-                P[pre + "si_w0raw"] = w0.contiguous()
-            P[f"{li}.WconvT"] = _pack_conv_T(layer.conv.weight, CP, CP)
-        hp.pack_tail_T(P, m, CP, device)
-        P["ones"] = torch.ones(max(2 * HPh, 256), device=device)
-        P["zeros"] = torch.zeros(max(2 * HPh, 256), device=device)
-        pk.resolve(P)
-    m._packedT, m._packedT_version, m._packedT_device = P, ver, device
-    return P
+    rows = _fc1_rows(hid, half, HPh, device)
+    P["fc1_rows"] = rows
+    for li, layer in enumerate(m.layers):
+        nH = m.heads[li]
+        dh, CA = C_ // nH, nH * 32
+        hm = _head_map(nH, dh, device)
+        for bi, blk in enumerate(layer.blocks):
+            pre = f"{li}.{bi}."
+            at = blk.attn
+            pack_attn_T(P, pre, at.qkv, at.proj, nH, dh, CP, device)
+            P[pre + "W1T"] = _pack_linear(blk.ffn.fc1.weight.t(), CP, 2 * HPh, col_map=rows)
+            P[pre + "W2T"] = _pack_linear(blk.ffn.fc2.weight.t(), HPh, CP)
+            P[pre + "dw_wf"] = _dw9(at.dwconv[0], hm, CA, device).flip(1)          # the depth-wise dgrad: the same conv with flipped taps
+            P[pre + "dw_b"] = _pack_vec(at.dwconv[0].bias, CA, row_map=hm)
+            P[pre + "dw_gam"] = _pack_vec(at.dwconv[1].weight, CA, row_map=hm)          # BatchNorm affine in the head-padded layout
+            P[pre + "dw_bet"] = _pack_vec(at.dwconv[1].bias, CA, row_map=hm)
+            P[pre + "sg_wf"] = _dw9(blk.ffn.sg.conv, slice(half), HPh, device).flip(1)
+            S2 = at.spatial_interaction[0].weight.shape[0]
+            w0 = torch.zeros(S2, CA, device=device)
+            w0[:, hm] = at.spatial_interaction[0].weight.float().reshape(S2, C_)
+            P[pre + "si_w0raw"] = w0.contiguous()
+        P[f"{li}.WconvT"] = _pack_conv_T(layer.conv.weight, CP, CP)
+    hp.pack_tail_T(P, m, CP, device)
+    P["ones"] = torch.ones(max(2 * HPh, 256), device=device)
+    P["zeros"] = torch.zeros(max(2 * HPh, 256), device=device)
 
 
 # ---- forward, keeping activations ---------------------------------------------------------------------------------------------------------

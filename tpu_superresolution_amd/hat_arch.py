@@ -28,16 +28,16 @@ permuted) once per parameter version on the device.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
-import threading
-from typing import Dict, List, Optional
+from typing import Dict, Optional
 
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
-from ._lib import GemmArgs, SrkUnsupported, check, lib
+from . import _lib, host_pass, ops
+from ._lib import SrkUnsupported, check, lib
+from .host_pass import _gemm
+from .packing import _pack_conv, _pack_vec, _rup, cached_pack, pack_attn, pack_mlp
 
 
 def _pair(v):
@@ -195,162 +195,6 @@ class Upsample(nn.Sequential):
         super().__init__(*m)
 
 
-# ---- weight packing (one-time, on the device) ----------------------------------------------------------------------------
-def _rup(v, m):
-    return (v + m - 1) // m * m
-
-
-# ---- packing helpers -------------------------------------------------------------------------------------------------------------------
-# A model is packed after every optimizer step (training), so the count of tiny torch kernels matters: inside ``batched_pack()`` the
-# helpers only RECORD their request and return a placeholder; ``resolve`` groups requests of the same kind / shape / index maps (the 42
-# qkv weights of HAT, ...), runs each group as ONE stack + scatter + cast and hands out views of the stacked result.  Outside the
-# context they run eagerly, one tensor at a time.
-_MAPS: Dict[tuple, torch.Tensor] = {}
-
-
-def _cached_map(key: tuple, make):
-    t = _MAPS.get(key)
-    if t is None:
-        t = _MAPS[key] = make()
-    return t
-
-
-class _Pending:
-    __slots__ = ("group", "index")
-
-    def __init__(self, group, index):
-        self.group, self.index = group, index
-
-
-class _Packer:
-    def __init__(self):
-        self.groups: Dict[tuple, list] = {}
-
-    def add(self, kind, src, args, maps):
-        key = (kind, tuple(src.shape), src.dtype, src.device, args, tuple(id(m_) if m_ is not None else None for m_ in maps))
-        g = self.groups.setdefault(key, [kind, args, maps, []])
-        g[3].append(src)
-        return _Pending(key, len(g[3]) - 1)
-
-    def resolve(self, P: dict) -> None:
-        done = {}
-        for key, (kind, args, maps, srcs) in self.groups.items():
-            done[key] = _PACK_MANY[kind](torch.stack([t.float() for t in srcs]), *args, *maps)
-        for name, v in P.items():
-            if isinstance(v, _Pending):
-                P[name] = done[v.group][v.index]
-
-
-_TLS = threading.local()        # the active packer is per thread (two threads may pack two models at once)
-
-
-def _active() -> Optional[_Packer]:
-    return getattr(_TLS, "packer", None)
-
-
-class batched_pack:
-    """with batched_pack() as pk: ... P[name] = _pack_linear(...) ...; pk.resolve(P)"""
-
-    def __enter__(self):
-        self.prev = _active()
-        _TLS.packer = _Packer()
-        return _TLS.packer
-
-    def __exit__(self, *exc):
-        _TLS.packer = self.prev
-
-
-def _many_linear(ws, NP, KP, row_map, col_map):
-    n, N, K = ws.shape
-    out = torch.zeros(n, NP, KP, dtype=torch.float32, device=ws.device)
-    rows = row_map if row_map is not None else torch.arange(N, device=ws.device)
-    cols = col_map if col_map is not None else torch.arange(K, device=ws.device)
-    out[:, rows[:, None], cols[None, :]] = ws
-    return out.to(torch.bfloat16)
-
-
-def _many_vec(bs, NP, row_map):
-    n, N = bs.shape
-    out = torch.zeros(n, NP, dtype=torch.float32, device=bs.device)
-    rows = row_map if row_map is not None else torch.arange(N, device=bs.device)
-    out[:, rows] = bs
-    return out
-
-
-def _many_conv(ws, NP, CinP, row_map):
-    n, Cout, Cin = ws.shape[:3]
-    out = torch.zeros(n, NP, 9, CinP, dtype=torch.float32, device=ws.device)
-    rows = row_map if row_map is not None else torch.arange(Cout, device=ws.device)
-    out[:, rows, :, :Cin] = ws.permute(0, 1, 3, 4, 2).reshape(n, Cout, 9, Cin)
-    return out.reshape(n, NP, 9 * CinP).to(torch.bfloat16)
-
-
-def _many_conv_T(ws, NP, CoutP, col_map):
-    n, Cout, Cin = ws.shape[:3]
-    out = torch.zeros(n, NP, 9, CoutP, dtype=torch.float32, device=ws.device)
-    cols = col_map if col_map is not None else torch.arange(Cout, device=ws.device)
-    out[:, :Cin, :, cols] = ws.flip(3, 4).permute(0, 2, 3, 4, 1).reshape(n, Cin, 9, Cout)
-    return out.reshape(n, NP, 9 * CoutP).to(torch.bfloat16)
-
-
-_PACK_MANY = {"linear": _many_linear, "vec": _many_vec, "conv": _many_conv, "convT": _many_conv_T}
-
-
-def _pack_linear(w: torch.Tensor, NP: int, KP: int, row_map=None, col_map=None) -> torch.Tensor:
-    """fp32 [N][K] -> bf16 [NP][KP], rows / columns scattered through the given index maps (zero elsewhere)."""
-    pk = _active()
-    if pk is not None:
-        return pk.add("linear", w, (NP, KP), (row_map, col_map))
-    return _many_linear(w.float()[None], NP, KP, row_map, col_map)[0].contiguous()
-
-
-def _pack_vec(b: Optional[torch.Tensor], NP: int, row_map=None, device=None) -> torch.Tensor:
-    if b is None:
-        return torch.zeros(NP, dtype=torch.float32, device=device)
-    pk = _active()
-    if pk is not None:
-        return pk.add("vec", b, (NP,), (row_map,))
-    return _many_vec(b.float()[None], NP, row_map)[0]
-
-
-def _pack_conv(w: torch.Tensor, NP: int, CinP: int, row_map=None) -> torch.Tensor:
-    """[Cout][Cin][3][3] -> bf16 [NP][9 * CinP], K tap-major: k = (3 ky + kx) * CinP + ci."""
-    pk = _active()
-    if pk is not None:
-        return pk.add("conv", w, (NP, CinP), (row_map,))
-    return _many_conv(w.float()[None], NP, CinP, row_map)[0].contiguous()
-
-
-def _pack_conv_T(w: torch.Tensor, NP: int, CoutP: int, col_map=None) -> torch.Tensor:
-    """[Cout][Cin][3][3] -> bf16 [NP (input channels)][9 * CoutP]: the dgrad's weight, taps flipped, K = (tap, output channel)."""
-    pk = _active()
-    if pk is not None:
-        return pk.add("convT", w, (NP, CoutP), (col_map,))
-    return _many_conv_T(w.float()[None], NP, CoutP, col_map)[0].contiguous()
-
-
-def _head_map(nH: int, dh: int, device) -> torch.Tensor:
-    """channel h * dh + d -> padded channel h * 32 + d   (one tensor per (heads, head_dim, device): the batched packer groups by identity)"""
-    def make():
-        c = torch.arange(nH * dh, device=device)
-        return (c // dh) * 32 + c % dh
-    return _cached_map(("head", nH, dh, str(device)), make)
-
-
-def _qkv_rows(nH: int, dh: int, device) -> torch.Tensor:
-    """row of the packed qkv weight of output feature (which, h, d)"""
-    return _cached_map(("qkv", nH, dh, str(device)), lambda: torch.cat([w * nH * 32 + _head_map(nH, dh, device) for w in range(3)]))
-
-
-def _ps_map(C_out: int, r: int, Cs: int, device) -> torch.Tensor:
-    """PixelShuffle conv: original output channel c * r^2 + i * r + j -> packed row (i * r + j) * Cs + c"""
-    def make():
-        n = torch.arange(C_out, device=device)
-        c, ij = n // (r * r), n % (r * r)
-        return ij * Cs + c
-    return _cached_map(("ps", C_out, r, Cs, str(device)), make)
-
-
 class HAT(nn.Module):
     r"""Hybrid Attention Transformer -- reference constructor signature, hat_arch.py:738-764."""
 
@@ -397,9 +241,6 @@ class HAT(nn.Module):
             self.upsample = Upsample(upscale, num_feat)
             self.conv_last = nn.Conv2d(num_feat, in_chans, 3, 1, 1)
         self.apply(self._init_weights)
-        self._packed: Optional[Dict[str, torch.Tensor]] = None
-        self._packed_version = -1
-        self._packed_device = None
 
     # -- reference helper API -------------------------------------------------------------------------------------------
     def _init_weights(self, m):
@@ -470,57 +311,35 @@ class HAT(nn.Module):
 
     def _pack(self, device) -> Dict[str, torch.Tensor]:
         """bf16 / padded / permuted copies of the parameters in the kernels' layouts, rebuilt when a parameter changed."""
-        ver = sum(p._version for p in self.parameters())
-        if self._packed is not None and self._packed_version == ver and self._packed_device == device:
-            return self._packed
+        return cached_pack(self, "fwd", device, lambda P: self._fill_pack(P, device))
+
+    def _fill_pack(self, P: dict, device) -> None:
         C, CP = self.embed_dim, _rup(self.embed_dim, 64)
-        hid = int(C * self.mlp_ratio)
-        HP = _rup(hid, 64)
-        P: Dict[str, torch.Tensor] = {}
-        from .host_pass import pack_tail          # (host_pass builds on this module's packing helpers and _gemm)
-        with torch.no_grad(), batched_pack() as pk:
-            for li, layer in enumerate(self.layers):
-                nH = self.heads[li]
-                dh, CA = C // nH, nH * 32
-                hm = _head_map(nH, dh, device)
-                qkv_rows = _qkv_rows(nH, dh, device)
-
-                def attn_pack(pre, qkv, proj):
-                    P[pre + "Wqkv"] = _pack_linear(qkv.weight, 3 * CA, CP, row_map=qkv_rows)
-                    P[pre + "bqkv"] = _pack_vec(qkv.bias, 3 * CA, row_map=qkv_rows)
-                    P[pre + "Wproj"] = _pack_linear(proj.weight, CP, CA, col_map=hm)
-                    P[pre + "bproj"] = _pack_vec(proj.bias, CP)
-
-                def mlp_pack(pre, mlp):
-                    P[pre + "W1"] = _pack_linear(mlp.fc1.weight, HP, CP)
-                    P[pre + "b1"] = _pack_vec(mlp.fc1.bias, HP)
-                    P[pre + "W2"] = _pack_linear(mlp.fc2.weight, CP, HP)
-                    P[pre + "b2"] = _pack_vec(mlp.fc2.bias, CP)
-
-                for bi, blk in enumerate(layer.residual_group.blocks):
-                    pre = f"{li}.{bi}."
-                    attn_pack(pre, blk.attn.qkv, blk.attn.proj)
-                    mlp_pack(pre, blk.mlp)
-                    cab = blk.conv_block.cab
-                    P[pre + "Wc0"] = _pack_conv(cab[0].weight, 64, CP)
-                    P[pre + "bc0"] = _pack_vec(cab[0].bias, 64)
-                    P[pre + "Wc2"] = _pack_conv(cab[2].weight, CP, 64)
-                    P[pre + "bc2"] = _pack_vec(cab[2].bias, CP)
-                    att = cab[3].attention
-                    P[pre + "ca_w1"] = att[1].weight.float().reshape(att[1].weight.shape[0], C).contiguous()
-                    P[pre + "ca_b1"] = att[1].bias.float().contiguous()
-                    P[pre + "ca_w2"] = att[3].weight.float().reshape(C, att[3].weight.shape[1]).contiguous()
-                    P[pre + "ca_b2"] = att[3].bias.float().contiguous()
-                oc = layer.residual_group.overlap_attn
-                pre = f"{li}.oca."
-                attn_pack(pre, oc.qkv, oc.proj)
-                mlp_pack(pre, oc.mlp)
-                P[f"{li}.Wconv"] = _pack_conv(layer.conv.weight, CP, CP)
-                P[f"{li}.bconv"] = _pack_vec(layer.conv.bias, CP)
-            pack_tail(P, self, CP, device)
-            pk.resolve(P)
-        self._packed, self._packed_version, self._packed_device = P, ver, device
-        return P
+        HP = _rup(int(C * self.mlp_ratio), 64)
+        for li, layer in enumerate(self.layers):
+            nH = self.heads[li]
+            dh = C // nH
+            for bi, blk in enumerate(layer.residual_group.blocks):
+                pre = f"{li}.{bi}."
+                pack_attn(P, pre, blk.attn.qkv, blk.attn.proj, nH, dh, CP, device)
+                pack_mlp(P, pre, blk.mlp.fc1, blk.mlp.fc2, HP, CP)
+                cab = blk.conv_block.cab
+                P[pre + "Wc0"] = _pack_conv(cab[0].weight, 64, CP)
+                P[pre + "bc0"] = _pack_vec(cab[0].bias, 64)
+                P[pre + "Wc2"] = _pack_conv(cab[2].weight, CP, 64)
+                P[pre + "bc2"] = _pack_vec(cab[2].bias, CP)
+                att = cab[3].attention
+                P[pre + "ca_w1"] = att[1].weight.float().reshape(att[1].weight.shape[0], C).contiguous()
+                P[pre + "ca_b1"] = att[1].bias.float().contiguous()
+                P[pre + "ca_w2"] = att[3].weight.float().reshape(C, att[3].weight.shape[1]).contiguous()
+                P[pre + "ca_b2"] = att[3].bias.float().contiguous()
+            oc = layer.residual_group.overlap_attn
+            pre = f"{li}.oca."
+            pack_attn(P, pre, oc.qkv, oc.proj, nH, dh, CP, device)
+            pack_mlp(P, pre, oc.mlp.fc1, oc.mlp.fc2, HP, CP)
+            P[f"{li}.Wconv"] = _pack_conv(layer.conv.weight, CP, CP)
+            P[f"{li}.bconv"] = _pack_vec(layer.conv.bias, CP)
+        host_pass.pack_tail(P, self, CP, device)
 
     # -- forward -----------------------------------------------------------------------------------------------------------
     def forward_features(self, x):
@@ -561,36 +380,7 @@ class HAT(nn.Module):
 
 
 # ---- the launch sequence ----------------------------------------------------------------------------------------------------
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
-
-
-def _gemm(st, loader, ep, A, W, M, N, K, *, lda=0, conv=None, bias=None, outf=None, outb=None, outb2=None, res=None, ldo=0, scale=0.0,
-          r=0, Cs=0, img=None, xn=None, aux=None, rowscale=None, rows_per_sample=0, ln=None):
-    a = GemmArgs()
-    a.loader, a.epilogue = loader, ep
-    a.A, a.lda, a.W, a.M, a.N, a.K = _ptr(A), lda, _ptr(W), M, N, K
-    if conv is not None:
-        a.B, a.H, a.Wd, a.CinP = conv
-    a.r, a.Cs = r, Cs
-    a.bias, a.outf, a.outb, a.outb2, a.res = _ptr(bias), _ptr(outf), _ptr(outb), _ptr(outb2), _ptr(res)
-    a.aux, a.rowscale, a.rows_per_sample = _ptr(aux), _ptr(rowscale), (rows_per_sample if rowscale is not None else 0)
-    a.ldo, a.scale = ldo or N, scale
-    if img is not None:
-        a.inv_range, a.Cimg, a.Hc, a.Wc = img["inv_range"], img["Cimg"], img["Hc"], img["Wc"]
-        for i in range(4):
-            a.mean[i] = img["mean"][i]
-    if xn is not None:
-        a.xn_out, a.xn_mean, a.xn_rstd, a.xn_gamma, a.xn_beta, a.xn_C = (_ptr(xn["out"]), _ptr(xn["mean"]), _ptr(xn["rstd"]),
-                                                                       _ptr(xn["gamma"]), _ptr(xn["beta"]), xn["C"])
-    if ln is not None:      # EP_LNBWD: LayerNorm backward fused into the dgrad's epilogue
-        a.ln_x, a.ln_mean, a.ln_rstd, a.ln_gamma = _ptr(ln["x"]), _ptr(ln["mean"]), _ptr(ln["rstd"]), _ptr(ln["gamma"])
-        a.ln_dgamma, a.ln_dbeta, a.ln_C = _ptr(ln["dgamma"]), _ptr(ln["dbeta"]), ln["C"]
-    check(lib().srk_gemm_ex(C.byref(a), st))
-
-
 def _hat_forward(m: HAT, x: torch.Tensor, P: Dict[str, torch.Tensor]) -> torch.Tensor:
-    from . import host_pass          # (host_pass builds on this module's packing helpers and _gemm)
     dev = x.device
     st = torch.cuda.current_stream(dev).cuda_stream
     B, Cin, H0, W0 = x.shape

@@ -24,50 +24,35 @@ from typing import Dict, Optional
 
 import torch
 
-from . import _lib, hat_arch as ha, host_pass as hp, ops
+from . import _lib, host_pass as hp, ops
 from ._lib import check, lib
-from .hat_arch import _gemm, _head_map, _pack_conv_T, _pack_linear, _qkv_rows, _rup
-from .host_pass import GradSink, _full
+from .host_pass import GradSink, _full, _gemm
+from .packing import _head_map, _pack_conv_T, _qkv_rows, _rup, cached_pack, pack_attn_T, pack_mlp_T
 
 
 # ---- packed operands of the backward pass (transposed copies for the dgrads) ---------------------------------------------------
 def pack_transposed(m, device) -> Dict[str, torch.Tensor]:
-    ver = sum(p._version for p in m.parameters())
-    if getattr(m, "_packedT", None) is not None and m._packedT_version == ver and m._packedT_device == device:
-        return m._packedT
+    return cached_pack(m, "T", device, lambda P: _fill_transposed(P, m, device))
+
+
+def _fill_transposed(P: dict, m, device) -> None:
     C_, CP = m.embed_dim, _rup(m.embed_dim, 64)
     HP = _rup(int(C_ * m.mlp_ratio), 64)
-    P: Dict[str, torch.Tensor] = {}
-    with torch.no_grad(), ha.batched_pack() as pk:      # the one name looked up on the module at every call (the packing test swaps it)
-        for li, layer in enumerate(m.layers):
-            nH = m.heads[li]
-            dh, CA = C_ // nH, nH * 32
-            hm = _head_map(nH, dh, device)
-            qkv_rows = _qkv_rows(nH, dh, device)
-
-            def attn_T(pre, qkv, proj):
-                P[pre + "WqkvT"] = _pack_linear(qkv.weight.t(), CP, 3 * CA, col_map=qkv_rows)        # [c][3 CA]
-                P[pre + "WprojT"] = _pack_linear(proj.weight.t(), CA, CP, row_map=hm)                # [ca][c]
-
-            def mlp_T(pre, mlp):
-                P[pre + "W1T"] = _pack_linear(mlp.fc1.weight.t(), CP, HP)
-                P[pre + "W2T"] = _pack_linear(mlp.fc2.weight.t(), HP, CP)
-
-            for bi, blk in enumerate(layer.residual_group.blocks):
-                pre = f"{li}.{bi}."
-                attn_T(pre, blk.attn.qkv, blk.attn.proj)
-                mlp_T(pre, blk.mlp)
-                cab = blk.conv_block.cab
-                P[pre + "Wc0T"] = _pack_conv_T(cab[0].weight, CP, 64)
-                P[pre + "Wc2T"] = _pack_conv_T(cab[2].weight, 64, CP)
-            oc = layer.residual_group.overlap_attn
-            attn_T(f"{li}.oca.", oc.qkv, oc.proj)
-            mlp_T(f"{li}.oca.", oc.mlp)
-            P[f"{li}.WconvT"] = _pack_conv_T(layer.conv.weight, CP, CP)
-        hp.pack_tail_T(P, m, CP, device)
-        pk.resolve(P)
-    m._packedT, m._packedT_version, m._packedT_device = P, ver, device
-    return P
+    for li, layer in enumerate(m.layers):
+        nH = m.heads[li]
+        dh = C_ // nH
+        for bi, blk in enumerate(layer.residual_group.blocks):
+            pre = f"{li}.{bi}."
+            pack_attn_T(P, pre, blk.attn.qkv, blk.attn.proj, nH, dh, CP, device)
+            pack_mlp_T(P, pre, blk.mlp.fc1, blk.mlp.fc2, HP, CP)
+            cab = blk.conv_block.cab
+            P[pre + "Wc0T"] = _pack_conv_T(cab[0].weight, CP, 64)
+            P[pre + "Wc2T"] = _pack_conv_T(cab[2].weight, 64, CP)
+        oc = layer.residual_group.overlap_attn
+        pack_attn_T(P, f"{li}.oca.", oc.qkv, oc.proj, nH, dh, CP, device)
+        pack_mlp_T(P, f"{li}.oca.", oc.mlp.fc1, oc.mlp.fc2, HP, CP)
+        P[f"{li}.WconvT"] = _pack_conv_T(layer.conv.weight, CP, CP)
+    hp.pack_tail_T(P, m, CP, device)
 
 
 # ---- forward, keeping activations ---------------------------------------------------------------------------------------------

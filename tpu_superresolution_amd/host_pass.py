@@ -26,8 +26,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from ._lib import check, lib
-from .hat_arch import _gemm, _pack_conv, _pack_conv_T, _pack_vec, _ps_map, _ptr, _rup
+from ._lib import GemmArgs, check, lib
+from .packing import _pack_conv, _pack_conv_T, _pack_vec, _ps_map, _rup
 
 _POISON = os.environ.get("SRK_DBG_POISON") == "1"
 
@@ -50,6 +50,35 @@ def _rows(TR: int, T: int, cols: int, kw: dict) -> torch.Tensor:
 
 def _kw(dev):
     return dict(dtype=torch.float32, device=dev), dict(dtype=torch.bfloat16, device=dev)
+
+
+# ---- launch helpers ----------------------------------------------------------------------------------------------------------------------
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+def _gemm(st, loader, ep, A, W, M, N, K, *, lda=0, conv=None, bias=None, outf=None, outb=None, outb2=None, res=None, ldo=0, scale=0.0,
+          r=0, Cs=0, img=None, xn=None, aux=None, rowscale=None, rows_per_sample=0, ln=None):
+    a = GemmArgs()
+    a.loader, a.epilogue = loader, ep
+    a.A, a.lda, a.W, a.M, a.N, a.K = _ptr(A), lda, _ptr(W), M, N, K
+    if conv is not None:
+        a.B, a.H, a.Wd, a.CinP = conv
+    a.r, a.Cs = r, Cs
+    a.bias, a.outf, a.outb, a.outb2, a.res = _ptr(bias), _ptr(outf), _ptr(outb), _ptr(outb2), _ptr(res)
+    a.aux, a.rowscale, a.rows_per_sample = _ptr(aux), _ptr(rowscale), (rows_per_sample if rowscale is not None else 0)
+    a.ldo, a.scale = ldo or N, scale
+    if img is not None:
+        a.inv_range, a.Cimg, a.Hc, a.Wc = img["inv_range"], img["Cimg"], img["Hc"], img["Wc"]
+        for i in range(4):
+            a.mean[i] = img["mean"][i]
+    if xn is not None:
+        a.xn_out, a.xn_mean, a.xn_rstd, a.xn_gamma, a.xn_beta, a.xn_C = (_ptr(xn["out"]), _ptr(xn["mean"]), _ptr(xn["rstd"]),
+                                                                       _ptr(xn["gamma"]), _ptr(xn["beta"]), xn["C"])
+    if ln is not None:      # EP_LNBWD: LayerNorm backward fused into the dgrad's epilogue
+        a.ln_x, a.ln_mean, a.ln_rstd, a.ln_gamma = _ptr(ln["x"]), _ptr(ln["mean"]), _ptr(ln["rstd"]), _ptr(ln["gamma"])
+        a.ln_dgamma, a.ln_dbeta, a.ln_C = _ptr(ln["dgamma"]), _ptr(ln["dbeta"]), ln["C"]
+    check(lib().srk_gemm_ex(C.byref(a), st))
 
 
 # ---- packed gradients back into the parameters' shapes ------------------------------------------------------------------------------------

@@ -28,6 +28,7 @@ import torch.nn as nn
 from . import ops
 from ._lib import SrkUnsupported
 from .engine import SwinIREngine, SwinIRPlan, _SwinIRFunction
+from .packing import params_version
 
 
 def _pair(v):
@@ -459,7 +460,7 @@ class SwinIR(nn.Module):
         if not self._param_views_ok(eng):
             self._engine = None
             eng = self._bind(x.device)
-        ver = sum(p._version for p in self.parameters())
+        ver = params_version(self)
         if ver != eng.pack_version:
             eng.packed_valid = False
             eng.pack_version = ver
@@ -502,7 +503,7 @@ class SwinIR(nn.Module):
             # inference reuses the bf16 pack only while no parameter has been written in place since it was made
             # (torch.optim.* steps, p.mul_(), ... bump the autograd version counter; FusedAdamW / load_state_dict /
             # mark_params_dirty / train()<->eval() switches clear packed_valid themselves)
-            ver = sum(p._version for p in self.parameters())
+            ver = params_version(self)
             if ver != eng.pack_version:
                 eng.packed_valid = False
                 eng.pack_version = ver

@@ -28,8 +28,8 @@ import torch
 
 from . import _lib, host_pass as hp, ops, swinir_w16
 from ._lib import SrkUnsupported, check, lib
-from .hat_arch import _gemm, _head_map, _pack_conv_T, _pack_linear, _qkv_rows, _rup, batched_pack
-from .host_pass import GradSink, _full, _rows
+from .host_pass import GradSink, _full, _gemm, _rows
+from .packing import _head_map, _pack_conv_T, _qkv_rows, _rup, cached_pack, pack_attn_T, pack_mlp_T
 
 
 def unsupported_reason(m) -> str:
@@ -48,29 +48,20 @@ def is_enabled(model) -> bool:
 
 # ---- packed operands of the backward pass (transposed copies for the dgrads) ---------------------------------------------------
 def pack_transposed(m, device) -> Dict[str, torch.Tensor]:
-    ver = sum(p._version for p in m.parameters())
-    if getattr(m, "_wsT_packed", None) is not None and m._wsT_version == ver and m._wsT_device == device:
-        return m._wsT_packed
+    return cached_pack(m, "wsT", device, lambda P: _fill_transposed(P, m, device))
+
+
+def _fill_transposed(P: dict, m, device) -> None:
     C_, CP = m.embed_dim, _rup(m.embed_dim, 64)
     HP = _rup(int(C_ * m.mlp_ratio), 64)
-    P: Dict[str, torch.Tensor] = {}
-    with torch.no_grad(), batched_pack() as pk:
-        for li, layer in enumerate(m.layers):
-            nH = m.heads[li]
-            dh, CA = C_ // nH, nH * 32
-            hm = _head_map(nH, dh, device)
-            qkv_rows = _qkv_rows(nH, dh, device)
-            for bi, blk in enumerate(layer.residual_group.blocks):
-                pre = f"{li}.{bi}."
-                P[pre + "WqkvT"] = _pack_linear(blk.attn.qkv.weight.t(), CP, 3 * CA, col_map=qkv_rows)        # [c][3 CA]
-                P[pre + "WprojT"] = _pack_linear(blk.attn.proj.weight.t(), CA, CP, row_map=hm)                # [ca][c]
-                P[pre + "W1T"] = _pack_linear(blk.mlp.fc1.weight.t(), CP, HP)
-                P[pre + "W2T"] = _pack_linear(blk.mlp.fc2.weight.t(), HP, CP)
-            P[f"{li}.WconvT"] = _pack_conv_T(layer.conv.weight, CP, CP)
-        hp.pack_tail_T(P, m, CP, device)
-        pk.resolve(P)
-    m._wsT_packed, m._wsT_version, m._wsT_device = P, ver, device
-    return P
+    for li, layer in enumerate(m.layers):
+        nH = m.heads[li]
+        for bi, blk in enumerate(layer.residual_group.blocks):
+            pre = f"{li}.{bi}."
+            pack_attn_T(P, pre, blk.attn.qkv, blk.attn.proj, nH, C_ // nH, CP, device)
+            pack_mlp_T(P, pre, blk.mlp.fc1, blk.mlp.fc2, HP, CP)
+        P[f"{li}.WconvT"] = _pack_conv_T(layer.conv.weight, CP, CP)
+    hp.pack_tail_T(P, m, CP, device)
 
 
 # ---- forward, keeping activations ---------------------------------------------------------------------------------------------

@@ -28,7 +28,8 @@ import torch
 
 from . import _lib, host_pass as hp, ops
 from ._lib import SrkUnsupported, check, lib
-from .hat_arch import _gemm, _head_map, _pack_conv, _pack_linear, _pack_vec, _qkv_rows, _rup, batched_pack
+from .host_pass import _gemm
+from .packing import _pack_conv, _pack_vec, _rup, cached_pack, pack_attn, pack_mlp
 
 
 def unsupported_reason(m) -> str:
@@ -50,35 +51,21 @@ def unsupported_reason(m) -> str:
 
 
 def pack(m, device) -> Dict[str, torch.Tensor]:
-    ver = sum(p._version for p in m.parameters())
-    if getattr(m, "_w16_packed", None) is not None and m._w16_version == ver and m._w16_device == device:
-        return m._w16_packed
+    return cached_pack(m, "w16", device, lambda P: _fill_pack(P, m, device))
+
+
+def _fill_pack(P: dict, m, device) -> None:
     C_, CP = m.embed_dim, _rup(m.embed_dim, 64)
-    hid = int(C_ * m.mlp_ratio)
-    HP = _rup(hid, 64)
-    P: Dict[str, torch.Tensor] = {}
-    with torch.no_grad(), batched_pack() as pk:
-        for li, layer in enumerate(m.layers):
-            nH = m.heads[li]
-            dh, CA = C_ // nH, nH * 32
-            hm = _head_map(nH, dh, device)
-            qkv_rows = _qkv_rows(nH, dh, device)
-            for bi, blk in enumerate(layer.residual_group.blocks):
-                pre = f"{li}.{bi}."
-                P[pre + "Wqkv"] = _pack_linear(blk.attn.qkv.weight, 3 * CA, CP, row_map=qkv_rows)
-                P[pre + "bqkv"] = _pack_vec(blk.attn.qkv.bias, 3 * CA, row_map=qkv_rows)
-                P[pre + "Wproj"] = _pack_linear(blk.attn.proj.weight, CP, CA, col_map=hm)
-                P[pre + "bproj"] = _pack_vec(blk.attn.proj.bias, CP)
-                P[pre + "W1"] = _pack_linear(blk.mlp.fc1.weight, HP, CP)
-                P[pre + "b1"] = _pack_vec(blk.mlp.fc1.bias, HP)
-                P[pre + "W2"] = _pack_linear(blk.mlp.fc2.weight, CP, HP)
-                P[pre + "b2"] = _pack_vec(blk.mlp.fc2.bias, CP)
-            P[f"{li}.Wconv"] = _pack_conv(layer.conv.weight, CP, CP)
-            P[f"{li}.bconv"] = _pack_vec(layer.conv.bias, CP)
-        hp.pack_tail(P, m, CP, device)
-        pk.resolve(P)
-    m._w16_packed, m._w16_version, m._w16_device = P, ver, device
-    return P
+    HP = _rup(int(C_ * m.mlp_ratio), 64)
+    for li, layer in enumerate(m.layers):
+        nH = m.heads[li]
+        for bi, blk in enumerate(layer.residual_group.blocks):
+            pre = f"{li}.{bi}."
+            pack_attn(P, pre, blk.attn.qkv, blk.attn.proj, nH, C_ // nH, CP, device)
+            pack_mlp(P, pre, blk.mlp.fc1, blk.mlp.fc2, HP, CP)
+        P[f"{li}.Wconv"] = _pack_conv(layer.conv.weight, CP, CP)
+        P[f"{li}.bconv"] = _pack_vec(layer.conv.bias, CP)
+    hp.pack_tail(P, m, CP, device)
 
 
 def forward(m, x: torch.Tensor) -> torch.Tensor:
